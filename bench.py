@@ -27,10 +27,13 @@ lanes) with global env ids rank*2^20+i and no data-path collective; the only col
 AFTER the timed region (its cost is reported separately as stats_readout_us).  `sharder` says which form ran: "single engine", "process-per-gpu", "in-process".
 
 Timing (">= 5 repetitions, report the median"): after W warm-up steps and ~60 ms of untimed stepping (the settle phase: a fresh process steps faster
-for its first ~20 ms than it does in the long run) the bench times R = 9 repetitions and reports their median (min / max in the full record).  One repetition =
-ONE gymrs_step_many call of P x K steps, bracketed by barrier + torch.cuda.synchronize() on both sides (wall clock) and by HIP events on the engine's stream
-(launch time); P is chosen once so that a repetition lasts >= 100 ms (MIN_REPETITION_SECONDS says why).  Per repetition the MAX over ranks is taken, then the
-MEDIAN over repetitions; ms_per_step = that time / (P * K), value = all lanes * P * K / that time.  Nothing but the K-step passes sits inside a timed repetition.
+for its first ~20 ms than it does in the long run) the engine is reset with a fixed seed, and the bench times exactly K = --steps steps per call shape, cut into
+R = 9 repetitions (fewer when K < 9) of ~K / R steps.  One repetition = ONE gymrs_step_many call, bracketed by barrier + torch.cuda.synchronize() on both sides
+(wall clock) and by HIP events on the engine's stream (launch time); one more repetition, untimed, goes first: as long as the others and at least 512 steps, so
+that the episodes the reset started together are out of step again when the clock starts (LEAD_IN_MIN_STEPS).  Per repetition the MAX over
+ranks is taken, then the MEDIAN over repetitions of the time per step: ms_per_step, and value = all lanes / ms_per_step.  Repetitions shorter than ~100 ms read
+up to ~2 % slow (MIN_REPETITION_SECONDS says why): pick K from a first run's ms_per_step.  `--dump-outputs DIR` writes the headline's arrays after its last
+timed step (dump_outputs); from the reset on, the steps a run takes depend on its arguments only.
 
 Inputs are resident in HBM before the timed region: the state arrays, and a ring of pre-generated random-policy action buffers (the `rng.gen_range(0..=1)` of
 examples/cartpole.rs:19, produced on the device by the Philox action stream).  See DESIGN.md section 4.
@@ -73,10 +76,10 @@ PATHS = {
 HEADLINE_PATH = "per_step_visible"
 # VALU issue roofline of the fused rollout kernel: 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles per wave64 instruction
 VALU_PEAK_WAVE_INSTR_PER_S = 256 * 4 * 2.4e9 / 2
-# A timed repetition = ONE gymrs_step_many call of P x K launches lasting at least this long.  Every repetition starts after an idle gap (barrier, synchronise,
-# events: ~0.1 ms), and for its first ~13 ms the device then runs ~1.7 % slower than in the long run (profiles/r04_launches_per_call.log: 800-2500 launches per call
-# 6.44-6.50 us each, 8000: 6.39, 20 000: 6.365): repetitions of 5 ms (rounds 2-4) measured mostly that recovery, and the driver's form (--steps 20) read 2 % lower
-# than the default form (--steps 1000) on every box.  100 ms repetitions report the sustained rate whatever K the command line names.
+# How long a repetition has to last to report the sustained rate (the config legs of measure_config time repetitions this long; the headline's repetitions
+# last what K = --steps gives them).  Every repetition starts after an idle gap (barrier, synchronise, events: ~0.1 ms), and for its first ~13 ms the device then
+# runs ~1.7 % slower than in the long run (profiles/r04_launches_per_call.log: 800-2500 launches per call 6.44-6.50 us each, 8000: 6.39, 20 000: 6.365):
+# repetitions of 5 ms (rounds 2-4) measured mostly that recovery.
 MIN_REPETITION_SECONDS = 100e-3
 REPETITIONS = 9
 # Untimed stepping between the warm-up and the first timed repetition.  A process that has just started steps FASTER for its
@@ -254,7 +257,8 @@ def cpu_baseline(kind: int, target_seconds: float):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=1000,
+                    help="timed steps per call shape: exactly this many steps lie inside the timed repetitions (split evenly over them)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--env", choices=sorted(ENVS), default="cartpole")
     ap.add_argument("--n-envs", type=int, default=0, help="lanes per GPU (default: the BASELINE config)")
@@ -274,8 +278,9 @@ def parse_args(argv=None):
                     help="sum the statistics with torch.distributed instead of the C ABI's own RCCL communicator")
     ap.add_argument("--native-rccl", action="store_true", help="(default since round 2; kept for old command lines)")
     ap.add_argument("--repetitions", type=int, default=REPETITIONS)
-    ap.add_argument("--min-repetition-ms", type=float, default=MIN_REPETITION_SECONDS * 1e3,
-                    help="a timed repetition lasts at least this long (default 100: the sustained rate, see MIN_REPETITION_SECONDS; runs under a profiler use 5)")
+    ap.add_argument("--min-repetition-ms", type=float, default=None,
+                    help="(no effect, kept for old command lines: --steps sets the timed steps, a repetition lasts what its share of them takes; "
+                         "a warning says so when it is given)")
     ap.add_argument("--no-probe", action="store_true", help="skip the in-process copy-kernel probe (roofline.peak_measured)")
     ap.add_argument("--no-queue-shape", action="store_true", help="skip the extra measurement of the per-step-visible shape through the engine's queue (roofline.queue_launch_us)")
     ap.add_argument("--no-configs", action="store_true",
@@ -288,10 +293,16 @@ def parse_args(argv=None):
                     help="ONE process drives all N GPUs through the C ABI's native sharder (gymrs_sharded_*: one engine + one host thread per device, grouped RCCL "
                          "all-reduce) instead of one process per GPU; the line's `sharder` says which form ran.  With --oversubscribe the N blocks share the box's GPUs")
     ap.add_argument("--full-out", default="", help="where the complete record goes (default: bench_full.json next to this script); the printed line names it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline call shape returned in its last step (observations, reward, done, "
+                         "truncated) as DIR/<name>.npy, f32; at most 64 MB in all (a fixed, seeded sample of lanes beyond that)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY: ranks share GPUs (rank r -> device r %% device_count) and meet over gloo, so that the "
                          "N>1 code path (spawner, global env offsets, aggregation) runs on a 1-GPU box; not a benchmark")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.min_repetition_ms is not None:
+        print("bench.py: --min-repetition-ms has no effect: --steps sets the number of timed steps (pick it from a first run's ms_per_step)", file=sys.stderr)
+    return args
 
 
 class HipBackend:
@@ -377,16 +388,35 @@ def choose_passes(seconds_per_pass: float, min_seconds: float = MIN_REPETITION_S
     return max(1, int(math.ceil(min_seconds / seconds_per_pass)))
 
 
-def timed_repetitions(backend, coll, stream, run_pass, passes, repetitions):
-    """R repetitions of `passes` x run_pass(); per repetition the MAX over ranks of (wall seconds, event ms)."""
+def repetition_sizes(steps: int, repetitions: int) -> list:
+    """The K = --steps timed steps cut into R repetitions (fewer when K < R) as evenly as whole steps allow."""
+    if steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    reps = max(1, min(repetitions, steps))
+    base, extra = divmod(steps, reps)
+    return [base + 1] * extra + [base] * (reps - extra)
+
+
+# The uncounted repetition in front of the timed ones lasts at least this many steps.  The timed steps start from a seeded reset with every episode in
+# step; under the random policy a CartPole episode lasts ~22 steps, so after a few hundred the lanes' episodes are out of step again, as in a long run.
+# (Pendulum's 200-step time limit keeps its lanes in step whatever comes before: they start together at the first reset.)
+LEAD_IN_MIN_STEPS = 512
+
+
+def lead_in_steps(sizes) -> int:
+    """Steps of the uncounted repetition in front of the timed ones: one repetition's share of K, and at least LEAD_IN_MIN_STEPS."""
+    return max(sizes[0], LEAD_IN_MIN_STEPS)
+
+
+def timed_repetitions(backend, coll, stream, run_call, sizes):
+    """One repetition per entry of `sizes`, each ONE run_call(k) of k steps; per repetition the MAX over ranks of (wall seconds, event ms)."""
     walls, kernels, own = [], [], []
-    for _ in range(repetitions):
+    for k in sizes:
         coll.barrier()
         backend.sync()
         t0 = time.perf_counter()
         m0 = backend.mark(stream)
-        for _ in range(passes):
-            run_pass()
+        run_call(k)
         m1 = backend.mark(stream)
         backend.sync()
         t1 = time.perf_counter()
@@ -398,6 +428,37 @@ def timed_repetitions(backend, coll, stream, run_pass, passes, repetitions):
         own.append(own_ms)
     backend.own_event_ms = own  # this rank's own event times (the returned ones are the max over ranks)
     return walls, kernels
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(where, engines, blocks=None, seed=0):
+    """--dump-outputs: the arrays a caller of the timed call shape receives after its last step -- observations (obs_dim x lanes), reward, done and truncated
+    (lanes each) -- as f32 .npy files in `where`.  `engines`: (file name prefix, engine) per block; the budget is shared by `blocks` blocks (default: these).
+    Where a block's arrays would not fit, the same seeded sample of its lanes is written for every array, with the lane ids as `lanes.npy` (f64)."""
+    import numpy as np
+
+    out = Path(where)
+    out.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, blocks or len(engines)) - 4096  # (room for the .npy headers)
+    written = {}
+    for prefix, eng in engines:
+        eng.sync()
+        arrays = {"obs": eng.get_obs()}
+        arrays["reward"], done, trunc = eng.get_step_result()
+        arrays["done"], arrays["truncated"] = done.astype(np.float32), trunc.astype(np.float32)
+        n = arrays["reward"].shape[0]
+        per_lane = 4 * (arrays["obs"].shape[0] + 3)
+        if n * per_lane > budget:
+            keep = np.sort(np.random.default_rng(seed).choice(n, size=budget // (per_lane + 8), replace=False))
+            arrays = {k: v[..., keep] for k, v in arrays.items()}
+            arrays["lanes"] = keep.astype(np.float64)
+        for name, a in arrays.items():
+            path = out / f"{prefix}{name}.npy"
+            np.save(path, np.ascontiguousarray(a, dtype=np.float64 if name == "lanes" else np.float32))
+            written[f"{prefix}{name}"] = list(a.shape)
+    return {"dir": str(out), "arrays": written}
 
 
 def load_pmc(name: str, env: str, sha: str):
@@ -430,7 +491,7 @@ def measure_pmc_traffic(args, env_name: str, sha: str):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = Path(tmp) / ctr
             cmd = ["rocprofv3", "--pmc", ctr, "-d", str(d), "-o", "r", "--", sys.executable, str(ROOT / "bench.py"), "--env", env_name,
-                   "--steps", "100", "--warmup", "20", "--cpu-seconds", "0", "--no-probe", "--no-configs", "--no-queue-shape", "--repetitions", "2", "--min-repetition-ms", "5"]
+                   "--steps", "100", "--warmup", "20", "--cpu-seconds", "0", "--no-probe", "--no-configs", "--no-queue-shape", "--repetitions", "2"]
             if args.n_envs:
                 cmd += ["--n-envs", str(args.n_envs)]
             if args.vec:
@@ -546,7 +607,7 @@ def run_rank(args, info, backend, make_collective=None):
         run_steps(args.steps)  # first calibration pass: clocks may still be ramping up after a short warm-up
         backend.sync()
         first = time.perf_counter() - t0
-        pinned = os.environ.get("GYMRS_BENCH_PASSES")  # tests pin the amount of work to compare two runs' statistics
+        pinned = os.environ.get("GYMRS_BENCH_PASSES")  # tests pin the untimed calibration work (one pass of each kind, no settle top-up)
         # ~2 ms more for the rate, and in any case until the device has been stepping for SETTLE_SECONDS (see there)
         again = max(choose_passes(first, 2e-3), choose_passes(first, SETTLE_SECONDS) - 1)
         again = 1 if pinned else min(again, 4096)
@@ -563,40 +624,45 @@ def run_rank(args, info, backend, make_collective=None):
             run_steps(args.steps * more)
             backend.sync()
             calibration_calls.append(args.steps * more)
-        passes = choose_passes(per_pass, args.min_repetition_ms * 1e-3)
         settle_ms = (time.perf_counter() - t_settle) * 1e3
-        if pinned:
-            passes = max(1, int(pinned))
-        passes = int(coll.max([passes])[0])  # every rank times the same work
+    # The timed steps start from a seeded reset: how much the calibration above stepped depends on the clock, what follows does not, so the
+    # same command computes the same arrays on every run (--dump-outputs) and the statistics of a run depend on its arguments only
+    eng.reset(seed=0)
     eng.stats_clear()
     steps_done[0] = 0
 
-    # ---- the timed region: R repetitions per call shape, the headline's first ----
-    reps = max(1, args.repetitions)
+    # ---- the timed region: per call shape exactly K = --steps steps in R repetitions, the headline's first ----
+    sizes = repetition_sizes(args.steps, args.repetitions)
+    reps = len(sizes)
     timed = {}
+    dumped = None
     for path in paths:
         with submission(path):
             before = extras().get("aql_launches", 0)
             if path != head:  # the other call shape: one untimed call of a repetition's length, so that its caches and clocks are its own
-                run_steps(args.steps * passes)
+                run_steps(sizes[0])
                 backend.sync()
-            # One call per repetition: P passes of K steps = one gymrs_step_many(P * K).  One more repetition up front, reported but not
-            # counted: whatever preceded the clock (stats_clear's kernels, the other call shape) has swept the caches.
+            # One gymrs_step_many call per repetition.  One more repetition up front (lead_in_steps), reported but not counted: whatever preceded
+            # the clock (the reset's and stats_clear's kernels, the other call shape) has swept the caches, and the episodes start in step.
             enqueue = []  # seconds until the call that enqueues a repetition returned: the launching thread's share
 
-            def one_repetition():
+            def one_repetition(k):
                 t = time.perf_counter()
-                run_steps(args.steps * passes)
+                run_steps(k)
                 enqueue.append(time.perf_counter() - t)
 
-            walls, kernels = timed_repetitions(backend, coll, stream, one_repetition, 1, reps + 1)
+            walls, kernels = timed_repetitions(backend, coll, stream, one_repetition, [lead_in_steps(sizes)] + sizes)
             ex = extras()
             chained = ex.get("aql_launches", 0) - before
-            timed[path] = {"walls": walls[1:], "kernels": kernels[1:], "lead_in_us": kernels[0] * 1e3 / (args.steps * passes),
-                           "own_us": [ms * 1e3 / (args.steps * passes) for ms in getattr(backend, "own_event_ms", kernels)[-reps:]],
-                           "enqueue_us": [e * 1e6 / (args.steps * passes) for e in enqueue[-reps:]],
+            own = getattr(backend, "own_event_ms", kernels)[-reps:]
+            timed[path] = {"walls": [w / k for w, k in zip(walls[1:], sizes)], "kernels": [ms / k for ms, k in zip(kernels[1:], sizes)],
+                           "wall_ms": [w * 1e3 for w in walls[1:]], "event_ms": kernels[1:], "lead_in_us": kernels[0] * 1e3 / lead_in_steps(sizes),
+                           "own_us": [ms * 1e3 / k for ms, k in zip(own, sizes)],
+                           "enqueue_us": [e * 1e6 / k for e, k in zip(enqueue[-reps:], sizes)],
                            "chained_launches": chained, "last_launch": ex.get("last_launch"), "handover": ex.get("aql_handover"),
                            "dispatcher": ex.get("aql")}
+        if path == head and args.dump_outputs:  # (after the clock, before the other call shape steps on)
+            dumped = dump_outputs(args.dump_outputs, [("" if info.world == 1 else f"rank{info.rank}_", eng)], blocks=info.world)
 
     # ---- read-out, after the clock: statistics all-reduce (the only collective of the path) ----
     backend.sync()
@@ -616,6 +682,8 @@ def run_rank(args, info, backend, make_collective=None):
 
     mine = {"rank": info.rank, "device": getattr(backend, "dev_index", None), "global_env_offset": run.offset,
             "cpu_affinity": getattr(args, "cpu_affinity", None), "numa_node": getattr(args, "numa_node", None), "paths": {}}
+    if dumped:
+        mine["dump_outputs"] = dumped
     for path, t in timed.items():
         mine["paths"][path] = {"launch_us": statistics.median(t["own_us"]), "launch_us_min": min(t["own_us"]), "launch_us_max": max(t["own_us"]),
                                "submission": submission_of(path, t), "handover": t["handover"] if path == "chain" else None}
@@ -630,19 +698,18 @@ def run_rank(args, info, backend, make_collective=None):
     out = None
     if info.is_root:
         sha = kernel_source_sha16()
-        steps_timed = args.steps * passes
         config_name = {"cartpole": "cartpole_2p20", "mountain_car": "mountain_car_2p20", "pendulum": "pendulum_2p22"}[args.env] if (
             args.n_envs in (0, n_default) and not args.vec) else None
         path_out = {}
         for path, t in timed.items():
-            wall = statistics.median(t["walls"])
-            kernel_ms = statistics.median(t["kernels"])
-            launch_us = kernel_ms * 1e3 / steps_timed
-            prec = {"what": PATHS[path][1] if path in PATHS else path, "value": run.job_rate(steps_timed, wall), "unit": "env-steps/s",
-                    "ms_per_step": wall * 1e3 / steps_timed, "launch_us": launch_us,
-                    "event_us_per_step": {"min": min(t["kernels"]) * 1e3 / steps_timed, "median": launch_us, "max": max(t["kernels"]) * 1e3 / steps_timed,
+            wall = statistics.median(t["walls"])  # seconds per step
+            kernel_ms = statistics.median(t["kernels"])  # event ms per step
+            launch_us = kernel_ms * 1e3
+            prec = {"what": PATHS[path][1] if path in PATHS else path, "value": run.job_rate(1, wall), "unit": "env-steps/s",
+                    "ms_per_step": wall * 1e3, "launch_us": launch_us,
+                    "event_us_per_step": {"min": min(t["kernels"]) * 1e3, "median": launch_us, "max": max(t["kernels"]) * 1e3,
                                           "spread": (max(t["kernels"]) - min(t["kernels"])) / kernel_ms},
-                    "wall_ms_per_repetition": [w * 1e3 for w in t["walls"]], "event_ms_per_repetition": t["kernels"],
+                    "wall_ms_per_repetition": t["wall_ms"], "event_ms_per_repetition": t["event_ms"],
                     "lead_in_repetition_us_per_step": t["lead_in_us"], "submission": submission_of(path, t)}
             if t["enqueue_us"]:
                 # rank 0's launching thread: how long the call that enqueues a repetition took, per launch.  Well below event_us_per_step = the device sets
@@ -687,13 +754,14 @@ def run_rank(args, info, backend, make_collective=None):
             },
             "timing": {
                 "repetitions": reps,
-                "passes_per_repetition": passes,
-                # untimed calls between the warm-up and the first repetition, in steps per call (priming, rate, settle)
+                # untimed calls between the warm-up and the reset in front of the timed steps, in steps per call (priming, rate, settle)
                 "calibration_passes": sum(calibration_calls) // args.steps,
                 "calibration_calls": calibration_calls,
-                "lead_in_repetition_us_per_step": hd["lead_in_repetition_us_per_step"],  # the uncounted repetition right after stats_clear
-                "settle_ms": settle_ms,  # untimed stepping right before the first repetition (calibration passes included)
-                "steps_per_repetition": steps_timed,
+                "lead_in_repetition_us_per_step": hd["lead_in_repetition_us_per_step"],  # the uncounted repetition right after the reset
+                "lead_in_steps": lead_in_steps(sizes),
+                "settle_ms": settle_ms,  # untimed stepping before the reset (calibration passes included)
+                "steps_per_repetition": sizes,  # one gymrs_step_many call each; they add up to --steps
+                "steps_timed": sum(sizes),
                 "wall_ms_per_repetition": hd["wall_ms_per_repetition"],
                 "event_ms_per_repetition": hd["event_ms_per_repetition"],
                 "event_us_per_step": hd["event_us_per_step"],
@@ -707,6 +775,8 @@ def run_rank(args, info, backend, make_collective=None):
             "episodes": {"sum_return": float(total[0]), "sum_length": float(total[1]), "n_episodes": float(total[2])},
             "sharder": "process-per-gpu" if info.world > 1 else "single engine",
         }
+        if dumped:  # every rank's files (one directory; with several ranks each prefixes its own with rank<r>_)
+            out["dump_outputs"] = {"dir": dumped["dir"], "arrays": {k: v for r in per_rank for k, v in r.get("dump_outputs", {}).get("arrays", {}).items()}}
         if per_step:
             out["roofline"] = hd["roofline"]
             out["paths"] = path_out
@@ -774,10 +844,9 @@ def run_rank(args, info, backend, make_collective=None):
             # The fused kernel touches HBM once per launch of R steps: it is bound by VALU issue, not by HBM.  Its roofline is
             # the instruction issue rate: SQ_INSTS_VALU per launch (PMC, profiles/pmc_valu.json) / launch time against
             # 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction.
-            kernel_ms = statistics.median(timed[head]["kernels"])
+            kernel_ms = statistics.median(timed[head]["kernels"])  # per step
             if args.rollout:
-                n_launch = max(1, -(-args.steps // args.rollout)) * passes
-                launch_us_r = kernel_ms * 1e3 / n_launch
+                launch_us_r = statistics.median(ms * 1e3 / -(-k // args.rollout) for ms, k in zip(timed[head]["event_ms"], sizes))  # per launch
                 out["mode"] = "fused_rollout_recorded" if args.record else "fused_rollout"
                 out["config"]["steps_per_launch"] = args.rollout
                 out["config"]["workload"] = workload + f" -- fused rollout, {args.rollout} steps per launch (NOT the per-step headline)"
@@ -785,10 +854,10 @@ def run_rank(args, info, backend, make_collective=None):
                 rec_v, note = load_pmc("pmc_valu.json", key, sha)
                 roof = {"bound": "valu", "achieved": None, "peak": VALU_PEAK_WAVE_INSTR_PER_S / 1e9, "unit": "G wave-instr/s", "frac": None,
                         "traffic": None, "kernel": "rollout_kernel<%s, %d, flags=%d>" % (args.env, 4, flags), "launch_us": launch_us_r,
-                        "ns_per_lane_step": kernel_ms * 1e6 / steps_timed / n, "kernel_source_sha16": sha}
+                        "ns_per_lane_step": kernel_ms * 1e6 / n, "kernel_source_sha16": sha}
                 if rec_v and rec_v.get("steps_per_launch") == args.rollout and rec_v.get("lanes") == n:
                     per_launch = rec_v["SQ_INSTS_VALU_per_launch"]
-                    roof["achieved"] = per_launch / (launch_us_r * 1e-6) / 1e9
+                    roof["achieved"] = per_launch / args.rollout / (kernel_ms * 1e-3) / 1e9  # (per step: a repetition's last launch may be shorter)
                     roof["frac"] = roof["achieved"] / roof["peak"]
                     roof["valu_instr_per_wave_step"] = per_launch / (n / 256.0) / args.rollout
                     roof["how"] = ("SQ_INSTS_VALU per launch (profiles/pmc_valu.json, same kernel sources) / HIP-event launch time; peak = "
@@ -799,11 +868,11 @@ def run_rank(args, info, backend, make_collective=None):
                 out["roofline"] = roof
             else:
                 out["mode"] = "hip_graph_replays"
-                launch_us = kernel_ms * 1e3 / steps_timed
+                launch_us = kernel_ms * 1e3
                 out["roofline"] = roofline_of("per_step_visible", n, bytes_per_step, launch_us, None, "graph replays: no committed traffic figure", extras().get("last_launch"), sha)
     if (info.is_root and info.world == 1 and backend.name == "hip" and per_step and HEADLINE_PATH in (out.get("paths") or {}) and hasattr(eng, "env_json")
             and not args.no_queue_shape):
-        q_us = measure_visible_through_queue(backend, eng, stream, act_ptr, act_stride, nbuf, args.steps * max(1, passes // 5))
+        q_us = measure_visible_through_queue(backend, eng, stream, act_ptr, act_stride, nbuf, args.steps * choose_passes(per_pass, 20e-3))
         if q_us:
             out["paths"][HEADLINE_PATH]["roofline"]["queue_launch_us"] = q_us  # (the same dict object as out["roofline"] when the headline is this shape)
     eng.close()
@@ -995,8 +1064,8 @@ def run_in_process(args):
     """`--in-process`: the whole job in ONE process through the C ABI's native sharder (include/gymrs_amd.h gymrs_sharded_*): a batch
     of N x lanes_per_gpu lanes cut into N contiguous blocks, one engine and one native host thread per device, the statistics summed by ONE grouped RCCL
     all-reduce after the clock (host-side sum where blocks share a device).  Same workload, same timing rules as the process-per-GPU form: W warm-up steps, a
-    settle phase, R repetitions of one gymrs_sharded_step_many(P * K) each between synchronises (wall clock) and between HIP events on EVERY block's stream
-    (the repetition's event time = the max over blocks), the median over repetitions."""
+    settle phase, a seeded reset, then K = --steps steps in R repetitions of one gymrs_sharded_step_many each between synchronises (wall clock) and between
+    HIP events on EVERY block's stream (the repetition's event time = the max over blocks), the median over repetitions of the time per step."""
     import torch
 
     gymrs = importlib.import_module("gym-rs_amd")
@@ -1053,39 +1122,40 @@ def run_in_process(args):
         while time.perf_counter() - t_settle < SETTLE_SECONDS:
             run_steps(max(args.steps, int(2e-3 / max(first / args.steps, 1e-9))))
             sh.sync()
-        per_pass, _ = timed(args.steps * 8)
-        passes = int(os.environ.get("GYMRS_BENCH_PASSES") or choose_passes(per_pass / 8, args.min_repetition_ms * 1e-3))
+        # the timed steps start from a seeded reset, as in the process-per-GPU form: the same command steps the same way on every run
+        sh.reset(seed=0)
         sh.stats_clear()
-        reps = max(1, args.repetitions)
+        sizes = repetition_sizes(args.steps, args.repetitions)
+        reps = len(sizes)
         walls, events = [], []
-        for _ in range(reps + 1):  # (one uncounted lead-in repetition, as in the process-per-GPU form)
-            w, ev = timed(args.steps * passes)
-            walls.append(w)
-            events.append(ev)
-        walls, events = walls[1:], events[1:]
+        for k in [lead_in_steps(sizes)] + sizes:  # (one uncounted lead-in repetition, as in the process-per-GPU form)
+            w, ev = timed(k)
+            walls.append(w / k)
+            events.append([ms / k for ms in ev])
+        walls, events = walls[1:], events[1:]  # per step
+        dumped = dump_outputs(args.dump_outputs, [("" if args.gpus == 1 else f"block{r}_", s) for r, s in enumerate(sh.shards)]) if args.dump_outputs else None
     total = sh.stats()
     reduce_path = sh.reduce_path
-    steps_timed = args.steps * passes
-    assert total[3] == float(n * args.gpus) * steps_timed * (reps + 1), (total, steps_timed)
+    assert total[3] == float(n * args.gpus) * (lead_in_steps(sizes) + args.steps), (total, sizes)
     wall = statistics.median(walls)
-    per_block_us = [statistics.median(e[r] for e in events) * 1e3 / steps_timed for r in range(args.gpus)]
-    launch_us = statistics.median(max(e) for e in events) * 1e3 / steps_timed
+    per_block_us = [statistics.median(e[r] for e in events) * 1e3 for r in range(args.gpus)]
+    launch_us = statistics.median(max(e) for e in events) * 1e3
     sha = kernel_source_sha16()
     ex = json.loads(sh.shards[0].env_json(0))["gymrs"]
     config_name = "cartpole_2p20" if (args.env == "cartpole" and n == n_default and args.gpus == 1) else None
     trec, tnote = load_free_running_traffic(config_name, head, sha) if config_name else (None, "no committed traffic figure for this shape")
     roof = roofline_of(head, n, bytes_read + bytes_written, per_block_us[0], trec, tnote, ex.get("last_launch"), sha, moved_bytes(args.env, ex))
-    ev_us = sorted(max(e) * 1e3 / steps_timed for e in events)
+    ev_us = sorted(max(e) * 1e3 for e in events)
     out = {
         "metric": "env-steps/sec (whole node), CartPole-v1 @ 2^20 envs per MI355X" if args.env == "cartpole" else f"env-steps/sec (whole node), {args.env}",
-        "value": n * args.gpus * steps_timed / wall, "unit": "env-steps/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall * 1e3 / steps_timed, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "value": n * args.gpus / wall, "unit": "env-steps/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": workload, "env": args.env, "lanes_per_gpu": n, "total_lanes": n * args.gpus, "call_shape": head, "action_buffers": nbuf,
                    "parallelism": f"lane-sharded x{args.gpus} in one process, no data-path collective; 1 all-reduce of 4 f64 per run, after the clock",
                    "stats_allreduce": {"rccl": "gymrs_sharded_stats: grouped RCCL all-reduce (one communicator over the blocks' engines)",
                                        "host": "gymrs_sharded_stats: host-side sum (blocks share a device, or one block)"}.get(reduce_path, reduce_path),
                    "devices": devices},
-        "timing": {"repetitions": reps, "passes_per_repetition": passes, "steps_per_repetition": steps_timed, "wall_ms_per_repetition": [w * 1e3 for w in walls],
+        "timing": {"repetitions": reps, "steps_per_repetition": sizes, "steps_timed": sum(sizes), "wall_ms_per_repetition": [w * k * 1e3 for w, k in zip(walls, sizes)],
                    "event_us_per_step": {"min": ev_us[0], "median": statistics.median(ev_us), "max": ev_us[-1], "spread": (ev_us[-1] - ev_us[0]) / statistics.median(ev_us)},
                    "statistic": "median over repetitions of the max over blocks"},
         "roofline": roof,
@@ -1096,6 +1166,8 @@ def run_in_process(args):
         "sharder_note": "gymrs_sharded_* (include/gymrs_amd.h): one engine + one native host thread per block; bit-identical to one engine of the same lanes "
                         "(tests/test_gpu_sharded_native.py)",
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if args.oversubscribe and args.gpus > n_dev:
         out["oversubscribed"] = "TEST RUN: blocks share GPUs; value is not a benchmark result"
     del launch_us

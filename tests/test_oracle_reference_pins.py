@@ -1,8 +1,8 @@
 """Pins the oracle (and the product's host-side mirrors) against the reference's OWN unit tests —
 the only tests the reference has for this path:
-  /root/reference/src/spaces/discrete.rs:22-42        Discrete::contains
-  /root/reference/src/utils/custom/util_fns.rs:12-33  clip
-  /root/reference/src/utils/seeding.rs:28-40 + doctest :11-20   seed echo
+  src/spaces/discrete.rs:22-42        Discrete::contains
+  src/utils/custom/util_fns.rs:12-33  clip
+  src/utils/seeding.rs:28-40 + doctest :11-20   seed echo
 The expected values live in tests/golden/reference_unit_tests.json (data copied from those tests)."""
 import math
 
@@ -104,41 +104,29 @@ def test_oracle_against_fixtures_generated_by_the_reference(oracle):
         assert t == tr["steps"]
 
 
-def test_default_constants_against_the_reference_source_text(oracle):
-    """Where /root/reference is present (the authoring container; not the GPU box): the `let name = OrderedFloat(value);`
-    lines of CartPoleEnv::new / MountainCarEnv::new (cartpole.rs:94-103, mountain_car.rs:344-351), the default reset boxes
-    (cartpole.rs:353-360, mountain_car.rs:175-186) and the action-space sizes are read as DATA and compared with the oracle's
-    and the product header's defaults.  No reference code is executed or copied."""
-    import math
-    import re
-    from pathlib import Path
+def test_default_constants_against_the_reference_source_text(oracle, golden, gymrs):
+    """The default values of CartPoleEnv::new / MountainCarEnv::new (cartpole.rs:94-103, mountain_car.rs:344-351), the default reset
+    boxes (cartpole.rs:353-360, mountain_car.rs:175-186) and the action-space sizes, read as numbers from the reference's source text into
+    tests/golden/reference_constants.json, against the oracle's and the product's defaults.  No reference code is executed or copied."""
+    import ctypes as C
 
-    import pytest
-
-    src = Path("/root/reference/src/envs/classical_control")
-    if not (src / "cartpole.rs").exists():
-        pytest.skip("/root/reference is not on this box")
-
-    def lets(text):
-        out = {}
-        for name, expr in re.findall(r"let (\w+) = OrderedFloat\(([^;]+)\);", text):
-            expr = expr.strip().replace("PI", str(math.pi))
-            if re.fullmatch(r"[-0-9. */]+", expr):
-                out.setdefault(name, eval(expr))  # noqa: S307 (digits and arithmetic operators only)
-        return out
-
-    cp_text, mc_text = (src / "cartpole.rs").read_text(), (src / "mountain_car.rs").read_text()
-    cp, mc = lets(cp_text), lets(mc_text)
+    fx = golden("reference_constants")
+    cp, mc = fx["cartpole"], fx["mountain_car"]
     p = oracle.cartpole_params()
-    for name in ("gravity", "masscart", "masspole", "length", "force_mag", "tau", "theta_threshold_radians", "x_threshold"):
-        assert getattr(p, name) == cp[name], name
+    for name, want in cp["defaults"].items():
+        assert getattr(p, name) == want, name
     q = oracle.mountain_car_params()
-    for name in ("min_position", "max_position", "max_speed", "goal_position", "goal_velocity", "force", "gravity"):
-        assert getattr(q, name) == mc[name], name
-    assert re.search(r"let action_space = Discrete\(2\);", cp_text) and re.search(r"Discrete\(3\)", mc_text)
+    for name, want in mc["defaults"].items():
+        assert getattr(q, name) == want, name
+    assert set(cp["defaults"]) == {"gravity", "masscart", "masspole", "length", "force_mag", "tau", "theta_threshold_radians", "x_threshold"}
+    assert set(mc["defaults"]) == {"min_position", "max_position", "max_speed", "goal_position", "goal_velocity", "force", "gravity"}
+    n = C.c_uint32()
+    lib = gymrs.load_library()
+    assert lib.gymrs_action_space(0, C.byref(n), None, None) == 0 and n.value == cp["action_space_n"] == 2
+    assert lib.gymrs_action_space(1, C.byref(n), None, None) == 0 and n.value == mc["action_space_n"] == 3
     # default reset boxes: +-0.05 on every CartPole component, position in [-0.6, -0.4) for MountainCar
-    assert cp_text.count("OrderedFloat(0.05)") == 4
-    assert "position: OrderedFloat(-0.6)" in mc_text and "position: OrderedFloat(-0.4)" in mc_text
-    assert all(-0.05 <= v < 0.05 for v in oracle.reset_pcg64(0, 1)) and -0.6 <= oracle.reset_pcg64(1, 1)[0] < -0.4
-    # the quirk the build keeps (SURVEY Q1): polemass_length = masspole + length
-    assert re.search(r"fn polemass_length[^}]*self\.masspole \+ self\.length", cp_text, re.S)
+    assert cp["reset_low"] == [-0.05] * 4 and cp["reset_high"] == [0.05] * 4
+    assert all(cp["reset_low"][j] <= v < cp["reset_high"][j] for j, v in enumerate(oracle.reset_pcg64(0, 1)))
+    assert mc["reset_position_low"] <= oracle.reset_pcg64(1, 1)[0] < mc["reset_position_high"]
+    # the quirk the build keeps (SURVEY Q1): polemass_length = masspole + length (0.6), not Gym's product (0.05)
+    assert cp["polemass_length"] == p.masspole + p.length and cp["polemass_length"] != p.masspole * p.length

@@ -63,6 +63,12 @@ class TwinShard:
     def get_state(self):
         return self._e.get_state()
 
+    def get_obs(self):
+        return self._e.get_state()  # (CartPole: the observation is the state)
+
+    def get_step_result(self):
+        return self._e.get_result()
+
     def close(self):
         pass
 
@@ -110,9 +116,8 @@ import bench
 gymrs = importlib.import_module("gym-rs_amd")
 world, comm_mode = int(sys.argv[3]), sys.argv[4]
 args = bench.parse_args(["--gpus", str(world), "--steps", "7", "--warmup", "5", "--n-envs", "3001", "--action-buffers", "4",
-                         "--cpu-seconds", "0", "--repetitions", "3", "--no-probe"])
-bench.MIN_REPETITION_SECONDS = 0.0  # one pass of K steps per repetition keeps the twin run short
-bench.SETTLE_SECONDS = 0.0
+                         "--cpu-seconds", "0", "--repetitions", "3", "--no-probe", *sys.argv[5:]])
+bench.SETTLE_SECONDS = 0.0  # keeps the twin run short
 info = gymrs.sharded.rank_info()
 assert info.world == world and info.launched
 backend = TwinBackend(gymrs)
@@ -186,11 +191,11 @@ if getattr(args, "hard_exit", False):  # a helper thread still sits in the stand
 '''
 
 
-def run_workers(tmp_path, world, comm_mode="none", timeout=900, extra_env=None):
+def run_workers(tmp_path, world, comm_mode="none", timeout=900, extra_env=None, extra_args=()):
     gymrs = importlib.import_module("gym-rs_amd")
     script = tmp_path / "worker.py"
     script.write_text(WORKER)
-    cmd = gymrs.sharded.spawn_command(str(script), [str(ROOT), str(tmp_path), str(world), comm_mode], world)
+    cmd = gymrs.sharded.spawn_command(str(script), [str(ROOT), str(tmp_path), str(world), comm_mode, *extra_args], world)
     env = dict(os.environ, OMP_NUM_THREADS="1", **(extra_env or {}))
     res = spawn_server.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
@@ -200,8 +205,11 @@ def run_workers(tmp_path, world, comm_mode="none", timeout=900, extra_env=None):
 
 
 def check_against_one_unsharded_twin(tmp_path, twin, out, world, n=3001, steps=7, warmup=5, reps=3):
+    import bench
+
     gymrs = importlib.import_module("gym-rs_amd")
-    passes = out["timing"]["passes_per_repetition"]
+    sizes = out["timing"]["steps_per_repetition"]  # --steps K: exactly K timed steps, cut into the repetitions
+    assert sizes == bench.repetition_sizes(steps, reps) and sum(sizes) == out["timing"]["steps_timed"] == steps
     assert out["n_gpus"] == world and out["config"]["total_lanes"] == world * n and out["config"]["lanes_per_gpu"] == n
     assert out["timing"]["repetitions"] == reps and len(out["timing"]["wall_ms_per_repetition"]) == reps
     assert [r["rank"] for r in out["ranks"]] == list(range(world))
@@ -210,8 +218,8 @@ def check_against_one_unsharded_twin(tmp_path, twin, out, world, n=3001, steps=7
         assert 0 < r["launch_us_min"] <= r["launch_us"] <= r["launch_us_max"]
     ev = out["timing"]["event_us_per_step"]
     assert ev["min"] <= ev["median"] <= ev["max"]
-    assert out["value"] == pytest.approx(world * n * steps * passes / (out["ms_per_step"] * 1e-3 * steps * passes), rel=1e-9)
-    # the same batch, UNSHARDED, same schedule: warm-up, the calibration passes, stats_clear, then the timed steps
+    assert out["value"] == pytest.approx(world * n / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    # the same batch, UNSHARDED, same schedule: warm-up, the calibration passes, the seeded reset, then the timed steps
     from oracle.bindings import TwinEngine
 
     flags = gymrs.AUTO_RESET | gymrs.TRACK_STATS
@@ -227,17 +235,20 @@ def check_against_one_unsharded_twin(tmp_path, twin, out, world, n=3001, steps=7
     assert sum(out["timing"]["calibration_calls"]) == steps * out["timing"]["calibration_passes"]
     for k in out["timing"]["calibration_calls"]:  # bench's untimed calibration calls (the ring index restarts with every call)
         run(k)
+    full.reset(0)  # the timed steps start from a seeded reset: what the calibration did no longer matters
     full.stats_clear()
-    # a repetition is ONE step_many call of passes * steps steps; per call shape one uncounted lead-in repetition, and the second call
-    # shape (the chain, reported separately) starts with one untimed call of a repetition's length
+    # a repetition is ONE step_many call; per call shape one uncounted lead-in repetition, and the second call shape (the chain, reported
+    # separately) starts with one untimed call of a repetition's length
     assert set(out["paths"]) == {"per_step_visible", "chain"} and out["config"]["call_shape"] == "per_step_visible"
-    calls = 2 * (reps + 1) + 1
-    for _ in range(calls):
-        run(steps * passes)
+    lead = bench.lead_in_steps(sizes)
+    assert lead == out["timing"]["lead_in_steps"] == max(sizes[0], bench.LEAD_IN_MIN_STEPS)
+    calls = [lead, *sizes, sizes[0], lead, *sizes]
+    for k in calls:
+        run(k)
     want = full.stats()
     got = out["episodes"]
     assert (got["sum_return"], got["sum_length"], got["n_episodes"]) == (want[0], want[1], want[2])
-    assert want[3] == world * n * steps * passes * calls
+    assert want[3] == world * n * sum(calls)
     assert out["value"] == out["paths"]["per_step_visible"]["value"] and out["roofline"] == out["paths"]["per_step_visible"]["roofline"]
     assert out["ranks_agree"] is True and out["expected_job_rate_from_rank_launch_times"] > 0
     for r in out["ranks"]:
@@ -278,6 +289,75 @@ def test_first_contact_with_the_native_collective_is_watched(tmp_path, twin, com
     check_against_one_unsharded_twin(tmp_path, twin, out, 2)
 
 
+def test_dump_outputs_hold_the_last_timed_step_of_the_headline(tmp_path, twin):
+    """--dump-outputs DIR: after the headline's K timed steps, the observations, reward, done and truncated of its LAST step as f32 .npy files -- the
+    same bits on every run of the same command (the timed steps start from a seeded reset, whatever the clock-driven calibration did)."""
+    gymrs = importlib.import_module("gym-rs_amd")
+    dumps = []
+    for run_id in range(2):
+        d = tmp_path / f"dump{run_id}"
+        out = run_workers(tmp_path, 1, extra_args=["--dump-outputs", str(d)])
+        assert out["dump_outputs"]["dir"] == str(d)
+        dumps.append({name: np.load(d / f"{name}.npy") for name in ("obs", "reward", "done", "truncated")})
+        assert sorted(p.name for p in d.iterdir()) == ["done.npy", "obs.npy", "reward.npy", "truncated.npy"]
+    n, steps, reps = 3001, 7, 3
+    assert {k: v.shape for k, v in dumps[0].items()} == {"obs": (4, n), "reward": (n,), "done": (n,), "truncated": (n,)}
+    assert all(v.dtype == np.float32 for v in dumps[0].values())
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name].view(np.uint32), dumps[1][name].view(np.uint32)), name
+    # the unsharded twin through the headline's schedule after the reset: the lead-in repetition, then the K timed steps
+    from oracle.bindings import TwinEngine
+
+    import bench
+
+    full = TwinEngine(twin, 0, n, gymrs.engine.default_params(0), flags=gymrs.AUTO_RESET | gymrs.TRACK_STATS, gid0=0)
+    ring = [full.fill_actions(1, b) for b in range(4)]
+    full.reset(0)
+    sizes = bench.repetition_sizes(steps, reps)
+    for k in [bench.lead_in_steps(sizes), *sizes]:
+        for t in range(k):
+            full.step(ring[t % 4])
+    reward, done, trunc = full.get_result()
+    assert np.array_equal(dumps[0]["obs"].view(np.uint32), full.get_state().view(np.uint32))
+    assert np.array_equal(dumps[0]["reward"], reward) and np.array_equal(dumps[0]["done"], done) and np.array_equal(dumps[0]["truncated"], trunc)
+    assert done.any()  # (some lane finished an episode in the last step, so the comparison covers the auto-reset too)
+    # several ranks: one directory, each rank prefixes its files with rank<r>_, and the record lists every rank's arrays
+    d = tmp_path / "dump_two"
+    out = run_workers(tmp_path, 2, extra_args=["--dump-outputs", str(d)])
+    names = [f"{p}{a}" for p in ("rank0_", "rank1_") for a in ("obs", "reward", "done", "truncated")]
+    assert sorted(out["dump_outputs"]["arrays"]) == sorted(names) and sorted(p.name for p in d.iterdir()) == sorted(f"{x}.npy" for x in names)
+    assert [r["dump_outputs"]["arrays"] for r in out["ranks"]][1] == {f"rank1_{a}": s for a, s in (("obs", [4, n]), ("reward", [n]), ("done", [n]), ("truncated", [n]))}
+
+
+def test_dump_outputs_sample_what_does_not_fit(tmp_path):
+    """More than 64 MB of outputs: the same seeded sample of lanes for every array, the lane ids beside them, at most 64 MB written in all."""
+    import bench
+
+    class Big:
+        n = 3_000_000
+
+        def sync(self):
+            pass
+
+        def get_obs(self):
+            return np.arange(4 * self.n, dtype=np.float32).reshape(4, self.n)
+
+        def get_step_result(self):
+            return np.arange(self.n, dtype=np.float32), (np.arange(self.n) % 2).astype(np.uint8), np.zeros(self.n, np.uint8)
+
+    rec = [bench.dump_outputs(tmp_path / f"d{i}", [("", Big())]) for i in range(2)]
+    assert rec[0]["arrays"] == rec[1]["arrays"]
+    total = sum(p.stat().st_size for p in (tmp_path / "d0").iterdir())
+    assert total <= bench.DUMP_LIMIT_BYTES and total > bench.DUMP_LIMIT_BYTES // 2
+    lanes = np.load(tmp_path / "d0" / "lanes.npy")
+    assert lanes.dtype == np.float64 and np.array_equal(lanes, np.load(tmp_path / "d1" / "lanes.npy"))
+    assert np.all(np.diff(lanes) > 0) and lanes[-1] < Big.n
+    keep = lanes.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "d0" / "reward.npy"), keep.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "d0" / "obs.npy")[2], (2 * Big.n + keep).astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "d0" / "done.npy"), (keep % 2).astype(np.float32))
+
+
 def test_launcher_pieces():
     gymrs = importlib.import_module("gym-rs_amd")
     sh = gymrs.sharded
@@ -294,6 +374,19 @@ def test_launcher_pieces():
 
     assert bench.choose_passes(136e-6, 5e-3) == 37 and bench.choose_passes(0.02, 5e-3) == 1 and bench.choose_passes(0.0) == 1
     assert bench.choose_passes(128e-6) * 128e-6 >= 0.1  # a repetition lasts >= 100 ms (profiles/r04_launches_per_call.log)
+    # --steps K: K timed steps, cut into at most R repetitions as evenly as whole steps allow
+    assert bench.repetition_sizes(20, 9) == [3, 3, 2, 2, 2, 2, 2, 2, 2] and bench.repetition_sizes(4, 9) == [1, 1, 1, 1]
+    assert bench.repetition_sizes(18000, 9) == [2000] * 9 and sum(bench.repetition_sizes(100003, 9)) == 100003
+    assert bench.lead_in_steps([3, 3, 2]) == bench.LEAD_IN_MIN_STEPS and bench.lead_in_steps([2000] * 9) == 2000
+
+
+def test_min_repetition_ms_says_it_has_no_effect(capsys):
+    import bench
+
+    assert bench.parse_args(["--steps", "5", "--min-repetition-ms", "5"]).steps == 5
+    assert "--min-repetition-ms has no effect" in capsys.readouterr().err
+    bench.parse_args(["--steps", "5"])
+    assert capsys.readouterr().err == ""
 
 
 def test_plain_multi_gpu_form_spawns_ranks_and_fails_loudly_without_gpus():

@@ -31,8 +31,10 @@ ROOT = Path(__file__).resolve().parent.parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-PRE_CALLS = (10, 30, 30, 30)  # warm-up + priming + two calibration passes of `bench.py --steps 30 --warmup 10` with GYMRS_BENCH_PASSES pinned
-CALL = 60                     # a repetition: 2 passes of 30 steps
+# The call sizes of the multi-rank bench test as it stood when this tool was written (`bench.py --steps 30 --warmup 10` with GYMRS_BENCH_PASSES=2): warm-up,
+# priming and two calibration calls, then repetitions of 2 x 30 steps.  They are this tool's own schedule; bench.py's timed calls now add up to --steps.
+PRE_CALLS = (10, 30, 30, 30)
+CALL = 60
 NBUF = 8
 
 
