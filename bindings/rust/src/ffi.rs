@@ -23,6 +23,8 @@ pub const GYMRS_PENDULUM: c_int = 2;
 pub const GYMRS_AUTO_RESET: u32 = 1;
 pub const GYMRS_TRACK_STATS: u32 = 2;
 pub const GYMRS_TIME_LIMIT: u32 = 4;
+/// keep the observation an episode ended in (needs GYMRS_AUTO_RESET): gymrs_final_obs_ptrs / gymrs_get_final_obs
+pub const GYMRS_FINAL_OBS: u32 = 8;
 
 /// `gymrs_cartpole_params`: the pub physics fields of `CartPoleEnv` (cartpole.rs:53-82), f64 like the reference.
 #[repr(C)]
@@ -107,6 +109,8 @@ extern "C" {
     pub fn gymrs_rollout_record(e: *mut GymrsEngine, n_steps: u32, action_seed: u64, action_t0: u64, out: *const Trajectory) -> c_int;
     pub fn gymrs_sync(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_get_state(e: *mut GymrsEngine, first: u64, count: u64, host_out: *mut f32) -> c_int;
+    pub fn gymrs_final_obs_ptrs(e: *mut GymrsEngine, out_ptrs: *mut *mut f32, obs_dim: *mut c_int) -> c_int;
+    pub fn gymrs_get_final_obs(e: *mut GymrsEngine, first: u64, count: u64, host_out: *mut f32) -> c_int;
     pub fn gymrs_set_state(e: *mut GymrsEngine, first: u64, count: u64, host_in: *const f32) -> c_int;
     pub fn gymrs_get_step_result(
         e: *mut GymrsEngine,

@@ -17,6 +17,7 @@ from .core import ActionReward, RewardRange
 from .spaces import BoxR, Discrete
 from .engine import (
     AUTO_RESET,
+    FINAL_OBS,
     TIME_LIMIT,
     TRACK_STATS,
     CARTPOLE,
@@ -48,6 +49,6 @@ __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
     "CartPoleParams", "MountainCarParams", "PendulumParams", "CartPoleEnv", "MountainCarEnv", "PendulumEnv",
     "CartPoleObservation", "MountainCarObservation", "PendulumObservation", "RenderMode",
-    "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
+    "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "FINAL_OBS", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json",
 ]

@@ -38,7 +38,9 @@ SIGNATURES = {
     "gymrs_reward_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "gymrs_done_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "gymrs_truncated_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gymrs_final_obs_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "gymrs_get_obs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gymrs_get_final_obs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_get_state": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_set_state": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_get_step_result": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -80,6 +80,7 @@ static StepArgs step_args(const gymrs_engine* e, const void* actions)
     a.truncated = e->truncated;
     a.beyond = e->beyond;
     a.ep_start = e->ep_start;
+    if (e->final_obs) a.final_obs = e->final_obs; // (GYMRS_FINAL_OBS needs auto-reset: no launch of such an engine reads `beyond`)
     a.wave_open = e->wave_open;
     a.wave_clean = e->wave_clean;
     a.block_stats = e->block_stats;
@@ -537,10 +538,12 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
     if (gymrs_status st = check_params(kind, params, "gymrs_engine_create")) return st;
     if (n_envs == 0) return fail(GYMRS_EINVAL, "gymrs_engine_create: n_envs must be > 0");
     if (n_envs > (1ull << 32)) return fail(GYMRS_EINVAL, "gymrs_engine_create: n_envs must be <= 2^32 per engine");
-    if (flags & ~(uint32_t)(GYMRS_AUTO_RESET | GYMRS_TRACK_STATS | GYMRS_TIME_LIMIT))
+    if (flags & ~(uint32_t)(GYMRS_AUTO_RESET | GYMRS_TRACK_STATS | GYMRS_TIME_LIMIT | GYMRS_FINAL_OBS))
         return fail(GYMRS_EINVAL, "gymrs_engine_create: unknown flag bits");
     if ((flags & GYMRS_TRACK_STATS) && !(flags & GYMRS_AUTO_RESET))
         return fail(GYMRS_EINVAL, "gymrs_engine_create: GYMRS_TRACK_STATS needs GYMRS_AUTO_RESET");
+    if ((flags & GYMRS_FINAL_OBS) && !(flags & GYMRS_AUTO_RESET))
+        return fail(GYMRS_EINVAL, "gymrs_engine_create: GYMRS_FINAL_OBS needs GYMRS_AUTO_RESET");
     int n_dev = 0;
     hipError_t derr = hipGetDeviceCount(&n_dev);
     if (derr != hipSuccess || n_dev <= 0)
@@ -633,6 +636,8 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
         }
         const size_t at_reward = place(npad * 4), at_done = place(npad), at_trunc = place(npad), at_beyond = place(npad),
                      at_start = place(npad * 4);
+        // GYMRS_FINAL_OBS: placed last, so that every other array lies where it lies without the flag
+        const size_t at_final = (flags & GYMRS_FINAL_OBS) ? place((size_t)final_obs_stride(n_envs) * 4 * e->obs_dim) : 0;
         void* pool = nullptr;
         hipError_t perr;
         if (n_envs <= kHostPoolMaxLanes) {
@@ -665,6 +670,7 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
         e->truncated = reinterpret_cast<uint8_t*>(b + at_trunc);
         e->beyond = reinterpret_cast<uint8_t*>(b + at_beyond);
         e->ep_start = reinterpret_cast<uint32_t*>(b + at_start);
+        if (flags & GYMRS_FINAL_OBS) e->final_obs = reinterpret_cast<float*>(b + at_final);
     }
     // one statistics slot per wavefront: most waves at 4 lanes per work-item (256 lanes per wave), rounded up to whole
     // workgroups of up to 16 waves
@@ -855,6 +861,7 @@ static gymrs_status reset_lanes(gymrs_engine* e, uint64_t seed, const float* lo,
         std::memcpy(a.pcg_scale, pcg->scale, sizeof(a.pcg_scale));
     }
     HIP_TRY(launch_reset(e->kind, a, e->stream));
+    if (e->final_obs) HIP_TRY(hipMemsetAsync(e->final_obs, 0, (size_t)final_obs_stride(e->n) * 4 * e->obs_dim, e->stream)); // no episode has ended yet
     e->tick += 1;
     e->uniform_start = e->tick;
     e->epoch = (uint32_t)e->tick; // what reset_kernel wrote into ep_start
@@ -1119,7 +1126,7 @@ static gymrs_status build_graph(gymrs_engine* e, const char* base, uint64_t stri
 
 // ---- chains of per-step launches through the engine's own AQL dispatcher (gymrs_aql.h) ---------------------------------
 // Which launches it takes: every flag set at 4 lanes per work-item (what the stand-alone code object holds, gymrs_step_aql.hip), on
-// engines whose arrays live in device memory; chains of at least kAqlMinChain steps (a chain costs three small packets and two
+// engines whose arrays live in device memory and that were created without GYMRS_FINAL_OBS (no chain kernel has that bit); chains of at least kAqlMinChain steps (a chain costs three small packets and two
 // stream operations of its own).  Everything else -- and every device on which the dispatcher's self-check fails -- goes
 // through HIP launches.
 constexpr uint32_t kAqlMinChain = 8;
@@ -1158,6 +1165,7 @@ static uint32_t chain_hint_bits(const gymrs_engine* e)
 static bool aql_usable(gymrs_engine* e, uint32_t n_steps)
 {
     if (n_steps < kAqlMinChain || e->vec != 4 || e->pool_host) return false;
+    if (e->flags & GYMRS_FINAL_OBS) return false; // the chain's code object holds no final-observation kernels: HIP launches
     if (!aql_enabled_by_env()) return false;
     if (!e->own_stream) { // a caller-provided stream may be under a capture: a chain cannot be captured
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1384,7 +1392,7 @@ gymrs_status gymrs_step_many(gymrs_engine* e, const void* actions_dev, uint64_t 
         if (gymrs_status st = flags_for_step(e, &flags)) return st;
         StepArgs a = step_args(e, base + (size_t)(t % n_buffers) * stride_bytes);
         if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return st;
-        if (e->dev_hooks & 8u) // (developer experiment: the chain's binary through HIP's queue)
+        if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS)) // (developer experiment: the chain's binary through HIP's queue)
             HIP_TRY(launch_step_through_hip_module(e, flags, a));
         else
             HIP_TRY(launch_step(e->kind, e->vec, flags, a, consts_ptr(e), e->stream));

@@ -28,6 +28,15 @@ gymrs_status gymrs_obs_ptrs(gymrs_engine* e, float** out_ptrs, int* obs_dim)
     return GYMRS_OK;
 }
 
+gymrs_status gymrs_final_obs_ptrs(gymrs_engine* e, float** out_ptrs, int* obs_dim)
+{
+    if (!e || !out_ptrs || !obs_dim) return fail(GYMRS_EINVAL, "gymrs_final_obs_ptrs: NULL argument");
+    if (!e->final_obs) return fail(GYMRS_EINVAL, "gymrs_final_obs_ptrs: the engine was created without GYMRS_FINAL_OBS");
+    for (int j = 0; j < e->obs_dim; ++j) out_ptrs[j] = e->final_obs + (size_t)j * final_obs_stride(e->n);
+    *obs_dim = e->obs_dim;
+    return GYMRS_OK;
+}
+
 gymrs_status gymrs_state_ptrs(gymrs_engine* e, float** out_ptrs, int* state_dim)
 {
     if (!e || !out_ptrs || !state_dim) return fail(GYMRS_EINVAL, "gymrs_state_ptrs: NULL argument");
@@ -72,6 +81,25 @@ gymrs_status gymrs_get_obs(gymrs_engine* e, uint64_t first, uint64_t count, floa
     int dim = 0;
     gymrs_obs_ptrs(e, ptrs, &dim);
     if (e->pool_host) { // small engine: the arrays ARE host memory (no copy-engine command on the single-env mirror path)
+        if (gymrs_status st_ = stream_sync_checked(e)) return st_;
+        for (int j = 0; j < dim; ++j) std::memcpy(host_out + (size_t)j * count, host_of(e, ptrs[j]) + first, count * sizeof(float));
+        return GYMRS_OK;
+    }
+    for (int j = 0; j < dim; ++j)
+        HIP_TRY(hipMemcpyAsync(host_out + (size_t)j * count, ptrs[j] + first, count * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (gymrs_status st_ = stream_sync_checked(e)) return st_;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_final_obs(gymrs_engine* e, uint64_t first, uint64_t count, float* host_out)
+{
+    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_final_obs: NULL argument");
+    float* ptrs[4];
+    int dim = 0;
+    if (gymrs_status st = gymrs_final_obs_ptrs(e, ptrs, &dim)) return st;
+    if (gymrs_status st = range_check(e, first, count, "gymrs_get_final_obs")) return st;
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->pool_host) {
         if (gymrs_status st_ = stream_sync_checked(e)) return st_;
         for (int j = 0; j < dim; ++j) std::memcpy(host_out + (size_t)j * count, host_of(e, ptrs[j]) + first, count * sizeof(float));
         return GYMRS_OK;
@@ -189,6 +217,9 @@ std::vector<Segment> snapshot_segments(const gymrs_engine* e)
     v.push_back({e->wave_open, (size_t)e->n_stat_blocks * sizeof(double)});
     v.push_back({e->stats_base, (size_t)kStatsBaseWords * sizeof(unsigned long long)});
     v.push_back({e->err, 2 * sizeof(uint32_t)});
+    // GYMRS_FINAL_OBS only (appended: the blob of an engine without the flag is what it was before the flag existed)
+    if (e->final_obs)
+        for (int j = 0; j < e->obs_dim; ++j) v.push_back({e->final_obs + (size_t)j * final_obs_stride(e->n), n * 4});
     return v;
 }
 size_t consts_size(gymrs_env_kind k)

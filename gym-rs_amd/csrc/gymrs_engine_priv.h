@@ -83,6 +83,7 @@ struct gymrs_engine {
     uint8_t* truncated = nullptr;
     uint8_t* beyond = nullptr;
     uint32_t* ep_start = nullptr;
+    float* final_obs = nullptr; // GYMRS_FINAL_OBS: obs_dim rows of final_obs_stride(n) lanes (StepArgs::final_obs), else NULL
     uint32_t* wave_clean = nullptr; // per-wavefront: its part of `reward` holds the env's constant reward (see step_block)
     int clean_shape = 0;           // lanes per workgroup row the flags were written with (vec * threads); 0 = all clear
     bool elide_reward = false;     // CartPole with GYMRS_AUTO_RESET from kElideRewardFromBytes per step on: the constant reward store is elided like MountainCar's

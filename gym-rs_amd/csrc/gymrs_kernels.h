@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "gymrs_physics.h"
 
 namespace gymrs {
@@ -34,7 +36,14 @@ struct StepArgs {
     float* reward;
     uint8_t* done;
     uint8_t* truncated; // written only with GYMRS_TIME_LIMIT
-    uint8_t* beyond;    // CartPole without auto-reset: steps_beyond_terminated.is_some()
+    // CartPole without auto-reset: steps_beyond_terminated.is_some().  The same slot carries, for the GYMRS_FINAL_OBS
+    // instantiations (auto-reset on, so `beyond` is never read there), the base of the final-observation arrays: obs_dim rows
+    // of final_obs_stride(n) lanes (TileRegs::FINAL, advance_tile).  A union and not a new member: every launch's kernel
+    // arguments keep their layout (KernArgView::fetch and the AQL dispatcher address them by offset).
+    union {
+        uint8_t* beyond;
+        float* final_obs;
+    };
     uint32_t* ep_start; // tick at which the lane's current episode started (low 32 bits)
     uint32_t* wave_clean; // [n_waves] constant-reward envs under auto-reset that elide the reward store: != 0 = the wave's part of `reward` holds the constant
     double* wave_open;  // [n_waves] Pendulum with GYMRS_TRACK_STATS: per-wavefront sum of the rewards of the open episodes
@@ -76,6 +85,11 @@ struct StepArgs {
     uint32_t trace_wpb; // wavefronts per workgroup of this launch (the stamps' index; blockDim would be a hidden kernel argument, which
                         // the engine's own dispatcher does not supply)
 };
+
+static_assert(offsetof(StepArgs, final_obs) == offsetof(StepArgs, beyond) && sizeof(float*) == sizeof(uint8_t*) && sizeof(StepArgs) == 296,
+              "GYMRS_FINAL_OBS shares the slot of `beyond`: the layout of StepArgs must not move");
+// Lanes between two rows of the final-observation arrays: n rounded up to 16, so that every row starts aligned for a vector store.
+__host__ __device__ inline uint64_t final_obs_stride(uint64_t n) { return (n + 15) & ~15ull; }
 
 // The kernel-argument segment of step_kernel as the host sees it (the engine's own AQL dispatcher, gymrs_aql.h, fills it by
 // hand; HIP launches marshal the same thing themselves): the parameters in order, naturally aligned.

@@ -137,15 +137,19 @@ static hipError_t rollout_one(const StepArgs& a, const RolloutArgs& r, const voi
 template <class Env, int VEC>
 static hipError_t rollout_flags(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, hipStream_t stream)
 {
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT;
-    if (!(flags & A)) flags &= ~S;
-    switch (flags & (A | S | T)) {
+    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
+    if (!(flags & A)) flags &= ~(S | F);
+    switch (flags & (A | S | T | F)) {
     case 0: return rollout_one<Env, VEC, 0>(a, r, consts, stream);
     case A: return rollout_one<Env, VEC, A>(a, r, consts, stream);
     case A | S: return rollout_one<Env, VEC, A | S>(a, r, consts, stream);
     case T: return rollout_one<Env, VEC, T>(a, r, consts, stream);
     case A | T: return rollout_one<Env, VEC, A | T>(a, r, consts, stream);
     case A | S | T: return rollout_one<Env, VEC, A | S | T>(a, r, consts, stream);
+    case A | F: return rollout_one<Env, VEC, A | F>(a, r, consts, stream);
+    case A | S | F: return rollout_one<Env, VEC, A | S | F>(a, r, consts, stream);
+    case A | T | F: return rollout_one<Env, VEC, A | T | F>(a, r, consts, stream);
+    case A | S | T | F: return rollout_one<Env, VEC, A | S | T | F>(a, r, consts, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -342,9 +342,9 @@ static hipError_t launch_one(const StepArgs& a, const void* consts, hipStream_t 
 template <class Env, int VEC, uint32_t NTBIT>
 static hipError_t launch_flags_nt(uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream)
 {
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT;
-    if (!(flags & A)) flags &= ~S; // statistics need auto-reset
-    switch (flags & (A | S | T)) {
+    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
+    if (!(flags & A)) flags &= ~(S | F); // statistics and final observations need auto-reset
+    switch (flags & (A | S | T | F)) {
 #ifdef GYMRS_DEV_MINIMAL // developer builds (tools/devbuild.py): only the headline flag sets, seconds instead of minutes
     case A | S: return launch_one<Env, VEC, A | S | NTBIT>(a, consts, stream);
     case A | S | T: return launch_one<Env, VEC, A | S | T | NTBIT>(a, consts, stream);
@@ -356,6 +356,10 @@ static hipError_t launch_flags_nt(uint32_t flags, const StepArgs& a, const void*
     case T: return launch_one<Env, VEC, T | NTBIT>(a, consts, stream);
     case A | T: return launch_one<Env, VEC, A | T | NTBIT>(a, consts, stream);
     case A | S | T: return launch_one<Env, VEC, A | S | T | NTBIT>(a, consts, stream);
+    case A | F: return launch_one<Env, VEC, A | F | NTBIT>(a, consts, stream);
+    case A | S | F: return launch_one<Env, VEC, A | S | F | NTBIT>(a, consts, stream);
+    case A | T | F: return launch_one<Env, VEC, A | T | F | NTBIT>(a, consts, stream);
+    case A | S | T | F: return launch_one<Env, VEC, A | S | T | F | NTBIT>(a, consts, stream);
     default: return hipErrorInvalidValue;
 #endif
     }

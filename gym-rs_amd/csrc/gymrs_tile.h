@@ -110,6 +110,25 @@ __device__ __forceinline__ void store_vec(T* __restrict__ p, uint64_t base, uint
     }
 }
 
+// Pendulum's observed (cos, sin) of the VEC angles of a work-item: the branch-free short-range form when every angle of the
+// wave is in its range, else the general one (the same bits either way; the choice only saves time).  This is the choice
+// store_tile spells out inline for obs_cos / obs_sin (kept there as it is: routed through this function the existing
+// Pendulum kernels come out with an inverted branch, i.e. different machine code); the final-observation stores use it.
+template <int VEC>
+__device__ __forceinline__ void obs_sincos(const Vec<float, VEC>& theta, Vec<float, VEC>& oc, Vec<float, VEC>& os)
+{
+    bool med = true;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) med = med && in_short_range(theta.v[k]);
+    if (__all(med)) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) sincos_short(theta.v[k], &os.v[k], &oc.v[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) sincosf_(theta.v[k], &os.v[k], &oc.v[k]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Env policies: what differs between the three env types.
 struct CartPoleT {
@@ -230,6 +249,10 @@ struct TileRegs {
     static constexpr bool AUTO = (FLAGS & GYMRS_AUTO_RESET) != 0;
     static constexpr bool STATS = AUTO && (FLAGS & GYMRS_TRACK_STATS) != 0;
     static constexpr bool TLIM = (FLAGS & GYMRS_TIME_LIMIT) != 0;
+    // GYMRS_FINAL_OBS: a re-armed lane's pre-reset observation goes to StepArgs::final_obs (advance_tile).  Only instantiations
+    // with this bit contain any of that code; every other one compiles to what it did before the flag existed.
+    static constexpr bool FINAL = AUTO && (FLAGS & GYMRS_FINAL_OBS) != 0;
+    static_assert(!FINAL || !(Env::kHasBeyond && !AUTO), "StepArgs::final_obs shares the slot of `beyond`: no FINAL kernel may read beyond");
     static constexpr bool NT = (FLAGS & kFlagNonTemporal) != 0;
     // Which accesses carry the hint when the launch asks for it.  The state arrays are the only ones the NEXT step reads
     // again; actions are read once, rewards / flags / Pendulum's (cos, sin) are written and never read by a step.
@@ -334,6 +357,54 @@ struct StepOut {
     bool reward_is_const; // wave-uniform: every stepped lane of the wave earned Env::kReward (constant-reward envs)
     unsigned long long masks[VEC]; // wave-uniform: bit i of masks[k] = work-item i re-armed its lane k in this step
 };
+
+// GYMRS_FINAL_OBS: the observation the finished lanes of a work-item show BEFORE their re-arm (`ls`, after the physics) goes to
+// row j of StepArgs::final_obs at lane base + k, for the lanes with need_reset[k] only.  Rows of other lanes keep what they hold.
+//   * CartPole / MountainCar: the observation is the state; one scattered dword store per row and finished lane (about 1 lane in
+//     22 of a random CartPole policy; a wave without one never gets here).
+//   * Pendulum never terminates: its lanes finish together, at the time limit, so a full tile stores dense vectors (once per
+//     episode).  (cos, sin) of the pre-reset angle come from obs_sincos, the choice store_tile makes: the bits a step without
+//     auto-reset would have stored in obs_cos / obs_sin.
+template <class Env, int VEC, uint32_t FLAGS, bool FULL>
+__device__ __forceinline__ void store_final_obs(const StepArgs& a, uint64_t base, const float (&ls)[Env::kState][VEC], const bool (&need_reset)[VEC])
+{
+    using R = TileRegs<Env, VEC, FLAGS>;
+    static_assert(R::FINAL, "final-observation stores belong to GYMRS_FINAL_OBS instantiations only");
+    const uint64_t stride = final_obs_stride(a.n);
+    float* const fo = a.final_obs;
+    if constexpr (Env::kHasObsExtra) {
+        static_assert(Env::kNeverTerminates && Env::kState == 2, "the obs_extra env is Pendulum: (cos, sin, theta_dot), one shared episode clock");
+        Vec<float, VEC> th, td, oc, os;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            th.v[k] = ls[0][k];
+            td.v[k] = ls[1][k];
+        }
+        obs_sincos<VEC>(th, oc, os);
+        if (FULL) { // every lane of a full tile was stepped, and all of them reached the shared time limit
+            store_vec<float, VEC, R::POL_O>(fo, base, a.n, true, oc);
+            store_vec<float, VEC, R::POL_O>(fo + stride, base, a.n, true, os);
+            store_vec<float, VEC, R::POL_O>(fo + 2 * stride, base, a.n, true, td);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                if (need_reset[k]) {
+                    fo[base + k] = oc.v[k];
+                    fo[stride + base + k] = os.v[k];
+                    fo[2 * stride + base + k] = td.v[k];
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            if (need_reset[k]) {
+#pragma unroll
+                for (int j = 0; j < Env::kState; ++j) fo[(uint64_t)j * stride + base + k] = ls[j][k];
+            }
+        }
+    }
+}
 
 // One Env::step() of a tile held in registers: physics + auto-reset of the finished lanes.  The per-step
 // kernel calls it once between load_tile and store_tile; the fused rollout kernel calls it in a loop.
@@ -482,6 +553,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
             total += (uint32_t)__popcll(m);
         }
         if (total != 0) { // quiet waves (MountainCar / Pendulum: nearly all) skip everything below
+            if constexpr (R::FINAL) store_final_obs<Env, VEC, FLAGS, FULL>(a, base, ls, need_reset);
             if (LOGGED && a.fold_step == 0 && lane == 0) {
                 // The whole episode bookkeeping of this step for the wave's 64 * VEC lanes: 8 * VEC contiguous bytes.  (Measured at
                 // 2^20 CartPole lanes: the scattered ep_start stores cost 0.45 us per launch -- ~47k partial cache lines -- and the

@@ -15,7 +15,7 @@ import numpy as np
 from ._lib import load_library
 
 CARTPOLE, MOUNTAIN_CAR, PENDULUM = 0, 1, 2
-AUTO_RESET, TRACK_STATS, TIME_LIMIT = 1, 2, 4
+AUTO_RESET, TRACK_STATS, TIME_LIMIT, FINAL_OBS = 1, 2, 4, 8
 
 _OK, _EINVAL, _EHIP, _ENCCL, _ENOMEM, _EACTION = range(6)
 
@@ -270,6 +270,13 @@ class BatchedEngine:
         _check(self._lib, self._lib.gymrs_obs_ptrs(self._h, ptrs, C.byref(dim)))
         return [ptrs[j] for j in range(dim.value)]
 
+    def final_obs_ptrs(self):
+        """FINAL_OBS engines: device views of the observation each lane's last finished episode ended in (gymrs_final_obs_ptrs)."""
+        ptrs = (C.c_void_p * 4)()
+        dim = C.c_int()
+        _check(self._lib, self._lib.gymrs_final_obs_ptrs(self._h, ptrs, C.byref(dim)))
+        return [ptrs[j] for j in range(dim.value)]
+
     def state_ptrs(self):
         ptrs = (C.c_void_p * 4)()
         dim = C.c_int()
@@ -298,6 +305,13 @@ class BatchedEngine:
         count = self.n_envs - first if count is None else count
         out = np.empty((self.obs_dim, count), dtype=np.float32)
         _check(self._lib, self._lib.gymrs_get_obs(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_final_obs(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """FINAL_OBS engines: host copy of the final observations, shape (obs_dim, count) like get_obs."""
+        count = self.n_envs - first if count is None else count
+        out = np.empty((self.obs_dim, count), dtype=np.float32)
+        _check(self._lib, self._lib.gymrs_get_final_obs(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def get_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -492,6 +506,17 @@ class ShardedEngine:
         count = self.n_total - first if count is None else count
         out = np.empty((self.state_dim, count), dtype=np.float32)
         _check(self._lib, self._lib.gymrs_sharded_get_state(self._h, first, count, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_final_obs(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """FINAL_OBS: the final observations of lanes [first, first + count) of the whole batch, gathered from the blocks (each block's
+        own views: ``shards[r].final_obs_ptrs()`` / ``get_final_obs``), shape (obs_dim, count)."""
+        count = self.n_total - first if count is None else count
+        out = np.empty((self.obs_dim, count), dtype=np.float32)
+        for s in self.shards:
+            lo, hi = max(first, s.first_lane), min(first + count, s.first_lane + s.n_envs)
+            if lo < hi:
+                out[:, lo - first:hi - first] = s.get_final_obs(lo - s.first_lane, hi - lo)
         return out
 
     def get_step_result(self, first: int = 0, count: Optional[int] = None):

@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-/* 3 (round 5): + gymrs_sharded_*, gymrs_allreduce_stats_multi; - gymrs_copy_probe (a measurement tool now: tools/copy_probe) */
+/* 3 (round 5): + gymrs_sharded_*, gymrs_allreduce_stats_multi; - gymrs_copy_probe (a measurement tool now: tools/copy_probe)
+ *   additive since, without a version bump (detect by symbol): GYMRS_FINAL_OBS, gymrs_final_obs_ptrs, gymrs_get_final_obs */
 #define GYMRS_ABI_VERSION 3
 
 typedef struct gymrs_engine gymrs_engine; /* opaque; owns device buffers + stream */
@@ -64,6 +65,8 @@ enum {
                                (needs GYMRS_AUTO_RESET) */
     GYMRS_TIME_LIMIT = 4u,  /* truncated = (steps in episode >= max_episode_steps); the cap the
                                reference leaves to its callers (examples/cartpole.rs:18) */
+    GYMRS_FINAL_OBS = 8u,   /* keep the observation an episode ended in (needs GYMRS_AUTO_RESET):
+                               see gymrs_final_obs_ptrs */
 };
 
 /* Physics constants: the `pub` fields of the reference env structs, in f64 like the reference
@@ -238,10 +241,25 @@ gymrs_status gymrs_state_ptrs(gymrs_engine* e, float** out_ptrs /* capacity 4 */
 gymrs_status gymrs_reward_ptr(gymrs_engine* e, float** out);
 gymrs_status gymrs_done_ptr(gymrs_engine* e, uint8_t** out);
 gymrs_status gymrs_truncated_ptr(gymrs_engine* e, uint8_t** out);
+/* GYMRS_FINAL_OBS: the observation each lane's most recently finished episode ended in -- what a Gymnasium vector env
+ * returns as `final_obs`, and what a learner bootstraps a truncated episode from.  The engine owns obs_dim
+ * SoA f32 arrays of n_envs lanes, laid out like gymrs_obs_ptrs: CartPole (x, x_dot, theta, theta_dot), MountainCar
+ * (position, velocity), Pendulum (cos, sin, theta_dot).
+ *   - When lane i returns done or truncated in a step (and is therefore re-armed), row i receives, bit for bit, the
+ *     observation lane i would have shown after that step without GYMRS_AUTO_RESET.  Rows of lanes that did not finish
+ *     in that step are not written; a lane whose action was rejected (GYMRS_EACTION) is not stepped and not written.
+ *   - gymrs_engine_create, gymrs_reset and gymrs_reset_pcg64 set every row to 0.0f; gymrs_set_state leaves them alone.
+ *   - Every stepping path keeps them: gymrs_step / _host / _many (eager, use_graph; with this flag gymrs_step_many always
+ *     submits HIP launches, GYMRS_AQL is not consulted), gymrs_rollout / _record (the arrays end as the equivalent
+ *     fill_actions + step loop leaves them; trajectories are unchanged), the blocks of a sharded engine.  Clone and
+ *     snapshot carry them (the snapshot of an engine without the flag is unchanged).
+ * Both calls return GYMRS_EINVAL on an engine created without the flag. */
+gymrs_status gymrs_final_obs_ptrs(gymrs_engine* e, float** out_ptrs /* capacity 4 */, int* obs_dim);
 
 /* Host copies (synchronising).  SoA: dim arrays of `count` floats, back to back.
  * get/set_state is the engine's Clone/Serialize equivalent (core.rs:25). */
 gymrs_status gymrs_get_obs(gymrs_engine* e, uint64_t first, uint64_t count, float* host_out);
+gymrs_status gymrs_get_final_obs(gymrs_engine* e, uint64_t first, uint64_t count, float* host_out);
 gymrs_status gymrs_get_state(gymrs_engine* e, uint64_t first, uint64_t count, float* host_out);
 gymrs_status gymrs_set_state(gymrs_engine* e, uint64_t first, uint64_t count, const float* host_in);
 gymrs_status gymrs_get_step_result(gymrs_engine* e, uint64_t first, uint64_t count, float* reward,

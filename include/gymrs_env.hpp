@@ -132,6 +132,15 @@ public:
     {
         check(gymrs_rollout_record(e_, n_steps, action_seed, action_t0, &out));
     }
+    // GYMRS_FINAL_OBS engines: zero-copy device views of the observation each lane's last finished episode ended in
+    // (obs_dim SoA rows, the layout of gymrs_obs_ptrs); throws on an engine created without the flag
+    std::vector<float*> final_obs_views()
+    {
+        float* p[4];
+        int d = 0;
+        check(gymrs_final_obs_ptrs(e_, p, &d));
+        return std::vector<float*>(p, p + d);
+    }
     std::array<double, 4> stats() // {sum_return, sum_length, n_episodes, n_steps}
     {
         std::array<double, 4> out{};

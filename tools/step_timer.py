@@ -2,7 +2,7 @@
 """Developer A/B timer (not part of the product or the tests): microseconds per step launch of ANY build of the
 library, through the entry points every ABI version has.
 
-    python tools/step_timer.py [--lib path/to/libgymrs_amd.so ...] [--env 0|1|2] [--n LANES] [--steps K] [--reps R]
+    python tools/step_timer.py [--lib path/to/libgymrs_amd.so ...] [--env 0|1|2] [--n LANES] [--steps K] [--reps R] [--flags-list 3,11]
 
 Several --lib arguments are timed alternately in the same process on the same box (box-to-box spread is larger than
 most kernel changes), R repetitions each; prints min / median per library.
@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--flags", type=int, default=-1)
+    ap.add_argument("--flags-list", default="", help="comma-separated engine flag sets (e.g. 3,11): one engine per (library, flags), timed alternately")
     ap.add_argument("--vec", type=int, default=4)
     ap.add_argument("--nt", type=int, default=0)
     ap.add_argument("--nts", default="", help="comma-separated memory hints: one engine per (library, hint), timed alternately")
@@ -79,13 +80,16 @@ def main():
     both = [m for _ in range(len(libs) // len(nts)) for m in nts]
     modes = [m[0] for m in both]
     aql_of = [m[1] for m in both]
+    fsets = [int(x) for x in args.flags_list.split(",") if x] or [flags]
+    libs, modes, aql_of = ([x for x in lst for _ in fsets] for lst in (libs, modes, aql_of))
+    flag_of = [f for _ in range(len(libs) // len(fsets)) for f in fsets]
 
     def with_aql(q):
         if q[0] is not None:
             os.environ["GYMRS_AQL"] = q[0]
-    for lb in libs:
+    for lb, fl in zip(libs, flag_of):
         h = C.c_void_p()
-        lb.ck(lb.lib.gymrs_engine_create(args.env, args.n, 0, 0, None, flags, C.byref(h)))
+        lb.ck(lb.lib.gymrs_engine_create(args.env, args.n, 0, 0, None, fl, C.byref(h)))
         handles.append(h)
     if ring is None:
         ring = torch.empty(nbuf * args.n * esz, dtype=torch.uint8, device="cuda:0")
@@ -100,7 +104,8 @@ def main():
         s = C.c_void_p()
         lb.ck(lb.lib.gymrs_get_stream(h, C.byref(s)))
         engines.append((lb, h, torch.cuda.ExternalStream(s.value, device="cuda:0")))
-    keys = [f"{lb.path} nt={nt}" + (f" GYMRS_AQL={q[0]}" if q[0] is not None else "") + (f" hooks={q[1]}" if q[1] is not None else "") for lb, nt, q in zip(libs, modes, aql_of)]
+    keys = [f"{lb.path} nt={nt}" + (f" GYMRS_AQL={q[0]}" if q[0] is not None else "") + (f" hooks={q[1]}" if q[1] is not None else "") +
+            (f" flags={fl}" if args.flags_list else "") for lb, nt, q, fl in zip(libs, modes, aql_of, flag_of)]
     for (lb, h, _), q in zip(engines, aql_of):
         if q[1] is not None:
             lb.lib.gymrs_dev_set_hooks.argtypes = [C.c_void_p, C.c_uint32]
