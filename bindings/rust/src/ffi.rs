@@ -127,6 +127,13 @@ extern "C" {
     // ABI 2
     pub fn gymrs_set_params(e: *mut GymrsEngine, params: *const c_void) -> c_int;
     pub fn gymrs_get_params(e: *mut GymrsEngine, params_out: *mut c_void) -> c_int;
+    /// per-lane physics: K rows of the kind's params and a u16 row index per lane (include/gymrs_amd.h)
+    pub fn gymrs_set_param_table(e: *mut GymrsEngine, rows: *const c_void, k: u32) -> c_int;
+    pub fn gymrs_get_param_table(e: *mut GymrsEngine, rows_out: *mut c_void, capacity: u32, k: *mut u32) -> c_int;
+    pub fn gymrs_param_index_ptr(e: *mut GymrsEngine, out: *mut *mut u16) -> c_int;
+    pub fn gymrs_set_param_index(e: *mut GymrsEngine, first: u64, count: u64, host_in: *const u16) -> c_int;
+    pub fn gymrs_get_param_index(e: *mut GymrsEngine, first: u64, count: u64, host_out: *mut u16) -> c_int;
+    pub fn gymrs_get_lane_params(e: *mut GymrsEngine, lane: u64, params_out: *mut c_void) -> c_int;
     pub fn gymrs_env_json(e: *mut GymrsEngine, lane: u64, buf: *mut c_char, cap: u64, needed: *mut u64) -> c_int;
     pub fn gymrs_params_from_json(kind: c_int, json: *const c_char, params: *mut c_void, state: *mut f64, state_dim: *mut c_int) -> c_int;
     // ABI 3: one batch over several GPUs in ONE process (one engine + one native host thread per block)

@@ -61,6 +61,12 @@ SIGNATURES = {
     "gymrs_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gymrs_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_params": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_set_param_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "gymrs_get_param_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gymrs_param_index_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gymrs_set_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gymrs_get_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gymrs_get_lane_params": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process

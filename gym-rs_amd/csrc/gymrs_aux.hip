@@ -443,12 +443,21 @@ hipError_t launch_fold_reset_log(unsigned long long* log, uint32_t row_words, ui
 hipError_t launch_step_cartpole(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream);
 hipError_t launch_step_mountain_car(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream);
 hipError_t launch_step_pendulum(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream);
+hipError_t launch_step_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream);
+hipError_t launch_step_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream);
 
 hipError_t launch_step(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const void* consts,
                        hipStream_t stream)
 {
     launch_begin();
     if (a.n == 0) return hipSuccess;
+    if (flags & kFlagTable) { // (consts is a TableConsts)
+        switch (kind) {
+        case GYMRS_CARTPOLE: return launch_step_table_cartpole(vec, flags, a, consts, stream);
+        case GYMRS_MOUNTAIN_CAR: return launch_step_table_mountain_car(vec, flags, a, consts, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (kind) {
     case GYMRS_CARTPOLE: return launch_step_cartpole(vec, flags, a, consts, stream);
     case GYMRS_MOUNTAIN_CAR: return launch_step_mountain_car(vec, flags, a, consts, stream);

@@ -64,7 +64,7 @@ static uint32_t launch_flags_of(const gymrs_engine* e)
     case 3: hint = kFlagNtOut; break;
     default: hint = (per_step <= (48ull << 20) || per_step >= (1024ull << 20)) ? kFlagNonTemporal : kFlagNtOut; break;
     }
-    return e->flags | hint;
+    return e->flags | hint | table_bit(e);
 }
 
 static StepArgs step_args(const gymrs_engine* e, const void* actions)
@@ -512,6 +512,8 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->wave_open);
     (void)hipFree(e->wave_clean);
     (void)hipFree(e->err);
+    (void)hipFree(e->table_dev);
+    (void)hipFree(e->param_index);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     (void)hipFree(e->tick_dev);
@@ -990,7 +992,7 @@ gymrs_status gymrs_step(gymrs_engine* e, const void* actions_dev)
     if (gymrs_status st = flags_for_step(e, &flags)) return st;
     StepArgs a = step_args(e, actions_dev);
     if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return st;
-    HIP_TRY(launch_step(e->kind, e->vec, flags, a, consts_ptr(e), e->stream));
+    HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
     e->last_flags = flags;
     e->last_path = 1;
     e->tick += 1;
@@ -1038,7 +1040,7 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    HIP_TRY(launch_rollout(e->kind, vec, e->flags, a, r, consts_ptr(e), e->stream));
+    HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
     for (uint32_t k = 0; k < n_steps; ++k) { // the host copy of the uniform episode clock (Pendulum time limit)
         e->tick += 1;
@@ -1103,7 +1105,7 @@ static gymrs_status build_graph(gymrs_engine* e, const char* base, uint64_t stri
         a.tick_base = e->tick_dev;
         // (a captured launch keeps the engine's own flags, time limit included: what is baked in cannot follow start_bound)
         a.fold_step = (launch_is_logged(e, launch_flags_of(e)) && t % kResetLogRows == kResetLogRows - 1) ? 1u : 0u; // a replay starts on an empty ring
-        err = launch_step(e->kind, e->vec, launch_flags_of(e), a, consts_ptr(e), e->stream);
+        err = launch_step(e->kind, e->vec, launch_flags_of(e), a, launch_consts(e), e->stream);
     }
     if (err == hipSuccess) err = launch_tick_advance(e->tick_dev, steps, e->stream);
     hipError_t end = hipStreamEndCapture(e->stream, &graph);
@@ -1166,6 +1168,7 @@ static bool aql_usable(gymrs_engine* e, uint32_t n_steps)
 {
     if (n_steps < kAqlMinChain || e->vec != 4 || e->pool_host) return false;
     if (e->flags & GYMRS_FINAL_OBS) return false; // the chain's code object holds no final-observation kernels: HIP launches
+    if (e->table_k) return false;                 // nor any parameter-table kernels
     if (!aql_enabled_by_env()) return false;
     if (!e->own_stream) { // a caller-provided stream may be under a capture: a chain cannot be captured
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1392,10 +1395,10 @@ gymrs_status gymrs_step_many(gymrs_engine* e, const void* actions_dev, uint64_t 
         if (gymrs_status st = flags_for_step(e, &flags)) return st;
         StepArgs a = step_args(e, base + (size_t)(t % n_buffers) * stride_bytes);
         if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return st;
-        if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS)) // (developer experiment: the chain's binary through HIP's queue)
+        if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS) && !e->table_k) // (developer experiment: the chain's binary through HIP's queue)
             HIP_TRY(launch_step_through_hip_module(e, flags, a));
         else
-            HIP_TRY(launch_step(e->kind, e->vec, flags, a, consts_ptr(e), e->stream));
+            HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
         e->last_flags = flags;
         e->last_path = 1;
         e->tick += 1;
@@ -1453,8 +1456,11 @@ gymrs_status gymrs_sync(gymrs_engine* e)
         static const uint32_t err_init[2] = {0u, 0xffffffffu};
         HIP_TRY(hipMemcpyAsync(e->err, err_init, sizeof(err_init), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        char buf[160];
-        std::snprintf(buf, sizeof(buf), "%u invalid action(s); first offending lane %u (usize invalid)", err[0], err[1]);
+        char buf[200];
+        if (e->table_k) // (a lane whose parameter index is >= K is rejected like an invalid action)
+            std::snprintf(buf, sizeof(buf), "%u invalid action or parameter index(es); first offending lane %u (usize invalid)", err[0], err[1]);
+        else
+            std::snprintf(buf, sizeof(buf), "%u invalid action(s); first offending lane %u (usize invalid)", err[0], err[1]);
         return fail(GYMRS_EACTION, buf);
     }
     return GYMRS_OK;

@@ -195,6 +195,13 @@ struct SnapshotHeader {
 static_assert(sizeof(CartPoleConsts) <= 96 && sizeof(MountainCarConsts) <= 96 && sizeof(PendulumConsts) <= 96, "consts blob too small");
 static_assert(sizeof(gymrs_cartpole_params) <= 96 && sizeof(gymrs_mountain_car_params) <= 96 && sizeof(gymrs_pendulum_params) <= 96, "params blob too small");
 constexpr uint32_t kSnapshotVersion = 4; // 4: the statistics baseline is {L, E, R} (round 6), not L alone
+// 5: an engine with a parameter table (gymrs_set_param_table): the v4 blob, then {u64 K, K f64 rows as set, the n-lane u16
+// index}.  An engine without a table writes v4, byte for byte; the loader takes both.
+constexpr uint32_t kSnapshotVersionTable = 5;
+size_t table_tail_bytes(const gymrs_engine* e, uint32_t k)
+{
+    return k ? sizeof(uint64_t) + (size_t)k * params_size(e->kind) + (size_t)e->n * sizeof(uint16_t) : 0;
+}
 
 struct Segment {
     void* dev;
@@ -275,10 +282,18 @@ gymrs_status gymrs_engine_clone(gymrs_engine* src, gymrs_engine** out)
         gymrs_engine_destroy(dst);
         return st;
     }
+    if (src->table_k) { // the parameter table and the index
+        if (gymrs_status st = gymrs_set_param_table(dst, src->table_params.data(), src->table_k)) {
+            gymrs_engine_destroy(dst);
+            return st;
+        }
+    }
     hipError_t err = hipSuccess;
     const std::vector<Segment> from = snapshot_segments(src), to = snapshot_segments(dst);
     for (size_t i = 0; i < from.size() && err == hipSuccess; ++i)
         err = hipMemcpyAsync(to[i].dev, from[i].dev, from[i].bytes, hipMemcpyDefault, dst->stream); // (a small engine's pool is mapped host memory)
+    if (src->table_k && err == hipSuccess)
+        err = hipMemcpyAsync(dst->param_index, src->param_index, (size_t)src->n * sizeof(uint16_t), hipMemcpyDefault, dst->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(dst->stream);
     if (err != hipSuccess) {
         gymrs_engine_destroy(dst);
@@ -293,7 +308,7 @@ gymrs_status gymrs_snapshot_size(gymrs_engine* e, uint64_t* bytes)
     if (!e || !bytes) return fail(GYMRS_EINVAL, "gymrs_snapshot_size: NULL argument");
     size_t total = sizeof(SnapshotHeader);
     for (const Segment& sg : snapshot_segments(e)) total += sg.bytes;
-    *bytes = total;
+    *bytes = total + table_tail_bytes(e, e->table_k);
     return GYMRS_OK;
 }
 
@@ -308,7 +323,7 @@ gymrs_status gymrs_snapshot_save(gymrs_engine* e, void* host_buf, uint64_t bytes
     SnapshotHeader h;
     std::memset(&h, 0, sizeof(h));
     std::memcpy(h.magic, "GYMRSNAP", 8);
-    h.version = kSnapshotVersion;
+    h.version = e->table_k ? kSnapshotVersionTable : kSnapshotVersion;
     h.kind = (uint32_t)e->kind;
     h.n = e->n;
     h.gid0 = e->gid0;
@@ -335,6 +350,14 @@ gymrs_status gymrs_snapshot_save(gymrs_engine* e, void* host_buf, uint64_t bytes
         HIP_TRY(hipMemcpyAsync(p, sg.dev, sg.bytes, hipMemcpyDefault, e->stream));
         p += sg.bytes;
     }
+    if (e->table_k) { // v5: the table as set and the index
+        const uint64_t k = e->table_k;
+        std::memcpy(p, &k, sizeof(k));
+        p += sizeof(k);
+        std::memcpy(p, e->table_params.data(), e->table_params.size());
+        p += e->table_params.size();
+        HIP_TRY(hipMemcpyAsync(p, e->param_index, (size_t)e->n * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+    }
     if (gymrs_status st_ = stream_sync_checked(e)) return st_;
     return GYMRS_OK;
 }
@@ -345,13 +368,23 @@ gymrs_status gymrs_snapshot_load(gymrs_engine* e, const void* host_buf, uint64_t
     if (bytes < sizeof(SnapshotHeader)) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: truncated snapshot");
     SnapshotHeader h;
     std::memcpy(&h, host_buf, sizeof(h));
-    if (std::memcmp(h.magic, "GYMRSNAP", 8) != 0 || h.version != kSnapshotVersion)
-        return fail(GYMRS_EINVAL, "gymrs_snapshot_load: not a gymrs snapshot of this version");
+    if (std::memcmp(h.magic, "GYMRSNAP", 8) != 0) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: not a gymrs snapshot");
+    if (h.version != kSnapshotVersion && h.version != kSnapshotVersionTable)
+        return fail(GYMRS_EINVAL, "gymrs_snapshot_load: snapshot version " + std::to_string(h.version) + ", expected " +
+                                      std::to_string(kSnapshotVersion) + " or " + std::to_string(kSnapshotVersionTable) + " (with a parameter table)");
     if (h.kind != (uint32_t)e->kind || h.n != e->n || h.flags != e->flags || h.state_dim != (uint32_t)e->state_dim ||
         h.n_stat_blocks != e->n_stat_blocks || h.consts_bytes != consts_size(e->kind))
         return fail(GYMRS_EINVAL, "gymrs_snapshot_load: snapshot was taken from an engine of another kind / size / flags");
-    uint64_t need = 0;
-    (void)gymrs_snapshot_size(e, &need);
+    size_t need = sizeof(SnapshotHeader);
+    for (const Segment& sg : snapshot_segments(e)) need += sg.bytes;
+    uint64_t table_k = 0; // v5: the parameter table behind the arrays
+    if (h.version == kSnapshotVersionTable) {
+        if (e->kind == GYMRS_PENDULUM) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: a snapshot with a parameter table, of a Pendulum engine");
+        if (bytes < need + sizeof(table_k)) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: truncated snapshot");
+        std::memcpy(&table_k, static_cast<const char*>(host_buf) + need, sizeof(table_k));
+        if (table_k == 0 || table_k > kMaxParamRows) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: corrupt parameter table size");
+        need += table_tail_bytes(e, (uint32_t)table_k);
+    }
     if (bytes < need) return fail(GYMRS_EINVAL, "gymrs_snapshot_load: truncated snapshot");
     HIP_TRY(hipSetDevice(e->device));
     drop_graph(e); // seed and reset box are baked into a captured graph
@@ -360,6 +393,15 @@ gymrs_status gymrs_snapshot_load(gymrs_engine* e, const void* host_buf, uint64_t
     for (const Segment& sg : snapshot_segments(e)) {
         HIP_TRY(hipMemcpyAsync(sg.dev, p, sg.bytes, hipMemcpyDefault, e->stream));
         p += sg.bytes;
+    }
+    if (table_k) { // (validates the rows again and synchronises)
+        p += sizeof(table_k);
+        if (gymrs_status st = gymrs_set_param_table(e, p, (uint32_t)table_k)) return st;
+        p += (size_t)table_k * params_size(e->kind);
+        HIP_TRY(hipMemcpyAsync(e->param_index, p, (size_t)e->n * sizeof(uint16_t), hipMemcpyHostToDevice, e->stream));
+    } else {
+        if (e->table_k) drop_graph(e);
+        e->table_k = 0; // a v4 blob: one set for every lane
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->gid0 = h.gid0;
@@ -630,7 +672,8 @@ gymrs_status gymrs_set_params(gymrs_engine* e, const void* params)
     }
     // Only the launch constants changed: state, steps_beyond_terminated, episode clocks, statistics, seed and tick
     // carry on, exactly like assigning a pub field of the reference struct between two step() calls.
-    drop_graph(e); // the constants are baked into a captured graph
+    e->table_k = 0; // every lane, one set: a parameter table is switched off
+    drop_graph(e);  // the constants are baked into a captured graph
     return GYMRS_OK;
 }
 
@@ -645,15 +688,157 @@ gymrs_status gymrs_get_params(gymrs_engine* e, void* params_out)
     return GYMRS_OK;
 }
 
+// ---- per-lane physics parameters -------------------------------------------------------------------------------------
+// A table is K rows of the kind's gymrs_<kind>_params; lane i steps with row index[i] (TableT kernels, gymrs_tile.h).  Like
+// gymrs_set_params, a table change touches the launch constants only, in stream order.
+extern "C++" {
+namespace {
+// The lane's parameter index; EINVAL when it is not in the table (table engines only; synchronising)
+gymrs_status lane_param_set(gymrs_engine* e, uint64_t lane, uint32_t* idx, const char* who)
+{
+    uint16_t v = 0;
+    if (e->pool_host) HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(&v, e->param_index + lane, sizeof(v), hipMemcpyDeviceToHost, e->stream));
+    if (gymrs_status st = stream_sync_checked(e)) return st;
+    if (v >= e->table_k)
+        return fail(GYMRS_EINVAL, std::string(who) + ": lane " + std::to_string(lane) + " has parameter index " + std::to_string(v) +
+                                      ", which is not below the table's " + std::to_string(e->table_k) + " rows");
+    *idx = v;
+    return GYMRS_OK;
+}
+const void* table_row(const gymrs_engine* e, uint32_t idx) { return e->table_params.data() + (size_t)idx * params_size(e->kind); }
+} // namespace
+} // extern "C++"
+
+gymrs_status gymrs_set_param_table(gymrs_engine* e, const void* rows, uint32_t k)
+{
+    static const char* who = "gymrs_set_param_table";
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_param_table: NULL engine");
+    if (e->kind == GYMRS_PENDULUM)
+        return fail(GYMRS_EINVAL, "gymrs_set_param_table: Pendulum engines take no parameter table (its max_torque also drives the random-policy actions)");
+    if (!rows && k == 0) { // back to one set for every lane (row 0 of the table, which params / consts hold)
+        if (e->table_k) drop_graph(e);
+        e->table_k = 0;
+        return GYMRS_OK;
+    }
+    if (!rows) return fail(GYMRS_EINVAL, "gymrs_set_param_table: rows is NULL but k > 0");
+    if (k == 0) return fail(GYMRS_EINVAL, "gymrs_set_param_table: k must be >= 1 (rows = NULL, k = 0 switches the table off)");
+    if (k > kMaxParamRows) return fail(GYMRS_EINVAL, "gymrs_set_param_table: k must be <= 65536 (the lane index is 16 bits)");
+    const size_t psz = params_size(e->kind);
+    const unsigned char* rp = static_cast<const unsigned char*>(rows);
+    std::vector<ParamRow> dev_rows(k);
+    for (uint32_t i = 0; i < k; ++i) {
+        const void* row = rp + (size_t)i * psz;
+        const std::string row_who = std::string(who) + ": row " + std::to_string(i);
+        if (gymrs_status st = check_params(e->kind, row, row_who.c_str())) return st;
+        if (e->kind == GYMRS_CARTPOLE) {
+            const gymrs_cartpole_params& p = *static_cast<const gymrs_cartpole_params*>(row);
+            const gymrs_cartpole_params& p0 = *reinterpret_cast<const gymrs_cartpole_params*>(rp);
+            if (p.max_episode_steps != p0.max_episode_steps)
+                return fail(GYMRS_EINVAL, row_who + ": max_episode_steps differs from row 0's (every row of a table shares the time limit)");
+            if (p.kinematics_integrator != p0.kinematics_integrator)
+                return fail(GYMRS_EINVAL, row_who + ": kinematics_integrator differs from row 0's (every row of a table shares it)");
+            dev_rows[i] = param_row(make_consts(p));
+        } else {
+            const gymrs_mountain_car_params& p = *static_cast<const gymrs_mountain_car_params*>(row);
+            const gymrs_mountain_car_params& p0 = *reinterpret_cast<const gymrs_mountain_car_params*>(rp);
+            if (p.max_episode_steps != p0.max_episode_steps)
+                return fail(GYMRS_EINVAL, row_who + ": max_episode_steps differs from row 0's (every row of a table shares the time limit)");
+            dev_rows[i] = param_row(make_consts(p));
+        }
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->table_dev) HIP_TRY(hipMalloc(&e->table_dev, (size_t)kMaxParamRows * sizeof(ParamRow))); // 2 MiB, on first use
+    if (!e->param_index) HIP_TRY(hipMalloc(&e->param_index, (size_t)(e->n + 15) / 16 * 16 * sizeof(uint16_t)));
+    if (e->table_k == 0) HIP_TRY(hipMemsetAsync(e->param_index, 0, (size_t)e->n * sizeof(uint16_t), e->stream)); // switched on: every lane row 0
+    // stream-ordered: steps enqueued before this call read the old rows; the host rows are consumed before the call returns
+    HIP_TRY(hipMemcpyAsync(e->table_dev, dev_rows.data(), (size_t)k * sizeof(ParamRow), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->table_params.assign(rp, rp + (size_t)k * psz);
+    if (e->kind == GYMRS_CARTPOLE) { // params / consts: row 0 (gymrs_get_params; the shared integrator and time limit)
+        e->params.cp = *reinterpret_cast<const gymrs_cartpole_params*>(rp);
+        e->consts.cp = make_consts(e->params.cp);
+        e->tconsts.integrator = e->consts.cp.integrator;
+        e->tconsts.max_steps = e->consts.cp.max_steps;
+    } else {
+        e->params.mc = *reinterpret_cast<const gymrs_mountain_car_params*>(rp);
+        e->consts.mc = make_consts(e->params.mc);
+        e->tconsts.integrator = 0;
+        e->tconsts.max_steps = e->consts.mc.max_steps;
+    }
+    e->tconsts.rows = e->table_dev;
+    e->tconsts.index = e->param_index;
+    e->tconsts.k = k;
+    e->tconsts.pad_ = 0;
+    e->table_k = k;
+    drop_graph(e); // the kernel and its constants are baked into a captured graph
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_param_table(gymrs_engine* e, void* rows_out, uint32_t capacity, uint32_t* k)
+{
+    if (!e || !k) return fail(GYMRS_EINVAL, "gymrs_get_param_table: NULL argument");
+    *k = e->table_k;
+    if (e->table_k == 0 || (!rows_out && capacity == 0)) return GYMRS_OK; // no table, or a query of K
+    if (!rows_out || capacity < e->table_k) return fail(GYMRS_EINVAL, "gymrs_get_param_table: capacity is smaller than the table (see *k)");
+    std::memcpy(rows_out, e->table_params.data(), e->table_params.size());
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_param_index_ptr(gymrs_engine* e, uint16_t** out)
+{
+    if (!e || !out) return fail(GYMRS_EINVAL, "gymrs_param_index_ptr: NULL argument");
+    if (!e->table_k) return fail(GYMRS_EINVAL, "gymrs_param_index_ptr: the engine has no parameter table (gymrs_set_param_table)");
+    *out = e->param_index;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_set_param_index(gymrs_engine* e, uint64_t first, uint64_t count, const uint16_t* host_in)
+{
+    if (!e || !host_in) return fail(GYMRS_EINVAL, "gymrs_set_param_index: NULL argument");
+    if (!e->table_k) return fail(GYMRS_EINVAL, "gymrs_set_param_index: the engine has no parameter table (gymrs_set_param_table)");
+    if (gymrs_status st = range_check(e, first, count, "gymrs_set_param_index")) return st;
+    if (count == 0) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(e->param_index + first, host_in, count * sizeof(uint16_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream)); // (the caller may reuse host_in when the call returns)
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_param_index(gymrs_engine* e, uint64_t first, uint64_t count, uint16_t* host_out)
+{
+    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_param_index: NULL argument");
+    if (!e->table_k) return fail(GYMRS_EINVAL, "gymrs_get_param_index: the engine has no parameter table (gymrs_set_param_table)");
+    if (gymrs_status st = range_check(e, first, count, "gymrs_get_param_index")) return st;
+    if (count == 0) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(host_out, e->param_index + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+    if (gymrs_status st = stream_sync_checked(e)) return st;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_out)
+{
+    if (!e || !params_out) return fail(GYMRS_EINVAL, "gymrs_get_lane_params: NULL argument");
+    if (lane >= e->n) return fail(GYMRS_EINVAL, "gymrs_get_lane_params: lane out of range");
+    if (!e->table_k) return gymrs_get_params(e, params_out);
+    HIP_TRY(hipSetDevice(e->device));
+    uint32_t idx = 0;
+    if (gymrs_status st = lane_param_set(e, lane, &idx, "gymrs_get_lane_params")) return st;
+    std::memcpy(params_out, table_row(e, idx), params_size(e->kind));
+    return GYMRS_OK;
+}
+
 // ---- #[derive(Serialize)] view -------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
-json::Object engine_extras(const gymrs_engine* e, uint64_t lane, uint32_t max_episode_steps)
+json::Object engine_extras(const gymrs_engine* e, uint64_t lane, uint32_t max_episode_steps, uint32_t param_set)
 {
     json::Object g;
     g.str("kind", e->kind == GYMRS_CARTPOLE ? "CartPole" : (e->kind == GYMRS_MOUNTAIN_CAR ? "MountainCar" : "Pendulum"));
     g.uint("n_envs", e->n).uint("global_env_id", e->gid0 + lane).uint("flags", e->flags).uint("seed", e->seed).uint("tick", e->tick);
     g.uint("max_episode_steps", max_episode_steps);
+    if (e->table_k) g.uint("param_set", param_set).uint("param_table_rows", e->table_k); // the row of the table this lane steps with
     // chains of per-step launches that went through the engine's own AQL dispatcher (gymrs_aql.h), and why not if none can
     g.uint("aql_chains", e->aql_chains).uint("aql_launches", e->aql_launches);
     if (e->aql) g.str("aql_handover", e->aql_handover.c_str());
@@ -665,12 +850,16 @@ json::Object engine_extras(const gymrs_engine* e, uint64_t lane, uint32_t max_ep
         if (e->last_path == 2)
             std::snprintf(buf, sizeof(buf), "chain: %s", aql_kernel_name(e, e->last_flags, threads).c_str());
         else
-            std::snprintf(buf, sizeof(buf), "HIP launch: gymrs::step_kernel<%s, %d, flags %u | hint %s, %d work-items>",
-                          e->kind == GYMRS_CARTPOLE ? "CartPoleT" : (e->kind == GYMRS_MOUNTAIN_CAR ? "MountainCarT" : "PendulumT"), e->vec,
-                          e->last_flags & 7u, hint, threads);
+            std::snprintf(buf, sizeof(buf), "HIP launch: gymrs::step_kernel<%s%s%s, %d, flags %u | hint %s, %d work-items>",
+                          (e->last_flags & kFlagTable) ? "TableT<" : "",
+                          e->kind == GYMRS_CARTPOLE ? "CartPoleT" : (e->kind == GYMRS_MOUNTAIN_CAR ? "MountainCarT" : "PendulumT"),
+                          (e->last_flags & kFlagTable) ? ">" : "", e->vec, e->last_flags & 7u, hint, threads);
         g.str("last_launch", buf);
     }
-    g.str("aql", e->aql ? "on" : (e->aql_tried ? e->aql_why.c_str() : "not tried"));
+    if (e->table_k) // gymrs_step_many submits HIP launches while a table is active
+        g.str("aql", "HIP launches: the engine holds a parameter table, and no chain kernel reads one");
+    else
+        g.str("aql", e->aql ? "on" : (e->aql_tried ? e->aql_why.c_str() : "not tried"));
     // 1: the per-step kernel does not rewrite a wave's part of `reward` while it holds the env's constant reward (MountainCar always, CartPole from 128 MiB per step on)
     g.uint("reward_store_elided", ((e->flags & GYMRS_AUTO_RESET) && (e->kind == GYMRS_MOUNTAIN_CAR || e->elide_reward)) ? 1 : 0);
     if (e->limit_elidable) { // diagnostics of the time-limit elision: launches that ran without the limit, bound refreshes
@@ -707,12 +896,15 @@ gymrs_status gymrs_env_json(gymrs_engine* e, uint64_t lane, char* buf, uint64_t 
         if (e->kind == GYMRS_CARTPOLE) HIP_TRY(hipMemcpyAsync(&beyond, e->beyond + lane, 1, hipMemcpyDeviceToHost, e->stream));
         if (gymrs_status st_ = stream_sync_checked(e)) return st_;
     }
+    uint32_t set = 0; // a table engine prints the lane's own row
+    if (e->table_k)
+        if (gymrs_status st_ = lane_param_set(e, lane, &set, "gymrs_env_json")) return st_;
     double low[4], high[4];
     int dim = 0;
     json::Object o;
     switch (e->kind) {
     case GYMRS_CARTPOLE: { // field order of cartpole.rs:52-87
-        const gymrs_cartpole_params& p = e->params.cp;
+        const gymrs_cartpole_params& p = e->table_k ? *static_cast<const gymrs_cartpole_params*>(table_row(e, set)) : e->params.cp;
         gymrs_observation_space(e->kind, &p, low, high, &dim);
         static const char* names[4] = {"x", "x_dot", "theta", "theta_dot"};
         json::Object lo, hi, state;
@@ -733,11 +925,11 @@ gymrs_status gymrs_env_json(gymrs_engine* e, uint64_t lane, char* buf, uint64_t 
             o.uint("steps_beyond_terminated", 0);
         else
             o.null("steps_beyond_terminated");
-        o.obj("gymrs", engine_extras(e, lane, e->consts.cp.max_steps));
+        o.obj("gymrs", engine_extras(e, lane, e->consts.cp.max_steps, set));
         break;
     }
     case GYMRS_MOUNTAIN_CAR: { // field order of mountain_car.rs:48-80
-        const gymrs_mountain_car_params& p = e->params.mc;
+        const gymrs_mountain_car_params& p = e->table_k ? *static_cast<const gymrs_mountain_car_params*>(table_row(e, set)) : e->params.mc;
         gymrs_observation_space(e->kind, &p, low, high, &dim);
         o.num("min_position", p.min_position).num("max_position", p.max_position).num("max_speed", p.max_speed);
         o.num("goal_position", p.goal_position).num("goal_velocity", p.goal_velocity).num("force", p.force).num("gravity", p.gravity);
@@ -748,7 +940,7 @@ gymrs_status gymrs_env_json(gymrs_engine* e, uint64_t lane, char* buf, uint64_t 
         space.obj("low", lo).obj("high", hi);
         o.str("render_mode", "None").uint("action_space", 3).obj("observation_space", space).obj("state", state);
         o.obj("metadata", metadata_json({"Human", "RgbArray", "SingleRgbArray", "None"}, 30)); // mountain_car.rs:108-118
-        o.obj("gymrs", engine_extras(e, lane, e->consts.mc.max_steps));
+        o.obj("gymrs", engine_extras(e, lane, e->consts.mc.max_steps, set));
         break;
     }
     case GYMRS_PENDULUM: { // not in the reference: params, state, engine extras
@@ -757,7 +949,7 @@ gymrs_status gymrs_env_json(gymrs_engine* e, uint64_t lane, char* buf, uint64_t 
         json::Object state;
         state.num("theta", (double)st[0]).num("theta_dot", (double)st[1]);
         o.str("render_mode", "None").obj("state", state);
-        o.obj("gymrs", engine_extras(e, lane, e->consts.pd.max_steps));
+        o.obj("gymrs", engine_extras(e, lane, e->consts.pd.max_steps, set));
         break;
     }
     }

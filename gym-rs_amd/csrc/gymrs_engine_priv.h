@@ -161,6 +161,13 @@ struct gymrs_engine {
     uint64_t aql_chains = 0, aql_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint32_t last_flags = 0;                   // launch flags (engine flags | hint bits) of the most recent per-step launch ...
     int last_path = 0;                         // ... and how it was submitted: 0 none yet, 1 HIP launch, 2 chain (the extras' "last_launch")
+    // Per-lane physics parameters (gymrs_set_param_table): table_k rows, lane i steps with row param_index[i].  table_k == 0: no
+    // table, every lane steps with `consts`.  While a table is active, params / consts hold row 0 (gymrs_get_params reports it).
+    uint32_t table_k = 0;
+    ParamRow* table_dev = nullptr;           // [kMaxParamRows] f32 rows (make_consts of each row), allocated on first use
+    uint16_t* param_index = nullptr;         // [n] the row of every lane, allocated on first use
+    std::vector<unsigned char> table_params; // the table_k rows as the caller set them (f64 gymrs_<kind>_params, back to back)
+    TableConsts tconsts{};                   // the by-value constants of a table launch
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };
@@ -183,6 +190,15 @@ GYMRS_HOST_INTERNAL inline const void* consts_ptr(const gymrs_engine* e)
     case GYMRS_MOUNTAIN_CAR: return &e->consts.mc;
     default: return &e->consts.pd;
     }
+}
+
+// What a step or rollout launch of the engine passes as its constants: the env's Consts, or with a parameter table (the launch
+// flags then carry kFlagTable) the TableConsts.
+GYMRS_HOST_INTERNAL inline const void* launch_consts(const gymrs_engine* e) { return e->table_k ? static_cast<const void*>(&e->tconsts) : consts_ptr(e); }
+GYMRS_HOST_INTERNAL inline uint32_t table_bit(const gymrs_engine* e) { return e->table_k ? kFlagTable : 0u; }
+GYMRS_HOST_INTERNAL inline size_t params_size(gymrs_env_kind k)
+{
+    return k == GYMRS_CARTPOLE ? sizeof(gymrs_cartpole_params) : (k == GYMRS_MOUNTAIN_CAR ? sizeof(gymrs_mountain_car_params) : sizeof(gymrs_pendulum_params));
 }
 
 // Host address of one of the pool's arrays (engines whose pool is mapped host memory).

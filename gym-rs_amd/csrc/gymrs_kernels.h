@@ -21,6 +21,63 @@ constexpr uint32_t kFlagNonTemporal = 0x100u; // internal launch flag (not an en
 constexpr uint32_t kFlagNtOut = 0x200u;
 constexpr uint32_t kFlagNtStateLoads = 0x400u;
 constexpr uint32_t kFlagHintMask = kFlagNonTemporal | kFlagNtOut | kFlagNtStateLoads;
+// Internal launch flag (not an engine flag, not a hint): the engine holds a parameter table (gymrs_set_param_table), so the
+// launch goes to the table instantiations (TableT, gymrs_table_<env>.hip) with a TableConsts instead of the env's Consts.
+constexpr uint32_t kFlagTable = 0x800u;
+
+// ---- per-lane physics parameters (gymrs_set_param_table) -------------------------------------------------------------------
+// One row of a parameter table on the device: the f32 constants make_consts derives from one gymrs_<kind>_params, without the
+// fields every row shares (CartPole's integrator, max_steps).  CartPole: the 8 floats of CartPoleConsts in order; MountainCar:
+// the 7 floats of MountainCarConsts, padded.  32 bytes: two dwordx4 loads per lane.
+struct alignas(16) ParamRow {
+    float v[8];
+};
+constexpr uint32_t kMaxParamRows = 65536; // the lane index is a uint16_t
+static_assert(offsetof(CartPoleConsts, integrator) == 8 * sizeof(float) && offsetof(MountainCarConsts, max_steps) == 7 * sizeof(float),
+              "a ParamRow holds the leading floats of the env's Consts");
+__host__ __device__ inline ParamRow param_row(const CartPoleConsts& c)
+{
+    return ParamRow{{c.gravity, c.tau, c.force_over_tm, c.pml_over_tm, c.len_43, c.len_mp_over_tm, c.theta_thr, c.x_thr}};
+}
+__host__ __device__ inline ParamRow param_row(const MountainCarConsts& c)
+{
+    return ParamRow{{c.min_position, c.max_position, c.max_speed, c.goal_position, c.goal_velocity, c.force, c.gravity, 0.0f}};
+}
+// the inverse, with the engine-wide fields added back
+__host__ __device__ inline void consts_of_row(const ParamRow& r, int32_t integrator, uint32_t max_steps, CartPoleConsts& c)
+{
+    c.gravity = r.v[0];
+    c.tau = r.v[1];
+    c.force_over_tm = r.v[2];
+    c.pml_over_tm = r.v[3];
+    c.len_43 = r.v[4];
+    c.len_mp_over_tm = r.v[5];
+    c.theta_thr = r.v[6];
+    c.x_thr = r.v[7];
+    c.integrator = integrator;
+    c.max_steps = max_steps;
+}
+__host__ __device__ inline void consts_of_row(const ParamRow& r, int32_t, uint32_t max_steps, MountainCarConsts& c)
+{
+    c.min_position = r.v[0];
+    c.max_position = r.v[1];
+    c.max_speed = r.v[2];
+    c.goal_position = r.v[3];
+    c.goal_velocity = r.v[4];
+    c.force = r.v[5];
+    c.gravity = r.v[6];
+    c.max_steps = max_steps;
+}
+// The by-value constants of a table launch (the kernel's `Consts` parameter; StepArgs keeps its layout): lane i steps with
+// rows[index[i]] when index[i] < k; a lane whose index is >= k is not stepped and is reported like an invalid action.
+struct TableConsts {
+    const ParamRow* rows;   // [k] device rows
+    const uint16_t* index;  // [n] device: the row of every lane
+    uint32_t k;             // rows in the table, 1 .. kMaxParamRows
+    int32_t integrator;     // CartPole: shared by every row (TableT::variant hoists it out of the lane code)
+    uint32_t max_steps;     // shared by every row (the time limit)
+    uint32_t pad_;
+};
 // Rows of the reset log.  Measured at 2^20 CartPole lanes (128 KiB per row, no folding): a ring of <= 8 rows stays where a
 // write is cheap (6.10 us per launch; 8 steps x 40 MB is about what passes through the 256 MB Infinity Cache before a line
 // is evicted), 16 rows 6.22, >= 32 rows 6.40 (touching the next row one step ahead with a scalar load made it worse:
@@ -104,6 +161,10 @@ struct StepKernArgs {
     StepArgs rest;
     Consts c;
 };
+// KernArgView::fetch reads `rest` and `c` of a table launch at these offsets (nothing else would notice a change)
+static_assert(offsetof(StepKernArgs<TableConsts>, rest) == 6 * 8 && alignof(TableConsts) <= 8 && sizeof(StepArgs) % alignof(TableConsts) == 0 &&
+                  offsetof(StepKernArgs<TableConsts>, c) == 6 * 8 + sizeof(StepArgs),
+              "the kernel-argument layout of the table launches");
 
 // The fused multi-step kernel (gymrs_rollout): n_steps consecutive steps of every lane in ONE launch, with
 // the random-policy actions of gymrs_fill_actions(action_seed, action_t0 + k) generated in registers.

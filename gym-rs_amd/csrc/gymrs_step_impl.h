@@ -186,6 +186,7 @@ __device__ __forceinline__ void step_block(const StepArgs& a, const typename Env
     GYMRS_STAMP(0);
     TileRegs<Env, VEC, FLAGS> d;
     load_tile<Env, VEC, FLAGS, FULL>(a, (uint64_t)vblock * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
+    load_param_index<Env, VEC, FLAGS, FULL>(a, c, (uint64_t)vblock * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
     step_block_loaded<Env, VEC, FLAGS, THREADS, FULL>(a, c, lds, vblock, d);
 }
 
@@ -257,6 +258,7 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
             // (the arrays only some flag sets read: their pointers travel in StepArgs)
             if (Env::kHasBeyond && !R::AUTO) d.beyond = load_vec<uint8_t, VEC, R::NT_SL>(a.beyond, base, a.n, true, uint8_t(0));
             if (R::TLIM && !Env::kNeverTerminates) d.ep_start = load_vec<uint32_t, VEC, false>(a.ep_start, base, a.n, true, 0u);
+            load_param_index<Env, VEC, FLAGS, true>(a, c, base, d);
             step_block_loaded<Env, VEC, FLAGS, THREADS, true>(a, c, lds, blockIdx.x, d);
         } else {
             KernArgView<Env>::fetch(a, c);
@@ -287,9 +289,13 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
             if ((uint64_t)(vb0 + kStepTiles - 1) * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= n_fast) {
                 TileRegs<Env, VEC, FLAGS> d[2];
                 load_tile<Env, VEC, FLAGS, true>(a, (uint64_t)vb0 * LPB + (uint64_t)threadIdx.x * VEC, d[0]);
+                load_param_index<Env, VEC, FLAGS, true>(a, c, (uint64_t)vb0 * LPB + (uint64_t)threadIdx.x * VEC, d[0]);
 #pragma unroll
                 for (int j = 0; j < kStepTiles; ++j) {
-                    if (j + 1 < kStepTiles) load_tile<Env, VEC, FLAGS, true>(a, (uint64_t)(vb0 + j + 1) * LPB + (uint64_t)threadIdx.x * VEC, d[(j + 1) & 1]);
+                    if (j + 1 < kStepTiles) {
+                        load_tile<Env, VEC, FLAGS, true>(a, (uint64_t)(vb0 + j + 1) * LPB + (uint64_t)threadIdx.x * VEC, d[(j + 1) & 1]);
+                        load_param_index<Env, VEC, FLAGS, true>(a, c, (uint64_t)(vb0 + j + 1) * LPB + (uint64_t)threadIdx.x * VEC, d[(j + 1) & 1]);
+                    }
                     step_block_loaded<Env, VEC, FLAGS, THREADS, true>(a, c, lds, vb0 + j, d[j & 1]);
                 }
             } else {

@@ -1,0 +1,19 @@
+// gymrs_table_cartpole.hip -- the per-step and rollout kernel tables of CartPole with per-lane parameter tables (TableT,
+// gymrs_tile.h): every flag set, hint variant, lanes-per-work-item and workgroup size of the uniform tables, in a translation
+// unit of its own so that the build compiles it in parallel with the others.
+#include "gymrs_rollout_impl.h"
+#include "gymrs_step_impl.h"
+
+namespace gymrs {
+
+hipError_t launch_step_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream)
+{
+    return launch_vec<TableT<CartPoleT>>(vec, flags, a, consts, stream);
+}
+
+hipError_t launch_rollout_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, hipStream_t stream)
+{
+    return rollout_vec<TableT<CartPoleT>>(vec, flags, a, r, consts, stream);
+}
+
+} // namespace gymrs

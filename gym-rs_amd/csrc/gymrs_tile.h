@@ -133,6 +133,7 @@ __device__ __forceinline__ void obs_sincos(const Vec<float, VEC>& theta, Vec<flo
 // Env policies: what differs between the three env types.
 struct CartPoleT {
     using Consts = CartPoleConsts;
+    static constexpr bool kTable = false; // one set of constants for every lane (TableT: a row per lane)
     using Action = uint8_t;
     static constexpr int kState = 4;
     static constexpr int kSampled = 4; // state words reset() draws (cartpole.rs:317-324)
@@ -173,6 +174,7 @@ struct CartPoleT {
 
 struct MountainCarT {
     using Consts = MountainCarConsts;
+    static constexpr bool kTable = false; // one set of constants for every lane (TableT: a row per lane)
     using Action = uint8_t;
     static constexpr int kState = 2;
     static constexpr int kSampled = 1; // state words reset() draws (velocity is set to 0, mountain_car.rs:162-167)
@@ -208,6 +210,7 @@ struct MountainCarT {
 
 struct PendulumT { // spec-derived, not in the reference
     using Consts = PendulumConsts;
+    static constexpr bool kTable = false; // one set of constants for every lane (TableT: a row per lane)
     using Action = float;
     static constexpr int kState = 2;
     static constexpr int kSampled = 2; // state words reset() draws (theta, theta_dot)
@@ -240,6 +243,35 @@ struct PendulumT { // spec-derived, not in the reference
         done = false;
     }
     __device__ static void sample(const u32x4& r, const SampleBox& b, float* st) { pendulum_sample(r, b, st[0], st[1]); }
+};
+
+// Per-lane physics parameters (gymrs_set_param_table): the env `Base` with a TableConsts as its by-value constants.  Every lane
+// loads its row index next to its state, fetches its ParamRow from the table and steps with Base's own advance on the Consts
+// that row stands for (lane_consts): the arithmetic of the uniform kernels, lane by lane.  Only these instantiations contain
+// any of it (advance_tile: `if constexpr (Env::kTable)`).  Reset draws do not depend on the physics fields.
+template <class Base>
+struct TableT : Base {
+    static_assert(!Base::kNeverTerminates, "no Pendulum tables: max_torque also drives the random-policy actions");
+    static constexpr bool kTable = true;
+    using LaneConsts = typename Base::Consts;
+    using Consts = TableConsts;
+    __device__ static int variant(const Consts& c) { return Base::kVariants == 1 || c.integrator == 0 ? 0 : 1; }
+    __device__ static LaneConsts lane_consts(const Consts& c, const ParamRow& r)
+    {
+        LaneConsts l;
+        consts_of_row(r, c.integrator, c.max_steps, l);
+        return l;
+    }
+};
+
+// the per-lane constants advance_tile keeps for a TableT (a uniform env keeps none: an unused placeholder)
+template <class Env, class = void>
+struct TableLane {
+    struct type {};
+};
+template <class Env>
+struct TableLane<Env, std::enable_if_t<Env::kTable>> {
+    using type = typename Env::LaneConsts;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -278,7 +310,15 @@ struct TileRegs {
     Vec<typename Env::Action, VEC> act;
     Vec<uint8_t, VEC> beyond;
     Vec<uint32_t, VEC> ep_start;
+    Vec<uint16_t, VEC> pidx; // TableT: the row of every lane (TableConsts::index)
 };
+
+// TableT: the lanes' row indices, loaded right behind the other loads of the tile (no-op for a uniform env)
+template <class Env, int VEC, uint32_t FLAGS, bool FULL>
+__device__ __forceinline__ void load_param_index(const StepArgs& a, const typename Env::Consts& c, uint64_t base, TileRegs<Env, VEC, FLAGS>& d)
+{
+    if constexpr (Env::kTable) d.pidx = load_vec<uint16_t, VEC, false>(c.index, base, a.n, FULL, uint16_t(0));
+}
 
 // ROLL = the fused multi-step kernel: actions are generated in registers and ep_start travels densely
 // (loaded once, updated in registers, stored once) instead of by sparse stores from the reset workers.
@@ -324,6 +364,33 @@ __device__ __forceinline__ void advance_fast_all(const typename Env::Consts& c, 
 #pragma unroll
         for (int j = 0; j < NS; ++j) ls[j][k] = lane_st[j];
     }
+}
+
+// TableT: the same, every lane with the constants of its own row
+template <class Env, int VEC, int V>
+__device__ __forceinline__ void advance_fast_rows(const typename Env::LaneConsts (&lc)[VEC], float (&ls)[Env::kState][VEC],
+                                                  const typename Env::Action (&la)[VEC], float (&rw)[VEC], bool (&dn)[VEC])
+{
+    constexpr int NS = Env::kState;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        float lane_st[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) lane_st[j] = ls[j][k];
+        Env::template advance_fast<V>(lc[k], lane_st, la[k], rw[k], dn[k]);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) ls[j][k] = lane_st[j];
+    }
+}
+
+// TableT: lane k's row index is in the table (always true for a uniform env)
+template <class Env, int VEC, uint32_t FLAGS>
+__device__ __forceinline__ bool lane_index_ok(const typename Env::Consts& c, const TileRegs<Env, VEC, FLAGS>& d, int k)
+{
+    if constexpr (Env::kTable)
+        return d.pidx.v[k] < c.k;
+    else
+        return true;
 }
 
 // Every action of a work-item's packed u8 actions is < N (Discrete(N).contains, discrete.rs:14-19), tested on the dwords:
@@ -459,29 +526,55 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
         const uint32_t kk = Env::range_key(lane_st);
         key = key > kk ? key : kk;
     }
-    const bool fast = FULL && key <= Env::kRangeMax && actions_all_below<Env::kActions>(d.act);
+    bool fast = FULL && key <= Env::kRangeMax && actions_all_below<Env::kActions>(d.act);
+    // TableT: every lane's row, fetched (through the vector memory path) as soon as its index has landed.  A lane whose index is
+    // out of the table reads row 0 instead and is not stepped; the fast path needs every index of the tile in the table.
+    [[maybe_unused]] typename TableLane<Env>::type lc[kVec];
+    if constexpr (Env::kTable) {
+        uint32_t top = 0;
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) {
+            uint32_t i = d.pidx.v[k];
+            // The rollout kernel refetches the rows every step (L1 / L2 hits): hoisted out of its loop, 8 * VEC more registers live
+            // across the whole rollout spilled at 4 lanes per work-item (up to 228 B of scratch per work-item).
+            if (ROLL) asm volatile("" : "+v"(i));
+            top = top > i ? top : i;
+            lc[k] = Env::lane_consts(c, c.rows[i < c.k ? i : 0u]);
+        }
+        fast = fast && top < c.k;
+    }
     out.reward_is_const = true; // the fast path pays the constant on every lane
 #pragma unroll
     for (int k = 0; k < kVec; ++k) out.masks[k] = 0;
     if (__all(fast)) { // wave-uniform: the common path
-        if (Env::kVariants == 1 || Env::variant(c) == 0)
-            advance_fast_all<Env, VEC, 0>(c, ls, la, rw, dn);
-        else
-            advance_fast_all<Env, VEC, 1>(c, ls, la, rw, dn);
+        if constexpr (Env::kTable) {
+            if (Env::kVariants == 1 || Env::variant(c) == 0)
+                advance_fast_rows<Env, VEC, 0>(lc, ls, la, rw, dn);
+            else
+                advance_fast_rows<Env, VEC, 1>(lc, ls, la, rw, dn);
+        } else {
+            if (Env::kVariants == 1 || Env::variant(c) == 0)
+                advance_fast_all<Env, VEC, 0>(c, ls, la, rw, dn);
+            else
+                advance_fast_all<Env, VEC, 1>(c, ls, la, rw, dn);
+        }
     } else { // general per-lane code: ragged tail, invalid actions, angles outside the fast range
         uint32_t n_bad = 0, first_bad = 0xffffffffu;
 #pragma unroll
         for (int k = 0; k < kVec; ++k) {
             const bool live = FULL || (base + k < a.n);
-            const bool ok = Env::valid(la[k]);
+            const bool ok = Env::valid(la[k]) && lane_index_ok(c, d, k);
             float lane_st[NS];
 #pragma unroll
             for (int j = 0; j < NS; ++j) lane_st[j] = ls[j][k];
             float r = 0.0f;
             bool dk = false;
             if (live && ok) {
-                Env::advance(c, lane_st, la[k], r, dk);
-            } else if (live) { // invalid action: the reference panics before touching the env
+                if constexpr (Env::kTable)
+                    Env::advance(lc[k], lane_st, la[k], r, dk);
+                else
+                    Env::advance(c, lane_st, la[k], r, dk);
+            } else if (live) { // invalid action (or, TableT, row index): the reference panics before touching the env
                 n_bad += 1;
                 first_bad = min(first_bad, (uint32_t)(base + k));
             }
@@ -501,7 +594,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
     Vec<uint8_t, kVec>&done = out.done, &trunc = out.trunc;
 #pragma unroll
     for (int k = 0; k < kVec; ++k) {
-        const bool stepped = (FULL || (base + k < a.n)) && Env::valid(la[k]);
+        const bool stepped = (FULL || (base + k < a.n)) && Env::valid(la[k]) && lane_index_ok(c, d, k);
         if (Env::kHasBeyond && !AUTO) { // cartpole.rs:455-464
             bool b = d.beyond.v[k] != 0;
             const float r = cartpole_reward(dn[k], b);

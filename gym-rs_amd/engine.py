@@ -201,6 +201,48 @@ class BatchedEngine:
         _check(self._lib, self._lib.gymrs_get_params(self._h, C.byref(p)))
         return p
 
+    # -- per-lane physics: a parameter table and a row index per lane (gymrs_set_param_table) --------
+    def set_param_table(self, rows) -> None:
+        """Give lane i the physics of ``rows[index[i]]`` (a sequence of this kind's params; ``None`` or ``[]`` switches the table
+        off, every lane then steps with row 0).  The first table starts every index at 0.  Only the launch constants change."""
+        rows = list(rows or [])
+        cls = _PARAMS[self.kind]
+        if any(not isinstance(r, cls) for r in rows):
+            raise TypeError(f"expected {cls.__name__} rows")
+        arr = (cls * len(rows))(*rows) if rows else None
+        _check(self._lib, self._lib.gymrs_set_param_table(self._h, arr, len(rows)))
+        self.params = self.get_params()
+
+    def param_table(self) -> list:
+        """The rows of the active table in f64 exactly as set ([] without a table)."""
+        k = C.c_uint32()
+        _check(self._lib, self._lib.gymrs_get_param_table(self._h, None, 0, C.byref(k)))
+        if k.value == 0:
+            return []
+        arr = (_PARAMS[self.kind] * k.value)()
+        _check(self._lib, self._lib.gymrs_get_param_table(self._h, arr, k.value, C.byref(k)))
+        return list(arr)
+
+    def param_index_ptr(self) -> int:
+        """Device address of the uint16 row index of every lane (zero-copy; the engine's stream orders writes to it)."""
+        return self._ptr(self._lib.gymrs_param_index_ptr)
+
+    def set_param_index(self, index, first: int = 0) -> None:
+        idx = np.ascontiguousarray(index, dtype=np.uint16)
+        _check(self._lib, self._lib.gymrs_set_param_index(self._h, int(first), idx.size, idx.ctypes.data_as(C.c_void_p)))
+
+    def get_param_index(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        count = self.n_envs - first if count is None else count
+        out = np.empty(count, dtype=np.uint16)
+        _check(self._lib, self._lib.gymrs_get_param_index(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def lane_params(self, lane: int):
+        """The params lane ``lane`` steps with: row index[lane] of the table (without one, get_params())."""
+        p = _PARAMS[self.kind]()
+        _check(self._lib, self._lib.gymrs_get_lane_params(self._h, int(lane), C.byref(p)))
+        return p
+
     def env_json(self, lane: int = 0) -> str:
         """What ``serde_json::to_string(&env)`` prints for the reference env lane ``lane`` stands for (core.rs:25)."""
         need = C.c_uint64()

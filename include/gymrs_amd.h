@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 /* 3 (round 5): + gymrs_sharded_*, gymrs_allreduce_stats_multi; - gymrs_copy_probe (a measurement tool now: tools/copy_probe)
- *   additive since, without a version bump (detect by symbol): GYMRS_FINAL_OBS, gymrs_final_obs_ptrs, gymrs_get_final_obs */
+ *   additive since, without a version bump (detect by symbol): GYMRS_FINAL_OBS, gymrs_final_obs_ptrs, gymrs_get_final_obs;
+ *   the parameter tables gymrs_set_param_table .. gymrs_get_lane_params */
 #define GYMRS_ABI_VERSION 3
 
 typedef struct gymrs_engine gymrs_engine; /* opaque; owns device buffers + stream */
@@ -343,6 +344,36 @@ gymrs_status gymrs_sharded_get_step_result(gymrs_sharded* h, uint64_t first, uin
 gymrs_status gymrs_set_params(gymrs_engine* e, const void* params);
 gymrs_status gymrs_get_params(gymrs_engine* e, void* params_out);
 
+/* ---- per-lane physics: parameter tables (CartPole, MountainCar) ------------------------------------------------------- */
+/* In the reference every env value has its own pub fields, so a Vec<CartPoleEnv> can give each env its own pole length or
+ * gravity (domain randomisation).  A parameter table is that for the lanes of one engine: K rows of the kind's params struct
+ * (1 <= K <= 65536) and a per-lane index, uint16_t[n_envs] in device memory; lane i steps with row index[i].  Lane i gives
+ * the same bits as lane i of an engine created with params = row[index[i]] (same size, offset, flags, seed and actions):
+ * state, reward, done, truncated, final observations, steps_beyond_terminated; the episode statistics are sums over lanes.
+ *   - Every row passes the checks of gymrs_set_params, and all rows share max_episode_steps and (CartPole)
+ *     kinematics_integrator: otherwise GYMRS_EINVAL, naming the first row that differs.  Pendulum: GYMRS_EINVAL.
+ *   - The first gymrs_set_param_table switches table mode on, with every index 0.  gymrs_set_param_table(e, NULL, 0) or
+ *     gymrs_set_params switch it off: every lane uses one set again (after (NULL, 0): row 0).  While a table is active,
+ *     gymrs_get_params reports row 0 and gymrs_step_many submits HIP launches (GYMRS_AQL is not consulted).
+ *   - A table change is a gymrs_set_params: only constants change, in stream order (steps enqueued before the call use
+ *     the old rows); the caller may free `rows` when the call returns.  A captured HIP graph is dropped.
+ *   - Reset draws do not depend on the physics fields: the resets and auto-reset re-arms are unchanged.  Rewriting the
+ *     index of lanes that just finished gives per-episode randomisation.
+ *   - A lane whose index is >= K is not stepped and reads nothing outside the table: like an invalid action, the next
+ *     gymrs_sync returns GYMRS_EACTION naming the lowest such lane ("invalid action or parameter index").
+ *   - gymrs_engine_clone copies table and index; a snapshot of an engine with a table is version 5 (v4 + table + index).
+ * gymrs_get_param_table: *k = K (0: no table); rows_out receives the K rows in f64 exactly as set (capacity >= K; rows_out
+ * NULL with capacity 0 only asks for K).  gymrs_param_index_ptr: zero-copy device view of the index, under the stream rules of
+ * the other *_ptr views (a kernel on the engine's stream may rewrite it between two steps).  gymrs_set_param_index /
+ * gymrs_get_param_index: host copies of lanes [first, first + count) (synchronising).  These three need a table.
+ * gymrs_get_lane_params: the params lane `lane` steps with (row index[lane]; without a table, gymrs_get_params). */
+gymrs_status gymrs_set_param_table(gymrs_engine* e, const void* rows /* k x gymrs_<kind>_params */, uint32_t k);
+gymrs_status gymrs_get_param_table(gymrs_engine* e, void* rows_out, uint32_t capacity, uint32_t* k);
+gymrs_status gymrs_param_index_ptr(gymrs_engine* e, uint16_t** out);
+gymrs_status gymrs_set_param_index(gymrs_engine* e, uint64_t first, uint64_t count, const uint16_t* host_in);
+gymrs_status gymrs_get_param_index(gymrs_engine* e, uint64_t first, uint64_t count, uint16_t* host_out);
+gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_out);
+
 /* ---- `#[derive(Serialize)]` view (core.rs:25; cartpole.rs:51-87, mountain_car.rs:46-80) -------- */
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible
  * fields in declaration order with the reference's field names -- CartPole: action_space, observation_space
@@ -353,7 +384,8 @@ gymrs_status gymrs_get_params(gymrs_engine* e, void* params_out);
  * {position, velocity}, metadata.  Non-finite floats print as null (serde_json).  `rand_random` is
  * #[serde(skip_serializing)] in the reference and absent here; the GUI-only `renderer` / `screen` members are
  * omitted (RenderMode::None, out of scope).  Engine-side additions sit under one extra key "gymrs": {kind, n_envs,
- * global_env_id, flags, seed, tick, max_episode_steps}.  Pendulum (not in the reference) prints its params, state
+ * global_env_id, flags, seed, tick, max_episode_steps}; with a parameter table the physics fields are the lane's own row,
+ * and "gymrs" adds param_set (the lane's index) and param_table_rows (K).  Pendulum (not in the reference) prints its params, state
  * and the "gymrs" object.
  * Writes at most cap bytes incl. the terminating NUL; *needed (may be NULL) receives the size required.  Returns
  * GYMRS_EINVAL when cap is too small (nothing useful written).  Synchronising (reads the lane's state). */

@@ -171,6 +171,28 @@ public:
     // the pub physics fields after construction (cartpole.rs:53-82): only the constants change, the episode carries on
     void set_params(const void* params) { check(gymrs_set_params(e_, params)); }
     void get_params(void* params_out) { check(gymrs_get_params(e_, params_out)); }
+    // per-lane physics (gymrs_set_param_table): lane i steps with rows[index[i]]; set_param_table(nullptr, 0) switches it off
+    void set_param_table(const void* rows, std::uint32_t k) { check(gymrs_set_param_table(e_, rows, k)); }
+    std::uint32_t param_table(void* rows_out, std::uint32_t capacity)
+    {
+        std::uint32_t k = 0;
+        check(gymrs_get_param_table(e_, rows_out, capacity, &k));
+        return k;
+    }
+    std::uint16_t* param_index_view()
+    {
+        std::uint16_t* p = nullptr;
+        check(gymrs_param_index_ptr(e_, &p));
+        return p;
+    }
+    void set_param_index(std::uint64_t first, std::uint64_t count, const std::uint16_t* index) { check(gymrs_set_param_index(e_, first, count, index)); }
+    std::vector<std::uint16_t> param_index(std::uint64_t first, std::uint64_t count)
+    {
+        std::vector<std::uint16_t> out(count);
+        check(gymrs_get_param_index(e_, first, count, out.data()));
+        return out;
+    }
+    void lane_params(std::uint64_t lane, void* params_out) { check(gymrs_get_lane_params(e_, lane, params_out)); }
     // `#[derive(Serialize)]` view of the reference env lane `lane` stands for (core.rs:25)
     std::string to_json(std::uint64_t lane = 0)
     {

@@ -2,7 +2,7 @@
 """Developer A/B timer (not part of the product or the tests): microseconds per step launch of ANY build of the
 library, through the entry points every ABI version has.
 
-    python tools/step_timer.py [--lib path/to/libgymrs_amd.so ...] [--env 0|1|2] [--n LANES] [--steps K] [--reps R] [--flags-list 3,11]
+    python tools/step_timer.py [--lib path/to/libgymrs_amd.so ...] [--env 0|1|2] [--n LANES] [--steps K] [--reps R] [--flags-list 3,11] [--lane-sets 0,1,16]
 
 Several --lib arguments are timed alternately in the same process on the same box (box-to-box spread is larger than
 most kernel changes), R repetitions each; prints min / median per library.
@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--flags", type=int, default=-1)
     ap.add_argument("--flags-list", default="", help="comma-separated engine flag sets (e.g. 3,11): one engine per (library, flags), timed alternately")
+    ap.add_argument("--lane-sets", default="", help="comma-separated parameter-table sizes K (0 = no table): one engine per (library, flags, K); "
+                    "K > 0 gives the engine K rows (default params, gravity and length scaled per row) and a random row index per lane")
     ap.add_argument("--vec", type=int, default=4)
     ap.add_argument("--nt", type=int, default=0)
     ap.add_argument("--nts", default="", help="comma-separated memory hints: one engine per (library, hint), timed alternately")
@@ -83,14 +85,34 @@ def main():
     fsets = [int(x) for x in args.flags_list.split(",") if x] or [flags]
     libs, modes, aql_of = ([x for x in lst for _ in fsets] for lst in (libs, modes, aql_of))
     flag_of = [f for _ in range(len(libs) // len(fsets)) for f in fsets]
+    ksets = [int(x) for x in args.lane_sets.split(",") if x] or [0]
+    libs, modes, aql_of, flag_of = ([x for x in lst for _ in ksets] for lst in (libs, modes, aql_of, flag_of))
+    k_of = [k for _ in range(len(libs) // len(ksets)) for k in ksets]
 
     def with_aql(q):
         if q[0] is not None:
             os.environ["GYMRS_AQL"] = q[0]
-    for lb, fl in zip(libs, flag_of):
+    for lb, fl, k in zip(libs, flag_of, k_of):
         h = C.c_void_p()
         lb.ck(lb.lib.gymrs_engine_create(args.env, args.n, 0, 0, None, fl, C.byref(h)))
         handles.append(h)
+        if k:  # a table of K rows and a random index (gymrs_set_param_table)
+            sys.path.insert(0, str(ROOT))
+            from importlib import import_module
+            import numpy as np
+            eng_mod = import_module("gym-rs_amd.engine")
+            rows = (eng_mod._PARAMS[args.env] * k)()
+            for r in range(k):
+                lb.ck(lb.lib.gymrs_default_params(args.env, C.byref(rows[r])))
+                s_ = 1.0 + 0.5 * (r / max(1, k - 1) - 0.5)
+                rows[r].gravity *= s_
+                if args.env == 0:
+                    rows[r].length *= 2.0 - s_
+            lb.lib.gymrs_set_param_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            lb.lib.gymrs_set_param_index.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+            lb.ck(lb.lib.gymrs_set_param_table(h, rows, k))
+            idx = np.random.default_rng(k).integers(0, k, args.n).astype(np.uint16)
+            lb.ck(lb.lib.gymrs_set_param_index(h, 0, args.n, idx.ctypes.data_as(C.c_void_p)))
     if ring is None:
         ring = torch.empty(nbuf * args.n * esz, dtype=torch.uint8, device="cuda:0")
         torch.cuda.synchronize()
@@ -105,7 +127,7 @@ def main():
         lb.ck(lb.lib.gymrs_get_stream(h, C.byref(s)))
         engines.append((lb, h, torch.cuda.ExternalStream(s.value, device="cuda:0")))
     keys = [f"{lb.path} nt={nt}" + (f" GYMRS_AQL={q[0]}" if q[0] is not None else "") + (f" hooks={q[1]}" if q[1] is not None else "") +
-            (f" flags={fl}" if args.flags_list else "") for lb, nt, q, fl in zip(libs, modes, aql_of, flag_of)]
+            (f" flags={fl}" if args.flags_list else "") + (f" K={k}" if args.lane_sets else "") for lb, nt, q, fl, k in zip(libs, modes, aql_of, flag_of, k_of)]
     for (lb, h, _), q in zip(engines, aql_of):
         if q[1] is not None:
             lb.lib.gymrs_dev_set_hooks.argtypes = [C.c_void_p, C.c_uint32]
