@@ -210,6 +210,21 @@ impl Engine {
         check(ffi::gymrs_rollout_record(self.raw, n_steps, action_seed, action_t0, out));
     }
 
+    /// Install a policy set (`gymrs_set_policy`): `weights` holds `n_policies` policies of `gymrs_policy_size(kind, hidden)` floats back to
+    /// back; lane `i` uses policy `((global_env_offset + i) / lanes_per_policy) % n_policies`.
+    pub fn set_policy(&mut self, weights: &[f32], hidden: u32, n_policies: u32, lanes_per_policy: u64) {
+        let mut size = 0u64;
+        check(unsafe { ffi::gymrs_policy_size(self.kind.raw(), hidden, &mut size) });
+        assert_eq!(weights.len() as u64, size * n_policies as u64);
+        let d = ffi::GymrsPolicyDesc { hidden, n_policies, lanes_per_policy };
+        check(unsafe { ffi::gymrs_set_policy(self.raw, &d, weights.as_ptr()) });
+    }
+
+    /// `n_steps` closed-loop steps fused into one launch: every step's actions are the policy's, computed from each lane's observation.
+    pub fn rollout_policy(&mut self, n_steps: u32) {
+        check(unsafe { ffi::gymrs_rollout_policy(self.raw, n_steps) });
+    }
+
     /// Wait for everything queued on the engine's stream.
     pub fn sync(&mut self) {
         check(unsafe { ffi::gymrs_sync(self.raw) });

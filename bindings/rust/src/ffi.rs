@@ -70,6 +70,15 @@ pub struct Trajectory {
     pub lane_stride: u64,
 }
 
+/// `gymrs_policy_desc`: the shape of a policy set (`gymrs_set_policy`, include/gymrs_amd.h "closed-loop rollouts").
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct GymrsPolicyDesc {
+    pub hidden: u32,
+    pub n_policies: u32,
+    pub lanes_per_policy: u64,
+}
+
 extern "C" {
     pub fn gymrs_abi_version() -> c_int;
     pub fn gymrs_last_error() -> *const c_char;
@@ -134,6 +143,14 @@ extern "C" {
     pub fn gymrs_set_param_index(e: *mut GymrsEngine, first: u64, count: u64, host_in: *const u16) -> c_int;
     pub fn gymrs_get_param_index(e: *mut GymrsEngine, first: u64, count: u64, host_out: *mut u16) -> c_int;
     pub fn gymrs_get_lane_params(e: *mut GymrsEngine, lane: u64, params_out: *mut c_void) -> c_int;
+    /// closed-loop rollouts: a small policy evaluated inside the kernel (detect by symbol; the ABI version stays 3)
+    pub fn gymrs_policy_size(kind: c_int, hidden: u32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_set_policy(e: *mut GymrsEngine, d: *const GymrsPolicyDesc, weights_host: *const f32) -> c_int;
+    pub fn gymrs_get_policy(e: *mut GymrsEngine, d_out: *mut GymrsPolicyDesc, weights_out: *mut f32, capacity_floats: u64) -> c_int;
+    pub fn gymrs_policy_weights_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_policy_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;
+    pub fn gymrs_rollout_policy(e: *mut GymrsEngine, n_steps: u32) -> c_int;
+    pub fn gymrs_rollout_policy_record(e: *mut GymrsEngine, n_steps: u32, out: *const Trajectory) -> c_int;
     pub fn gymrs_env_json(e: *mut GymrsEngine, lane: u64, buf: *mut c_char, cap: u64, needed: *mut u64) -> c_int;
     pub fn gymrs_params_from_json(kind: c_int, json: *const c_char, params: *mut c_void, state: *mut f64, state_dim: *mut c_int) -> c_int;
     // ABI 3: one batch over several GPUs in ONE process (one engine + one native host thread per block)

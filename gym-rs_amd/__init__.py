@@ -43,12 +43,12 @@ from .envs import (
 )
 from ._lib import library_path, load_library
 from . import sharded
-from .engine import params_from_json
+from .engine import params_from_json, policy_size
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
     "CartPoleParams", "MountainCarParams", "PendulumParams", "CartPoleEnv", "MountainCarEnv", "PendulumEnv",
     "CartPoleObservation", "MountainCarObservation", "PendulumObservation", "RenderMode",
     "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "FINAL_OBS", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
-    "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json",
+    "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
 ]

@@ -67,6 +67,14 @@ SIGNATURES = {
     "gymrs_set_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_get_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_get_lane_params": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    # closed-loop rollouts (gymrs_policy_desc: {u32 hidden, u32 n_policies, u64 lanes_per_policy})
+    "gymrs_policy_size": (C.c_int, [C.c_int, C.c_uint32, u64p]),
+    "gymrs_set_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gymrs_get_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "gymrs_policy_weights_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),
+    "gymrs_policy_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_rollout_policy": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gymrs_rollout_policy_record": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process

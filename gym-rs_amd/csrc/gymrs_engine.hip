@@ -514,6 +514,7 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->err);
     (void)hipFree(e->table_dev);
     (void)hipFree(e->param_index);
+    (void)hipFree(e->policy_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     (void)hipFree(e->tick_dev);
@@ -1004,10 +1005,15 @@ gymrs_status gymrs_step(gymrs_engine* e, const void* actions_dev)
 
 // The caller loop of the reference's examples (examples/cartpole.rs:15-30: random action, step, reset on
 // done, accumulate the return) fused into one launch; see rollout_kernel.
+// closed = gymrs_rollout_policy: the actions come from the engine's policy set (gymrs_set_policy) instead of the Philox stream.
 static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
-                                 const gymrs_trajectory* rec, const char* who)
+                                 const gymrs_trajectory* rec, const char* who, bool closed = false)
 {
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
+    if (closed && !e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (closed && e->table_k)
+        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
+                                                     "use gymrs_policy_actions + gymrs_step");
     if (n_steps == 0) return GYMRS_OK;
     HIP_TRY(hipSetDevice(e->device));
     StepArgs a = step_args(e, nullptr);
@@ -1040,7 +1046,10 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
+    if (closed)
+        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags, a, r, launch_consts(e), e->policy, e->stream));
+    else
+        HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
     for (uint32_t k = 0; k < n_steps; ++k) { // the host copy of the uniform episode clock (Pendulum time limit)
         e->tick += 1;
@@ -1064,6 +1073,18 @@ gymrs_status gymrs_rollout_record(gymrs_engine* e, uint32_t n_steps, uint64_t ac
 {
     if (!out) return fail(GYMRS_EINVAL, "gymrs_rollout_record: trajectory is NULL");
     return rollout_impl(e, n_steps, action_seed, action_t0, out, "gymrs_rollout_record");
+}
+
+gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps)
+{
+    return rollout_impl(e, n_steps, 0, 0, nullptr, "gymrs_rollout_policy", true);
+}
+
+gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, const gymrs_trajectory* out)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: NULL engine");
+    if (!out) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: trajectory is NULL");
+    return rollout_impl(e, n_steps, 0, 0, out, "gymrs_rollout_policy_record", true);
 }
 
 gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)

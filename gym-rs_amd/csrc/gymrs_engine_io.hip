@@ -649,6 +649,91 @@ gymrs_status gymrs_fill_actions(gymrs_engine* e, void* actions_dev, uint64_t see
     return GYMRS_OK;
 }
 
+// ---- closed-loop rollouts: the policy set --------------------------------------------------------------------------------
+gymrs_status gymrs_policy_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats)
+{
+    if (!n_floats) return fail(GYMRS_EINVAL, "gymrs_policy_size: n_floats is NULL");
+    if (kind != GYMRS_CARTPOLE && kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, "gymrs_policy_size: policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_policy_size: hidden must be <= 64");
+    *n_floats = policy_floats(kind, hidden);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_policy: NULL engine");
+    if (!d) { // remove the policy (launches already enqueued still read the buffer: wait for them)
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipFree(e->policy_dev));
+        e->policy_dev = nullptr;
+        e->policy_capacity = 0;
+        e->policy = PolicyArgs{};
+        return GYMRS_OK;
+    }
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, "gymrs_set_policy: policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (d->hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_set_policy: hidden must be <= 64");
+    if (d->n_policies == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: n_policies must be >= 1");
+    if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: lanes_per_policy must be >= 1");
+    if (!weights_host) return fail(GYMRS_EINVAL, "gymrs_set_policy: weights_host is NULL");
+    const uint64_t stride = policy_floats(e->kind, d->hidden), total = stride * d->n_policies;
+    HIP_TRY(hipSetDevice(e->device));
+    if (total > e->policy_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipFree(e->policy_dev));
+        e->policy_dev = nullptr;
+        e->policy_capacity = 0;
+        e->policy = PolicyArgs{};
+        HIP_TRY(hipMalloc(&e->policy_dev, (size_t)total * sizeof(float)));
+        e->policy_capacity = total;
+    }
+    // stream-ordered: launches enqueued before this call read the old set; the host weights are consumed before the call returns
+    HIP_TRY(hipMemcpyAsync(e->policy_dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->policy.weights = e->policy_dev;
+    e->policy.lanes_per_policy = d->lanes_per_policy;
+    e->policy.n_policies = d->n_policies;
+    e->policy.hidden = d->hidden;
+    e->policy.stride = (uint32_t)stride;
+    e->policy.pad_ = 0;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
+{
+    if (!e || !d_out) return fail(GYMRS_EINVAL, "gymrs_get_policy: NULL argument");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_get_policy: the engine has no policy (gymrs_set_policy)");
+    d_out->hidden = e->policy.hidden;
+    d_out->n_policies = e->policy.n_policies;
+    d_out->lanes_per_policy = e->policy.lanes_per_policy;
+    if (!weights_out && capacity_floats == 0) return GYMRS_OK; // a query of the description
+    const uint64_t total = (uint64_t)e->policy.stride * e->policy.n_policies;
+    if (!weights_out || capacity_floats < total) return fail(GYMRS_EINVAL, "gymrs_get_policy: capacity_floats is smaller than the policy set");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(weights_out, e->policy_dev, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
+}
+
+gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
+{
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_weights_ptr: NULL argument");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_policy_weights_ptr: the engine has no policy (gymrs_set_policy)");
+    *dev_out = e->policy_dev;
+    if (n_floats) *n_floats = (uint64_t)e->policy.stride * e->policy.n_policies;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev)
+{
+    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: NULL argument");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: the engine has no policy (gymrs_set_policy)");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_policy_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->policy, e->stream));
+    return GYMRS_OK;
+}
+
 // ---- the pub physics fields after construction -------------------------------------------------------------------
 gymrs_status gymrs_set_params(gymrs_engine* e, const void* params)
 {

@@ -168,6 +168,11 @@ struct gymrs_engine {
     uint16_t* param_index = nullptr;         // [n] the row of every lane, allocated on first use
     std::vector<unsigned char> table_params; // the table_k rows as the caller set them (f64 gymrs_<kind>_params, back to back)
     TableConsts tconsts{};                   // the by-value constants of a table launch
+    // The policy set of the closed-loop calls (gymrs_set_policy): `policy` is what the policy kernels get by value, policy_dev the
+    // engine-owned device buffer policy.weights points to (NULL = no policy).  Not part of clone or snapshot.
+    PolicyArgs policy{};
+    float* policy_dev = nullptr;
+    uint64_t policy_capacity = 0; // floats policy_dev holds
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };

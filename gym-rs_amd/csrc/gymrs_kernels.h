@@ -291,4 +291,31 @@ hipError_t launch_stats(const StatsArgs& a, int mode, hipStream_t stream);
 // device words of scratch; the result goes to host_out2 (device-visible host memory): [0] = the age, then [1] = seq.
 hipError_t launch_max_age(const uint32_t* ep_start, uint64_t n, uint32_t tick_ref, uint32_t* partials, uint32_t* host_out2, uint32_t seq,
                           hipStream_t stream);
+
+// ---- closed-loop rollouts (gymrs_set_policy) --------------------------------------------------------------------------------
+// A policy set on the device: n_policies policies of `stride` floats back to back (the layout of include/gymrs_amd.h); lane i
+// of the batch (GLOBAL id) uses policy (i / lanes_per_policy) % n_policies.  Passed by value next to the other kernel arguments
+// of the policy kernels (gymrs_rollout_policy.hip); the launch arguments of every other kernel keep their layout.
+struct PolicyArgs {
+    const float* weights;
+    uint64_t lanes_per_policy; // >= 1
+    uint32_t n_policies;       // >= 1
+    uint32_t hidden;           // H: 0 = affine, else the width of the one hidden ReLU layer (<= kMaxPolicyHidden)
+    uint32_t stride;           // S = policy_floats(kind, hidden)
+    uint32_t pad_;
+};
+constexpr uint32_t kMaxPolicyHidden = 64;
+// S: floats of one policy; 0 for an env kind that takes none (Pendulum: a Box action)
+inline uint64_t policy_floats(gymrs_env_kind kind, uint32_t hidden)
+{
+    const uint64_t d = kind == GYMRS_CARTPOLE ? 4 : 2, a = kind == GYMRS_CARTPOLE ? 2 : 3;
+    if (kind != GYMRS_CARTPOLE && kind != GYMRS_MOUNTAIN_CAR) return 0;
+    return hidden == 0 ? a * (d + 1) : (uint64_t)hidden * (d + 1) + a * ((uint64_t)hidden + 1);
+}
+// actions[i] = policy(observation of lane i) for the n lanes whose observation rows are s[0 .. obs_dim)
+hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, void* actions, uint64_t n, uint64_t gid0, const PolicyArgs& p,
+                                 hipStream_t stream);
+// launch_rollout with the policy as the action source (r.action_seed / action_t0 / n_actions are not read)
+hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                 const PolicyArgs& p, hipStream_t stream);
 } // namespace gymrs

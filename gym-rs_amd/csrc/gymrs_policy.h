@@ -1,0 +1,141 @@
+// gymrs_policy.h -- evaluation of a small policy (affine, or one hidden ReLU layer) on the observation tile of a work-item:
+// shared by policy_actions_kernel and the closed-loop rollout kernel (gymrs_rollout_policy.hip).  gfx950 device code only.
+//
+// The arithmetic is fixed to the bit (include/gymrs_amd.h, "closed-loop rollouts"): every multiply-add is ONE fused
+// v_fma_f32 in the order written there, the ReLU is a compare-select (NaN and -0 give +0), the action is the first maximum
+// (a NaN never wins).  Nothing here may be contracted or reordered; the library is built with -ffp-contract=off.
+//
+// Where the weights come from is decided per wave, wave-uniformly (UNI):
+//   * every lane of the wave uses the same policy: the weights are wave-uniform operands, fetched through the scalar path
+//     (loads from the constant address space at a wave-uniform address) straight into SGPRs, a few rows of the hidden layer at
+//     a time: up to 450 floats do not live in registers across a step.
+//   * lanes of one wave use different policies (e.g. lanes_per_policy = 1): every lane gathers its own weights through the
+//     vector memory path from the table, which a population of small policies keeps in the L2.
+// Both give the same bits: the same operations on the same values.
+#pragma once
+#include "gymrs_tile.h"
+
+namespace gymrs {
+
+// Which policy the VEC lanes of a work-item use: lane (g0 + k) of the batch uses policy ((g0 + k) / lanes_per_policy) %
+// n_policies.  Two 64-bit divisions per work-item and launch, the other lanes follow by counting.  `uniform` (wave-uniform):
+// the 64 * VEC lanes of this wavefront all use pol[0].  Must be called with every work-item of the wave active.
+template <int VEC>
+__device__ __forceinline__ void policy_select(const PolicyArgs& p, uint64_t g0, uint32_t (&pol)[VEC], bool& uniform)
+{
+    const uint64_t q0 = g0 / p.lanes_per_policy;
+    uint64_t r = g0 - q0 * p.lanes_per_policy;
+    uint32_t m = (uint32_t)(q0 % p.n_policies);
+    // the wave's first lane is lane 0 of its first work-item: how many lanes its block of lanes_per_policy still has
+    const uint32_t r_lo = __builtin_amdgcn_readfirstlane((uint32_t)r), r_hi = __builtin_amdgcn_readfirstlane((uint32_t)(r >> 32));
+    const uint64_t r_first = ((uint64_t)r_hi << 32) | r_lo;
+    uniform = p.n_policies == 1 || p.lanes_per_policy - r_first >= (uint64_t)(64 * VEC);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        pol[k] = m;
+        if (++r == p.lanes_per_policy) {
+            r = 0;
+            if (++m == p.n_policies) m = 0;
+        }
+    }
+}
+
+// The weights as a work-item reads them.  UNI: one wave-uniform base in the constant address space (scalar loads);
+// else one policy index per lane (vector loads from the table).
+template <int VEC, bool UNI>
+struct PolicyWeights;
+template <int VEC>
+struct PolicyWeights<VEC, true> {
+    typedef const __attribute__((address_space(4))) float* Ptr;
+    Ptr w;
+    __device__ __forceinline__ PolicyWeights(const PolicyArgs& p, const uint32_t (&pol)[VEC])
+    {
+        const uint64_t addr = reinterpret_cast<uint64_t>(p.weights) + (uint64_t)__builtin_amdgcn_readfirstlane(pol[0]) * p.stride * sizeof(float);
+        w = reinterpret_cast<Ptr>(addr);
+    }
+    __device__ __forceinline__ float operator()(int, uint32_t i) const { return w[i]; }
+};
+template <int VEC>
+struct PolicyWeights<VEC, false> {
+    const float* __restrict__ base;
+    uint32_t stride;
+    uint32_t pol[VEC];
+    __device__ __forceinline__ PolicyWeights(const PolicyArgs& p, const uint32_t (&pol_)[VEC]) : base(p.weights), stride(p.stride)
+    {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) pol[k] = pol_[k];
+    }
+    __device__ __forceinline__ float operator()(int k, uint32_t i) const { return base[(uint64_t)pol[k] * stride + i]; }
+};
+
+// The actions of the VEC lanes of a work-item from their observations x[j].v[k] (D rows in gymrs_obs_ptrs order).  The hidden
+// layer is consumed unit by unit: A accumulators and one temporary per lane, whatever H is; its loop stays rolled (four
+// units per trip), so H = 64 costs no more code than H = 4.
+template <class Env, int VEC, bool UNI>
+__device__ __forceinline__ void policy_eval(const PolicyWeights<VEC, UNI>& W, uint32_t H, const Vec<float, VEC> (&x)[Env::kState],
+                                            Vec<uint8_t, VEC>& act)
+{
+    constexpr int D = Env::kState, A = (int)Env::kActions;
+    static_assert(A >= 2 && sizeof(typename Env::Action) == 1, "policies are for the Discrete envs");
+    float y[A][VEC];
+    if (H == 0) { // affine: W[A][D], b[A]
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) y[a][k] = W(k, A * D + a);
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) y[a][k] = __builtin_fmaf(W(k, a * D + j), x[j].v[k], y[a][k]);
+            }
+        }
+    } else { // W1[H][D], b1[H], W2[A][H], b2[A]
+        const uint32_t o_b1 = H * D, o_w2 = o_b1 + H, o_b2 = o_w2 + A * H;
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) y[a][k] = W(k, o_b2 + a);
+        }
+        constexpr int kUnits = UNI ? 4 : 1; // gathered: one unit's 1 + D + A vector loads per lane in flight, not four units' weights
+#pragma unroll kUnits
+        for (uint32_t h = 0; h < H; ++h) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                float z = W(k, o_b1 + h);
+#pragma unroll
+                for (int j = 0; j < D; ++j) z = __builtin_fmaf(W(k, h * D + j), x[j].v[k], z);
+                const float r = (z > 0.0f) ? z : 0.0f;
+#pragma unroll
+                for (int a = 0; a < A; ++a) y[a][k] = __builtin_fmaf(W(k, o_w2 + a * H + h), r, y[a][k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        uint8_t best = 0;
+        float yb = y[0][k];
+#pragma unroll
+        for (int a = 1; a < A; ++a) {
+            if (y[a][k] > yb) {
+                yb = y[a][k];
+                best = (uint8_t)a;
+            }
+        }
+        act.v[k] = best;
+    }
+}
+
+// The action source of rollout_block (gymrs_rollout_impl.h) that closes the loop: d.act from d.st.
+template <class Env, int VEC, bool UNI>
+struct PolicyActions {
+    static constexpr bool kPolicy = true;
+    PolicyWeights<VEC, UNI> w;
+    uint32_t hidden;
+    __device__ __forceinline__ PolicyActions(const PolicyArgs& p, const uint32_t (&pol)[VEC]) : w(p, pol), hidden(p.hidden) {}
+    __device__ __forceinline__ void fill(const Vec<float, VEC> (&st)[Env::kState], Vec<uint8_t, VEC>& act) const
+    {
+        policy_eval<Env, VEC, UNI>(w, hidden, st, act);
+    }
+};
+
+} // namespace gymrs

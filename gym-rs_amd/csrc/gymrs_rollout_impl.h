@@ -15,9 +15,14 @@ namespace gymrs {
 // REC (gymrs_rollout_record): additionally every step's observation, action, reward and flags are written to
 // trajectory buffers -- what a random-policy data collection loop keeps.  Then HBM sees 22 B per CartPole
 // lane-step (no state re-read, no launch per step) instead of 38 B + a launch + an action-generation kernel.
-template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC>
+// Src = where a step's actions come from: RandomActions (the Philox draws of gymrs_fill_actions, below), or a source with
+// kPolicy that computes d.act from d.st (PolicyActions, gymrs_policy.h: gymrs_rollout_policy).
+struct RandomActions {
+    static constexpr bool kPolicy = false;
+};
+template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC, class Src = RandomActions>
 __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, const typename Env::Consts& c,
-                                              ResetLds<Env, VEC, kBlock>& lds)
+                                              ResetLds<Env, VEC, kBlock>& lds, const Src& src = Src())
 {
     constexpr int kVec = VEC;
     using R = TileRegs<Env, VEC, FLAGS>;
@@ -48,7 +53,9 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
     for (uint32_t k = 0; k < r.n_steps; ++k) {
         const uint64_t t = r.action_t0 + k;
         const uint64_t slot = kDiscrete ? (t >> 1) : t; // Discrete: a block serves two steps (16-bit halves)
-        if (aligned) {
+        if constexpr (Src::kPolicy) {
+            src.fill(d.st, d.act);
+        } else if (aligned) {
             if (!kDiscrete || k == 0 || (t & 1u) == 0) {
 #pragma unroll
                 for (int b = 0; b < kBlocks; ++b) blk[b] = action_block(r.action_seed, gid + 4 * b, slot);

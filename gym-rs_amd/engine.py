@@ -65,6 +65,11 @@ class Trajectory(C.Structure):
                 ("truncated", C.c_void_p), ("lane_stride", C.c_uint64)]
 
 
+class PolicyDesc(C.Structure):
+    """``gymrs_policy_desc`` (include/gymrs_amd.h)."""
+    _fields_ = [("hidden", C.c_uint32), ("n_policies", C.c_uint32), ("lanes_per_policy", C.c_uint64)]
+
+
 _PARAMS = {CARTPOLE: CartPoleParams, MOUNTAIN_CAR: MountainCarParams, PENDULUM: PendulumParams}
 _STATE_DIM = {CARTPOLE: 4, MOUNTAIN_CAR: 2, PENDULUM: 2}
 _OBS_DIM = {CARTPOLE: 4, MOUNTAIN_CAR: 2, PENDULUM: 3}
@@ -76,6 +81,15 @@ def default_params(kind: int):
     p = _PARAMS[kind]()
     _check(lib, lib.gymrs_default_params(kind, C.byref(p)))
     return p
+
+
+def policy_size(kind: int, hidden: int = 0) -> int:
+    """Floats of one policy of ``gymrs_set_policy``: affine (``hidden`` = 0) ``W[A][D], b[A]``, else ``W1[H][D], b1[H], W2[A][H],
+    b2[A]`` (host only, no GPU).  Raises for Pendulum and ``hidden`` > 64."""
+    lib = load_library()
+    n = C.c_uint64()
+    _check(lib, lib.gymrs_policy_size(int(kind), int(hidden), C.byref(n)))
+    return n.value
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -427,6 +441,54 @@ class BatchedEngine:
 
     def fill_actions(self, actions_dev: int, seed: int, t: int) -> None:
         _check(self._lib, self._lib.gymrs_fill_actions(self._h, C.c_void_p(actions_dev), int(seed), int(t)))
+
+    # -- closed-loop rollouts: a small policy evaluated inside the kernel (gymrs_set_policy) -----------
+    def set_policy(self, weights, hidden: int = 0, lanes_per_policy: int = 1) -> None:
+        """Install a policy set: ``weights`` is an array of shape (n_policies, policy_size(kind, hidden)) (or one flat policy),
+        f32, laid out as include/gymrs_amd.h says; lane i uses policy ((global_env_offset + i) // lanes_per_policy) % n_policies.
+        ``None`` removes the policy.  Touches no lane state, tick or statistics."""
+        if weights is None:
+            _check(self._lib, self._lib.gymrs_set_policy(self._h, None, None))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        size = policy_size(self.kind, hidden)
+        if w.size == 0 or w.size % size != 0:
+            raise ValueError(f"weights must hold a whole number (>= 1) of policies of {size} floats, got {w.size}")
+        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_policy))
+        _check(self._lib, self._lib.gymrs_set_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+
+    def get_policy(self):
+        """(weights of shape (n_policies, policy_size), hidden, lanes_per_policy) as set (synchronising)."""
+        desc = PolicyDesc()
+        _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
+        size = policy_size(self.kind, desc.hidden)
+        w = np.empty((desc.n_policies, size), dtype=np.float32)
+        _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size))
+        return w, int(desc.hidden), int(desc.lanes_per_policy)
+
+    def policy_weights_ptr(self) -> Tuple[int, int]:
+        """(device address, number of floats) of the policy set: zero-copy; a kernel on the engine's stream may rewrite the
+        weights between two launches.  Valid until the next set_policy or close."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.gymrs_policy_weights_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def policy_actions(self, actions_dev: int) -> None:
+        """Write the policy's uint8 action for every lane's current observation to ``actions_dev`` (one launch)."""
+        _check(self._lib, self._lib.gymrs_policy_actions(self._h, C.c_void_p(actions_dev)))
+
+    def rollout_policy(self, n_steps: int) -> None:
+        """``n_steps`` closed-loop steps of every lane in one kernel launch: the effect of ``policy_actions(buf); step(buf)``
+        n_steps times, bit for bit."""
+        _check(self._lib, self._lib.gymrs_rollout_policy(self._h, int(n_steps)))
+
+    def rollout_policy_record(self, n_steps: int, *, obs: int, actions: int, reward: int, done: int, truncated: int = 0,
+                              lane_stride: Optional[int] = None) -> None:
+        """``rollout_policy`` that also keeps the trajectory; buffers as for ``rollout_record`` (``actions`` = the policy's)."""
+        stride = int(lane_stride) if lane_stride is not None else (self.n_envs + 15) // 16 * 16
+        traj = Trajectory(C.c_void_p(obs), C.c_void_p(actions), C.c_void_p(reward), C.c_void_p(done),
+                          C.c_void_p(truncated or None), stride)
+        _check(self._lib, self._lib.gymrs_rollout_policy_record(self._h, int(n_steps), C.byref(traj)))
 
     def tick(self) -> Tuple[int, int]:
         t, s = C.c_uint64(), C.c_uint64()

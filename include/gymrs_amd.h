@@ -374,6 +374,55 @@ gymrs_status gymrs_set_param_index(gymrs_engine* e, uint64_t first, uint64_t cou
 gymrs_status gymrs_get_param_index(gymrs_engine* e, uint64_t first, uint64_t count, uint16_t* host_out);
 gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_out);
 
+/* ---- closed-loop rollouts: a small policy evaluated inside the kernel (CartPole, MountainCar) ----------------------------- */
+/* gymrs_rollout plays the random policy only.  With a policy set, gymrs_rollout_policy advances n_steps steps in ONE launch with
+ * actions computed from each lane's own observation, step after step, state in registers: population evaluation (evolution
+ * strategies, random search, PBT) and on-policy data collection with a small policy (gymrs_rollout_policy_record).
+ * The policy, defined to the bit.  D = observation size (4 / 2), A = number of actions (2 / 3), H = hidden width, 0 <= H <= 64;
+ * all f32; x[0..D) = the lane's observation in gymrs_obs_ptrs order; fmaf = the fused multiply-add with ONE rounding, nothing else
+ * is contracted or reordered:
+ *     H == 0 (affine):    y[a] = b[a];  for j = 0..D-1: y[a] = fmaf(W[a][j], x[j], y[a])            for a = 0..A-1
+ *     H  > 0 (one layer): y[a] = b2[a]                                                              for a = 0..A-1
+ *                         for h = 0..H-1:
+ *                             z = b1[h];  for j = 0..D-1: z = fmaf(W1[h][j], x[j], z)
+ *                             r = (z > 0.0f) ? z : 0.0f                 (compare-select: NaN and -0 give +0)
+ *                             for a = 0..A-1: y[a] = fmaf(W2[a][h], r, y[a])
+ *     action = 0;  for a = 1..A-1: if (y[a] > y[action]) action = a     (first maximum; NaN never wins)
+ * One policy is S consecutive floats, row-major: H == 0: W[A][D], b[A] (S = A*(D+1): 10 / 9); H > 0: W1[H][D], b1[H], W2[A][H],
+ * b2[A] (S = H*(D+1) + A*(H+1); CartPole H = 16: 114).  gymrs_policy_size returns S (host only, no GPU; GYMRS_EINVAL for
+ * Pendulum and hidden > 64).
+ * A policy set is n_policies >= 1 policies back to back (n_policies * S floats) and a block size lanes_per_policy >= 1: lane i
+ * of the engine uses policy ((global_env_offset + i) / lanes_per_policy) % n_policies -- keyed by the global id like the reset
+ * and action streams, so the result does not depend on how a batch is cut into engines.
+ *   - gymrs_set_policy copies the set to an engine-owned device buffer in stream order (launches enqueued before it use the old
+ *     set; the caller may free weights_host on return).  d == NULL removes the policy.  GYMRS_EINVAL: Pendulum, hidden > 64,
+ *     n_policies == 0, lanes_per_policy == 0, NULL weights.  Non-finite weights are legal (the definition above says what they
+ *     do).  It touches no lane state, tick or statistics.  gymrs_get_policy reads the set back (weights_out NULL with capacity 0
+ *     only asks for the description; synchronising).
+ *   - gymrs_policy_weights_ptr: zero-copy device view of the n_policies * S floats (*n_floats, may be NULL) under the stream
+ *     rules of the other *_ptr views: a learner on the engine's stream rewrites weights in place and the next launch reads
+ *     them.  Valid until the next gymrs_set_policy or destroy.
+ *   - gymrs_policy_actions: one launch; writes n_envs uint8_t actions computed from the current observations to actions_dev (the
+ *     per-step counterpart, as gymrs_fill_actions is to gymrs_rollout).  It only reads observations, so it also works while a
+ *     parameter table is active.
+ *   - gymrs_rollout_policy(e, K): exactly the effect of `for k in 0..K: gymrs_policy_actions(e, buf); gymrs_step(e, buf);` in ONE
+ *     launch: state, reward / done / truncated of the last step, final observations, statistics, steps_beyond_terminated, tick.
+ *     Every flag set gymrs_rollout accepts, both lanes_per_thread values, any n_envs and any global_env_offset.  K == 0 is a
+ *     no-op.  gymrs_rollout_policy_record is to it what gymrs_rollout_record is to gymrs_rollout (same gymrs_trajectory, same
+ *     buffer checks, same rows; the `actions` rows hold the policy's actions).
+ *   - Without a policy set, the three stepping calls, gymrs_get_policy and gymrs_policy_weights_ptr return GYMRS_EINVAL.  While a
+ *     parameter table is active, gymrs_rollout_policy / _record return GYMRS_EINVAL and say so (the per-step loop covers it).
+ *   - The policy is NOT part of gymrs_engine_clone or of a snapshot (its bytes and version are unchanged): set it again on the
+ *     clone or the restored engine.  The sharded layer (gymrs_sharded_*) has no policy calls yet. */
+typedef struct { uint32_t hidden; uint32_t n_policies; uint64_t lanes_per_policy; } gymrs_policy_desc;
+gymrs_status gymrs_policy_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats);
+gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host);
+gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats);
+gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats);
+gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev);
+gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps);
+gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, const gymrs_trajectory* out);
+
 /* ---- `#[derive(Serialize)]` view (core.rs:25; cartpole.rs:51-87, mountain_car.rs:46-80) -------- */
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible
  * fields in declaration order with the reference's field names -- CartPole: action_space, observation_space

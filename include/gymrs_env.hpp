@@ -193,6 +193,36 @@ public:
         return out;
     }
     void lane_params(std::uint64_t lane, void* params_out) { check(gymrs_get_lane_params(e_, lane, params_out)); }
+    // closed-loop rollouts (gymrs_set_policy): n_policies policies of policy_size(kind, hidden) floats back to back; lane i uses
+    // policy ((global_env_offset + i) / lanes_per_policy) % n_policies; clear_policy() removes the set
+    static std::uint64_t policy_size(gymrs_env_kind kind, std::uint32_t hidden)
+    {
+        std::uint64_t n = 0;
+        check(gymrs_policy_size(kind, hidden, &n));
+        return n;
+    }
+    void set_policy(const float* weights_host, std::uint32_t hidden, std::uint32_t n_policies, std::uint64_t lanes_per_policy)
+    {
+        const gymrs_policy_desc d{hidden, n_policies, lanes_per_policy};
+        check(gymrs_set_policy(e_, &d, weights_host));
+    }
+    void clear_policy() { check(gymrs_set_policy(e_, nullptr, nullptr)); }
+    gymrs_policy_desc policy(float* weights_out = nullptr, std::uint64_t capacity_floats = 0)
+    {
+        gymrs_policy_desc d{};
+        check(gymrs_get_policy(e_, &d, weights_out, capacity_floats));
+        return d;
+    }
+    float* policy_weights_view(std::uint64_t* n_floats = nullptr)
+    {
+        float* p = nullptr;
+        check(gymrs_policy_weights_ptr(e_, &p, n_floats));
+        return p;
+    }
+    void policy_actions(void* actions_dev) { check(gymrs_policy_actions(e_, actions_dev)); }
+    // n_steps of (policy_actions, step) fused into one launch; the second form keeps the trajectory
+    void rollout_policy(std::uint32_t n_steps) { check(gymrs_rollout_policy(e_, n_steps)); }
+    void rollout_policy_record(std::uint32_t n_steps, const gymrs_trajectory& out) { check(gymrs_rollout_policy_record(e_, n_steps, &out)); }
     // `#[derive(Serialize)]` view of the reference env lane `lane` stands for (core.rs:25)
     std::string to_json(std::uint64_t lane = 0)
     {
