@@ -2,14 +2,13 @@
 share code with them: the CPU f32 twin (oracle.bindings.TwinEngine) stepped with actions the TEST computes from the twin's
 observations by its own restatement of the policy, tests/cpp/policy_ref.c (plain C, libm's fmaf, gcc -O2 -ffp-contract=off).
 fmaf is correctly rounded and so is v_fma_f32: every comparison is bit for bit, no tolerance and no skipped lanes."""
-import ctypes as C
 import time
-from pathlib import Path
 
+import closed_loop_ref
 import numpy as np
 import pytest
-import spawn_server
 import torch
+from closed_loop_ref import make_weights
 
 from oracle.bindings import TwinEngine
 
@@ -26,47 +25,8 @@ def bits(a):
 
 
 @pytest.fixture(scope="module")
-def policy_ref(tmp_path_factory):
-    out = tmp_path_factory.mktemp("policy_ref") / "libpolicy_ref.so"
-    src = Path(__file__).resolve().parent / "cpp" / "policy_ref.c"
-    spawn_server.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", str(src), "-o", str(out), "-lm"], check=True)
-    lib = C.CDLL(str(out))
-    lib.policy_ref.restype = None
-    lib.policy_ref.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-
-    def ref(kind, hidden, weights, lanes_per_policy, gid0, obs):
-        d, a = DIMS[kind]
-        w = np.ascontiguousarray(weights, np.float32)
-        obs = np.ascontiguousarray(obs, np.float32)
-        assert obs.shape[0] == d and w.size % size_of(kind, hidden) == 0
-        n = obs.shape[1]
-        act = np.empty(n, np.uint8)
-        lib.policy_ref(d, a, hidden, w.size // size_of(kind, hidden), lanes_per_policy, gid0, n, w.ctypes.data, obs.ctypes.data, act.ctypes.data)
-        return act
-
-    return ref
-
-
-def size_of(kind, hidden):
-    d, a = DIMS[kind]
-    return a * (d + 1) if hidden == 0 else hidden * (d + 1) + a * (hidden + 1)
-
-
-def make_weights(kind, hidden, n_policies, seed):
-    """seeded normals, f32: scale 1 (affine), 1 / sqrt(fan_in) (hidden)"""
-    d, a = DIMS[kind]
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n_policies):
-        if hidden == 0:
-            parts = [rng.standard_normal(a * d), rng.standard_normal(a)]
-        else:
-            parts = [rng.standard_normal(hidden * d) / np.sqrt(d), rng.standard_normal(hidden) / np.sqrt(d),
-                     rng.standard_normal(a * hidden) / np.sqrt(hidden), rng.standard_normal(a) / np.sqrt(hidden)]
-        out.append(np.concatenate(parts).astype(np.float32))
-    w = np.stack(out)
-    assert w.shape == (n_policies, size_of(kind, hidden))
-    return w
+def policy_ref():
+    return closed_loop_ref.policy_ref  # (kind, hidden, weights, lanes_per_policy, gid0, obs) -> actions; built from cpp/policy_ref.c
 
 
 def gpu_actions(eng, buf):
