@@ -120,6 +120,14 @@ def lanes_per_copy(n, vec, gid0, n_policies, lanes_per_policy):
     return {COPIES[c]: int(k) for c, k in enumerate(count) if k}
 
 
+def final_obs_after(tw0, state, act):
+    """The observation the flags = 0 twin tw0 shows after stepping `state` with `act`: what a lane whose step ends an episode keeps
+    as its final observation (the auto-reset twin has re-armed that lane by then)"""
+    tw0.set_state(state)
+    tw0.step(act)
+    return tw0.get_obs()
+
+
 def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, reset_seed, schedule, prepare=None):
     """What an engine of n lanes at global offset gid0 holds after each launch of `schedule` (steps per launch) of closed-loop
     stepping from reset(reset_seed).  `weights`: one policy set, or a list of one set per launch (a learner rewriting them between
@@ -165,13 +173,12 @@ def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, r
             alone = [policy_ref(kind, hidden, w[i:i + 1], 1, 0, obs) for i in range(len(w))]
             for x in alone[1:]:
                 disagree |= x != alone[0]
-            tw0.set_state(tw.get_state())
-            tw0.step(act)
+            last = final_obs_after(tw0, tw.get_state(), act)
             tw.step(act)
             r, dn, tr = tw.get_result()
             ended = (dn | tr) != 0
             if flags & A:  # (the engine keeps final observations only with auto-reset)
-                final[:, ended] = tw0.get_obs()[:, ended]
+                final[:, ended] = last[:, ended]
             episodes += ended
             tick += 1
             for row, x in zip((rec.obs, rec.actions, rec.reward, rec.done, rec.truncated), (tw.get_obs(), act, r, dn, tr)):
