@@ -225,6 +225,30 @@ impl Engine {
         check(unsafe { ffi::gymrs_rollout_policy(self.raw, n_steps) });
     }
 
+    /// `rollout_policy` that also adds every step's reward / done / truncated to the record of the lane's policy.
+    pub fn rollout_policy_fitness(&mut self, n_steps: u32) {
+        check(unsafe { ffi::gymrs_rollout_policy_fitness(self.raw, n_steps) });
+    }
+
+    /// The records of policies `first..first+count` (synchronising).
+    pub fn policy_fitness(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyFitness> {
+        let mut out = vec![ffi::GymrsPolicyFitness::default(); count as usize];
+        check(unsafe { ffi::gymrs_get_policy_fitness(self.raw, first, count, out.as_mut_ptr()) });
+        out
+    }
+
+    /// Zero-copy device view of the records and their number; valid until the next `set_policy` or drop.
+    pub fn policy_fitness_ptr(&mut self) -> (*mut ffi::GymrsPolicyFitness, u32) {
+        let (mut p, mut n) = (std::ptr::null_mut(), 0u32);
+        check(unsafe { ffi::gymrs_policy_fitness_ptr(self.raw, &mut p, &mut n) });
+        (p, n)
+    }
+
+    /// Zero the records (in stream order).
+    pub fn policy_fitness_clear(&mut self) {
+        check(unsafe { ffi::gymrs_policy_fitness_clear(self.raw) });
+    }
+
     /// Wait for everything queued on the engine's stream.
     pub fn sync(&mut self) {
         check(unsafe { ffi::gymrs_sync(self.raw) });

@@ -79,6 +79,16 @@ pub struct GymrsPolicyDesc {
     pub lanes_per_policy: u64,
 }
 
+/// `gymrs_policy_fitness`: one policy's counters (`gymrs_rollout_policy_fitness`, include/gymrs_amd.h "per-policy fitness"), 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct GymrsPolicyFitness {
+    pub reward_sum: i64,
+    pub episodes: u64,
+    pub done: u64,
+    pub truncated: u64,
+}
+
 extern "C" {
     pub fn gymrs_abi_version() -> c_int;
     pub fn gymrs_last_error() -> *const c_char;
@@ -151,6 +161,10 @@ extern "C" {
     pub fn gymrs_policy_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;
     pub fn gymrs_rollout_policy(e: *mut GymrsEngine, n_steps: u32) -> c_int;
     pub fn gymrs_rollout_policy_record(e: *mut GymrsEngine, n_steps: u32, out: *const Trajectory) -> c_int;
+    pub fn gymrs_rollout_policy_fitness(e: *mut GymrsEngine, n_steps: u32) -> c_int;
+    pub fn gymrs_policy_fitness_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyFitness, n_policies: *mut u32) -> c_int;
+    pub fn gymrs_get_policy_fitness(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
+    pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_env_json(e: *mut GymrsEngine, lane: u64, buf: *mut c_char, cap: u64, needed: *mut u64) -> c_int;
     pub fn gymrs_params_from_json(kind: c_int, json: *const c_char, params: *mut c_void, state: *mut f64, state_dim: *mut c_int) -> c_int;
     // ABI 3: one batch over several GPUs in ONE process (one engine + one native host thread per block)
@@ -187,6 +201,11 @@ extern "C" {
     ) -> c_int;
     pub fn gymrs_sharded_fill_actions(h: *mut GymrsSharded, actions_dev: *const *mut c_void, seed: u64, t: u64) -> c_int;
     pub fn gymrs_sharded_rollout(h: *mut GymrsSharded, n_steps: u32, action_seed: u64, action_t0: u64) -> c_int;
+    pub fn gymrs_sharded_set_policy(h: *mut GymrsSharded, d: *const GymrsPolicyDesc, weights_host: *const f32) -> c_int;
+    pub fn gymrs_sharded_rollout_policy(h: *mut GymrsSharded, n_steps: u32) -> c_int;
+    pub fn gymrs_sharded_rollout_policy_fitness(h: *mut GymrsSharded, n_steps: u32) -> c_int;
+    pub fn gymrs_sharded_get_policy_fitness(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
+    pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_set_params(h: *mut GymrsSharded, params: *const c_void) -> c_int;
     pub fn gymrs_sharded_sync(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_stats(h: *mut GymrsSharded, out4: *mut f64) -> c_int;

@@ -112,6 +112,38 @@ impl ShardedEngine {
         check(unsafe { ffi::gymrs_sharded_rollout(self.raw, n_steps, action_seed, action_t0) });
     }
 
+    /// The same policy set on every block (`gymrs_sharded_set_policy`): `weights` holds `n_policies` policies of
+    /// `gymrs_policy_size(kind, hidden)` floats back to back, keyed by global lane ids.
+    pub fn set_policy(&mut self, weights: &[f32], hidden: u32, n_policies: u32, lanes_per_policy: u64) {
+        let mut size = 0u64;
+        check(unsafe { ffi::gymrs_policy_size(self.kind.raw(), hidden, &mut size) });
+        assert_eq!(weights.len() as u64, size * n_policies as u64);
+        let d = ffi::GymrsPolicyDesc { hidden, n_policies, lanes_per_policy };
+        check(unsafe { ffi::gymrs_sharded_set_policy(self.raw, &d, weights.as_ptr()) });
+    }
+
+    /// `n_steps` closed-loop steps of every lane fused into one launch per block.
+    pub fn rollout_policy(&mut self, n_steps: u32) {
+        check(unsafe { ffi::gymrs_sharded_rollout_policy(self.raw, n_steps) });
+    }
+
+    /// `rollout_policy` that also counts per-policy fitness on every block.
+    pub fn rollout_policy_fitness(&mut self, n_steps: u32) {
+        check(unsafe { ffi::gymrs_sharded_rollout_policy_fitness(self.raw, n_steps) });
+    }
+
+    /// The records of policies `first..first+count` of the whole batch: the blocks' records summed (exact; synchronising).
+    pub fn policy_fitness(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyFitness> {
+        let mut out = vec![ffi::GymrsPolicyFitness::default(); count as usize];
+        check(unsafe { ffi::gymrs_sharded_get_policy_fitness(self.raw, first, count, out.as_mut_ptr()) });
+        out
+    }
+
+    /// Zero every block's records (in stream order).
+    pub fn policy_fitness_clear(&mut self) {
+        check(unsafe { ffi::gymrs_sharded_policy_fitness_clear(self.raw) });
+    }
+
     /// Wait for every block's stream; panics like the reference's `assert!` if a step saw an action outside the action space.
     pub fn sync(&mut self) {
         check(unsafe { ffi::gymrs_sharded_sync(self.raw) });

@@ -75,6 +75,11 @@ SIGNATURES = {
     "gymrs_policy_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_rollout_policy": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gymrs_rollout_policy_record": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    # per-policy fitness (gymrs_policy_fitness: {i64 reward_sum, u64 episodes, u64 done, u64 truncated})
+    "gymrs_rollout_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gymrs_policy_fitness_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    "gymrs_get_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gymrs_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process
@@ -88,6 +93,11 @@ SIGNATURES = {
     "gymrs_sharded_step_many": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]),
     "gymrs_sharded_fill_actions": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint64, C.c_uint64]),
     "gymrs_sharded_rollout": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "gymrs_sharded_set_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gymrs_sharded_rollout_policy": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gymrs_sharded_rollout_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gymrs_sharded_get_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gymrs_sharded_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_sync": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_stats": (C.c_int, [C.c_void_p, f64p]),

@@ -515,6 +515,7 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->table_dev);
     (void)hipFree(e->param_index);
     (void)hipFree(e->policy_dev);
+    (void)hipFree(e->fitness_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     (void)hipFree(e->tick_dev);
@@ -1006,14 +1007,19 @@ gymrs_status gymrs_step(gymrs_engine* e, const void* actions_dev)
 // The caller loop of the reference's examples (examples/cartpole.rs:15-30: random action, step, reset on
 // done, accumulate the return) fused into one launch; see rollout_kernel.
 // closed = gymrs_rollout_policy: the actions come from the engine's policy set (gymrs_set_policy) instead of the Philox stream.
+// fitness = gymrs_rollout_policy_fitness: closed, and the kernel adds to the per-policy counters (same checks, same bookkeeping).
 static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
-                                 const gymrs_trajectory* rec, const char* who, bool closed = false)
+                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false)
 {
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
+    if (fitness && e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
     if (closed && !e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
     if (closed && e->table_k)
         return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
                                                      "use gymrs_policy_actions + gymrs_step");
+    if (fitness && n_steps > kMaxFitnessSteps)
+        return fail(GYMRS_EINVAL, std::string(who) + ": n_steps is above GYMRS_POLICY_FITNESS_MAX_STEPS (the in-register counters are 32 bits wide)");
     if (n_steps == 0) return GYMRS_OK;
     HIP_TRY(hipSetDevice(e->device));
     StepArgs a = step_args(e, nullptr);
@@ -1046,7 +1052,10 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    if (closed)
+    if (fitness) {
+        if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
+        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags, a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
+    } else if (closed)
         HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags, a, r, launch_consts(e), e->policy, e->stream));
     else
         HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
@@ -1078,6 +1087,11 @@ gymrs_status gymrs_rollout_record(gymrs_engine* e, uint32_t n_steps, uint64_t ac
 gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps)
 {
     return rollout_impl(e, n_steps, 0, 0, nullptr, "gymrs_rollout_policy", true);
+}
+
+gymrs_status gymrs_rollout_policy_fitness(gymrs_engine* e, uint32_t n_steps)
+{
+    return rollout_impl(e, n_steps, 0, 0, nullptr, "gymrs_rollout_policy_fitness", true, true);
 }
 
 gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, const gymrs_trajectory* out)

@@ -670,7 +670,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
         e->policy_dev = nullptr;
         e->policy_capacity = 0;
         e->policy = PolicyArgs{};
-        return GYMRS_OK;
+        return discard_policy_fitness(e);
     }
     if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
         return fail(GYMRS_EINVAL, "gymrs_set_policy: policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
@@ -680,6 +680,13 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
     if (!weights_host) return fail(GYMRS_EINVAL, "gymrs_set_policy: weights_host is NULL");
     const uint64_t stride = policy_floats(e->kind, d->hidden), total = stride * d->n_policies;
     HIP_TRY(hipSetDevice(e->device));
+    // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
+    // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
+    if (e->fitness_dev && d->n_policies == e->policy.n_policies) {
+        HIP_TRY(hipMemsetAsync(e->fitness_dev, 0, (size_t)d->n_policies * sizeof(gymrs_policy_fitness), e->stream));
+    } else if (gymrs_status st = discard_policy_fitness(e)) {
+        return st;
+    }
     if (total > e->policy_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
         HIP_TRY(hipStreamSynchronize(e->stream));
         HIP_TRY(hipFree(e->policy_dev));
@@ -731,6 +738,68 @@ gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev)
     if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: the engine has no policy (gymrs_set_policy)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_policy_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->policy, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- per-policy fitness: the table behind gymrs_rollout_policy_fitness -----------------------------------------------------
+extern "C++" {
+// A gymrs_set_policy that removes the policy or changes n_policies: the table goes (launches already enqueued still add to it: wait for them).
+GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e)
+{
+    if (!e->fitness_dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(e->fitness_dev));
+    e->fitness_dev = nullptr;
+    return GYMRS_OK;
+}
+
+// The checks the four fitness calls share, then the table: n_policies zeroed records at the first use after a gymrs_set_policy.
+GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who)
+{
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (e->fitness_dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t bytes = (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness);
+    HIP_TRY(hipMalloc(&e->fitness_dev, bytes));
+    if (hipError_t err = hipMemsetAsync(e->fitness_dev, 0, bytes, e->stream)) {
+        (void)hipFree(e->fitness_dev);
+        e->fitness_dev = nullptr;
+        HIP_TRY(err);
+    }
+    return GYMRS_OK;
+}
+} // extern "C++"
+
+gymrs_status gymrs_policy_fitness_ptr(gymrs_engine* e, gymrs_policy_fitness** dev_out, uint32_t* n_policies)
+{
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_fitness_ptr: NULL argument");
+    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_policy_fitness_ptr")) return st;
+    *dev_out = e->fitness_dev;
+    if (n_policies) *n_policies = e->policy.n_policies;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_policy_fitness(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out)
+{
+    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_policy_fitness: NULL argument");
+    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_get_policy_fitness")) return st;
+    if ((uint64_t)first + count > e->policy.n_policies) return fail(GYMRS_EINVAL, "gymrs_get_policy_fitness: first + count is beyond n_policies");
+    if (count == 0) return stream_sync_checked(e);
+    HIP_TRY(hipMemcpyAsync(host_out, e->fitness_dev + first, (size_t)count * sizeof(gymrs_policy_fitness), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
+}
+
+gymrs_status gymrs_policy_fitness_clear(gymrs_engine* e)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_policy_fitness_clear: NULL engine");
+    const bool fresh = e->fitness_dev == nullptr; // (a table that comes into being here is already zero)
+    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_policy_fitness_clear")) return st;
+    if (fresh) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemsetAsync(e->fitness_dev, 0, (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness), e->stream));
     return GYMRS_OK;
 }
 

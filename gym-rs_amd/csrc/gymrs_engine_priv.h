@@ -173,6 +173,10 @@ struct gymrs_engine {
     PolicyArgs policy{};
     float* policy_dev = nullptr;
     uint64_t policy_capacity = 0; // floats policy_dev holds
+    // The per-policy counters of gymrs_rollout_policy_fitness: policy.n_policies records, allocated (zeroed) at the first fitness
+    // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
+    // stays the same).  Not part of clone or snapshot.
+    gymrs_policy_fitness* fitness_dev = nullptr;
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };
@@ -221,3 +225,5 @@ GYMRS_HOST_INTERNAL void limit_restart(gymrs_engine* e, uint64_t bound, bool tru
 GYMRS_HOST_INTERNAL std::string aql_kernel_name(const gymrs_engine* e, uint32_t flags, int threads);
 // defined in gymrs_engine_io.hip (RCCL is resolved there, at first use)
 GYMRS_HOST_INTERNAL void comm_destroy(gymrs_engine* e);
+GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who); // the fitness calls' checks + the zeroed table
+GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e);

@@ -318,4 +318,10 @@ hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, voi
 // launch_rollout with the policy as the action source (r.action_seed / action_t0 / n_actions are not read)
 hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                  const PolicyArgs& p, hipStream_t stream);
+// launch_rollout_policy (non-recording) that also adds every step's reward / done / truncated of every lane to the record of
+// the lane's policy in fitness[n_policies] (gymrs_rollout_fitness.hip): integer atomics, once per wave and launch.  The
+// in-register accumulators are 32 bits wide: r.n_steps <= kMaxFitnessSteps (GYMRS_POLICY_FITNESS_MAX_STEPS).
+constexpr uint32_t kMaxFitnessSteps = GYMRS_POLICY_FITNESS_MAX_STEPS;
+hipError_t launch_rollout_policy_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                         const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream);
 } // namespace gymrs

@@ -20,9 +20,14 @@ namespace gymrs {
 struct RandomActions {
     static constexpr bool kPolicy = false;
 };
-template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC, class Src = RandomActions>
+// Fit = what is folded out of every step's reward / done / truncated while they are still in registers: nothing (NoFitness: every
+// line that names it compiles away), or the per-policy counters of gymrs_rollout_policy_fitness (gymrs_rollout_fitness.hip).
+struct NoFitness {
+    static constexpr bool kOn = false;
+};
+template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC, class Src = RandomActions, class Fit = NoFitness>
 __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, const typename Env::Consts& c,
-                                              ResetLds<Env, VEC, kBlock>& lds, const Src& src = Src())
+                                              ResetLds<Env, VEC, kBlock>& lds, const Src& src = Src(), Fit* fit = nullptr)
 {
     constexpr int kVec = VEC;
     using R = TileRegs<Env, VEC, FLAGS>;
@@ -84,6 +89,7 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
             if (a.truncate_all && R::AUTO) ustart = a.tick + 1;
         }
         advance_tile<Env, VEC, FLAGS, FULL, true, kBlock>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x);
+        if constexpr (Fit::kOn) fit->template step<FULL>(out, base, a.n);
         if constexpr (REC) {
             const uint64_t row = (uint64_t)k * r.rec_stride;
             constexpr int kObs = Env::kHasObsExtra ? 3 : Env::kState;
@@ -106,6 +112,7 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
         }
     }
     store_tile<Env, VEC, FLAGS, FULL, true>(a, base, d, out);
+    if constexpr (Fit::kOn) fit->flush();
     if (R::STATS && (threadIdx.x & 63u) == 0) {
         bs[0] = resets;
         if (!Env::kConstReward) {

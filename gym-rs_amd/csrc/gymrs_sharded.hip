@@ -453,6 +453,60 @@ gymrs_status gymrs_sharded_rollout(gymrs_sharded* h, uint32_t n_steps, uint64_t 
     return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_rollout(e, n_steps, action_seed, action_t0); }; });
 }
 
+// The closed-loop calls on every block: the same policy set everywhere, keyed by GLOBAL lane ids like the action stream above.
+gymrs_status gymrs_sharded_set_policy(gymrs_sharded* h, const gymrs_policy_desc* d, const float* weights_host)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_set_policy: handle is NULL");
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_policy(e, d, weights_host); }; });
+}
+
+gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_policy: handle is NULL");
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_rollout_policy(e, n_steps); }; });
+}
+
+gymrs_status gymrs_sharded_rollout_policy_fitness(gymrs_sharded* h, uint32_t n_steps)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_policy_fitness: handle is NULL");
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_rollout_policy_fitness(e, n_steps); }; });
+}
+
+gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_policy_fitness_clear: handle is NULL");
+    return h->all([](int) { return [](gymrs_engine*& e) { return gymrs_policy_fitness_clear(e); }; });
+}
+
+// Records [first, first + count) of the batch: every block's records (read by its worker), added up on the caller's thread.
+gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out)
+{
+    if (!h || !host_out) return fail(GYMRS_EINVAL, "gymrs_sharded_get_policy_fitness: NULL argument");
+    return guarded("gymrs_sharded_get_policy_fitness", [&]() -> gymrs_status {
+        const size_t k = h->w.size();
+        // (count == 0 is a range check and a synchronise on every block, as on one engine: one spare record per block keeps the pointers non-NULL)
+        std::vector<gymrs_policy_fitness> part(k * (size_t)count + k);
+        gymrs_policy_fitness* parts = part.data();
+        if (gymrs_status st = h->all([=](int r) {
+                gymrs_policy_fitness* mine = parts + (size_t)r * count;
+                return [=](gymrs_engine*& e) { return gymrs_get_policy_fitness(e, first, count, mine); };
+            }))
+            return st;
+        for (uint32_t p = 0; p < count; ++p) {
+            gymrs_policy_fitness sum = {0, 0, 0, 0};
+            for (size_t r = 0; r < k; ++r) {
+                const gymrs_policy_fitness& f = parts[r * count + p];
+                sum.reward_sum += f.reward_sum;
+                sum.episodes += f.episodes;
+                sum.done += f.done;
+                sum.truncated += f.truncated;
+            }
+            host_out[p] = sum;
+        }
+        return GYMRS_OK;
+    });
+}
+
 // `env.gravity = ...` for every lane of the batch (gymrs_set_params on every block).
 gymrs_status gymrs_sharded_set_params(gymrs_sharded* h, const void* params)
 {

@@ -65,6 +65,11 @@ class Trajectory(C.Structure):
                 ("truncated", C.c_void_p), ("lane_stride", C.c_uint64)]
 
 
+class PolicyFitness(C.Structure):
+    """``gymrs_policy_fitness`` (include/gymrs_amd.h): one policy's counters, 32 bytes."""
+    _fields_ = [("reward_sum", C.c_int64), ("episodes", C.c_uint64), ("done", C.c_uint64), ("truncated", C.c_uint64)]
+
+
 class PolicyDesc(C.Structure):
     """``gymrs_policy_desc`` (include/gymrs_amd.h)."""
     _fields_ = [("hidden", C.c_uint32), ("n_policies", C.c_uint32), ("lanes_per_policy", C.c_uint64)]
@@ -490,6 +495,34 @@ class BatchedEngine:
                           C.c_void_p(truncated or None), stride)
         _check(self._lib, self._lib.gymrs_rollout_policy_record(self._h, int(n_steps), C.byref(traj)))
 
+    # -- per-policy fitness: counters accumulated inside the closed-loop rollout kernel ------------------
+    def rollout_policy_fitness(self, n_steps: int) -> None:
+        """``rollout_policy`` that also adds every step's reward / done / truncated to the record of the lane's policy
+        (``policy_fitness``).  Leaves the engine bit for bit as ``rollout_policy`` does."""
+        _check(self._lib, self._lib.gymrs_rollout_policy_fitness(self._h, int(n_steps)))
+
+    def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The records of policies [first, first + count) as an int64 array of shape (count, 4): columns reward_sum, episodes,
+        done, truncated (synchronising).  ``count`` defaults to the rest of the set."""
+        if count is None:
+            desc = PolicyDesc()
+            _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
+            count = int(desc.n_policies) - int(first)
+        out = np.zeros((max(int(count), 0), 4), dtype=np.int64)
+        _check(self._lib, self._lib.gymrs_get_policy_fitness(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def policy_fitness_ptr(self) -> Tuple[int, int]:
+        """(device address, n_policies) of the records (``PolicyFitness``, 32 bytes each): zero-copy, under the stream rules of
+        the other views.  Valid until the next set_policy or close."""
+        p, n = C.c_void_p(), C.c_uint32()
+        _check(self._lib, self._lib.gymrs_policy_fitness_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def policy_fitness_clear(self) -> None:
+        """Zero the records (in stream order)."""
+        _check(self._lib, self._lib.gymrs_policy_fitness_clear(self._h))
+
     def tick(self) -> Tuple[int, int]:
         t, s = C.c_uint64(), C.c_uint64()
         _check(self._lib, self._lib.gymrs_get_tick(self._h, C.byref(t), C.byref(s)))
@@ -582,6 +615,46 @@ class ShardedEngine:
     def rollout(self, n_steps: int, action_seed: int, action_t0: int = 0) -> None:
         """``BatchedEngine.rollout`` on every block: ``n_steps`` random-policy steps fused into one launch per block."""
         _check(self._lib, self._lib.gymrs_sharded_rollout(self._h, int(n_steps), int(action_seed), int(action_t0)))
+
+    # -- closed-loop rollouts and per-policy fitness on every block (the policy set is keyed by global lane ids) --
+    def set_policy(self, weights, hidden: int = 0, lanes_per_policy: int = 1) -> None:
+        """``BatchedEngine.set_policy`` on every block: the same set everywhere.  ``None`` removes the policy."""
+        if weights is None:
+            _check(self._lib, self._lib.gymrs_sharded_set_policy(self._h, None, None))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        size = policy_size(self.kind, hidden)
+        if w.size == 0 or w.size % size != 0:
+            raise ValueError(f"weights must hold a whole number (>= 1) of policies of {size} floats, got {w.size}")
+        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_policy))
+        _check(self._lib, self._lib.gymrs_sharded_set_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+
+    def rollout_policy(self, n_steps: int) -> None:
+        """``BatchedEngine.rollout_policy`` on every block."""
+        _check(self._lib, self._lib.gymrs_sharded_rollout_policy(self._h, int(n_steps)))
+
+    def rollout_policy_fitness(self, n_steps: int) -> None:
+        """``BatchedEngine.rollout_policy_fitness`` on every block."""
+        _check(self._lib, self._lib.gymrs_sharded_rollout_policy_fitness(self._h, int(n_steps)))
+
+    def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The records of the WHOLE batch, (count, 4) int64 as ``BatchedEngine.policy_fitness``: the blocks' records summed
+        (exact; synchronising)."""
+        if count is None:  # (every block holds the same set: block 0's description is the batch's)
+            desc = PolicyDesc()
+            _check(self._lib, self._lib.gymrs_get_policy(self.shards[0]._h, C.byref(desc), None, 0))
+            count = int(desc.n_policies) - int(first)
+        out = np.zeros((max(int(count), 0), 4), dtype=np.int64)
+        _check(self._lib, self._lib.gymrs_sharded_get_policy_fitness(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def policy_fitness_ptr(self):
+        """[(device address, n_policies)] per block: each block's own records (``shards[r].policy_fitness_ptr()``); their sum
+        is the batch's."""
+        return [s.policy_fitness_ptr() for s in self.shards]
+
+    def policy_fitness_clear(self) -> None:
+        _check(self._lib, self._lib.gymrs_sharded_policy_fitness_clear(self._h))
 
     def set_params(self, params) -> None:
         """Assign the pub physics fields of every lane of the batch (``gymrs_set_params`` on every block)."""

@@ -395,7 +395,8 @@ gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_
  * of the engine uses policy ((global_env_offset + i) / lanes_per_policy) % n_policies -- keyed by the global id like the reset
  * and action streams, so the result does not depend on how a batch is cut into engines.
  *   - gymrs_set_policy copies the set to an engine-owned device buffer in stream order (launches enqueued before it use the old
- *     set; the caller may free weights_host on return).  d == NULL removes the policy.  GYMRS_EINVAL: Pendulum, hidden > 64,
+ *     set; the caller may free weights_host on return: the call waits for its own copy, so it synchronises the engine's
+ *     stream).  d == NULL removes the policy.  GYMRS_EINVAL: Pendulum, hidden > 64,
  *     n_policies == 0, lanes_per_policy == 0, NULL weights.  Non-finite weights are legal (the definition above says what they
  *     do).  It touches no lane state, tick or statistics.  gymrs_get_policy reads the set back (weights_out NULL with capacity 0
  *     only asks for the description; synchronising).
@@ -413,7 +414,7 @@ gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_
  *   - Without a policy set, the three stepping calls, gymrs_get_policy and gymrs_policy_weights_ptr return GYMRS_EINVAL.  While a
  *     parameter table is active, gymrs_rollout_policy / _record return GYMRS_EINVAL and say so (the per-step loop covers it).
  *   - The policy is NOT part of gymrs_engine_clone or of a snapshot (its bytes and version are unchanged): set it again on the
- *     clone or the restored engine.  The sharded layer (gymrs_sharded_*) has no policy calls yet. */
+ *     clone or the restored engine.  The sharded layer mirrors the set / rollout / fitness calls (gymrs_sharded_set_policy ...). */
 typedef struct { uint32_t hidden; uint32_t n_policies; uint64_t lanes_per_policy; } gymrs_policy_desc;
 gymrs_status gymrs_policy_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats);
 gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host);
@@ -422,6 +423,48 @@ gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t
 gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev);
 gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps);
 gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, const gymrs_trajectory* out);
+/* Per-policy fitness: what a population search needs back from the device, counted inside the kernel.
+ * gymrs_rollout_policy_fitness(e, K) leaves the engine bit for bit as gymrs_rollout_policy(e, K) does (state, reward / done /
+ * truncated of the last step, final observations, statistics, steps_beyond_terminated, tick) and additionally, for every policy p,
+ * every step k of the launch and every lane i of this engine with ((global_env_offset + i) / lanes_per_policy) % n_policies == p,
+ * with reward, done, truncated = the values gymrs_rollout_policy_record would have written to its rows for (k, i):
+ *     fitness[p].reward_sum += (int64)reward          (CartPole pays 0 or 1, MountainCar -1: the conversion is exact)
+ *     fitness[p].episodes   += (done | truncated) != 0
+ *     fitness[p].done       += done
+ *     fitness[p].truncated  += truncated              (0 without GYMRS_TIME_LIMIT)
+ * Integer sums: exact, independent of the order of addition and of how a batch is cut into engines (add the records of the
+ * engines).  done and truncated can both be set in one step, hence `episodes`.  Without auto-reset the counters still follow the
+ * rows (CartPole's reward_sum is then the steps survived: the reward is 0 beyond termination).  The counters are accumulated in
+ * 32-bit registers over the launch and added to the table with 64-bit integer atomics once per launch, so
+ * n_steps <= GYMRS_POLICY_FITNESS_MAX_STEPS (GYMRS_EINVAL above it; split the launch).  Every flag set gymrs_rollout_policy
+ * accepts, both lanes_per_thread values, any n_envs and any global_env_offset; K == 0 is a no-op.
+ *   - The table holds n_policies records.  It comes into being, zeroed, at the first of the four calls below after a
+ *     gymrs_set_policy (not in gymrs_set_policy: 2^20 one-lane policies would pay 32 MB they may never use); every
+ *     gymrs_set_policy discards it (removal included): the next use sees zeros.  Where the new set has the same n_policies -- a
+ *     search's next generation -- the memory is kept and zeroed in stream order; otherwise gymrs_set_policy waits for the
+ *     engine's stream and frees it.  gymrs_reset, gymrs_rollout_policy, _record, gymrs_step and the statistics calls do not
+ *     touch it.
+ *   - gymrs_policy_fitness_clear zeroes it in stream order.  gymrs_get_policy_fitness copies records [first, first + count) to
+ *     the host and synchronises.  gymrs_policy_fitness_ptr: zero-copy device view (*n_policies may be NULL) under the stream rules
+ *     of the other *_ptr views, valid until the next gymrs_set_policy or destroy.
+ *   - GYMRS_EINVAL: NULL arguments, no policy set, first + count > n_policies, Pendulum (it takes no policy), an active parameter
+ *     table (gymrs_rollout_policy_fitness: as gymrs_rollout_policy), n_steps above the bound.
+ *   - Not part of gymrs_engine_clone or of a snapshot (like the policy; snapshot bytes and version are unchanged). */
+#define GYMRS_POLICY_FITNESS_MAX_STEPS (1u << 24)
+typedef struct { int64_t reward_sum; uint64_t episodes; uint64_t done; uint64_t truncated; } gymrs_policy_fitness; /* 32 B */
+gymrs_status gymrs_rollout_policy_fitness(gymrs_engine* e, uint32_t n_steps);
+gymrs_status gymrs_policy_fitness_ptr(gymrs_engine* e, gymrs_policy_fitness** dev_out, uint32_t* n_policies);
+gymrs_status gymrs_get_policy_fitness(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out);
+gymrs_status gymrs_policy_fitness_clear(gymrs_engine* e);
+/* The same on a sharded batch (gymrs_sharded_*): every block gets the same policy set -- the global-id key makes the batch do
+ * what one engine would -- and the calls run on every block through its worker.  gymrs_sharded_get_policy_fitness sums the
+ * blocks' records on the host (integers: exact) and synchronises; every block keeps a table of its own, so a population of
+ * n_policies costs n_shards * n_policies * 32 B of device memory once fitness is used. */
+gymrs_status gymrs_sharded_set_policy(gymrs_sharded* h, const gymrs_policy_desc* d, const float* weights_host);
+gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps);
+gymrs_status gymrs_sharded_rollout_policy_fitness(gymrs_sharded* h, uint32_t n_steps);
+gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out);
+gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
 
 /* ---- `#[derive(Serialize)]` view (core.rs:25; cartpole.rs:51-87, mountain_car.rs:46-80) -------- */
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible

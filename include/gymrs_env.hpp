@@ -223,6 +223,21 @@ public:
     // n_steps of (policy_actions, step) fused into one launch; the second form keeps the trajectory
     void rollout_policy(std::uint32_t n_steps) { check(gymrs_rollout_policy(e_, n_steps)); }
     void rollout_policy_record(std::uint32_t n_steps, const gymrs_trajectory& out) { check(gymrs_rollout_policy_record(e_, n_steps, &out)); }
+    // per-policy fitness: rollout_policy that also adds every step's reward / done / truncated to the record of the lane's policy
+    void rollout_policy_fitness(std::uint32_t n_steps) { check(gymrs_rollout_policy_fitness(e_, n_steps)); }
+    std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
+    {
+        std::vector<gymrs_policy_fitness> out(count);
+        check(gymrs_get_policy_fitness(e_, first, count, out.data()));
+        return out;
+    }
+    gymrs_policy_fitness* policy_fitness_view(std::uint32_t* n_policies = nullptr)
+    {
+        gymrs_policy_fitness* p = nullptr;
+        check(gymrs_policy_fitness_ptr(e_, &p, n_policies));
+        return p;
+    }
+    void policy_fitness_clear() { check(gymrs_policy_fitness_clear(e_)); }
     // `#[derive(Serialize)]` view of the reference env lane `lane` stands for (core.rs:25)
     std::string to_json(std::uint64_t lane = 0)
     {
@@ -307,6 +322,22 @@ public:
         check(gymrs_sharded_fill_actions(h_, actions_dev.data(), seed, t));
     }
     void rollout(std::uint32_t n_steps, std::uint64_t action_seed, std::uint64_t action_t0 = 0) { check(gymrs_sharded_rollout(h_, n_steps, action_seed, action_t0)); }
+    // closed-loop rollouts and per-policy fitness on every block (the same policy set everywhere, keyed by global lane ids)
+    void set_policy(const float* weights_host, std::uint32_t hidden, std::uint32_t n_policies, std::uint64_t lanes_per_policy)
+    {
+        const gymrs_policy_desc d{hidden, n_policies, lanes_per_policy};
+        check(gymrs_sharded_set_policy(h_, &d, weights_host));
+    }
+    void clear_policy() { check(gymrs_sharded_set_policy(h_, nullptr, nullptr)); }
+    void rollout_policy(std::uint32_t n_steps) { check(gymrs_sharded_rollout_policy(h_, n_steps)); }
+    void rollout_policy_fitness(std::uint32_t n_steps) { check(gymrs_sharded_rollout_policy_fitness(h_, n_steps)); }
+    std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count) // the blocks' records, summed
+    {
+        std::vector<gymrs_policy_fitness> out(count);
+        check(gymrs_sharded_get_policy_fitness(h_, first, count, out.data()));
+        return out;
+    }
+    void policy_fitness_clear() { check(gymrs_sharded_policy_fitness_clear(h_)); }
     void set_params(const void* params) { check(gymrs_sharded_set_params(h_, params)); }
     void sync() { check(gymrs_sharded_sync(h_)); }
     std::array<double, 4> stats() // {sum_return, sum_length, n_episodes, n_steps} of the whole batch
