@@ -249,6 +249,29 @@ impl Engine {
         check(unsafe { ffi::gymrs_policy_fitness_clear(self.raw) });
     }
 
+    /// Play `episodes_per_lane` whole episodes of every lane under its policy in one launch (`gymrs_evaluate_policy`): episode `e`
+    /// starts where `reset(seed + e)` would put the lane and ends at its first done or after `max_episode_steps` steps (0 = the
+    /// params' limit).  `lengths_dev`: device `u32 [episodes_per_lane][n_envs]` for length | done << 31, or null.
+    pub fn evaluate_policy(&mut self, episodes_per_lane: u32, max_episode_steps: u32, seed: u64, common_starts: bool, lengths_dev: *mut u32) {
+        let flags = if common_starts { ffi::GYMRS_EVAL_COMMON_STARTS } else { 0 };
+        let d = ffi::GymrsEvalDesc { episodes_per_lane, max_episode_steps, seed, flags, reserved: 0, lengths_dev };
+        check(unsafe { ffi::gymrs_evaluate_policy(self.raw, &d) });
+    }
+
+    /// The episodic records of policies `first..first+count` of the latest `evaluate_policy` (synchronising).
+    pub fn policy_eval(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyEval> {
+        let mut out = vec![ffi::GymrsPolicyEval::default(); count as usize];
+        check(unsafe { ffi::gymrs_get_policy_eval(self.raw, first, count, out.as_mut_ptr()) });
+        out
+    }
+
+    /// Zero-copy device view of the episodic records and their number; valid until the next `set_policy` or drop.
+    pub fn policy_eval_ptr(&mut self) -> (*mut ffi::GymrsPolicyEval, u32) {
+        let (mut p, mut n) = (std::ptr::null_mut(), 0u32);
+        check(unsafe { ffi::gymrs_policy_eval_ptr(self.raw, &mut p, &mut n) });
+        (p, n)
+    }
+
     /// Wait for everything queued on the engine's stream.
     pub fn sync(&mut self) {
         check(unsafe { ffi::gymrs_sync(self.raw) });

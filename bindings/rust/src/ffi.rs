@@ -89,6 +89,44 @@ pub struct GymrsPolicyFitness {
     pub truncated: u64,
 }
 
+/// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
+pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
+/// `GYMRS_POLICY_EVAL_MAX_STEPS`: the bound of `episodes_per_lane * max_episode_steps`.
+pub const GYMRS_POLICY_EVAL_MAX_STEPS: u32 = 16777216;
+
+/// `gymrs_eval_desc`: what `gymrs_evaluate_policy` plays (include/gymrs_amd.h "episodic policy evaluation"), 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsEvalDesc {
+    pub episodes_per_lane: u32,
+    pub max_episode_steps: u32,
+    pub seed: u64,
+    pub flags: u32,
+    pub reserved: u32,
+    pub lengths_dev: *mut u32,
+}
+
+/// `gymrs_policy_eval`: one policy's episodic record, 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct GymrsPolicyEval {
+    pub return_sum: i64,
+    pub return_sq_sum: u64,
+    pub episodes: u64,
+    pub done: u64,
+    pub truncated: u64,
+    pub steps: u64,
+    pub return_min: i64,
+    pub return_max: i64,
+}
+
+impl Default for GymrsPolicyEval {
+    /// The identity record: what a policy without an episode holds.
+    fn default() -> Self {
+        GymrsPolicyEval { return_sum: 0, return_sq_sum: 0, episodes: 0, done: 0, truncated: 0, steps: 0, return_min: i64::MAX, return_max: i64::MIN }
+    }
+}
+
 extern "C" {
     pub fn gymrs_abi_version() -> c_int;
     pub fn gymrs_last_error() -> *const c_char;
@@ -165,6 +203,9 @@ extern "C" {
     pub fn gymrs_policy_fitness_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyFitness, n_policies: *mut u32) -> c_int;
     pub fn gymrs_get_policy_fitness(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
+    pub fn gymrs_evaluate_policy(e: *mut GymrsEngine, d: *const GymrsEvalDesc) -> c_int;
+    pub fn gymrs_get_policy_eval(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
+    pub fn gymrs_policy_eval_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyEval, n_policies: *mut u32) -> c_int;
     pub fn gymrs_env_json(e: *mut GymrsEngine, lane: u64, buf: *mut c_char, cap: u64, needed: *mut u64) -> c_int;
     pub fn gymrs_params_from_json(kind: c_int, json: *const c_char, params: *mut c_void, state: *mut f64, state_dim: *mut c_int) -> c_int;
     // ABI 3: one batch over several GPUs in ONE process (one engine + one native host thread per block)
@@ -206,6 +247,8 @@ extern "C" {
     pub fn gymrs_sharded_rollout_policy_fitness(h: *mut GymrsSharded, n_steps: u32) -> c_int;
     pub fn gymrs_sharded_get_policy_fitness(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
+    pub fn gymrs_sharded_evaluate_policy(h: *mut GymrsSharded, d: *const GymrsEvalDesc) -> c_int;
+    pub fn gymrs_sharded_get_policy_eval(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
     pub fn gymrs_sharded_set_params(h: *mut GymrsSharded, params: *const c_void) -> c_int;
     pub fn gymrs_sharded_sync(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_stats(h: *mut GymrsSharded, out4: *mut f64) -> c_int;

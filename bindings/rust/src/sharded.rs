@@ -144,6 +144,21 @@ impl ShardedEngine {
         check(unsafe { ffi::gymrs_sharded_policy_fitness_clear(self.raw) });
     }
 
+    /// `Engine::evaluate_policy` on every block (no per-episode lengths: ask the blocks themselves).
+    pub fn evaluate_policy(&mut self, episodes_per_lane: u32, max_episode_steps: u32, seed: u64, common_starts: bool) {
+        let flags = if common_starts { ffi::GYMRS_EVAL_COMMON_STARTS } else { 0 };
+        let d = ffi::GymrsEvalDesc { episodes_per_lane, max_episode_steps, seed, flags, reserved: 0, lengths_dev: std::ptr::null_mut() };
+        check(unsafe { ffi::gymrs_sharded_evaluate_policy(self.raw, &d) });
+    }
+
+    /// The episodic records of policies `first..first+count` of the whole batch: the blocks' records merged (sums added, min of
+    /// mins, max of maxes; synchronising).
+    pub fn policy_eval(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyEval> {
+        let mut out = vec![ffi::GymrsPolicyEval::default(); count as usize];
+        check(unsafe { ffi::gymrs_sharded_get_policy_eval(self.raw, first, count, out.as_mut_ptr()) });
+        out
+    }
+
     /// Wait for every block's stream; panics like the reference's `assert!` if a step saw an action outside the action space.
     pub fn sync(&mut self) {
         check(unsafe { ffi::gymrs_sharded_sync(self.raw) });

@@ -80,6 +80,10 @@ SIGNATURES = {
     "gymrs_policy_fitness_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
     "gymrs_get_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gymrs_policy_fitness_clear": (C.c_int, [C.c_void_p]),
+    # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
+    "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "gymrs_policy_eval_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process
@@ -98,6 +102,8 @@ SIGNATURES = {
     "gymrs_sharded_rollout_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gymrs_sharded_get_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gymrs_sharded_policy_fitness_clear": (C.c_int, [C.c_void_p]),
+    "gymrs_sharded_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_sharded_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gymrs_sharded_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_sync": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_stats": (C.c_int, [C.c_void_p, f64p]),

@@ -2,6 +2,7 @@
 // SoA arrays, clone / snapshot (Env: Clone + Serialize, core.rs:25), episode statistics and their RCCL all-reduce, the pub physics fields after
 // construction, the #[derive(Serialize)] JSON view.  The engine object and the stepping paths: gymrs_engine_priv.h, gymrs_engine.hip.
 #include "gymrs_engine_priv.h"
+#include "gymrs_evaluate.h"
 
 static RcclApi g_rccl;
 
@@ -670,6 +671,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
         e->policy_dev = nullptr;
         e->policy_capacity = 0;
         e->policy = PolicyArgs{};
+        if (gymrs_status st = discard_policy_eval(e)) return st;
         return discard_policy_fitness(e);
     }
     if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
@@ -687,6 +689,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
     } else if (gymrs_status st = discard_policy_fitness(e)) {
         return st;
     }
+    if (gymrs_status st = discard_policy_eval(e)) return st; // the episodic records belong to the set they were played with
     if (total > e->policy_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
         HIP_TRY(hipStreamSynchronize(e->stream));
         HIP_TRY(hipFree(e->policy_dev));
@@ -801,6 +804,95 @@ gymrs_status gymrs_policy_fitness_clear(gymrs_engine* e)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMemsetAsync(e->fitness_dev, 0, (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness), e->stream));
     return GYMRS_OK;
+}
+
+// ---- episodic policy evaluation: gymrs_evaluate_policy and its table ------------------------------------------------------------
+extern "C++" {
+// Every gymrs_set_policy: the table goes (launches already enqueued still add to it: wait for them).
+GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e)
+{
+    if (!e->eval_dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(e->eval_dev));
+    e->eval_dev = nullptr;
+    return GYMRS_OK;
+}
+
+// The checks the three calls share, then the table: n_policies identity records at the first use after a gymrs_set_policy.
+static gymrs_status ensure_policy_eval(gymrs_engine* e, const char* who)
+{
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (e->eval_dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMalloc(&e->eval_dev, (size_t)e->policy.n_policies * sizeof(gymrs_policy_eval)));
+    if (hipError_t err = launch_policy_eval_identity(e->eval_dev, e->policy.n_policies, e->stream)) {
+        (void)hipFree(e->eval_dev);
+        e->eval_dev = nullptr;
+        HIP_TRY(err);
+    }
+    return GYMRS_OK;
+}
+} // extern "C++"
+
+gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
+{
+    const std::string who = "gymrs_evaluate_policy";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, who + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
+    if (e->table_k)
+        return fail(GYMRS_EINVAL, who + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
+                                        "use gymrs_policy_actions + gymrs_step");
+    if (d->episodes_per_lane == 0) return fail(GYMRS_EINVAL, who + ": episodes_per_lane must be >= 1");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (d->flags & ~GYMRS_EVAL_COMMON_STARTS) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_EVAL_COMMON_STARTS is the only one)");
+    if (reinterpret_cast<uintptr_t>(d->lengths_dev) % alignof(uint32_t) != 0) return fail(GYMRS_EINVAL, who + ": lengths_dev must be 4-byte aligned");
+    const uint32_t dflt = e->kind == GYMRS_CARTPOLE ? e->consts.cp.max_steps : e->consts.mc.max_steps; // the params' max_episode_steps (500 / 200 by default)
+    const uint32_t m = d->max_episode_steps ? d->max_episode_steps : dflt;
+    if ((uint64_t)d->episodes_per_lane * m > kMaxEvalSteps)
+        return fail(GYMRS_EINVAL, who + ": episodes_per_lane * max_episode_steps is above GYMRS_POLICY_EVAL_MAX_STEPS (it bounds the launch's running "
+                                        "time and keeps a lane's step count in 32 bits); split the evaluation");
+    if (gymrs_status st = ensure_policy_eval(e, "gymrs_evaluate_policy")) return st;
+    HIP_TRY(hipSetDevice(e->device));
+    // the latest call's results: identities first, in stream order, then this launch's episodes
+    HIP_TRY(launch_policy_eval_identity(e->eval_dev, e->policy.n_policies, e->stream));
+    EvalArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = e->n;
+    a.gid0 = e->gid0;
+    a.seed = d->seed;
+    a.episodes = d->episodes_per_lane;
+    a.max_steps = m;
+    a.flags = d->flags;
+    a.lengths = d->lengths_dev;
+    a.table = e->eval_dev;
+    a.box = make_sample_box(e->dflt_lo, e->dflt_hi, e->state_dim); // gymrs_reset without bounds
+    HIP_TRY(launch_evaluate_policy(e->kind, a, consts_ptr(e), e->policy, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_policy_eval_ptr(gymrs_engine* e, gymrs_policy_eval** dev_out, uint32_t* n_policies)
+{
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_eval_ptr: NULL argument");
+    if (gymrs_status st = ensure_policy_eval(e, "gymrs_policy_eval_ptr")) return st;
+    *dev_out = e->eval_dev;
+    if (n_policies) *n_policies = e->policy.n_policies;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_policy_eval(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_eval* host_out)
+{
+    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_policy_eval: NULL argument");
+    if (gymrs_status st = ensure_policy_eval(e, "gymrs_get_policy_eval")) return st;
+    if ((uint64_t)first + count > e->policy.n_policies) return fail(GYMRS_EINVAL, "gymrs_get_policy_eval: first + count is beyond n_policies");
+    if (count == 0) return stream_sync_checked(e);
+    HIP_TRY(hipMemcpyAsync(host_out, e->eval_dev + first, (size_t)count * sizeof(gymrs_policy_eval), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
 }
 
 // ---- the pub physics fields after construction -------------------------------------------------------------------

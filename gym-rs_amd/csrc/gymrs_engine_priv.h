@@ -177,6 +177,9 @@ struct gymrs_engine {
     // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
     // stays the same).  Not part of clone or snapshot.
     gymrs_policy_fitness* fitness_dev = nullptr;
+    // The per-policy episodic records of gymrs_evaluate_policy: policy.n_policies records holding the latest call's results, allocated
+    // (as identities) at first use after a gymrs_set_policy; every gymrs_set_policy frees it.  Not part of clone or snapshot.
+    gymrs_policy_eval* eval_dev = nullptr;
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };
@@ -227,3 +230,4 @@ GYMRS_HOST_INTERNAL std::string aql_kernel_name(const gymrs_engine* e, uint32_t 
 GYMRS_HOST_INTERNAL void comm_destroy(gymrs_engine* e);
 GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who); // the fitness calls' checks + the zeroed table
 GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e);
+GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e);

@@ -507,6 +507,49 @@ gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, 
     });
 }
 
+// Episodic evaluation on every block.  The per-episode lengths are an array of ONE engine's lanes: ask the blocks themselves for them.
+gymrs_status gymrs_sharded_evaluate_policy(gymrs_sharded* h, const gymrs_eval_desc* d)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_evaluate_policy: handle is NULL");
+    if (!d) return fail(GYMRS_EINVAL, "gymrs_sharded_evaluate_policy: NULL desc");
+    if (d->lengths_dev) return fail(GYMRS_EINVAL, "gymrs_sharded_evaluate_policy: lengths_dev must be NULL (the blocks live on several devices)");
+    const gymrs_eval_desc desc = *d;
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_evaluate_policy(e, &desc); }; });
+}
+
+// Records [first, first + count) of the batch: every block's records (read by its worker), merged on the caller's thread: sums added,
+// the min of the mins, the max of the maxes (a block without a lane of the policy holds the identity).
+gymrs_status gymrs_sharded_get_policy_eval(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_eval* host_out)
+{
+    if (!h || !host_out) return fail(GYMRS_EINVAL, "gymrs_sharded_get_policy_eval: NULL argument");
+    return guarded("gymrs_sharded_get_policy_eval", [&]() -> gymrs_status {
+        const size_t k = h->w.size();
+        std::vector<gymrs_policy_eval> part(k * (size_t)count + k); // (one spare record per block keeps the pointers non-NULL at count == 0)
+        gymrs_policy_eval* parts = part.data();
+        if (gymrs_status st = h->all([=](int r) {
+                gymrs_policy_eval* mine = parts + (size_t)r * count;
+                return [=](gymrs_engine*& e) { return gymrs_get_policy_eval(e, first, count, mine); };
+            }))
+            return st;
+        for (uint32_t p = 0; p < count; ++p) {
+            gymrs_policy_eval m = {0, 0, 0, 0, 0, 0, INT64_MAX, INT64_MIN};
+            for (size_t r = 0; r < k; ++r) {
+                const gymrs_policy_eval& f = parts[r * count + p];
+                m.return_sum = (int64_t)((uint64_t)m.return_sum + (uint64_t)f.return_sum);
+                m.return_sq_sum += f.return_sq_sum;
+                m.episodes += f.episodes;
+                m.done += f.done;
+                m.truncated += f.truncated;
+                m.steps += f.steps;
+                m.return_min = f.return_min < m.return_min ? f.return_min : m.return_min;
+                m.return_max = f.return_max > m.return_max ? f.return_max : m.return_max;
+            }
+            host_out[p] = m;
+        }
+        return GYMRS_OK;
+    });
+}
+
 // `env.gravity = ...` for every lane of the batch (gymrs_set_params on every block).
 gymrs_status gymrs_sharded_set_params(gymrs_sharded* h, const void* params)
 {

@@ -70,6 +70,26 @@ class PolicyFitness(C.Structure):
     _fields_ = [("reward_sum", C.c_int64), ("episodes", C.c_uint64), ("done", C.c_uint64), ("truncated", C.c_uint64)]
 
 
+class PolicyEval(C.Structure):
+    """``gymrs_policy_eval`` (include/gymrs_amd.h): one policy's episodic record, 64 bytes."""
+    _fields_ = [("return_sum", C.c_int64), ("return_sq_sum", C.c_uint64), ("episodes", C.c_uint64), ("done", C.c_uint64),
+                ("truncated", C.c_uint64), ("steps", C.c_uint64), ("return_min", C.c_int64), ("return_max", C.c_int64)]
+
+
+class EvalDesc(C.Structure):
+    """``gymrs_eval_desc`` (include/gymrs_amd.h), 32 bytes."""
+    _fields_ = [("episodes_per_lane", C.c_uint32), ("max_episode_steps", C.c_uint32), ("seed", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("lengths_dev", C.c_void_p)]
+
+
+EVAL_COMMON_STARTS = 1  # GYMRS_EVAL_COMMON_STARTS
+
+
+def _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags) -> EvalDesc:
+    f = (EVAL_COMMON_STARTS if common_starts else 0) if flags is None else int(flags)
+    return EvalDesc(int(episodes_per_lane), int(max_episode_steps), int(seed) & (2**64 - 1), f, 0, C.c_void_p(lengths or None))
+
+
 class PolicyDesc(C.Structure):
     """``gymrs_policy_desc`` (include/gymrs_amd.h)."""
     _fields_ = [("hidden", C.c_uint32), ("n_policies", C.c_uint32), ("lanes_per_policy", C.c_uint64)]
@@ -523,6 +543,37 @@ class BatchedEngine:
         """Zero the records (in stream order)."""
         _check(self._lib, self._lib.gymrs_policy_fitness_clear(self._h))
 
+    # -- episodic policy evaluation: E whole episodes per lane in one launch ---------------------------------
+    def evaluate_policy(self, episodes_per_lane: int, max_episode_steps: int = 0, seed: int = 0, common_starts: bool = False,
+                        lengths: int = 0, flags: Optional[int] = None) -> None:
+        """Play ``episodes_per_lane`` whole episodes of every lane under its policy (``gymrs_evaluate_policy``): episode ``e`` of a
+        lane starts where ``reset(seed + e)`` would put it and ends at its first done or after ``max_episode_steps`` steps (0 = the
+        params' limit).  ``common_starts`` gives every policy the same start states.  ``lengths``: device address of a uint32
+        ``[episodes_per_lane][n_envs]`` array for length | done << 31 of every episode, or 0.  ``flags`` overrides
+        ``common_starts`` with raw ``GYMRS_EVAL_*`` bits.  The engine's lanes are neither read nor written; the results
+        (``policy_eval``) are those of the latest call."""
+        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags)
+        _check(self._lib, self._lib.gymrs_evaluate_policy(self._h, C.byref(desc)))
+
+    def policy_eval(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The episodic records of policies [first, first + count) as an int64 array of shape (count, 8): columns return_sum,
+        return_sq_sum, episodes, done, truncated, steps, return_min, return_max (synchronising; return_sq_sum is the uint64's
+        bits).  ``count`` defaults to the rest of the set."""
+        if count is None:
+            desc = PolicyDesc()
+            _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
+            count = int(desc.n_policies) - int(first)
+        out = np.zeros((max(int(count), 0), 8), dtype=np.int64)
+        _check(self._lib, self._lib.gymrs_get_policy_eval(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def policy_eval_ptr(self) -> Tuple[int, int]:
+        """(device address, n_policies) of the episodic records (``PolicyEval``, 64 bytes each): zero-copy, under the stream
+        rules of the other views.  Valid until the next set_policy or close."""
+        p, n = C.c_void_p(), C.c_uint32()
+        _check(self._lib, self._lib.gymrs_policy_eval_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def tick(self) -> Tuple[int, int]:
         t, s = C.c_uint64(), C.c_uint64()
         _check(self._lib, self._lib.gymrs_get_tick(self._h, C.byref(t), C.byref(s)))
@@ -655,6 +706,27 @@ class ShardedEngine:
 
     def policy_fitness_clear(self) -> None:
         _check(self._lib, self._lib.gymrs_sharded_policy_fitness_clear(self._h))
+
+    def evaluate_policy(self, episodes_per_lane: int, max_episode_steps: int = 0, seed: int = 0, common_starts: bool = False,
+                        lengths: int = 0, flags: Optional[int] = None) -> None:
+        """``BatchedEngine.evaluate_policy`` on every block (``lengths`` must stay 0: ask ``shards[r]`` for per-episode lengths)."""
+        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags)
+        _check(self._lib, self._lib.gymrs_sharded_evaluate_policy(self._h, C.byref(desc)))
+
+    def policy_eval(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The episodic records of the WHOLE batch, (count, 8) int64 as ``BatchedEngine.policy_eval``: the blocks' records merged
+        (sums added, min of mins, max of maxes; synchronising)."""
+        if count is None:
+            desc = PolicyDesc()
+            _check(self._lib, self._lib.gymrs_get_policy(self.shards[0]._h, C.byref(desc), None, 0))
+            count = int(desc.n_policies) - int(first)
+        out = np.zeros((max(int(count), 0), 8), dtype=np.int64)
+        _check(self._lib, self._lib.gymrs_sharded_get_policy_eval(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def policy_eval_ptr(self):
+        """[(device address, n_policies)] per block: each block's own records (``shards[r].policy_eval_ptr()``)."""
+        return [s.policy_eval_ptr() for s in self.shards]
 
     def set_params(self, params) -> None:
         """Assign the pub physics fields of every lane of the batch (``gymrs_set_params`` on every block)."""

@@ -465,6 +465,47 @@ gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps);
 gymrs_status gymrs_sharded_rollout_policy_fitness(gymrs_sharded* h, uint32_t n_steps);
 gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out);
 gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
+/* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
+ * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
+ * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):
+ *   - start: the state gymrs_reset(seed = d->seed + ep (mod 2^64), no bounds) gives the lane with global id g: the default
+ *     box, the Philox block keyed (seed + ep, g, tick 0, reset stream), the env's sample.  With GYMRS_EVAL_COMMON_STARTS in
+ *     d->flags the id in the key is g % lanes_per_policy (what an engine at offset 0 gives lane g % lanes_per_policy): every
+ *     policy meets the same lanes_per_policy x E start states (common random numbers).
+ *   - steps: the action is the policy's (the definition under "closed-loop rollouts"), the physics the env's step with the
+ *     engine's current uniform parameters (the general path covers out-of-range angles and NaN states, as in gymrs_step).
+ *   - end: with M = d->max_episode_steps, or the params' max_episode_steps (default 500 / 200) when that is 0, the episode ends
+ *     at the first step k >= 1 that reports done, or at k = M.  L = k; done = the last step's done flag; truncated = (L == M)
+ *     (both may be set, as in gymrs_step); return = +L (CartPole) or -L (MountainCar): both envs pay a constant per step.
+ * Every episode adds to the record of its policy: return_sum += return, return_sq_sum += return^2, episodes += 1, done += done,
+ * truncated += truncated, steps += L (all modulo 2^64), return_min / return_max = the lowest / highest return.  A policy with
+ * no lane in this engine keeps the identity {0, 0, 0, 0, 0, 0, INT64_MAX, INT64_MIN}.  Integers throughout: exact, independent
+ * of scheduling and of how a batch is cut into engines (add the sums, take the min of the mins and the max of the maxes).
+ * d->lengths_dev (may be NULL): device uint32 [E][n_envs], 4-byte aligned; entry [ep][i] = L | (done ? 0x80000000 : 0).
+ *   - The call reads no lane array and writes none: state, observations, reward / done / truncated, final observations,
+ *     steps_beyond_terminated, tick, statistics, the reset log, the fitness table and the parameter index stay bit for bit; the
+ *     engine's flags and gymrs_set_tuning do not matter (4 lanes per work-item).
+ *   - The table holds n_policies records of the LATEST call: it is set to the identity in stream order and then filled; it does
+ *     not accumulate.  It follows the fitness table's lifetime: allocated (as identities) at first use after a gymrs_set_policy,
+ *     discarded by every gymrs_set_policy, not part of clone or snapshot.  gymrs_get_policy_eval copies records [first, first +
+ *     count) and synchronises; gymrs_policy_eval_ptr is the zero-copy view (*n_policies may be NULL), valid until the next
+ *     gymrs_set_policy or destroy.
+ *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, an active parameter table, E == 0, reserved != 0, unknown
+ *     flag bits, a misaligned lengths_dev, E * M > GYMRS_POLICY_EVAL_MAX_STEPS (the bound of the kernel's running time, and
+ *     what keeps a lane's sum of L in 32 bits).  Non-finite weights are legal.
+ *   - Not built: moving episodes between the lanes of a wave (a wave runs until its slowest lane is through), parameter tables,
+ *     8 lanes per work-item.
+ * gymrs_sharded_evaluate_policy runs it on every block (lengths_dev must be NULL there); gymrs_sharded_get_policy_eval merges
+ * the blocks' records on the host. */
+#define GYMRS_EVAL_COMMON_STARTS 1u
+#define GYMRS_POLICY_EVAL_MAX_STEPS 16777216u
+typedef struct { uint32_t episodes_per_lane, max_episode_steps; uint64_t seed; uint32_t flags, reserved; uint32_t* lengths_dev; } gymrs_eval_desc; /* 32 B */
+typedef struct { int64_t return_sum; uint64_t return_sq_sum, episodes, done, truncated, steps; int64_t return_min, return_max; } gymrs_policy_eval; /* 64 B */
+gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d);
+gymrs_status gymrs_get_policy_eval(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_eval* host_out);
+gymrs_status gymrs_policy_eval_ptr(gymrs_engine* e, gymrs_policy_eval** dev_out, uint32_t* n_policies);
+gymrs_status gymrs_sharded_evaluate_policy(gymrs_sharded* h, const gymrs_eval_desc* d);
+gymrs_status gymrs_sharded_get_policy_eval(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_eval* host_out);
 
 /* ---- `#[derive(Serialize)]` view (core.rs:25; cartpole.rs:51-87, mountain_car.rs:46-80) -------- */
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible

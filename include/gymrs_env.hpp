@@ -238,6 +238,26 @@ public:
         return p;
     }
     void policy_fitness_clear() { check(gymrs_policy_fitness_clear(e_)); }
+    // episodic policy evaluation: E whole episodes per lane in one launch; the records are those of the latest call
+    void evaluate_policy(const gymrs_eval_desc& d) { check(gymrs_evaluate_policy(e_, &d)); }
+    void evaluate_policy(std::uint32_t episodes_per_lane, std::uint32_t max_episode_steps = 0, std::uint64_t seed = 0, bool common_starts = false,
+                         std::uint32_t* lengths_dev = nullptr)
+    {
+        const gymrs_eval_desc d{episodes_per_lane, max_episode_steps, seed, common_starts ? GYMRS_EVAL_COMMON_STARTS : 0u, 0u, lengths_dev};
+        check(gymrs_evaluate_policy(e_, &d));
+    }
+    std::vector<gymrs_policy_eval> policy_eval(std::uint32_t first, std::uint32_t count)
+    {
+        std::vector<gymrs_policy_eval> out(count);
+        check(gymrs_get_policy_eval(e_, first, count, out.data()));
+        return out;
+    }
+    gymrs_policy_eval* policy_eval_view(std::uint32_t* n_policies = nullptr)
+    {
+        gymrs_policy_eval* p = nullptr;
+        check(gymrs_policy_eval_ptr(e_, &p, n_policies));
+        return p;
+    }
     // `#[derive(Serialize)]` view of the reference env lane `lane` stands for (core.rs:25)
     std::string to_json(std::uint64_t lane = 0)
     {
@@ -338,6 +358,14 @@ public:
         return out;
     }
     void policy_fitness_clear() { check(gymrs_sharded_policy_fitness_clear(h_)); }
+    // episodic policy evaluation on every block (d.lengths_dev must be NULL); the blocks' records merged
+    void evaluate_policy(const gymrs_eval_desc& d) { check(gymrs_sharded_evaluate_policy(h_, &d)); }
+    std::vector<gymrs_policy_eval> policy_eval(std::uint32_t first, std::uint32_t count)
+    {
+        std::vector<gymrs_policy_eval> out(count);
+        check(gymrs_sharded_get_policy_eval(h_, first, count, out.data()));
+        return out;
+    }
     void set_params(const void* params) { check(gymrs_sharded_set_params(h_, params)); }
     void sync() { check(gymrs_sharded_sync(h_)); }
     std::array<double, 4> stats() // {sum_return, sum_length, n_episodes, n_steps} of the whole batch
