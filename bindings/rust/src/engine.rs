@@ -258,6 +258,14 @@ impl Engine {
         check(unsafe { ffi::gymrs_evaluate_policy(self.raw, &d) });
     }
 
+    /// `evaluate_policy` with `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `step` would use for it
+    /// (without a table: exactly `evaluate_policy`).  An engine with a table refuses the plain call.
+    pub fn evaluate_policy_lane_params(&mut self, episodes_per_lane: u32, max_episode_steps: u32, seed: u64, common_starts: bool, lengths_dev: *mut u32) {
+        let flags = ffi::GYMRS_EVAL_LANE_PARAMS | if common_starts { ffi::GYMRS_EVAL_COMMON_STARTS } else { 0 };
+        let d = ffi::GymrsEvalDesc { episodes_per_lane, max_episode_steps, seed, flags, reserved: 0, lengths_dev };
+        check(unsafe { ffi::gymrs_evaluate_policy(self.raw, &d) });
+    }
+
     /// The episodic records of policies `first..first+count` of the latest `evaluate_policy` (synchronising).
     pub fn policy_eval(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyEval> {
         let mut out = vec![ffi::GymrsPolicyEval::default(); count as usize];

@@ -91,6 +91,8 @@ pub struct GymrsPolicyFitness {
 
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
+/// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
+pub const GYMRS_EVAL_LANE_PARAMS: u32 = 4;
 /// `GYMRS_POLICY_EVAL_MAX_STEPS`: the bound of `episodes_per_lane * max_episode_steps`.
 pub const GYMRS_POLICY_EVAL_MAX_STEPS: u32 = 16777216;
 
@@ -248,6 +250,10 @@ extern "C" {
     pub fn gymrs_sharded_get_policy_fitness(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_evaluate_policy(h: *mut GymrsSharded, d: *const GymrsEvalDesc) -> c_int;
+    pub fn gymrs_sharded_set_param_table(h: *mut GymrsSharded, rows: *const c_void, k: u32) -> c_int;
+    pub fn gymrs_sharded_get_param_table(h: *mut GymrsSharded, rows_out: *mut c_void, capacity: u32, k: *mut u32) -> c_int;
+    pub fn gymrs_sharded_set_param_index(h: *mut GymrsSharded, first: u64, count: u64, index_host: *const u16) -> c_int;
+    pub fn gymrs_sharded_get_param_index(h: *mut GymrsSharded, first: u64, count: u64, index_out: *mut u16) -> c_int;
     pub fn gymrs_sharded_get_policy_eval(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
     pub fn gymrs_sharded_set_params(h: *mut GymrsSharded, params: *const c_void) -> c_int;
     pub fn gymrs_sharded_sync(h: *mut GymrsSharded) -> c_int;

@@ -151,6 +151,42 @@ impl ShardedEngine {
         check(unsafe { ffi::gymrs_sharded_evaluate_policy(self.raw, &d) });
     }
 
+    /// `evaluate_policy` with `GYMRS_EVAL_LANE_PARAMS`: every lane plays with its row of the table of `set_param_table`.
+    pub fn evaluate_policy_lane_params(&mut self, episodes_per_lane: u32, max_episode_steps: u32, seed: u64, common_starts: bool) {
+        let flags = ffi::GYMRS_EVAL_LANE_PARAMS | if common_starts { ffi::GYMRS_EVAL_COMMON_STARTS } else { 0 };
+        let d = ffi::GymrsEvalDesc { episodes_per_lane, max_episode_steps, seed, flags, reserved: 0, lengths_dev: std::ptr::null_mut() };
+        check(unsafe { ffi::gymrs_sharded_evaluate_policy(self.raw, &d) });
+    }
+
+    /// Per-lane physics on the batch (`gymrs_sharded_set_param_table`): the same `k` rows of the kind's params struct on every block;
+    /// an empty slice switches the table off.
+    ///
+    /// # Safety
+    /// `P` must be the C params struct of this engine's kind (`ffi::GymrsCartPoleParams`, ...).
+    pub unsafe fn set_param_table<P>(&mut self, rows: &[P]) {
+        let p = if rows.is_empty() { std::ptr::null() } else { rows.as_ptr() as *const c_void };
+        check(ffi::gymrs_sharded_set_param_table(self.raw, p, rows.len() as u32));
+    }
+
+    /// The number of rows of the active table (0: none), read from block 0.
+    pub fn param_table_rows(&mut self) -> u32 {
+        let mut k = 0u32;
+        check(unsafe { ffi::gymrs_sharded_get_param_table(self.raw, std::ptr::null_mut(), 0, &mut k) });
+        k
+    }
+
+    /// The rows of lanes `first..first+index.len()` of the BATCH, cut across the blocks.
+    pub fn set_param_index(&mut self, first: u64, index: &[u16]) {
+        check(unsafe { ffi::gymrs_sharded_set_param_index(self.raw, first, index.len() as u64, index.as_ptr()) });
+    }
+
+    /// The row indices of lanes `first..first+count` of the batch.
+    pub fn param_index(&mut self, first: u64, count: u64) -> Vec<u16> {
+        let mut out = vec![0u16; count as usize];
+        check(unsafe { ffi::gymrs_sharded_get_param_index(self.raw, first, count, out.as_mut_ptr()) });
+        out
+    }
+
     /// The episodic records of policies `first..first+count` of the whole batch: the blocks' records merged (sums added, min of
     /// mins, max of maxes; synchronising).
     pub fn policy_eval(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyEval> {

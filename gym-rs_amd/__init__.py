@@ -43,7 +43,7 @@ from .envs import (
 )
 from ._lib import library_path, load_library
 from . import sharded
-from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, EvalDesc, EVAL_COMMON_STARTS
+from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, EvalDesc, EVAL_COMMON_STARTS, EVAL_LANE_PARAMS
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -51,5 +51,5 @@ __all__ = [
     "CartPoleObservation", "MountainCarObservation", "PendulumObservation", "RenderMode",
     "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "FINAL_OBS", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
-    "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS",
+    "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
 ]

@@ -104,6 +104,11 @@ SIGNATURES = {
     "gymrs_sharded_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    # per-lane physics on a sharded batch (the index in batch lane numbering)
+    "gymrs_sharded_set_param_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "gymrs_sharded_get_param_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gymrs_sharded_set_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gymrs_sharded_get_param_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gymrs_sharded_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_sync": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_stats": (C.c_int, [C.c_void_p, f64p]),

@@ -845,14 +845,15 @@ gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
     if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
         return fail(GYMRS_EINVAL, who + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
     if (!e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
-    if (e->table_k)
-        return fail(GYMRS_EINVAL, who + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
-                                        "use gymrs_policy_actions + gymrs_step");
+    if (e->table_k && !(d->flags & GYMRS_EVAL_LANE_PARAMS)) // (opt-in: a plain descriptor never plays a table engine with one set of parameters)
+        return fail(GYMRS_EINVAL, who + ": a parameter table is active (gymrs_set_param_table): set GYMRS_EVAL_LANE_PARAMS in flags and every lane "
+                                        "plays with its own row, or use gymrs_policy_actions + gymrs_step");
     if (d->episodes_per_lane == 0) return fail(GYMRS_EINVAL, who + ": episodes_per_lane must be >= 1");
     if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    if (d->flags & ~GYMRS_EVAL_COMMON_STARTS) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_EVAL_COMMON_STARTS is the only one)");
+    if (d->flags & ~(GYMRS_EVAL_COMMON_STARTS | GYMRS_EVAL_LANE_PARAMS))
+        return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_EVAL_COMMON_STARTS and GYMRS_EVAL_LANE_PARAMS are the only ones)");
     if (reinterpret_cast<uintptr_t>(d->lengths_dev) % alignof(uint32_t) != 0) return fail(GYMRS_EINVAL, who + ": lengths_dev must be 4-byte aligned");
-    const uint32_t dflt = e->kind == GYMRS_CARTPOLE ? e->consts.cp.max_steps : e->consts.mc.max_steps; // the params' max_episode_steps (500 / 200 by default)
+    const uint32_t dflt = e->kind == GYMRS_CARTPOLE ? e->consts.cp.max_steps : e->consts.mc.max_steps; // the params' max_episode_steps (500 / 200 by default; a table: the limit its rows share)
     const uint32_t m = d->max_episode_steps ? d->max_episode_steps : dflt;
     if ((uint64_t)d->episodes_per_lane * m > kMaxEvalSteps)
         return fail(GYMRS_EINVAL, who + ": episodes_per_lane * max_episode_steps is above GYMRS_POLICY_EVAL_MAX_STEPS (it bounds the launch's running "
@@ -868,11 +869,11 @@ gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
     a.seed = d->seed;
     a.episodes = d->episodes_per_lane;
     a.max_steps = m;
-    a.flags = d->flags;
+    a.flags = d->flags & GYMRS_EVAL_COMMON_STARTS; // (GYMRS_EVAL_LANE_PARAMS chooses the kernel; without a table it changes nothing)
     a.lengths = d->lengths_dev;
     a.table = e->eval_dev;
     a.box = make_sample_box(e->dflt_lo, e->dflt_hi, e->state_dim); // gymrs_reset without bounds
-    HIP_TRY(launch_evaluate_policy(e->kind, a, consts_ptr(e), e->policy, e->stream));
+    HIP_TRY(launch_evaluate_policy(e->kind, e->table_k ? kFlagTable : 0u, a, launch_consts(e), e->policy, e->stream));
     return GYMRS_OK;
 }
 

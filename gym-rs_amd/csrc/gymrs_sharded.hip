@@ -507,7 +507,7 @@ gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, 
     });
 }
 
-// Episodic evaluation on every block.  The per-episode lengths are an array of ONE engine's lanes: ask the blocks themselves for them.
+// Episodic evaluation on every block (the flags pass through: GYMRS_EVAL_LANE_PARAMS plays every block's table).  The per-episode lengths are an array of ONE engine's lanes: ask the blocks themselves for them.
 gymrs_status gymrs_sharded_evaluate_policy(gymrs_sharded* h, const gymrs_eval_desc* d)
 {
     if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_evaluate_policy: handle is NULL");
@@ -555,6 +555,49 @@ gymrs_status gymrs_sharded_set_params(gymrs_sharded* h, const void* params)
 {
     if (!h || !params) return fail(GYMRS_EINVAL, "gymrs_sharded_set_params: NULL argument");
     return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_params(e, params); }; });
+}
+
+// Per-lane physics on a batch: the same rows on every block, the index in BATCH lane numbering (cut like gymrs_sharded_get_state's ranges).
+gymrs_status gymrs_sharded_set_param_table(gymrs_sharded* h, const void* rows, uint32_t k)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_set_param_table: handle is NULL");
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_param_table(e, rows, k); }; });
+}
+
+gymrs_status gymrs_sharded_get_param_table(gymrs_sharded* h, void* rows_out, uint32_t capacity, uint32_t* k)
+{
+    if (!h || !k) return fail(GYMRS_EINVAL, "gymrs_sharded_get_param_table: NULL argument");
+    return h->all([=](int r) {
+        return [=](gymrs_engine*& e) -> gymrs_status { return r == 0 ? gymrs_get_param_table(e, rows_out, capacity, k) : GYMRS_OK; };
+    });
+}
+
+gymrs_status gymrs_sharded_set_param_index(gymrs_sharded* h, uint64_t first, uint64_t count, const uint16_t* index_host)
+{
+    if (!h || !index_host) return fail(GYMRS_EINVAL, "gymrs_sharded_set_param_index: NULL argument");
+    if (first > h->n_total || count > h->n_total - first) return fail(GYMRS_EINVAL, "gymrs_sharded_set_param_index: lane range out of bounds");
+    return h->all([=](int r) {
+        const Worker* wk = h->w[(size_t)r];
+        const uint64_t lo = first > wk->first ? first : wk->first;
+        const uint64_t hi = (first + count) < (wk->first + wk->count) ? (first + count) : (wk->first + wk->count);
+        return [=](gymrs_engine*& e) -> gymrs_status { // (a block the range misses still says whether it has a table)
+            return lo >= hi ? gymrs_set_param_index(e, 0, 0, index_host) : gymrs_set_param_index(e, lo - wk->first, hi - lo, index_host + (lo - first));
+        };
+    });
+}
+
+gymrs_status gymrs_sharded_get_param_index(gymrs_sharded* h, uint64_t first, uint64_t count, uint16_t* index_out)
+{
+    if (!h || !index_out) return fail(GYMRS_EINVAL, "gymrs_sharded_get_param_index: NULL argument");
+    if (first > h->n_total || count > h->n_total - first) return fail(GYMRS_EINVAL, "gymrs_sharded_get_param_index: lane range out of bounds");
+    return h->all([=](int r) {
+        const Worker* wk = h->w[(size_t)r];
+        const uint64_t lo = first > wk->first ? first : wk->first;
+        const uint64_t hi = (first + count) < (wk->first + wk->count) ? (first + count) : (wk->first + wk->count);
+        return [=](gymrs_engine*& e) -> gymrs_status {
+            return lo >= hi ? gymrs_get_param_index(e, 0, 0, index_out) : gymrs_get_param_index(e, lo - wk->first, hi - lo, index_out + (lo - first));
+        };
+    });
 }
 
 gymrs_status gymrs_sharded_sync(gymrs_sharded* h)

@@ -83,10 +83,11 @@ class EvalDesc(C.Structure):
 
 
 EVAL_COMMON_STARTS = 1  # GYMRS_EVAL_COMMON_STARTS
+EVAL_LANE_PARAMS = 4  # GYMRS_EVAL_LANE_PARAMS
 
 
-def _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags) -> EvalDesc:
-    f = (EVAL_COMMON_STARTS if common_starts else 0) if flags is None else int(flags)
+def _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags, lane_params=False) -> EvalDesc:
+    f = ((EVAL_COMMON_STARTS if common_starts else 0) | (EVAL_LANE_PARAMS if lane_params else 0)) if flags is None else int(flags)
     return EvalDesc(int(episodes_per_lane), int(max_episode_steps), int(seed) & (2**64 - 1), f, 0, C.c_void_p(lengths or None))
 
 
@@ -545,14 +546,16 @@ class BatchedEngine:
 
     # -- episodic policy evaluation: E whole episodes per lane in one launch ---------------------------------
     def evaluate_policy(self, episodes_per_lane: int, max_episode_steps: int = 0, seed: int = 0, common_starts: bool = False,
-                        lengths: int = 0, flags: Optional[int] = None) -> None:
+                        lengths: int = 0, flags: Optional[int] = None, lane_params: bool = False) -> None:
         """Play ``episodes_per_lane`` whole episodes of every lane under its policy (``gymrs_evaluate_policy``): episode ``e`` of a
         lane starts where ``reset(seed + e)`` would put it and ends at its first done or after ``max_episode_steps`` steps (0 = the
         params' limit).  ``common_starts`` gives every policy the same start states.  ``lengths``: device address of a uint32
-        ``[episodes_per_lane][n_envs]`` array for length | done << 31 of every episode, or 0.  ``flags`` overrides
-        ``common_starts`` with raw ``GYMRS_EVAL_*`` bits.  The engine's lanes are neither read nor written; the results
+        ``[episodes_per_lane][n_envs]`` array for length | done << 31 of every episode, or 0.  ``lane_params``
+        (``GYMRS_EVAL_LANE_PARAMS``): every lane plays with the row of the parameter table ``step`` would use for it (without a
+        table it changes nothing); without it an engine with a table refuses the call.  ``flags`` overrides ``common_starts`` and
+        ``lane_params`` with raw ``GYMRS_EVAL_*`` bits.  The engine's lanes are neither read nor written; the results
         (``policy_eval``) are those of the latest call."""
-        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags)
+        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags, lane_params)
         _check(self._lib, self._lib.gymrs_evaluate_policy(self._h, C.byref(desc)))
 
     def policy_eval(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -708,9 +711,10 @@ class ShardedEngine:
         _check(self._lib, self._lib.gymrs_sharded_policy_fitness_clear(self._h))
 
     def evaluate_policy(self, episodes_per_lane: int, max_episode_steps: int = 0, seed: int = 0, common_starts: bool = False,
-                        lengths: int = 0, flags: Optional[int] = None) -> None:
-        """``BatchedEngine.evaluate_policy`` on every block (``lengths`` must stay 0: ask ``shards[r]`` for per-episode lengths)."""
-        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags)
+                        lengths: int = 0, flags: Optional[int] = None, lane_params: bool = False) -> None:
+        """``BatchedEngine.evaluate_policy`` on every block (``lengths`` must stay 0: ask ``shards[r]`` for per-episode lengths).
+        ``lane_params`` plays the table of ``set_param_table`` / ``set_param_index``."""
+        desc = _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags, lane_params)
         _check(self._lib, self._lib.gymrs_sharded_evaluate_policy(self._h, C.byref(desc)))
 
     def policy_eval(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
@@ -734,6 +738,40 @@ class ShardedEngine:
             raise TypeError(f"expected {_PARAMS[self.kind].__name__}")
         _check(self._lib, self._lib.gymrs_sharded_set_params(self._h, C.byref(params)))
         self.params = type(params).from_buffer_copy(params)
+
+    # -- per-lane physics on the batch: the same rows on every block, the index in batch lane numbering --
+    def set_param_table(self, rows) -> None:
+        """``BatchedEngine.set_param_table`` on every block: the same rows everywhere (``None`` or ``[]`` switches the table off)."""
+        rows = list(rows or [])
+        cls = _PARAMS[self.kind]
+        if any(not isinstance(r, cls) for r in rows):
+            raise TypeError(f"expected {cls.__name__} rows")
+        arr = (cls * len(rows))(*rows) if rows else None
+        _check(self._lib, self._lib.gymrs_sharded_set_param_table(self._h, arr, len(rows)))
+        p = cls()
+        _check(self._lib, self._lib.gymrs_get_params(self.shards[0]._h, C.byref(p)))
+        self.params = p
+
+    def param_table(self) -> list:
+        """The rows of the active table in f64 exactly as set ([] without a table), read from block 0."""
+        k = C.c_uint32()
+        _check(self._lib, self._lib.gymrs_sharded_get_param_table(self._h, None, 0, C.byref(k)))
+        if k.value == 0:
+            return []
+        arr = (_PARAMS[self.kind] * k.value)()
+        _check(self._lib, self._lib.gymrs_sharded_get_param_table(self._h, arr, k.value, C.byref(k)))
+        return list(arr)
+
+    def set_param_index(self, index, first: int = 0) -> None:
+        """The rows of lanes [first, first + len(index)) of the BATCH, cut across the blocks."""
+        idx = np.ascontiguousarray(index, dtype=np.uint16)
+        _check(self._lib, self._lib.gymrs_sharded_set_param_index(self._h, int(first), idx.size, idx.ctypes.data_as(C.c_void_p)))
+
+    def get_param_index(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        count = self.n_total - first if count is None else count
+        out = np.empty(count, dtype=np.uint16)
+        _check(self._lib, self._lib.gymrs_sharded_get_param_index(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def sync(self) -> None:
         _check(self._lib, self._lib.gymrs_sharded_sync(self._h))

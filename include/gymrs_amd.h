@@ -366,13 +366,25 @@ gymrs_status gymrs_get_params(gymrs_engine* e, void* params_out);
  * NULL with capacity 0 only asks for K).  gymrs_param_index_ptr: zero-copy device view of the index, under the stream rules of
  * the other *_ptr views (a kernel on the engine's stream may rewrite it between two steps).  gymrs_set_param_index /
  * gymrs_get_param_index: host copies of lanes [first, first + count) (synchronising).  These three need a table.
- * gymrs_get_lane_params: the params lane `lane` steps with (row index[lane]; without a table, gymrs_get_params). */
+ * gymrs_get_lane_params: the params lane `lane` steps with (row index[lane]; without a table, gymrs_get_params).
+ * Which calls honour the table: gymrs_step / gymrs_step_many / gymrs_rollout / gymrs_rollout_record (every flag set), and
+ * gymrs_evaluate_policy with GYMRS_EVAL_LANE_PARAMS ("episodic policy evaluation" below).  gymrs_rollout_policy, _record and
+ * _fitness refuse an active table (they take no flags word through which a caller could opt in).
+ * A sharded batch (gymrs_sharded_*): gymrs_sharded_set_param_table puts the SAME k rows on every block (rows = NULL, k = 0
+ * switches the table off); gymrs_sharded_get_param_table reads them back from block 0.  gymrs_sharded_set_param_index /
+ * gymrs_sharded_get_param_index copy lanes [first, first + count) in BATCH lane numbering, split across the blocks the way
+ * gymrs_sharded_get_state splits its ranges (a range beyond the batch: GYMRS_EINVAL; they need a table).  Lane i of the batch
+ * then steps, rolls out and is evaluated exactly as lane i of one engine with that table and index. */
 gymrs_status gymrs_set_param_table(gymrs_engine* e, const void* rows /* k x gymrs_<kind>_params */, uint32_t k);
 gymrs_status gymrs_get_param_table(gymrs_engine* e, void* rows_out, uint32_t capacity, uint32_t* k);
 gymrs_status gymrs_param_index_ptr(gymrs_engine* e, uint16_t** out);
 gymrs_status gymrs_set_param_index(gymrs_engine* e, uint64_t first, uint64_t count, const uint16_t* host_in);
 gymrs_status gymrs_get_param_index(gymrs_engine* e, uint64_t first, uint64_t count, uint16_t* host_out);
 gymrs_status gymrs_get_lane_params(gymrs_engine* e, uint64_t lane, void* params_out);
+gymrs_status gymrs_sharded_set_param_table(gymrs_sharded* h, const void* rows /* k x gymrs_<kind>_params */, uint32_t k);
+gymrs_status gymrs_sharded_get_param_table(gymrs_sharded* h, void* rows_out, uint32_t capacity, uint32_t* k);
+gymrs_status gymrs_sharded_set_param_index(gymrs_sharded* h, uint64_t first, uint64_t count, const uint16_t* index_host);
+gymrs_status gymrs_sharded_get_param_index(gymrs_sharded* h, uint64_t first, uint64_t count, uint16_t* index_out);
 
 /* ---- closed-loop rollouts: a small policy evaluated inside the kernel (CartPole, MountainCar) ----------------------------- */
 /* gymrs_rollout plays the random policy only.  With a policy set, gymrs_rollout_policy advances n_steps steps in ONE launch with
@@ -474,13 +486,22 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
  *     policy meets the same lanes_per_policy x E start states (common random numbers).
  *   - steps: the action is the policy's (the definition under "closed-loop rollouts"), the physics the env's step with the
  *     engine's current uniform parameters (the general path covers out-of-range angles and NaN states, as in gymrs_step).
- *   - end: with M = d->max_episode_steps, or the params' max_episode_steps (default 500 / 200) when that is 0, the episode ends
+ *     With GYMRS_EVAL_LANE_PARAMS in d->flags every lane plays with the parameters gymrs_step would use for it right now: row
+ *     index[i] of the active parameter table ("per-lane physics"), or, without a table, the uniform parameters -- then the
+ *     call is bit-identical to the call without the flag, so a search loop may set it unconditionally.  Rows and index are
+ *     read in stream order (an index rewritten through gymrs_param_index_ptr on the engine's stream is seen by the next
+ *     evaluation); every lane fetches its row once per launch.  A lane whose index is >= K (possible through the zero-copy
+ *     view only) plays no episode, adds nothing to any record and leaves its lengths_dev entries unwritten; no error is
+ *     raised.  Start states do not depend on the physics fields.
+ *   - end: with M = d->max_episode_steps, or the params' max_episode_steps (default 500 / 200; the one every row of a table
+ *     shares) when that is 0, the episode ends
  *     at the first step k >= 1 that reports done, or at k = M.  L = k; done = the last step's done flag; truncated = (L == M)
  *     (both may be set, as in gymrs_step); return = +L (CartPole) or -L (MountainCar): both envs pay a constant per step.
  * Every episode adds to the record of its policy: return_sum += return, return_sq_sum += return^2, episodes += 1, done += done,
  * truncated += truncated, steps += L (all modulo 2^64), return_min / return_max = the lowest / highest return.  A policy with
  * no lane in this engine keeps the identity {0, 0, 0, 0, 0, 0, INT64_MAX, INT64_MIN}.  Integers throughout: exact, independent
- * of scheduling and of how a batch is cut into engines (add the sums, take the min of the mins and the max of the maxes).
+ * of scheduling and of how a batch is cut into engines (add the sums, take the min of the mins and the max of the maxes; with
+ * a table: provided the engines hold the same rows and the matching slices of the index).
  * d->lengths_dev (may be NULL): device uint32 [E][n_envs], 4-byte aligned; entry [ep][i] = L | (done ? 0x80000000 : 0).
  *   - The call reads no lane array and writes none: state, observations, reward / done / truncated, final observations,
  *     steps_beyond_terminated, tick, statistics, the reset log, the fitness table and the parameter index stay bit for bit; the
@@ -490,14 +511,21 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
  *     discarded by every gymrs_set_policy, not part of clone or snapshot.  gymrs_get_policy_eval copies records [first, first +
  *     count) and synchronises; gymrs_policy_eval_ptr is the zero-copy view (*n_policies may be NULL), valid until the next
  *     gymrs_set_policy or destroy.
- *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, an active parameter table, E == 0, reserved != 0, unknown
- *     flag bits, a misaligned lengths_dev, E * M > GYMRS_POLICY_EVAL_MAX_STEPS (the bound of the kernel's running time, and
+ *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, an active parameter table without GYMRS_EVAL_LANE_PARAMS (a
+ *     plain descriptor is never played with one set of parameters behind the caller's back), E == 0, reserved != 0, unknown
+ *     flag bits (bit 1 is not assigned), a misaligned lengths_dev, E * M > GYMRS_POLICY_EVAL_MAX_STEPS (the bound of the kernel's running time, and
  *     what keeps a lane's sum of L in 32 bits).  Non-finite weights are legal.
- *   - Not built: moving episodes between the lanes of a wave (a wave runs until its slowest lane is through), parameter tables,
- *     8 lanes per work-item.
- * gymrs_sharded_evaluate_policy runs it on every block (lengths_dev must be NULL there); gymrs_sharded_get_policy_eval merges
- * the blocks' records on the host. */
+ *   - Not built: moving episodes between the lanes of a wave (a wave runs until its slowest lane is through), 8 lanes per
+ *     work-item, and policy x table for the fused rollout calls: gymrs_rollout_policy, _record and _fitness still refuse an
+ *     active parameter table, because they take no flags word through which a caller could opt in.
+ *   - Per-(policy, row) records need no further call: replicate every policy's weights K times (n_policies' = P * K, policy
+ *     q = p * K + r carries p's weights) and set index[i] = ((global_env_offset + i) / lanes_per_policy) % K; record q is then
+ *     policy p under row r, and a robust objective is the minimum over r.
+ * gymrs_sharded_evaluate_policy runs it on every block (lengths_dev must be NULL there; the flags pass through, so
+ * GYMRS_EVAL_LANE_PARAMS works with gymrs_sharded_set_param_table / _index); gymrs_sharded_get_policy_eval merges the blocks'
+ * records on the host. */
 #define GYMRS_EVAL_COMMON_STARTS 1u
+#define GYMRS_EVAL_LANE_PARAMS 4u /* bit 2 */
 #define GYMRS_POLICY_EVAL_MAX_STEPS 16777216u
 typedef struct { uint32_t episodes_per_lane, max_episode_steps; uint64_t seed; uint32_t flags, reserved; uint32_t* lengths_dev; } gymrs_eval_desc; /* 32 B */
 typedef struct { int64_t return_sum; uint64_t return_sq_sum, episodes, done, truncated, steps; int64_t return_min, return_max; } gymrs_policy_eval; /* 64 B */

@@ -246,6 +246,15 @@ public:
         const gymrs_eval_desc d{episodes_per_lane, max_episode_steps, seed, common_starts ? GYMRS_EVAL_COMMON_STARTS : 0u, 0u, lengths_dev};
         check(gymrs_evaluate_policy(e_, &d));
     }
+    // lane_params (GYMRS_EVAL_LANE_PARAMS): every lane plays with the row of the parameter table step() would use for it; without a
+    // table it changes nothing.  Without it an engine with a table refuses the call.
+    void evaluate_policy(std::uint32_t episodes_per_lane, std::uint32_t max_episode_steps, std::uint64_t seed, bool common_starts,
+                         std::uint32_t* lengths_dev, bool lane_params)
+    {
+        const gymrs_eval_desc d{episodes_per_lane, max_episode_steps, seed,
+                                (common_starts ? GYMRS_EVAL_COMMON_STARTS : 0u) | (lane_params ? GYMRS_EVAL_LANE_PARAMS : 0u), 0u, lengths_dev};
+        check(gymrs_evaluate_policy(e_, &d));
+    }
     std::vector<gymrs_policy_eval> policy_eval(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_eval> out(count);
@@ -367,6 +376,22 @@ public:
         return out;
     }
     void set_params(const void* params) { check(gymrs_sharded_set_params(h_, params)); }
+    // per-lane physics on the batch: the same rows on every block (set_param_table(nullptr, 0) switches it off), the index in BATCH
+    // lane numbering; evaluate_policy with GYMRS_EVAL_LANE_PARAMS in d.flags plays it
+    void set_param_table(const void* rows, std::uint32_t k) { check(gymrs_sharded_set_param_table(h_, rows, k)); }
+    std::uint32_t param_table(void* rows_out, std::uint32_t capacity) // K; rows_out (capacity >= K, or nullptr with 0) from block 0
+    {
+        std::uint32_t k = 0;
+        check(gymrs_sharded_get_param_table(h_, rows_out, capacity, &k));
+        return k;
+    }
+    void set_param_index(std::uint64_t first, std::uint64_t count, const std::uint16_t* index) { check(gymrs_sharded_set_param_index(h_, first, count, index)); }
+    std::vector<std::uint16_t> param_index(std::uint64_t first, std::uint64_t count)
+    {
+        std::vector<std::uint16_t> out(count);
+        check(gymrs_sharded_get_param_index(h_, first, count, out.data()));
+        return out;
+    }
     void sync() { check(gymrs_sharded_sync(h_)); }
     std::array<double, 4> stats() // {sum_return, sum_length, n_episodes, n_steps} of the whole batch
     {
