@@ -110,8 +110,9 @@ def hard_push_rows(max_steps=MAX_STEPS):
     return rows
 
 
-def states_leave_the_fast_range(kind, n, gid0, row, weights, hidden, lanes_per_policy, starts, max_steps):
-    """How many lane-steps of play(...) with `row` start from a state outside the fast path's range while the lane is still playing"""
+def states_leave_the_fast_range(kind, n, gid0, row, weights, hidden, lanes_per_policy, starts, max_steps, lanes=None):
+    """How many lane-steps of play(...) with `row` start from a state outside the fast path's range while the lane is still playing
+    (`lanes`: a boolean mask of the lanes to count, default all)"""
     from oracle.bindings import TwinEngine
     w = np.ascontiguousarray(weights, np.float32).reshape(-1, ref.size_of(kind, hidden))
     tw = TwinEngine(lp.twin(), kind, n, row, flags=0, gid0=gid0)
@@ -119,7 +120,7 @@ def states_leave_the_fast_range(kind, n, gid0, row, weights, hidden, lanes_per_p
     for st in starts:
         tw.reset(0)
         tw.set_state(st)
-        playing = np.ones(n, bool)
+        playing = np.ones(n, bool) if lanes is None else np.array(lanes, bool)
         for k in range(1, max_steps + 1):
             count += int((lp.beyond_range(kind, tw.get_state()) & playing).sum())
             tw.step(ref.policy_ref(kind, hidden, w, lanes_per_policy, gid0, tw.get_obs()))

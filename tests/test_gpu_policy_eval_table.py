@@ -233,7 +233,9 @@ def test_cartpole_semi_implicit_integrator(gymrs, common):
 
 @pytest.mark.parametrize("kind", [0, 1])
 def test_non_finite_weights_under_a_table(gymrs, kind):
-    """NaN observations-times-weights are legal and the states they lead to take the general path"""
+    """NaN and infinite weights are legal: the logits they give are NaN or infinite and the argmax rule still picks a discrete action.
+    The states stay inside the fast path's range (an action of a Discrete env, whatever it was chosen from, moves no state out of
+    it); tests/test_gpu_policy_slowpaths.py has the cases that leave it."""
     n, gid0, lpp = 1300, 12345, 500
     w = make_weights(kind, 7, P, seed=18)
     w[0, 3], w[1, 5], w[2, -1] = np.nan, np.inf, -np.inf

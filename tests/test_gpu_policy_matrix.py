@@ -33,27 +33,31 @@ def where(got, want, classes):
     return {COPIES[c]: int((classes[lanes] == c).sum()) for c in np.unique(classes[lanes])}, lanes[:8].tolist()
 
 
-def same(what, got, want, classes, at):
+def same(what, got, want, classes, at, nan_equal=False):
+    """nan_equal (tests/test_gpu_policy_slowpaths.py, whose states hold NaNs): a NaN equals any NaN, as in tests/test_gpu_slowpaths.py"""
     got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
     assert got.shape == want.shape and got.dtype == want.dtype, (what, at, got.shape, want.shape, got.dtype, want.dtype)
     if got.dtype == np.float32:
+        if nan_equal:
+            both = np.isnan(got) & np.isnan(want)
+            got, want = np.where(both, np.float32(0), got), np.where(both, np.float32(0), want)
         got, want = got.view(np.uint32), want.view(np.uint32)
     assert np.array_equal(got, want), (what, at) + where(got, want, classes)
 
 
-def assert_launch(eng, want, flags, classes, at, first=0):
+def assert_launch(eng, want, flags, classes, at, first=0, nan_equal=False):
     """The engine after a launch == the reference's record of it (`want`), lanes [first, first + n_envs) of the reference's batch"""
     sl = slice(first, first + eng.n_envs)
     classes = classes[sl]
-    same("state", eng.get_state(), want.state[:, sl], classes, at)
-    same("obs", eng.get_obs(), want.obs[:, sl], classes, at)
+    same("state", eng.get_state(), want.state[:, sl], classes, at, nan_equal)
+    same("obs", eng.get_obs(), want.obs[:, sl], classes, at, nan_equal)
     r, d, tr = eng.get_step_result()
-    same("reward", r, want.reward[sl], classes, at)
+    same("reward", r, want.reward[sl], classes, at, nan_equal)
     same("done", d, want.done[sl], classes, at)
     if flags & T:
         same("truncated", tr, want.truncated[sl], classes, at)
     if flags & F:
-        same("final_obs", eng.get_final_obs(), want.final[:, sl], classes, at)
+        same("final_obs", eng.get_final_obs(), want.final[:, sl], classes, at, nan_equal)
     assert eng.tick()[0] == want.tick, (at, eng.tick(), want.tick)
 
 
