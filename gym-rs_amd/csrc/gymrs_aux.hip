@@ -79,13 +79,14 @@ __global__ __launch_bounds__(kBlock) void fill_actions_kernel(typename Env::Acti
 constexpr int kStatsThreads = 1024;
 constexpr int kStatsMaxBlocks = kStatsPartials;
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+// (butterfly sums of the read-out kernels: every lane ends with the total.  The wave_* reductions of gymrs_tile.h are the kernels' own.)
+__device__ __forceinline__ unsigned long long shfl_sum_u64(unsigned long long v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
-__device__ __forceinline__ double wave_sum_f64(double v)
+__device__ __forceinline__ double shfl_sum_f64(double v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -99,9 +100,9 @@ __device__ __forceinline__ void block_sum3(unsigned long long& len, unsigned lon
     __shared__ unsigned long long s_len[WAVES], s_ep[WAVES];
     __shared__ double s_ret[WAVES];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    len = wave_sum_u64(len);
-    ep = wave_sum_u64(ep);
-    ret = wave_sum_f64(ret);
+    len = shfl_sum_u64(len);
+    ep = shfl_sum_u64(ep);
+    ret = shfl_sum_f64(ret);
     if (lane == 0) {
         s_len[wave] = len;
         s_ep[wave] = ep;
@@ -112,9 +113,9 @@ __device__ __forceinline__ void block_sum3(unsigned long long& len, unsigned lon
         len = lane < WAVES ? s_len[lane] : 0ull;
         ep = lane < WAVES ? s_ep[lane] : 0ull;
         ret = lane < WAVES ? s_ret[lane] : 0.0;
-        len = wave_sum_u64(len);
-        ep = wave_sum_u64(ep);
-        ret = wave_sum_f64(ret);
+        len = shfl_sum_u64(len);
+        ep = shfl_sum_u64(ep);
+        ret = shfl_sum_f64(ret);
     }
 }
 
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(kStatsThreads) void stats_partial_kernel(const uint
 // workgroup; max_age_finalize_kernel (one workgroup) takes the maximum of those and hands it to the host through mapped
 // host memory -- no copy engine in the stream: a 4-byte device-to-host copy costs the compute queue tens of
 // microseconds of cross-engine synchronisation.  ~4 + 3 us at 2^20 lanes, a few times per time limit.
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+__device__ __forceinline__ uint32_t shfl_max_u32(uint32_t v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -228,11 +229,11 @@ __global__ __launch_bounds__(kStatsThreads) void max_age_partial_kernel(const ui
         upd(x.w);
     }
     for (uint64_t i = (n4 << 2) + tid; i < n; i += stride) upd(ep_start[i]);
-    age = wave_max_u32(age);
+    age = shfl_max_u32(age);
     if ((threadIdx.x & 63u) == 0) s_age[threadIdx.x >> 6] = age;
     __syncthreads();
     if (threadIdx.x < 64) {
-        age = wave_max_u32(threadIdx.x < kStatsThreads / 64 ? s_age[threadIdx.x] : 0u);
+        age = shfl_max_u32(threadIdx.x < kStatsThreads / 64 ? s_age[threadIdx.x] : 0u);
         if (threadIdx.x == 0) partials[blockIdx.x] = age;
     }
 }
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(kStatsMaxBlocks) void max_age_finalize_kernel(const
 {
     __shared__ uint32_t s_age[kStatsMaxBlocks / 64];
     uint32_t age = threadIdx.x < n_partials ? partials[threadIdx.x] : 0u;
-    age = wave_max_u32(age);
+    age = shfl_max_u32(age);
     if ((threadIdx.x & 63u) == 0) s_age[threadIdx.x >> 6] = age;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -38,18 +38,12 @@ hipError_t launch_evaluate_policy(gymrs_env_kind kind, uint32_t flags, const Eva
         default: return hipErrorInvalidValue;
         }
     }
-    switch (kind) {
-    case GYMRS_CARTPOLE:
-        hipLaunchKernelGGL((evaluate_policy_kernel<CartPoleT>), dim3(step_grid(a.n, kEvalVec)), dim3(kBlock), 0, stream, a,
-                           *static_cast<const CartPoleConsts*>(consts), p);
-        break;
-    case GYMRS_MOUNTAIN_CAR:
-        hipLaunchKernelGGL((evaluate_policy_kernel<MountainCarT>), dim3(step_grid(a.n, kEvalVec)), dim3(kBlock), 0, stream, a,
-                           *static_cast<const MountainCarConsts*>(consts), p);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_policy_env(kind, [&](auto env) {
+        using Env = typename decltype(env)::type;
+        hipLaunchKernelGGL((evaluate_policy_kernel<Env>), dim3(step_grid(a.n, kEvalVec)), dim3(kBlock), 0, stream, a,
+                           *static_cast<const typename Env::Consts*>(consts), p);
+        return hipGetLastError();
+    });
 }
 
 } // namespace gymrs

@@ -15,33 +15,6 @@ namespace gymrs {
 
 constexpr int kEvalVec = 4;
 
-__device__ __forceinline__ void eval_add(unsigned long long* p, unsigned long long v)
-{
-    if (v != 0) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Sum of a 64-bit value over the wavefront, modulo 2^64 (wave-uniform): 16-bit quarters summed on their own (64 x 2^16 fits 32
-// bits).  Must be called with every work-item of the wave active.
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-    unsigned long long s = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s += (unsigned long long)wave_sum_u32((uint32_t)(v >> (16 * q)) & 0xffffu) << (16 * q);
-    return s;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m, 64));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-
 // One record's worth of accumulators, in episode lengths.  A lane plays at most E * M <= kMaxEvalSteps (2^24) steps, so 32 bits
 // hold the steps, episodes and flags of a work-item's four lanes; the squares need 64.
 struct EvalAcc {
@@ -76,12 +49,12 @@ __device__ __forceinline__ void eval_commit(gymrs_policy_eval* rec, unsigned lon
 {
     if (episodes == 0) return; // (the record keeps its identity)
     unsigned long long* w = reinterpret_cast<unsigned long long*>(rec); // {return_sum, return_sq_sum, episodes, done, truncated, steps, min, max}
-    eval_add(w + 0, SIGN > 0 ? steps : 0ull - steps); // two's complement
-    eval_add(w + 1, sq);
-    eval_add(w + 2, episodes);
-    eval_add(w + 3, done);
-    eval_add(w + 4, trunc);
-    eval_add(w + 5, steps);
+    atomic_add_nonzero(w + 0, SIGN > 0 ? steps : 0ull - steps); // two's complement
+    atomic_add_nonzero(w + 1, sq);
+    atomic_add_nonzero(w + 2, episodes);
+    atomic_add_nonzero(w + 3, done);
+    atomic_add_nonzero(w + 4, trunc);
+    atomic_add_nonzero(w + 5, steps);
     const long long lo = SIGN > 0 ? (long long)lmin : -(long long)lmax, hi = SIGN > 0 ? (long long)lmax : -(long long)lmin;
     (void)__hip_atomic_fetch_min(reinterpret_cast<long long*>(w + 6), lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     (void)__hip_atomic_fetch_max(reinterpret_cast<long long*>(w + 7), hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

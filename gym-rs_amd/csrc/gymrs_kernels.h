@@ -1,5 +1,15 @@
-// gymrs_kernels.h — launch interface between the engine (gymrs_engine.hip) and the gfx950 kernels
-// (gymrs_step_<env>.hip, gymrs_rollout.hip, gymrs_aux.hip).  Plain structs passed by value as kernel arguments (uniform -> SGPRs).
+// gymrs_kernels.h — launch interface between the engine (gymrs_engine.hip, gymrs_engine_io.hip) and the gfx950 kernels.  Plain
+// structs passed by value as kernel arguments (uniform -> SGPRs).  The kernel files:
+//   gymrs_step_<env>.hip     the per-step kernel table of one env type (gymrs_step_impl.h), one translation unit each
+//   gymrs_table_<env>.hip    the per-step, rollout and evaluation kernels of one env type with a parameter table (TableT)
+//   gymrs_step_aql.hip       the per-step kernels once more, as the code object of the engine's own AQL dispatcher
+//   gymrs_rollout.hip        the fused random-policy rollout (gymrs_rollout_impl.h)
+//   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h)
+//   gymrs_rollout_fitness.hip  that rollout with per-policy fitness counters
+//   gymrs_evaluate.hip       episodic policy evaluation (gymrs_evaluate.h, gymrs_evaluate_impl.h)
+//   gymrs_aux.hip            everything off the per-step path: reset, action fill, statistics, folds
+// gymrs_launch.h holds the one launch table (flag sets x lanes per work-item) the step and rollout families dispatch through;
+// gymrs_tile.h the device code they share.
 #pragma once
 #include <hip/hip_runtime.h>
 

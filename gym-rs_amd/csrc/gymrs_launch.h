@@ -1,0 +1,92 @@
+// gymrs_launch.h -- THE launch table of the kernel library: which (lanes per work-item, flag set) pairs a kernel family is
+// built for, and how a launch's run-time values reach the instantiation built for them.  Every family with a table goes
+// through here: the per-step kernels (gymrs_step_impl.h), the random-policy rollout (gymrs_rollout_impl.h), the closed-loop
+// rollout (gymrs_rollout_policy.hip) and its fitness variant (gymrs_rollout_fitness.hip).
+//
+// Plain host C++17, no HIP: a function here turns a run-time value into a compile-time constant (a std::integral_constant
+// handed to a generic callable, whose body names the kernel template) or refuses it with the caller's `invalid` result.
+// tests/test_launch_table.py compiles this header alone and walks it.
+#pragma once
+#include <cstdint>
+#include <type_traits>
+
+#include "gymrs_amd.h"
+
+namespace gymrs {
+
+template <uint32_t V>
+using FlagSet = std::integral_constant<uint32_t, V>;
+template <int V>
+using Lanes = std::integral_constant<int, V>;
+
+// Developer builds (tools/devbuild.py, -DGYMRS_DEV_MINIMAL): a table dispatched with MINIMAL = kDevMinimal shrinks to the
+// headline flag sets at 4 lanes per work-item -- seconds instead of minutes.  The per-step table does; the others stay whole.
+#ifdef GYMRS_DEV_MINIMAL
+constexpr bool kDevMinimal = true;
+#else
+constexpr bool kDevMinimal = false;
+#endif
+
+namespace detail {
+template <bool BUILT, class C, class R, class Fn>
+R reach(R invalid, Fn& fn)
+{
+    if constexpr (BUILT)
+        return fn(C{});
+    else
+        return invalid;
+}
+} // namespace detail
+
+// The ten flag sets.  Statistics and final observations need auto-reset: without it both bits are dropped.
+template <bool MINIMAL = false, class R, class Fn>
+R dispatch_flag_set(uint32_t flags, R invalid, Fn&& fn)
+{
+    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
+    constexpr bool ALL = !MINIMAL;
+    if (!(flags & A)) flags &= ~(S | F);
+    switch (flags & (A | S | T | F)) {
+    case 0: return detail::reach<ALL, FlagSet<0>>(invalid, fn);
+    case A: return detail::reach<ALL, FlagSet<A>>(invalid, fn);
+    case A | S: return detail::reach<true, FlagSet<A | S>>(invalid, fn);
+    case T: return detail::reach<ALL, FlagSet<T>>(invalid, fn);
+    case A | T: return detail::reach<ALL, FlagSet<A | T>>(invalid, fn);
+    case A | S | T: return detail::reach<true, FlagSet<A | S | T>>(invalid, fn);
+    case A | F: return detail::reach<ALL, FlagSet<A | F>>(invalid, fn);
+    case A | S | F: return detail::reach<ALL, FlagSet<A | S | F>>(invalid, fn);
+    case A | T | F: return detail::reach<ALL, FlagSet<A | T | F>>(invalid, fn);
+    case A | S | T | F: return detail::reach<ALL, FlagSet<A | S | T | F>>(invalid, fn);
+    default: return invalid;
+    }
+}
+
+// Lanes per work-item: 4 or 8.
+template <bool MINIMAL = false, class R, class Fn>
+R dispatch_lanes(int vec, R invalid, Fn&& fn)
+{
+    switch (vec) {
+    case 4: return detail::reach<true, Lanes<4>>(invalid, fn);
+    case 8: return detail::reach<!MINIMAL, Lanes<8>>(invalid, fn);
+    default: return invalid;
+    }
+}
+
+// Both: fn(Lanes<VEC>, FlagSet<FLAGS>).
+template <bool MINIMAL = false, class R, class Fn>
+R dispatch_table(int vec, uint32_t flags, R invalid, Fn&& fn)
+{
+    return dispatch_lanes<MINIMAL>(vec, invalid, [&](auto lanes) {
+        return dispatch_flag_set<MINIMAL>(flags, invalid, [&](auto flag_set) { return fn(lanes, flag_set); });
+    });
+}
+
+// A rollout that records its trajectory (RolloutArgs::rec_obs): the recording variant of a rollout kernel exists at 4 lanes per
+// work-item only.  fn(std::bool_constant<REC>).
+template <int VEC, class R, class Fn>
+R dispatch_recording(bool record, R invalid, Fn&& fn)
+{
+    if (record) return detail::reach<VEC == 4, std::true_type>(invalid, fn);
+    return detail::reach<true, std::false_type>(invalid, fn);
+}
+
+} // namespace gymrs

@@ -1,5 +1,6 @@
 // gymrs_policy.h -- evaluation of a small policy (affine, or one hidden ReLU layer) on the observation tile of a work-item:
-// shared by policy_actions_kernel and the closed-loop rollout kernel (gymrs_rollout_policy.hip).  gfx950 device code only.
+// shared by policy_actions_kernel, the closed-loop rollout kernels (rollout_policy_body, gymrs_rollout_impl.h) and the episodic
+// evaluation kernel (gymrs_evaluate_impl.h).  gfx950 device code, and the host's choice of the env type of a policy launch.
 //
 // The arithmetic is fixed to the bit (include/gymrs_amd.h, "closed-loop rollouts"): every multiply-add is ONE fused
 // v_fma_f32 in the order written there, the ReLU is a compare-select (NaN and -0 give +0), the action is the first maximum
@@ -137,5 +138,20 @@ struct PolicyActions {
         policy_eval<Env, VEC, UNI>(w, hidden, st, act);
     }
 };
+
+// Host side: the envs that take a policy (the Discrete ones), by kind.  fn(EnvTag<Env>); any other kind is refused.
+template <class Env>
+struct EnvTag {
+    using type = Env;
+};
+template <class Fn>
+hipError_t dispatch_policy_env(gymrs_env_kind kind, Fn&& fn)
+{
+    switch (kind) {
+    case GYMRS_CARTPOLE: return fn(EnvTag<CartPoleT>{});
+    case GYMRS_MOUNTAIN_CAR: return fn(EnvTag<MountainCarT>{});
+    default: return hipErrorInvalidValue;
+    }
+}
 
 } // namespace gymrs

@@ -7,20 +7,6 @@
 
 namespace gymrs {
 
-__device__ __forceinline__ void fitness_add(unsigned long long* p, unsigned long long v)
-{
-    if (v != 0) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The sum of a 32-bit signed accumulator over the wavefront, exact in 64 bits (wave-uniform): the halves are summed on their own
-// (64 x 2^16 fits 32 bits).  Must be called with every work-item of the wave active.
-__device__ __forceinline__ long long wave_sum_i64(int32_t v)
-{
-    const uint32_t lo = wave_sum_u32((uint32_t)v & 0xffffu);
-    const int32_t hi = (int32_t)wave_sum_u32((uint32_t)(v >> 16)); // |v >> 16| <= 2^15: the sum of 64 of them is exact modulo 2^32
-    return (long long)hi * 65536 + (long long)lo;
-}
-
 // One record's worth of accumulators.  32 bits each: a launch adds at most n_steps to a lane's counter and VEC * n_steps to a
 // work-item's, and the host refuses n_steps > kMaxFitnessSteps (2^24; VEC <= 8).  Without GYMRS_TIME_LIMIT (TLIM) no step is
 // truncated: `truncated` stays 0 and `episodes` is `done`, so two registers do (the gathered path holds a set per LANE).
@@ -53,10 +39,10 @@ __device__ __forceinline__ void fitness_commit(gymrs_policy_fitness* rec, long l
                                                unsigned long long trunc)
 {
     unsigned long long* w = reinterpret_cast<unsigned long long*>(rec); // {reward_sum (two's complement), episodes, done, truncated}
-    fitness_add(w + 0, (unsigned long long)reward);
-    fitness_add(w + 1, episodes);
-    fitness_add(w + 2, done);
-    fitness_add(w + 3, trunc);
+    atomic_add_nonzero(w + 0, (unsigned long long)reward);
+    atomic_add_nonzero(w + 1, episodes);
+    atomic_add_nonzero(w + 2, done);
+    atomic_add_nonzero(w + 3, trunc);
 }
 
 // The Fit hook of rollout_block.  UNI (the wave's lanes all use one policy): one accumulator set per work-item, an integer wave
@@ -121,6 +107,8 @@ struct PolicyFitness<VEC, TLIM, false> {
     }
 };
 
+// rollout_policy_kernel's body (gymrs_rollout_policy.hip, where a note says why the two are not one function) with the hook
+// above.  No recording variant.
 template <class Env, int VEC, uint32_t FLAGS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(16 / VEC, 16 / VEC))) void rollout_policy_fitness_kernel(
     const StepArgs a, const RolloutArgs r, const typename Env::Consts c, const PolicyArgs p, gymrs_policy_fitness* const fitness)
@@ -150,58 +138,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(16 / VEC
     }
 }
 
-template <class Env, int VEC, uint32_t FLAGS>
-static hipError_t fitness_one(const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p, gymrs_policy_fitness* fitness,
-                              hipStream_t stream)
-{
-    launch_begin();
-    hipLaunchKernelGGL((rollout_policy_fitness_kernel<Env, VEC, FLAGS>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream, a, r,
-                       *static_cast<const typename Env::Consts*>(consts), p, fitness);
-    return hipGetLastError();
-}
-
-template <class Env, int VEC>
-static hipError_t fitness_flags(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
-    if (!(flags & A)) flags &= ~(S | F);
-    switch (flags & (A | S | T | F)) {
-    case 0: return fitness_one<Env, VEC, 0>(a, r, consts, p, fitness, stream);
-    case A: return fitness_one<Env, VEC, A>(a, r, consts, p, fitness, stream);
-    case A | S: return fitness_one<Env, VEC, A | S>(a, r, consts, p, fitness, stream);
-    case T: return fitness_one<Env, VEC, T>(a, r, consts, p, fitness, stream);
-    case A | T: return fitness_one<Env, VEC, A | T>(a, r, consts, p, fitness, stream);
-    case A | S | T: return fitness_one<Env, VEC, A | S | T>(a, r, consts, p, fitness, stream);
-    case A | F: return fitness_one<Env, VEC, A | F>(a, r, consts, p, fitness, stream);
-    case A | S | F: return fitness_one<Env, VEC, A | S | F>(a, r, consts, p, fitness, stream);
-    case A | T | F: return fitness_one<Env, VEC, A | T | F>(a, r, consts, p, fitness, stream);
-    case A | S | T | F: return fitness_one<Env, VEC, A | S | T | F>(a, r, consts, p, fitness, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <class Env>
-static hipError_t fitness_vec(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                              gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    switch (vec) {
-    case 4: return fitness_flags<Env, 4>(flags, a, r, consts, p, fitness, stream);
-    case 8: return fitness_flags<Env, 8>(flags, a, r, consts, p, fitness, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_rollout_policy_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                          const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream)
 {
     if (a.n == 0 || r.n_steps == 0) return hipSuccess;
     if ((flags & kFlagTable) || r.rec_obs || !fitness || r.n_steps > kMaxFitnessSteps) return hipErrorInvalidValue;
-    switch (kind) {
-    case GYMRS_CARTPOLE: return fitness_vec<CartPoleT>(vec, flags, a, r, consts, p, fitness, stream);
-    case GYMRS_MOUNTAIN_CAR: return fitness_vec<MountainCarT>(vec, flags, a, r, consts, p, fitness, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_policy_env(kind, [&](auto env) {
+        using Env = typename decltype(env)::type;
+        return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
+            constexpr int VEC = decltype(lanes)::value;
+            launch_begin();
+            hipLaunchKernelGGL((rollout_policy_fitness_kernel<Env, VEC, decltype(flag_set)::value>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream,
+                               a, r, *static_cast<const typename Env::Consts*>(consts), p, fitness);
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace gymrs

@@ -1,6 +1,8 @@
-// gymrs_rollout_impl.h -- the fused multi-step (random-policy rollout) kernel, gfx950, and its launch table: included by
+// gymrs_rollout_impl.h -- the fused multi-step kernel, gfx950: rollout_block (also the body of the closed-loop kernels of
+// gymrs_rollout_policy.hip and gymrs_rollout_fitness.hip) and the random-policy rollout_kernel with its launch: included by
 // gymrs_rollout.hip (the uniform envs) and by gymrs_table_<env>.hip (TableT, per-lane parameter tables).
 #pragma once
+#include "gymrs_launch.h"
 #include "gymrs_tile.h"
 
 namespace gymrs {
@@ -136,51 +138,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((Env::kT
         rollout_block<Env, VEC, FLAGS, false, REC>(a, r, c, lds);
 }
 
-template <class Env, int VEC, uint32_t FLAGS>
-static hipError_t rollout_one(const StepArgs& a, const RolloutArgs& r, const void* consts, hipStream_t stream)
-{
-    launch_begin();
-    if constexpr (VEC == 4) { // the recording variant exists at 4 lanes per work-item only
-        if (r.rec_obs) {
-            hipLaunchKernelGGL((rollout_kernel<Env, VEC, FLAGS, true>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream, a, r,
-                               *static_cast<const typename Env::Consts*>(consts));
-            return hipGetLastError();
-        }
-    }
-    if (r.rec_obs) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((rollout_kernel<Env, VEC, FLAGS, false>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream, a, r,
-                       *static_cast<const typename Env::Consts*>(consts));
-    return hipGetLastError();
-}
-
-template <class Env, int VEC>
-static hipError_t rollout_flags(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, hipStream_t stream)
-{
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
-    if (!(flags & A)) flags &= ~(S | F);
-    switch (flags & (A | S | T | F)) {
-    case 0: return rollout_one<Env, VEC, 0>(a, r, consts, stream);
-    case A: return rollout_one<Env, VEC, A>(a, r, consts, stream);
-    case A | S: return rollout_one<Env, VEC, A | S>(a, r, consts, stream);
-    case T: return rollout_one<Env, VEC, T>(a, r, consts, stream);
-    case A | T: return rollout_one<Env, VEC, A | T>(a, r, consts, stream);
-    case A | S | T: return rollout_one<Env, VEC, A | S | T>(a, r, consts, stream);
-    case A | F: return rollout_one<Env, VEC, A | F>(a, r, consts, stream);
-    case A | S | F: return rollout_one<Env, VEC, A | S | F>(a, r, consts, stream);
-    case A | T | F: return rollout_one<Env, VEC, A | T | F>(a, r, consts, stream);
-    case A | S | T | F: return rollout_one<Env, VEC, A | S | T | F>(a, r, consts, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
+// The launch: lanes per work-item x flag set (gymrs_launch.h) x recording.
 template <class Env>
 static hipError_t rollout_vec(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, hipStream_t stream)
 {
-    switch (vec) {
-    case 4: return rollout_flags<Env, 4>(flags, a, r, consts, stream);
-    case 8: return rollout_flags<Env, 8>(flags, a, r, consts, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
+        constexpr int VEC = decltype(lanes)::value;
+        return dispatch_recording<VEC>(r.rec_obs != nullptr, hipErrorInvalidValue, [&](auto rec) {
+            launch_begin();
+            hipLaunchKernelGGL((rollout_kernel<Env, VEC, decltype(flag_set)::value, decltype(rec)::value>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0,
+                               stream, a, r, *static_cast<const typename Env::Consts*>(consts));
+            return hipGetLastError();
+        });
+    });
 }
 
 } // namespace gymrs

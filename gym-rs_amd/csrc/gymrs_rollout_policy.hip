@@ -1,6 +1,6 @@
-// gymrs_rollout_policy.hip -- the closed-loop kernels (gymrs_policy.h): policy_actions_kernel (the per-step counterpart:
-// observations -> actions) and rollout_policy_kernel, the fused multi-step kernel of gymrs_rollout_impl.h with the policy as
-// its action source.  CartPole and MountainCar (the Discrete envs), uniform constants only (no parameter table).
+// gymrs_rollout_policy.hip -- the closed-loop kernels (gymrs_policy.h) and their launches: policy_actions_kernel (the per-step
+// counterpart: observations -> actions) and rollout_policy_kernel, the fused multi-step kernel of gymrs_rollout_impl.h with the
+// policy as its action source.  CartPole and MountainCar (the Discrete envs), uniform constants only (no parameter table).
 #include "gymrs_policy.h"
 #include "gymrs_rollout_impl.h"
 
@@ -41,25 +41,23 @@ hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, voi
                                  hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    launch_begin();
     const uint64_t n_fast = (reinterpret_cast<uintptr_t>(actions) % 4 == 0) ? n : 0;
     uint8_t* out = static_cast<uint8_t*>(actions);
-    switch (kind) {
-    case GYMRS_CARTPOLE:
-        hipLaunchKernelGGL(policy_actions_kernel<CartPoleT>, dim3(step_grid(n, 4)), dim3(kBlock), 0, stream, s[0], s[1], s[2], s[3], out, n, n_fast,
-                           gid0, p);
-        break;
-    case GYMRS_MOUNTAIN_CAR:
-        hipLaunchKernelGGL(policy_actions_kernel<MountainCarT>, dim3(step_grid(n, 4)), dim3(kBlock), 0, stream, s[0], s[1], s[0], s[1], out, n,
-                           n_fast, gid0, p);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_policy_env(kind, [&](auto env) {
+        using Env = typename decltype(env)::type;
+        launch_begin();
+        // (the kernel takes four rows whatever the env: a 2-row observation passes its own again)
+        hipLaunchKernelGGL(policy_actions_kernel<Env>, dim3(step_grid(n, 4)), dim3(kBlock), 0, stream, s[0], s[1], s[2 % Env::kState],
+                           s[3 % Env::kState], out, n, n_fast, gid0, p);
+        return hipGetLastError();
+    });
 }
 
 // gymrs_rollout_policy / _record: rollout_block with the policy as its action source.  FULL / ragged and uniform / gathered
 // weights are both chosen per wave, wave-uniformly.  The register budget is rollout_kernel's (16 / VEC waves per SIMD).
+// (rollout_policy_fitness_kernel, gymrs_rollout_fitness.hip, repeats this body with a Fit hook: moved into one shared inline
+// function, the four kernel-argument pointer loads of the state rows leave the two weight branches for the kernel's entry and
+// every instantiation comes out with other register spills.)
 template <class Env, int VEC, uint32_t FLAGS, bool REC>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(16 / VEC, 16 / VEC))) void rollout_policy_kernel(
     const StepArgs a, const RolloutArgs r, const typename Env::Consts c, const PolicyArgs p)
@@ -86,65 +84,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(16 / VEC
     }
 }
 
-template <class Env, int VEC, uint32_t FLAGS>
-static hipError_t rollout_policy_one(const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p, hipStream_t stream)
-{
-    launch_begin();
-    if constexpr (VEC == 4) { // the recording variant exists at 4 lanes per work-item only
-        if (r.rec_obs) {
-            hipLaunchKernelGGL((rollout_policy_kernel<Env, VEC, FLAGS, true>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream, a, r,
-                               *static_cast<const typename Env::Consts*>(consts), p);
-            return hipGetLastError();
-        }
-    }
-    if (r.rec_obs) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((rollout_policy_kernel<Env, VEC, FLAGS, false>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream, a, r,
-                       *static_cast<const typename Env::Consts*>(consts), p);
-    return hipGetLastError();
-}
-
-template <class Env, int VEC>
-static hipError_t rollout_policy_flags(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                       hipStream_t stream)
-{
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
-    if (!(flags & A)) flags &= ~(S | F);
-    switch (flags & (A | S | T | F)) {
-    case 0: return rollout_policy_one<Env, VEC, 0>(a, r, consts, p, stream);
-    case A: return rollout_policy_one<Env, VEC, A>(a, r, consts, p, stream);
-    case A | S: return rollout_policy_one<Env, VEC, A | S>(a, r, consts, p, stream);
-    case T: return rollout_policy_one<Env, VEC, T>(a, r, consts, p, stream);
-    case A | T: return rollout_policy_one<Env, VEC, A | T>(a, r, consts, p, stream);
-    case A | S | T: return rollout_policy_one<Env, VEC, A | S | T>(a, r, consts, p, stream);
-    case A | F: return rollout_policy_one<Env, VEC, A | F>(a, r, consts, p, stream);
-    case A | S | F: return rollout_policy_one<Env, VEC, A | S | F>(a, r, consts, p, stream);
-    case A | T | F: return rollout_policy_one<Env, VEC, A | T | F>(a, r, consts, p, stream);
-    case A | S | T | F: return rollout_policy_one<Env, VEC, A | S | T | F>(a, r, consts, p, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <class Env>
-static hipError_t rollout_policy_vec(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                     hipStream_t stream)
-{
-    switch (vec) {
-    case 4: return rollout_policy_flags<Env, 4>(flags, a, r, consts, p, stream);
-    case 8: return rollout_policy_flags<Env, 8>(flags, a, r, consts, p, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                  const PolicyArgs& p, hipStream_t stream)
 {
     if (a.n == 0 || r.n_steps == 0) return hipSuccess;
     if (flags & kFlagTable) return hipErrorInvalidValue; // no policy x table kernels (the engine refuses first)
-    switch (kind) {
-    case GYMRS_CARTPOLE: return rollout_policy_vec<CartPoleT>(vec, flags, a, r, consts, p, stream);
-    case GYMRS_MOUNTAIN_CAR: return rollout_policy_vec<MountainCarT>(vec, flags, a, r, consts, p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_policy_env(kind, [&](auto env) {
+        using Env = typename decltype(env)::type;
+        return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
+            constexpr int VEC = decltype(lanes)::value;
+            return dispatch_recording<VEC>(r.rec_obs != nullptr, hipErrorInvalidValue, [&](auto rec) {
+                launch_begin();
+                hipLaunchKernelGGL((rollout_policy_kernel<Env, VEC, decltype(flag_set)::value, decltype(rec)::value>), dim3(step_grid(a.n, VEC)),
+                                   dim3(kBlock), 0, stream, a, r, *static_cast<const typename Env::Consts*>(consts), p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 } // namespace gymrs

@@ -37,6 +37,7 @@
 //     folds the ring inside the kernel (step_block below).  The other variants keep the scattered stores (after a dense
 //     ep_start read of the same wave they hit) and a per-wave counter slot (plain load at start, plain store at end).
 #pragma once
+#include "gymrs_launch.h"
 #include "gymrs_tile.h"
 
 namespace gymrs {
@@ -345,52 +346,22 @@ static hipError_t launch_one(const StepArgs& a, const void* consts, hipStream_t 
     return hipGetLastError();
 }
 
-template <class Env, int VEC, uint32_t NTBIT>
-static hipError_t launch_flags_nt(uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream)
-{
-    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
-    if (!(flags & A)) flags &= ~(S | F); // statistics and final observations need auto-reset
-    switch (flags & (A | S | T | F)) {
-#ifdef GYMRS_DEV_MINIMAL // developer builds (tools/devbuild.py): only the headline flag sets, seconds instead of minutes
-    case A | S: return launch_one<Env, VEC, A | S | NTBIT>(a, consts, stream);
-    case A | S | T: return launch_one<Env, VEC, A | S | T | NTBIT>(a, consts, stream);
-    default: return hipErrorInvalidValue;
-#else
-    case 0: return launch_one<Env, VEC, 0 | NTBIT>(a, consts, stream);
-    case A: return launch_one<Env, VEC, A | NTBIT>(a, consts, stream);
-    case A | S: return launch_one<Env, VEC, A | S | NTBIT>(a, consts, stream);
-    case T: return launch_one<Env, VEC, T | NTBIT>(a, consts, stream);
-    case A | T: return launch_one<Env, VEC, A | T | NTBIT>(a, consts, stream);
-    case A | S | T: return launch_one<Env, VEC, A | S | T | NTBIT>(a, consts, stream);
-    case A | F: return launch_one<Env, VEC, A | F | NTBIT>(a, consts, stream);
-    case A | S | F: return launch_one<Env, VEC, A | S | F | NTBIT>(a, consts, stream);
-    case A | T | F: return launch_one<Env, VEC, A | T | F | NTBIT>(a, consts, stream);
-    case A | S | T | F: return launch_one<Env, VEC, A | S | T | F | NTBIT>(a, consts, stream);
-    default: return hipErrorInvalidValue;
-#endif
-    }
-}
-
-// hint variants of a HIP launch: every access (small batches and far beyond the caches), only the stores nobody reads again
-// (kFlagNtOut: in between, profiles/r04_hints_by_size.log), none
-template <class Env, int VEC>
-static hipError_t launch_flags(uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream)
-{
-    if (flags & kFlagNonTemporal) return launch_flags_nt<Env, VEC, kFlagNonTemporal>(flags, a, consts, stream);
-    if (flags & kFlagNtOut) return launch_flags_nt<Env, VEC, kFlagNtOut>(flags, a, consts, stream);
-    return launch_flags_nt<Env, VEC, 0u>(flags, a, consts, stream);
-}
-
+// Lanes per work-item x hint variant x flag set (gymrs_launch.h; developer builds shrink this table: kDevMinimal).  The hint
+// variants of a HIP launch: every access (small batches and far beyond the caches), only the stores nobody reads again
+// (kFlagNtOut: in between, profiles/r04_hints_by_size.log), none.
 template <class Env>
 static hipError_t launch_vec(int vec, uint32_t flags, const StepArgs& a, const void* consts, hipStream_t stream)
 {
-    switch (vec) {
-    case 4: return launch_flags<Env, 4>(flags, a, consts, stream);
-#ifndef GYMRS_DEV_MINIMAL
-    case 8: return launch_flags<Env, 8>(flags, a, consts, stream);
-#endif
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_lanes<kDevMinimal>(vec, hipErrorInvalidValue, [&](auto lanes) {
+        auto hinted = [&](auto hint) {
+            return dispatch_flag_set<kDevMinimal>(flags, hipErrorInvalidValue, [&](auto flag_set) {
+                return launch_one<Env, decltype(lanes)::value, decltype(flag_set)::value | decltype(hint)::value>(a, consts, stream);
+            });
+        };
+        if (flags & kFlagNonTemporal) return hinted(FlagSet<kFlagNonTemporal>{});
+        if (flags & kFlagNtOut) return hinted(FlagSet<kFlagNtOut>{});
+        return hinted(FlagSet<0u>{});
+    });
 }
 
 } // namespace gymrs

@@ -1,6 +1,6 @@
-// gymrs_tile.h -- device code shared by the per-step kernel (gymrs_step_impl.h) and the fused rollout kernel
-// (gymrs_rollout.hip): the env policies, the register tile of a work-item, and one Env::step() of that tile
-// (physics + wave-level auto-reset).  gfx950 device code only.
+// gymrs_tile.h -- device code shared by the per-step kernel (gymrs_step_impl.h), the fused rollout kernels
+// (gymrs_rollout_impl.h) and the episodic evaluation kernel (gymrs_evaluate_impl.h): the wave reductions, the env policies, the
+// register tile of a work-item, and one Env::step() of that tile (physics + wave-level auto-reset).  gfx950 device code only.
 #pragma once
 #include <type_traits>
 
@@ -52,6 +52,45 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     v = dpp_add(v, integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{});
     v = dpp_add(v, integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{});
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The sum of a 32-bit signed accumulator over the wavefront, exact in 64 bits (wave-uniform): the halves are summed on their own
+// (64 x 2^16 fits 32 bits).  Must be called with every work-item of the wave active.
+__device__ __forceinline__ long long wave_sum_i64(int32_t v)
+{
+    const uint32_t lo = wave_sum_u32((uint32_t)v & 0xffffu);
+    const int32_t hi = (int32_t)wave_sum_u32((uint32_t)(v >> 16)); // |v >> 16| <= 2^15: the sum of 64 of them is exact modulo 2^32
+    return (long long)hi * 65536 + (long long)lo;
+}
+
+// Sum of a 64-bit value over the wavefront, modulo 2^64 (wave-uniform): 16-bit quarters summed on their own (64 x 2^16 fits 32
+// bits).  Must be called with every work-item of the wave active.
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    unsigned long long s = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s += (unsigned long long)wave_sum_u32((uint32_t)(v >> (16 * q)) & 0xffffu) << (16 * q);
+    return s;
+}
+// Minimum / maximum over the wavefront (wave-uniform).  Must be called with every work-item of the wave active.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m, 64));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, 64));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// One word of a record shared by every wave of the device (per-policy fitness, episodic evaluation): an agent-scope integer
+// atomic, skipped when there is nothing to add.
+__device__ __forceinline__ void atomic_add_nonzero(unsigned long long* p, unsigned long long v)
+{
+    if (v != 0) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------------------------
