@@ -230,6 +230,25 @@ impl Engine {
         check(unsafe { ffi::gymrs_rollout_policy_fitness(self.raw, n_steps) });
     }
 
+    /// `gymrs_rollout_closed_loop` without a record: `rollout_policy` (`fitness`: `rollout_policy_fitness`) behind one descriptor.
+    /// `lane_params` (`GYMRS_CLOSED_LOOP_LANE_PARAMS`) lets it run while a parameter table is active: every lane steps with the row
+    /// `step` would use for it, `n_steps` steps in one launch (without a table: no change).  An engine with a table refuses the plain call.
+    pub fn rollout_closed_loop(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 } | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_rollout_closed_loop(self.raw, &d) });
+    }
+
+    /// `rollout_closed_loop` that also keeps the trajectory (`rollout_policy_record`'s rows; no fitness: there is no recording fitness kernel).
+    ///
+    /// # Safety
+    /// As `rollout_record`.
+    pub unsafe fn rollout_closed_loop_record(&mut self, n_steps: u32, lane_params: bool, out: &ffi::Trajectory) {
+        let flags = if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: out, reserved: 0 };
+        check(ffi::gymrs_rollout_closed_loop(self.raw, &d));
+    }
+
     /// The records of policies `first..first+count` (synchronising).
     pub fn policy_fitness(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyFitness> {
         let mut out = vec![ffi::GymrsPolicyFitness::default(); count as usize];

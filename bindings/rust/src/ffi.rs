@@ -89,6 +89,21 @@ pub struct GymrsPolicyFitness {
     pub truncated: u64,
 }
 
+/// `GYMRS_CLOSED_LOOP_FITNESS`: `gymrs_rollout_closed_loop` also counts per-policy fitness (`gymrs_rollout_policy_fitness`).
+pub const GYMRS_CLOSED_LOOP_FITNESS: u32 = 1;
+/// `GYMRS_CLOSED_LOOP_LANE_PARAMS`: every lane steps with the row of the parameter table `gymrs_step` would use for it (no table: no change).
+pub const GYMRS_CLOSED_LOOP_LANE_PARAMS: u32 = 4;
+
+/// `gymrs_closed_loop_desc`: what `gymrs_rollout_closed_loop` runs (include/gymrs_amd.h "closed-loop rollouts behind one descriptor"), 24 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsClosedLoopDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub record: *const Trajectory,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -205,6 +220,7 @@ extern "C" {
     pub fn gymrs_policy_fitness_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyFitness, n_policies: *mut u32) -> c_int;
     pub fn gymrs_get_policy_fitness(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
+    pub fn gymrs_rollout_closed_loop(e: *mut GymrsEngine, d: *const GymrsClosedLoopDesc) -> c_int;
     pub fn gymrs_evaluate_policy(e: *mut GymrsEngine, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_get_policy_eval(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
     pub fn gymrs_policy_eval_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyEval, n_policies: *mut u32) -> c_int;
@@ -249,6 +265,7 @@ extern "C" {
     pub fn gymrs_sharded_rollout_policy_fitness(h: *mut GymrsSharded, n_steps: u32) -> c_int;
     pub fn gymrs_sharded_get_policy_fitness(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
+    pub fn gymrs_sharded_rollout_closed_loop(h: *mut GymrsSharded, d: *const GymrsClosedLoopDesc) -> c_int;
     pub fn gymrs_sharded_evaluate_policy(h: *mut GymrsSharded, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_sharded_set_param_table(h: *mut GymrsSharded, rows: *const c_void, k: u32) -> c_int;
     pub fn gymrs_sharded_get_param_table(h: *mut GymrsSharded, rows_out: *mut c_void, capacity: u32, k: *mut u32) -> c_int;

@@ -127,6 +127,13 @@ impl ShardedEngine {
         check(unsafe { ffi::gymrs_sharded_rollout_policy(self.raw, n_steps) });
     }
 
+    /// `Engine::rollout_closed_loop` on every block (`gymrs_sharded_rollout_closed_loop`; no record: the blocks live on several devices).
+    pub fn rollout_closed_loop(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 } | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_sharded_rollout_closed_loop(self.raw, &d) });
+    }
+
     /// `rollout_policy` that also counts per-policy fitness on every block.
     pub fn rollout_policy_fitness(&mut self, n_steps: u32) {
         check(unsafe { ffi::gymrs_sharded_rollout_policy_fitness(self.raw, n_steps) });

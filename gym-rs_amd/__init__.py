@@ -44,6 +44,7 @@ from .envs import (
 from ._lib import library_path, load_library
 from . import sharded
 from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, EvalDesc, EVAL_COMMON_STARTS, EVAL_LANE_PARAMS
+from .engine import ClosedLoopDesc, CLOSED_LOOP_FITNESS, CLOSED_LOOP_LANE_PARAMS
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -52,4 +53,5 @@ __all__ = [
     "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "FINAL_OBS", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
     "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
+    "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS",
 ]

@@ -1005,18 +1005,34 @@ gymrs_status gymrs_step(gymrs_engine* e, const void* actions_dev)
     return GYMRS_OK;
 }
 
+// the buffer checks of the recording rollouts (gymrs_trajectory)
+static gymrs_status check_trajectory(const gymrs_engine* e, const gymrs_trajectory* rec, const char* who)
+{
+    if (!rec->obs || !rec->actions || !rec->reward || !rec->done)
+        return fail(GYMRS_EINVAL, std::string(who) + ": obs, actions, reward and done buffers are required");
+    if (rec->lane_stride < e->n || rec->lane_stride % 16 != 0)
+        return fail(GYMRS_EINVAL, std::string(who) + ": lane_stride must be >= n_envs and a multiple of 16");
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(rec->obs) | reinterpret_cast<uintptr_t>(rec->actions) |
+                           reinterpret_cast<uintptr_t>(rec->reward) | reinterpret_cast<uintptr_t>(rec->done) |
+                           reinterpret_cast<uintptr_t>(rec->truncated);
+    if (bits % 16 != 0) return fail(GYMRS_EINVAL, std::string(who) + ": trajectory buffers must be 16-byte aligned");
+    return GYMRS_OK;
+}
+
 // The caller loop of the reference's examples (examples/cartpole.rs:15-30: random action, step, reset on
 // done, accumulate the return) fused into one launch; see rollout_kernel.
 // closed = gymrs_rollout_policy: the actions come from the engine's policy set (gymrs_set_policy) instead of the Philox stream.
 // fitness = gymrs_rollout_policy_fitness: closed, and the kernel adds to the per-policy counters (same checks, same bookkeeping).
+// lane_params = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_LANE_PARAMS: closed (or fitness) under an active parameter table,
+// every lane with its own row (the TableT instantiations of the policy kernels); without a table it changes nothing.
 static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
-                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false)
+                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false, bool lane_params = false)
 {
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
     if (fitness && e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
         return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
     if (closed && !e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
-    if (closed && e->table_k)
+    if (closed && e->table_k && !lane_params)
         return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
                                                      "use gymrs_policy_actions + gymrs_step");
     if (fitness && n_steps > kMaxFitnessSteps)
@@ -1035,14 +1051,7 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     r.max_torque = e->max_torque;
     int vec = e->vec == 8 ? 8 : 4;
     if (rec) {
-        if (!rec->obs || !rec->actions || !rec->reward || !rec->done)
-            return fail(GYMRS_EINVAL, std::string(who) + ": obs, actions, reward and done buffers are required");
-        if (rec->lane_stride < e->n || rec->lane_stride % 16 != 0)
-            return fail(GYMRS_EINVAL, std::string(who) + ": lane_stride must be >= n_envs and a multiple of 16");
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(rec->obs) | reinterpret_cast<uintptr_t>(rec->actions) |
-                               reinterpret_cast<uintptr_t>(rec->reward) | reinterpret_cast<uintptr_t>(rec->done) |
-                               reinterpret_cast<uintptr_t>(rec->truncated);
-        if (bits % 16 != 0) return fail(GYMRS_EINVAL, std::string(who) + ": trajectory buffers must be 16-byte aligned");
+        if (gymrs_status st = check_trajectory(e, rec, who)) return st;
         r.rec_obs = rec->obs;
         r.rec_action = rec->actions;
         r.rec_reward = rec->reward;
@@ -1055,9 +1064,9 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
     if (fitness) {
         if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
-        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags, a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
+        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
     } else if (closed)
-        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags, a, r, launch_consts(e), e->policy, e->stream));
+        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->stream));
     else
         HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
@@ -1100,6 +1109,29 @@ gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, cons
     if (!e) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: NULL engine");
     if (!out) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: trajectory is NULL");
     return rollout_impl(e, n_steps, 0, 0, out, "gymrs_rollout_policy_record", true);
+}
+
+// The closed-loop calls behind one descriptor with a flags word (include/gymrs_amd.h): what gymrs_rollout_policy, _record and
+// _fitness do, and -- with GYMRS_CLOSED_LOOP_LANE_PARAMS -- the same under an active parameter table.
+gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_desc* d)
+{
+    const char* who = "gymrs_rollout_closed_loop";
+    if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, std::string(who) + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
+    if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS))
+        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS and GYMRS_CLOSED_LOOP_LANE_PARAMS are the only ones)");
+    const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0, lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0;
+    if (fitness && d->record) return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_FITNESS with a record: there is no recording fitness kernel");
+    if (e->table_k && !lane_params) // (opt-in: a plain descriptor is never played with a table behind the caller's back)
+        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table): set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags "
+                                                     "and every lane steps with its own row");
+    if (d->record)
+        if (gymrs_status st = check_trajectory(e, d->record, who)) return st;
+    return rollout_impl(e, d->n_steps, 0, 0, d->record, who, true, fitness, lane_params);
 }
 
 gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)

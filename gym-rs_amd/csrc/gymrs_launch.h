@@ -1,7 +1,7 @@
 // gymrs_launch.h -- THE launch table of the kernel library: which (lanes per work-item, flag set) pairs a kernel family is
 // built for, and how a launch's run-time values reach the instantiation built for them.  Every family with a table goes
 // through here: the per-step kernels (gymrs_step_impl.h), the random-policy rollout (gymrs_rollout_impl.h), the closed-loop
-// rollout (gymrs_rollout_policy.hip) and its fitness variant (gymrs_rollout_fitness.hip).
+// rollout and its fitness variant (gymrs_rollout_policy_impl.h).
 //
 // Plain host C++17, no HIP: a function here turns a run-time value into a compile-time constant (a std::integral_constant
 // handed to a generic callable, whose body names the kernel template) or refuses it with the caller's `invalid` result.

@@ -1,5 +1,5 @@
 // gymrs_rollout_impl.h -- the fused multi-step kernel, gfx950: rollout_block (also the body of the closed-loop kernels of
-// gymrs_rollout_policy.hip and gymrs_rollout_fitness.hip) and the random-policy rollout_kernel with its launch: included by
+// gymrs_rollout_policy_impl.h) and the random-policy rollout_kernel with its launch: included by
 // gymrs_rollout.hip (the uniform envs) and by gymrs_table_<env>.hip (TableT, per-lane parameter tables).
 #pragma once
 #include "gymrs_launch.h"
@@ -23,7 +23,7 @@ struct RandomActions {
     static constexpr bool kPolicy = false;
 };
 // Fit = what is folded out of every step's reward / done / truncated while they are still in registers: nothing (NoFitness: every
-// line that names it compiles away), or the per-policy counters of gymrs_rollout_policy_fitness (gymrs_rollout_fitness.hip).
+// line that names it compiles away), or the per-policy counters of gymrs_rollout_policy_fitness (gymrs_rollout_policy_impl.h).
 struct NoFitness {
     static constexpr bool kOn = false;
 };

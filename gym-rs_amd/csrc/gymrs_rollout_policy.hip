@@ -1,8 +1,8 @@
 // gymrs_rollout_policy.hip -- the closed-loop kernels (gymrs_policy.h) and their launches: policy_actions_kernel (the per-step
-// counterpart: observations -> actions) and rollout_policy_kernel, the fused multi-step kernel of gymrs_rollout_impl.h with the
-// policy as its action source.  CartPole and MountainCar (the Discrete envs), uniform constants only (no parameter table).
-#include "gymrs_policy.h"
-#include "gymrs_rollout_impl.h"
+// counterpart: observations -> actions) and rollout_policy_kernel (gymrs_rollout_policy_impl.h), the fused multi-step kernel with
+// the policy as its action source, for CartPole and MountainCar (the Discrete envs) with uniform constants.  The parameter-table
+// instantiations (kFlagTable) live in one translation unit per env type, gymrs_table_policy_<env>.hip.
+#include "gymrs_rollout_policy_impl.h"
 
 namespace gymrs {
 
@@ -53,54 +53,23 @@ hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, voi
     });
 }
 
-// gymrs_rollout_policy / _record: rollout_block with the policy as its action source.  FULL / ragged and uniform / gathered
-// weights are both chosen per wave, wave-uniformly.  The register budget is rollout_kernel's (16 / VEC waves per SIMD).
-// (rollout_policy_fitness_kernel, gymrs_rollout_fitness.hip, repeats this body with a Fit hook: moved into one shared inline
-// function, the four kernel-argument pointer loads of the state rows leave the two weight branches for the kernel's entry and
-// every instantiation comes out with other register spills.)
-template <class Env, int VEC, uint32_t FLAGS, bool REC>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(16 / VEC, 16 / VEC))) void rollout_policy_kernel(
-    const StepArgs a, const RolloutArgs r, const typename Env::Consts c, const PolicyArgs p)
-{
-    constexpr int LPB = kBlock * VEC;
-    __shared__ ResetLds<Env, VEC, kBlock> lds;
-    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;
-    uint32_t pol[VEC];
-    bool uniform;
-    policy_select<VEC>(p, a.gid0 + base, pol, uniform);
-    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; // wave-uniform, see step_kernel
-    if (uniform) {
-        const PolicyActions<Env, VEC, true> src(p, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, REC>(a, r, c, lds, src);
-        else
-            rollout_block<Env, VEC, FLAGS, false, REC>(a, r, c, lds, src);
-    } else {
-        const PolicyActions<Env, VEC, false> src(p, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, REC>(a, r, c, lds, src);
-        else
-            rollout_block<Env, VEC, FLAGS, false, REC>(a, r, c, lds, src);
-    }
-}
+hipError_t launch_rollout_policy_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                                const PolicyArgs& p, hipStream_t stream);
+hipError_t launch_rollout_policy_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                                    const PolicyArgs& p, hipStream_t stream);
 
 hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                  const PolicyArgs& p, hipStream_t stream)
 {
     if (a.n == 0 || r.n_steps == 0) return hipSuccess;
-    if (flags & kFlagTable) return hipErrorInvalidValue; // no policy x table kernels (the engine refuses first)
-    return dispatch_policy_env(kind, [&](auto env) {
-        using Env = typename decltype(env)::type;
-        return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
-            constexpr int VEC = decltype(lanes)::value;
-            return dispatch_recording<VEC>(r.rec_obs != nullptr, hipErrorInvalidValue, [&](auto rec) {
-                launch_begin();
-                hipLaunchKernelGGL((rollout_policy_kernel<Env, VEC, decltype(flag_set)::value, decltype(rec)::value>), dim3(step_grid(a.n, VEC)),
-                                   dim3(kBlock), 0, stream, a, r, *static_cast<const typename Env::Consts*>(consts), p);
-                return hipGetLastError();
-            });
-        });
-    });
+    if (flags & kFlagTable) {
+        switch (kind) {
+        case GYMRS_CARTPOLE: return launch_rollout_policy_table_cartpole(vec, flags, a, r, consts, p, stream);
+        case GYMRS_MOUNTAIN_CAR: return launch_rollout_policy_table_mountain_car(vec, flags, a, r, consts, p, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    return dispatch_policy_env(kind, [&](auto env) { return rollout_policy_vec<typename decltype(env)::type>(vec, flags, a, r, consts, p, stream); });
 }
 
 } // namespace gymrs

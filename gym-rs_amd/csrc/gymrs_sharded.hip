@@ -507,6 +507,17 @@ gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, 
     });
 }
 
+// gymrs_rollout_closed_loop on every block (the flags pass through: GYMRS_CLOSED_LOOP_LANE_PARAMS steps every block's lanes with the block's table and
+// index).  A trajectory is an array of ONE engine's lanes: ask the blocks themselves for it.
+gymrs_status gymrs_sharded_rollout_closed_loop(gymrs_sharded* h, const gymrs_closed_loop_desc* d)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_closed_loop: handle is NULL");
+    if (!d) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_closed_loop: NULL desc");
+    if (d->record) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_closed_loop: record must be NULL (the blocks live on several devices)");
+    const gymrs_closed_loop_desc desc = *d; // by value into the workers
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_rollout_closed_loop(e, &desc); }; });
+}
+
 // Episodic evaluation on every block (the flags pass through: GYMRS_EVAL_LANE_PARAMS plays every block's table).  The per-episode lengths are an array of ONE engine's lanes: ask the blocks themselves for them.
 gymrs_status gymrs_sharded_evaluate_policy(gymrs_sharded* h, const gymrs_eval_desc* d)
 {

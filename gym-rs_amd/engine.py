@@ -86,6 +86,27 @@ EVAL_COMMON_STARTS = 1  # GYMRS_EVAL_COMMON_STARTS
 EVAL_LANE_PARAMS = 4  # GYMRS_EVAL_LANE_PARAMS
 
 
+class ClosedLoopDesc(C.Structure):
+    """``gymrs_closed_loop_desc`` (include/gymrs_amd.h), 24 bytes."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("record", C.POINTER(Trajectory)), ("reserved", C.c_uint64)]
+
+
+CLOSED_LOOP_FITNESS = 1  # GYMRS_CLOSED_LOOP_FITNESS
+CLOSED_LOOP_LANE_PARAMS = 4  # GYMRS_CLOSED_LOOP_LANE_PARAMS
+
+
+def _closed_loop_desc(n_envs, n_steps, lane_params, fitness, record, flags=None) -> ClosedLoopDesc:
+    """``record``: None, a ``Trajectory``, or a mapping with the keyword arguments of ``rollout_policy_record`` (device addresses
+    ``obs``, ``actions``, ``reward``, ``done``, optionally ``truncated`` and ``lane_stride``).  The descriptor keeps it alive."""
+    f = ((CLOSED_LOOP_FITNESS if fitness else 0) | (CLOSED_LOOP_LANE_PARAMS if lane_params else 0)) if flags is None else int(flags)
+    traj = record
+    if record is not None and not isinstance(record, Trajectory):
+        stride = record.get("lane_stride")
+        traj = Trajectory(C.c_void_p(record["obs"]), C.c_void_p(record["actions"]), C.c_void_p(record["reward"]), C.c_void_p(record["done"]),
+                          C.c_void_p(record.get("truncated") or None), int(stride) if stride is not None else (n_envs + 15) // 16 * 16)
+    return ClosedLoopDesc(int(n_steps), f, C.pointer(traj) if traj is not None else None, 0)
+
+
 def _eval_desc(episodes_per_lane, max_episode_steps, seed, common_starts, lengths, flags, lane_params=False) -> EvalDesc:
     f = ((EVAL_COMMON_STARTS if common_starts else 0) | (EVAL_LANE_PARAMS if lane_params else 0)) if flags is None else int(flags)
     return EvalDesc(int(episodes_per_lane), int(max_episode_steps), int(seed) & (2**64 - 1), f, 0, C.c_void_p(lengths or None))
@@ -522,6 +543,17 @@ class BatchedEngine:
         (``policy_fitness``).  Leaves the engine bit for bit as ``rollout_policy`` does."""
         _check(self._lib, self._lib.gymrs_rollout_policy_fitness(self._h, int(n_steps)))
 
+    # -- the closed-loop calls behind one descriptor, and under per-lane physics ---------------------------
+    def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
+                            flags: Optional[int] = None) -> None:
+        """``gymrs_rollout_closed_loop``: ``rollout_policy`` (with ``record``: ``rollout_policy_record``; with ``fitness``:
+        ``rollout_policy_fitness``) behind one descriptor.  ``lane_params`` (``GYMRS_CLOSED_LOOP_LANE_PARAMS``) lets it run while a
+        parameter table is active: every lane steps with the row ``step`` would use for it, n_steps steps in one launch; without a
+        table it changes nothing, so a training loop may always set it.  ``record``: a ``Trajectory`` or a mapping with the keyword
+        arguments of ``rollout_policy_record``.  ``flags`` passes a raw flags word instead of the two booleans."""
+        desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags)
+        _check(self._lib, self._lib.gymrs_rollout_closed_loop(self._h, C.byref(desc)))
+
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of policies [first, first + count) as an int64 array of shape (count, 4): columns reward_sum, episodes,
         done, truncated (synchronising).  ``count`` defaults to the rest of the set."""
@@ -690,6 +722,12 @@ class ShardedEngine:
     def rollout_policy_fitness(self, n_steps: int) -> None:
         """``BatchedEngine.rollout_policy_fitness`` on every block."""
         _check(self._lib, self._lib.gymrs_sharded_rollout_policy_fitness(self._h, int(n_steps)))
+
+    def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
+                            flags: Optional[int] = None) -> None:
+        """``BatchedEngine.rollout_closed_loop`` on every block (``record`` must stay None: the blocks live on several devices)."""
+        desc = _closed_loop_desc(self.n_total, n_steps, lane_params, fitness, record, flags)
+        _check(self._lib, self._lib.gymrs_sharded_rollout_closed_loop(self._h, C.byref(desc)))
 
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of the WHOLE batch, (count, 4) int64 as ``BatchedEngine.policy_fitness``: the blocks' records summed

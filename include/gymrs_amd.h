@@ -368,7 +368,8 @@ gymrs_status gymrs_get_params(gymrs_engine* e, void* params_out);
  * gymrs_get_param_index: host copies of lanes [first, first + count) (synchronising).  These three need a table.
  * gymrs_get_lane_params: the params lane `lane` steps with (row index[lane]; without a table, gymrs_get_params).
  * Which calls honour the table: gymrs_step / gymrs_step_many / gymrs_rollout / gymrs_rollout_record (every flag set), and
- * gymrs_evaluate_policy with GYMRS_EVAL_LANE_PARAMS ("episodic policy evaluation" below).  gymrs_rollout_policy, _record and
+ * gymrs_evaluate_policy with GYMRS_EVAL_LANE_PARAMS ("episodic policy evaluation" below) and gymrs_rollout_closed_loop with
+ * GYMRS_CLOSED_LOOP_LANE_PARAMS ("closed-loop rollouts behind one descriptor" below).  gymrs_rollout_policy, _record and
  * _fitness refuse an active table (they take no flags word through which a caller could opt in).
  * A sharded batch (gymrs_sharded_*): gymrs_sharded_set_param_table puts the SAME k rows on every block (rows = NULL, k = 0
  * switches the table off); gymrs_sharded_get_param_table reads them back from block 0.  gymrs_sharded_set_param_index /
@@ -424,7 +425,8 @@ gymrs_status gymrs_sharded_get_param_index(gymrs_sharded* h, uint64_t first, uin
  *     no-op.  gymrs_rollout_policy_record is to it what gymrs_rollout_record is to gymrs_rollout (same gymrs_trajectory, same
  *     buffer checks, same rows; the `actions` rows hold the policy's actions).
  *   - Without a policy set, the three stepping calls, gymrs_get_policy and gymrs_policy_weights_ptr return GYMRS_EINVAL.  While a
- *     parameter table is active, gymrs_rollout_policy / _record return GYMRS_EINVAL and say so (the per-step loop covers it).
+ *     parameter table is active, gymrs_rollout_policy / _record return GYMRS_EINVAL and say so (the per-step loop covers it, and
+ *     gymrs_rollout_closed_loop below does it in one launch).
  *   - The policy is NOT part of gymrs_engine_clone or of a snapshot (its bytes and version are unchanged): set it again on the
  *     clone or the restored engine.  The sharded layer mirrors the set / rollout / fitness calls (gymrs_sharded_set_policy ...). */
 typedef struct { uint32_t hidden; uint32_t n_policies; uint64_t lanes_per_policy; } gymrs_policy_desc;
@@ -477,6 +479,38 @@ gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps);
 gymrs_status gymrs_sharded_rollout_policy_fitness(gymrs_sharded* h, uint32_t n_steps);
 gymrs_status gymrs_sharded_get_policy_fitness(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out);
 gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
+/* Closed-loop rollouts behind one descriptor, and under per-lane physics (policy x table).
+ * gymrs_rollout_closed_loop(e, d) is the three fused closed-loop calls above behind a descriptor with a flags word: d->n_steps = K,
+ * d->record (may be NULL) = the trajectory of gymrs_rollout_policy_record, GYMRS_CLOSED_LOOP_FITNESS in d->flags = the counters of
+ * gymrs_rollout_policy_fitness.
+ *   - No parameter table active: bit-identical to the call the descriptor stands for -- gymrs_rollout_policy(e, K); with record
+ *     != NULL gymrs_rollout_policy_record(e, K, record); with GYMRS_CLOSED_LOOP_FITNESS gymrs_rollout_policy_fitness(e, K) -- with or
+ *     without GYMRS_CLOSED_LOOP_LANE_PARAMS (the same kernels are launched), so a training loop may set that flag unconditionally,
+ *     as with GYMRS_EVAL_LANE_PARAMS.
+ *   - A table active, GYMRS_CLOSED_LOOP_LANE_PARAMS not set: GYMRS_EINVAL naming the flag (a plain descriptor is never played
+ *     with a table behind the caller's back).
+ *   - A table active and the flag set: exactly the effect of `for k in 0..K: gymrs_policy_actions(e, buf); gymrs_step(e, buf);` on
+ *     this engine, in ONE launch: state, reward / done / truncated of the last step, final observations, statistics,
+ *     steps_beyond_terminated, tick.  Lane i steps with rows[index[i]] ("per-lane physics"); rows and index are read in stream
+ *     order (an index rewritten through gymrs_param_index_ptr on the engine's stream is seen by the next launch).  Every flag
+ *     set gymrs_rollout accepts, both lanes_per_thread values (recording runs at 4, like every recording kernel), any n_envs and
+ *     any global_env_offset; the policy of a lane is chosen by its global id as above.  The rows of `record` and the fitness
+ *     counters are defined as above ("the values gymrs_rollout_policy_record would have written").
+ *   - A lane whose index is >= K (possible through the zero-copy view only) is treated as gymrs_rollout treats it: it is not
+ *     stepped, pays 0 and sets no flag in every step of the launch (its record rows say so), adds nothing to any fitness
+ *     record, and the next gymrs_sync returns GYMRS_EACTION naming the lowest such lane.
+ *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, reserved != 0, unknown flag bits (bit 1 is not assigned),
+ *     GYMRS_CLOSED_LOOP_FITNESS together with a record (there is no recording fitness kernel), a record that fails the buffer
+ *     checks of gymrs_rollout_policy_record, n_steps > GYMRS_POLICY_FITNESS_MAX_STEPS with GYMRS_CLOSED_LOOP_FITNESS.  n_steps == 0
+ *     is a no-op after these checks.
+ * gymrs_sharded_rollout_closed_loop runs it on every block through its worker; record must be NULL there (the blocks live on
+ * several devices, as with lengths_dev); the fitness records are read with gymrs_sharded_get_policy_fitness.  k blocks on one
+ * GPU give bit for bit what one engine gives. */
+#define GYMRS_CLOSED_LOOP_FITNESS 1u
+#define GYMRS_CLOSED_LOOP_LANE_PARAMS 4u /* bit 2, the bit of GYMRS_EVAL_LANE_PARAMS */
+typedef struct { uint32_t n_steps; uint32_t flags; const gymrs_trajectory* record; uint64_t reserved; } gymrs_closed_loop_desc; /* 24 B */
+gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_desc* d);
+gymrs_status gymrs_sharded_rollout_closed_loop(gymrs_sharded* h, const gymrs_closed_loop_desc* d);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):
@@ -517,7 +551,8 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
  *     what keeps a lane's sum of L in 32 bits).  Non-finite weights are legal.
  *   - Not built: moving episodes between the lanes of a wave (a wave runs until its slowest lane is through), 8 lanes per
  *     work-item, and policy x table for the fused rollout calls: gymrs_rollout_policy, _record and _fitness still refuse an
- *     active parameter table, because they take no flags word through which a caller could opt in.
+ *     active parameter table, because they take no flags word through which a caller could opt in (gymrs_rollout_closed_loop,
+ *     above, has one: GYMRS_CLOSED_LOOP_LANE_PARAMS).
  *   - Per-(policy, row) records need no further call: replicate every policy's weights K times (n_policies' = P * K, policy
  *     q = p * K + r carries p's weights) and set index[i] = ((global_env_offset + i) / lanes_per_policy) % K; record q is then
  *     policy p under row r, and a robust objective is the minimum over r.

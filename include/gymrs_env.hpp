@@ -225,6 +225,14 @@ public:
     void rollout_policy_record(std::uint32_t n_steps, const gymrs_trajectory& out) { check(gymrs_rollout_policy_record(e_, n_steps, &out)); }
     // per-policy fitness: rollout_policy that also adds every step's reward / done / truncated to the record of the lane's policy
     void rollout_policy_fitness(std::uint32_t n_steps) { check(gymrs_rollout_policy_fitness(e_, n_steps)); }
+    // the three calls above behind one descriptor with a flags word; lane_params (GYMRS_CLOSED_LOOP_LANE_PARAMS): under an active
+    // parameter table every lane steps with its own row, n_steps steps in one launch (without a table: no change)
+    void rollout_closed_loop(const gymrs_closed_loop_desc& d) { check(gymrs_rollout_closed_loop(e_, &d)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params = false, bool fitness = false, const gymrs_trajectory* record = nullptr)
+    {
+        const gymrs_closed_loop_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u), record, 0};
+        check(gymrs_rollout_closed_loop(e_, &d));
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
@@ -360,6 +368,13 @@ public:
     void clear_policy() { check(gymrs_sharded_set_policy(h_, nullptr, nullptr)); }
     void rollout_policy(std::uint32_t n_steps) { check(gymrs_sharded_rollout_policy(h_, n_steps)); }
     void rollout_policy_fitness(std::uint32_t n_steps) { check(gymrs_sharded_rollout_policy_fitness(h_, n_steps)); }
+    // VecEnv::rollout_closed_loop on every block (record must stay NULL: the blocks live on several devices)
+    void rollout_closed_loop(const gymrs_closed_loop_desc& d) { check(gymrs_sharded_rollout_closed_loop(h_, &d)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params = false, bool fitness = false)
+    {
+        const gymrs_closed_loop_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u), nullptr, 0};
+        check(gymrs_sharded_rollout_closed_loop(h_, &d));
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count) // the blocks' records, summed
     {
         std::vector<gymrs_policy_fitness> out(count);
