@@ -249,6 +249,55 @@ impl Engine {
         check(ffi::gymrs_rollout_closed_loop(self.raw, &d));
     }
 
+    /// Install the exploration settings (`gymrs_set_exploration`): a step explores with probability `threshold` / 65536 (`threshold` in
+    /// 0..=65536), drawing from a Philox stream keyed (`seed`, global lane id, engine tick).  `None` removes them.  Launches play them only
+    /// through `rollout_closed_loop_explore`, `rollout_closed_loop_explore_record` and `explore_actions`; every other call stays greedy.
+    pub fn set_exploration(&mut self, settings: Option<(u64, u32)>) {
+        match settings {
+            Some((seed, threshold)) => {
+                let x = ffi::GymrsExploration { seed, threshold, reserved: 0 };
+                check(unsafe { ffi::gymrs_set_exploration(self.raw, &x) });
+            }
+            None => check(unsafe { ffi::gymrs_set_exploration(self.raw, std::ptr::null()) }),
+        }
+    }
+
+    /// `(seed, threshold)` as set (`gymrs_get_exploration`); panics when the engine has no exploration settings.
+    pub fn exploration(&mut self) -> (u64, u32) {
+        let mut x = ffi::GymrsExploration { seed: 0, threshold: 0, reserved: 0 };
+        check(unsafe { ffi::gymrs_get_exploration(self.raw, &mut x) });
+        (x.seed, x.threshold)
+    }
+
+    /// `rollout_closed_loop` with `GYMRS_CLOSED_LOOP_EXPLORE`: every step plays the epsilon-greedy action of `set_exploration`.
+    pub fn rollout_closed_loop_explore(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_EXPLORE
+            | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 }
+            | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_rollout_closed_loop(self.raw, &d) });
+    }
+
+    /// `rollout_closed_loop_record` with `GYMRS_CLOSED_LOOP_EXPLORE`: the `actions` rows hold the action taken; which of them were
+    /// exploratory is recomputed with `explore_draw` from (global lane id, tick of the row).
+    ///
+    /// # Safety
+    /// As `rollout_record`.
+    pub unsafe fn rollout_closed_loop_explore_record(&mut self, n_steps: u32, lane_params: bool, out: &ffi::Trajectory) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_EXPLORE | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: out, reserved: 0 };
+        check(ffi::gymrs_rollout_closed_loop(self.raw, &d));
+    }
+
+    /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
+    /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
+    ///
+    /// # Safety
+    /// `actions_dev` must be a device address of at least `len()` bytes that stays valid until `sync()`.
+    pub unsafe fn explore_actions(&mut self, actions_dev: *mut c_void) {
+        check(ffi::gymrs_explore_actions(self.raw, actions_dev));
+    }
+
     /// The records of policies `first..first+count` (synchronising).
     pub fn policy_fitness(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyFitness> {
         let mut out = vec![ffi::GymrsPolicyFitness::default(); count as usize];
@@ -344,6 +393,15 @@ impl Engine {
     pub fn restore(&mut self, blob: &[u8]) {
         check(unsafe { ffi::gymrs_snapshot_load(self.raw, blob.as_ptr() as *const c_void, blob.len() as u64) });
     }
+}
+
+/// `(explored, random action)` of the epsilon-greedy draw that takes the lane with global id `global_id` from engine tick `tick` to
+/// `tick + 1` under `(seed, threshold)` (`gymrs_explore_draw`; host only, no GPU).
+pub fn explore_draw(seed: u64, threshold: u32, n_actions: u32, global_id: u64, tick: u64) -> (bool, u8) {
+    let x = ffi::GymrsExploration { seed, threshold, reserved: 0 };
+    let (mut explored, mut action) = (0u8, 0u8);
+    check(unsafe { ffi::gymrs_explore_draw(&x, n_actions, global_id, tick, &mut explored, &mut action) });
+    (explored != 0, action)
 }
 
 impl Clone for Engine {

@@ -93,6 +93,18 @@ pub struct GymrsPolicyFitness {
 pub const GYMRS_CLOSED_LOOP_FITNESS: u32 = 1;
 /// `GYMRS_CLOSED_LOOP_LANE_PARAMS`: every lane steps with the row of the parameter table `gymrs_step` would use for it (no table: no change).
 pub const GYMRS_CLOSED_LOOP_LANE_PARAMS: u32 = 4;
+/// `GYMRS_CLOSED_LOOP_EXPLORE`: every step plays the epsilon-greedy action of the engine's exploration settings (`gymrs_set_exploration`).
+pub const GYMRS_CLOSED_LOOP_EXPLORE: u32 = 16;
+
+/// `gymrs_exploration`: the exploration settings of an engine (include/gymrs_amd.h "exploration"), 16 bytes.  A step explores when the low
+/// half of its Philox word, keyed (seed, global lane id, engine tick), is below `threshold` (0..=65536: epsilon = threshold / 65536).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct GymrsExploration {
+    pub seed: u64,
+    pub threshold: u32,
+    pub reserved: u32,
+}
 
 /// `gymrs_closed_loop_desc`: what `gymrs_rollout_closed_loop` runs (include/gymrs_amd.h "closed-loop rollouts behind one descriptor"), 24 bytes.
 #[repr(C)]
@@ -221,6 +233,17 @@ extern "C" {
     pub fn gymrs_get_policy_fitness(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_rollout_closed_loop(e: *mut GymrsEngine, d: *const GymrsClosedLoopDesc) -> c_int;
+    pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
+    pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
+    pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;
+    pub fn gymrs_explore_draw(
+        x: *const GymrsExploration,
+        n_actions: u32,
+        global_id: u64,
+        tick: u64,
+        explored: *mut u8,
+        random_action: *mut u8,
+    ) -> c_int;
     pub fn gymrs_evaluate_policy(e: *mut GymrsEngine, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_get_policy_eval(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
     pub fn gymrs_policy_eval_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyEval, n_policies: *mut u32) -> c_int;
@@ -266,6 +289,7 @@ extern "C" {
     pub fn gymrs_sharded_get_policy_fitness(h: *mut GymrsSharded, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_rollout_closed_loop(h: *mut GymrsSharded, d: *const GymrsClosedLoopDesc) -> c_int;
+    pub fn gymrs_sharded_set_exploration(h: *mut GymrsSharded, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_sharded_evaluate_policy(h: *mut GymrsSharded, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_sharded_set_param_table(h: *mut GymrsSharded, rows: *const c_void, k: u32) -> c_int;
     pub fn gymrs_sharded_get_param_table(h: *mut GymrsSharded, rows_out: *mut c_void, capacity: u32, k: *mut u32) -> c_int;

@@ -134,6 +134,26 @@ impl ShardedEngine {
         check(unsafe { ffi::gymrs_sharded_rollout_closed_loop(self.raw, &d) });
     }
 
+    /// `Engine::set_exploration` on every block (`gymrs_sharded_set_exploration`): the same settings everywhere, keyed by global lane ids.
+    pub fn set_exploration(&mut self, settings: Option<(u64, u32)>) {
+        match settings {
+            Some((seed, threshold)) => {
+                let x = ffi::GymrsExploration { seed, threshold, reserved: 0 };
+                check(unsafe { ffi::gymrs_sharded_set_exploration(self.raw, &x) });
+            }
+            None => check(unsafe { ffi::gymrs_sharded_set_exploration(self.raw, std::ptr::null()) }),
+        }
+    }
+
+    /// `rollout_closed_loop` with `GYMRS_CLOSED_LOOP_EXPLORE` on every block: k blocks equal one engine.
+    pub fn rollout_closed_loop_explore(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_EXPLORE
+            | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 }
+            | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_sharded_rollout_closed_loop(self.raw, &d) });
+    }
+
     /// `rollout_policy` that also counts per-policy fitness on every block.
     pub fn rollout_policy_fitness(&mut self, n_steps: u32) {
         check(unsafe { ffi::gymrs_sharded_rollout_policy_fitness(self.raw, n_steps) });

@@ -45,6 +45,7 @@ from ._lib import library_path, load_library
 from . import sharded
 from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, EvalDesc, EVAL_COMMON_STARTS, EVAL_LANE_PARAMS
 from .engine import ClosedLoopDesc, CLOSED_LOOP_FITNESS, CLOSED_LOOP_LANE_PARAMS
+from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -54,4 +55,5 @@ __all__ = [
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
     "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
     "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS",
+    "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw",
 ]

@@ -82,6 +82,11 @@ SIGNATURES = {
     "gymrs_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     # the closed-loop calls behind one descriptor (gymrs_closed_loop_desc 24 B: {u32 n_steps, u32 flags, trajectory*, u64 reserved})
     "gymrs_rollout_closed_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # epsilon-greedy exploration (gymrs_exploration 16 B: {u64 seed, u32 threshold, u32 reserved})
+    "gymrs_set_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_get_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_explore_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_explore_draw": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -105,6 +110,7 @@ SIGNATURES = {
     "gymrs_sharded_get_policy_fitness": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gymrs_sharded_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_rollout_closed_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_sharded_set_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     # per-lane physics on a sharded batch (the index in batch lane numbering)

@@ -1025,8 +1025,11 @@ static gymrs_status check_trajectory(const gymrs_engine* e, const gymrs_trajecto
 // fitness = gymrs_rollout_policy_fitness: closed, and the kernel adds to the per-policy counters (same checks, same bookkeeping).
 // lane_params = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_LANE_PARAMS: closed (or fitness) under an active parameter table,
 // every lane with its own row (the TableT instantiations of the policy kernels); without a table it changes nothing.
+// explore = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_EXPLORE: closed (or fitness) playing the epsilon-greedy action of the
+// engine's exploration settings (the exploring copies of the policy kernels, gymrs_explore.hip).
 static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
-                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false, bool lane_params = false)
+                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false, bool lane_params = false,
+                                 bool explore = false)
 {
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
     if (fitness && e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
@@ -1062,7 +1065,12 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    if (fitness) {
+    if (explore) {
+        if (fitness)
+            if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
+        HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->explore,
+                                       fitness ? e->fitness_dev : nullptr, e->stream));
+    } else if (fitness) {
         if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
         HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
     } else if (closed)
@@ -1122,16 +1130,20 @@ gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_
         return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
     if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
     if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
-    if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS))
-        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS and GYMRS_CLOSED_LOOP_LANE_PARAMS are the only ones)");
-    const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0, lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0;
+    if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
+        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS, GYMRS_CLOSED_LOOP_LANE_PARAMS and "
+                                                     "GYMRS_CLOSED_LOOP_EXPLORE are the only ones)");
+    const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0, lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0,
+               explore = (d->flags & GYMRS_CLOSED_LOOP_EXPLORE) != 0;
+    if (explore && !e->explore_set)
+        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
     if (fitness && d->record) return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_FITNESS with a record: there is no recording fitness kernel");
     if (e->table_k && !lane_params) // (opt-in: a plain descriptor is never played with a table behind the caller's back)
         return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table): set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags "
                                                      "and every lane steps with its own row");
     if (d->record)
         if (gymrs_status st = check_trajectory(e, d->record, who)) return st;
-    return rollout_impl(e, d->n_steps, 0, 0, d->record, who, true, fitness, lane_params);
+    return rollout_impl(e, d->n_steps, 0, 0, d->record, who, true, fitness, lane_params, explore);
 }
 
 gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)

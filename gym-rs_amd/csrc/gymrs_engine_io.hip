@@ -744,6 +744,60 @@ gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev)
     return GYMRS_OK;
 }
 
+// ---- epsilon-greedy exploration: the settings, the per-step call and the host-side draw ------------------------------------------
+static gymrs_status check_exploration(const gymrs_exploration* x, const std::string& who)
+{
+    if (x->threshold > kExploreOne) return fail(GYMRS_EINVAL, who + ": threshold must be <= 65536 (epsilon = threshold / 65536)");
+    if (x->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_set_exploration(gymrs_engine* e, const gymrs_exploration* x)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_exploration: NULL engine");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, "gymrs_set_exploration: exploration is for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!x) { // (launches already enqueued carry their own copy of the settings)
+        e->explore = ExploreArgs{};
+        e->explore_set = false;
+        return GYMRS_OK;
+    }
+    if (gymrs_status st = check_exploration(x, "gymrs_set_exploration")) return st;
+    e->explore = ExploreArgs{x->seed, x->threshold, 0};
+    e->explore_set = true;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_exploration(gymrs_engine* e, gymrs_exploration* x_out)
+{
+    if (!e || !x_out) return fail(GYMRS_EINVAL, "gymrs_get_exploration: NULL argument");
+    if (!e->explore_set) return fail(GYMRS_EINVAL, "gymrs_get_exploration: the engine has no exploration settings (gymrs_set_exploration)");
+    *x_out = gymrs_exploration{e->explore.seed, e->explore.threshold, 0};
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev)
+{
+    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_explore_actions: NULL argument");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_explore_actions: the engine has no policy (gymrs_set_policy)");
+    if (!e->explore_set) return fail(GYMRS_EINVAL, "gymrs_explore_actions: the engine has no exploration settings (gymrs_set_exploration)");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_explore_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->tick, e->policy, e->explore, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, uint64_t global_id, uint64_t tick, uint8_t* explored,
+                                uint8_t* random_action)
+{
+    if (!x) return fail(GYMRS_EINVAL, "gymrs_explore_draw: NULL settings");
+    if (gymrs_status st = check_exploration(x, "gymrs_explore_draw")) return st;
+    if (n_actions == 0 || n_actions > 256) return fail(GYMRS_EINVAL, "gymrs_explore_draw: n_actions must be in 1 .. 256");
+    const uint32_t w = explore_word(x->seed, global_id, tick);
+    if (explored) *explored = explore_decides(w, x->threshold) ? 1 : 0;
+    if (random_action) *random_action = explore_random(w, n_actions);
+    return GYMRS_OK;
+}
+
 // ---- per-policy fitness: the table behind gymrs_rollout_policy_fitness -----------------------------------------------------
 extern "C++" {
 // A gymrs_set_policy that removes the policy or changes n_policies: the table goes (launches already enqueued still add to it: wait for them).

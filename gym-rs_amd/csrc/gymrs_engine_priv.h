@@ -180,6 +180,10 @@ struct gymrs_engine {
     // The per-policy episodic records of gymrs_evaluate_policy: policy.n_policies records holding the latest call's results, allocated
     // (as identities) at first use after a gymrs_set_policy; every gymrs_set_policy frees it.  Not part of clone or snapshot.
     gymrs_policy_eval* eval_dev = nullptr;
+    // The exploration settings (gymrs_set_exploration): what the exploring kernels get by value, so a change takes effect in
+    // stream order.  gymrs_set_policy keeps them.  Not part of clone or snapshot.
+    ExploreArgs explore{};
+    bool explore_set = false;
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };

@@ -6,6 +6,7 @@
 //   gymrs_rollout.hip        the fused random-policy rollout (gymrs_rollout_impl.h)
 //   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h)
 //   gymrs_rollout_fitness.hip  that rollout with per-policy fitness counters
+//   gymrs_explore.hip        the closed-loop kernels once more with the epsilon-greedy action source (gymrs_rollout_explore_impl.h)
 //   gymrs_evaluate.hip       episodic policy evaluation (gymrs_evaluate.h, gymrs_evaluate_impl.h)
 //   gymrs_aux.hip            everything off the per-step path: reset, action fill, statistics, folds
 // gymrs_launch.h holds the one launch table (flag sets x lanes per work-item) the step and rollout families dispatch through;
@@ -315,6 +316,13 @@ struct PolicyArgs {
     uint32_t pad_;
 };
 constexpr uint32_t kMaxPolicyHidden = 64;
+// The exploration settings of an engine (gymrs_set_exploration) as the exploring kernels get them by value, after PolicyArgs
+// (gymrs_explore.hip): the draw is keyed (seed, global id, engine tick) on stream 2 of gymrs_philox.h.
+struct ExploreArgs {
+    uint64_t seed;
+    uint32_t threshold; // 0 .. 65536: a step explores when the low half of its word is below it
+    uint32_t pad_;
+};
 // S: floats of one policy; 0 for an env kind that takes none (Pendulum: a Box action)
 inline uint64_t policy_floats(gymrs_env_kind kind, uint32_t hidden)
 {
@@ -334,4 +342,11 @@ hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, c
 constexpr uint32_t kMaxFitnessSteps = GYMRS_POLICY_FITNESS_MAX_STEPS;
 hipError_t launch_rollout_policy_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                          const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream);
+// ---- epsilon-greedy exploration (gymrs_set_exploration; gymrs_explore.hip, gymrs_table_explore_<env>.hip) ----------------------
+// launch_policy_actions mixed with the exploration draw of engine tick `tick`
+hipError_t launch_explore_actions(gymrs_env_kind kind, const float* const* s, void* actions, uint64_t n, uint64_t gid0, uint64_t tick,
+                                  const PolicyArgs& p, const ExploreArgs& x, hipStream_t stream);
+// launch_rollout_policy / launch_rollout_policy_fitness (fitness != NULL) playing the epsilon-greedy action of every step
+hipError_t launch_rollout_explore(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                  const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
 } // namespace gymrs

@@ -11,7 +11,7 @@
 // Counter layout (same in oracle/gymrs_oracle.c, which restates it independently):
 //   key     = (seed lo, seed hi)
 //   counter = (gid lo, gid hi, tick lo, (tick hi & 0xffff) | stream << 16)
-//   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests)
+//   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests), stream 2 = epsilon-greedy exploration
 #pragma once
 #include "gymrs_math.h"
 
@@ -81,6 +81,17 @@ GYMRS_HD uint8_t action_discrete(uint64_t seed, uint64_t gid, uint64_t t, uint32
 {
     return discrete_from_word(action_word(seed, gid, t >> 1), t, n_actions);
 }
+
+// Epsilon-greedy exploration (stream 2; include/gymrs_amd.h, "exploration"): the step that takes lane gid from engine tick t to
+// t + 1 reads word (gid & 3) of block (gid >> 2, t) -- four neighbouring lanes share one block per step, as above.  The low half
+// of the word decides (explored = low < threshold, threshold in [0, 65536]: epsilon = threshold / 65536 exactly), the high half
+// is the random action by discrete_from_word's formula.
+constexpr uint32_t kStreamExplore = 2;
+constexpr uint32_t kExploreOne = 65536u; // the threshold that explores on every step
+GYMRS_HD u32x4 explore_block(uint64_t seed, uint64_t gid, uint64_t tick) { return draw4(seed, gid >> 2, tick, kStreamExplore); }
+GYMRS_HD uint32_t explore_word(uint64_t seed, uint64_t gid, uint64_t tick) { return pick_word(explore_block(seed, gid, tick), (uint32_t)gid & 3u); }
+GYMRS_HD bool explore_decides(uint32_t word, uint32_t threshold) { return (word & 0xffffu) < threshold; }
+GYMRS_HD uint8_t explore_random(uint32_t word, uint32_t n_actions) { return (uint8_t)(((word >> 16) * n_actions) >> 16); }
 
 // u32 -> uniform f32 on [low, high): 24 random bits, u * scale + low, kept below `high` (half-open like
 // rand's Uniform::new, cartpole.rs:363).  Everything that does not depend on the random word is prepared

@@ -129,13 +129,60 @@ __device__ __forceinline__ void policy_eval(const PolicyWeights<VEC, UNI>& W, ui
 // The action source of rollout_block (gymrs_rollout_impl.h) that closes the loop: d.act from d.st.
 template <class Env, int VEC, bool UNI>
 struct PolicyActions {
-    static constexpr bool kPolicy = true;
+    static constexpr bool kPolicy = true, kExplore = false;
     PolicyWeights<VEC, UNI> w;
     uint32_t hidden;
     __device__ __forceinline__ PolicyActions(const PolicyArgs& p, const uint32_t (&pol)[VEC]) : w(p, pol), hidden(p.hidden) {}
     __device__ __forceinline__ void fill(const Vec<float, VEC> (&st)[Env::kState], Vec<uint8_t, VEC>& act) const
     {
         policy_eval<Env, VEC, UNI>(w, hidden, st, act);
+    }
+};
+
+// Epsilon-greedy (include/gymrs_amd.h, "exploration"): the lanes of a work-item whose draw of this step says so take the random
+// action in place of act.v[k].  gid = the global id of the work-item's first lane, tick = the engine tick the step starts from.
+// aligned (wave-uniform: the shard offset is a multiple of 4): four lanes share one Philox block, else every lane evaluates the
+// block its word lies in (same values, slower).  A = the env's number of actions.
+template <int VEC, uint32_t A>
+__device__ __forceinline__ void explore_mix(const ExploreArgs& x, uint64_t gid, uint64_t tick, bool aligned, Vec<uint8_t, VEC>& act)
+{
+    if (aligned) {
+#pragma unroll
+        for (int b = 0; b < VEC / 4; ++b) {
+            const u32x4 blk = explore_block(x.seed, gid + 4 * b, tick);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                act.v[4 * b + i] = explore_decides(blk.v[i], x.threshold) ? explore_random(blk.v[i], A) : act.v[4 * b + i];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const uint32_t w = explore_word(x.seed, gid + i, tick);
+            act.v[i] = explore_decides(w, x.threshold) ? explore_random(w, A) : act.v[i];
+        }
+    }
+}
+
+// The exploring action source of rollout_block: the policy's argmax, then the select above.  Both ends of the threshold are
+// wave-uniform shortcuts that give the bits of the definition: at 0 no draw is below it (no Philox block is evaluated: the greedy
+// launch at the greedy launch's cost), at 65536 every draw is (the policy is not evaluated: its action would be replaced).
+template <class Env, int VEC, bool UNI>
+struct ExploringActions {
+    static constexpr bool kPolicy = true, kExplore = true;
+    PolicyWeights<VEC, UNI> w;
+    uint32_t hidden;
+    ExploreArgs x;
+    __device__ __forceinline__ ExploringActions(const PolicyArgs& p, const uint32_t (&pol)[VEC], const ExploreArgs& x_) : w(p, pol), hidden(p.hidden), x(x_) {}
+    __device__ __forceinline__ void fill(const Vec<float, VEC> (&st)[Env::kState], Vec<uint8_t, VEC>& act, uint64_t gid, uint64_t tick,
+                                         bool aligned) const
+    {
+        if (x.threshold < kExploreOne) {
+            policy_eval<Env, VEC, UNI>(w, hidden, st, act);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) act.v[k] = 0;
+        }
+        if (x.threshold != 0) explore_mix<VEC, (uint32_t)Env::kActions>(x, gid, tick, aligned, act);
     }
 };
 

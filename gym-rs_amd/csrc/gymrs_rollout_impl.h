@@ -18,9 +18,11 @@ namespace gymrs {
 // trajectory buffers -- what a random-policy data collection loop keeps.  Then HBM sees 22 B per CartPole
 // lane-step (no state re-read, no launch per step) instead of 38 B + a launch + an action-generation kernel.
 // Src = where a step's actions come from: RandomActions (the Philox draws of gymrs_fill_actions, below), or a source with
-// kPolicy that computes d.act from d.st (PolicyActions, gymrs_policy.h: gymrs_rollout_policy).
+// kPolicy that computes d.act from d.st (PolicyActions, gymrs_policy.h: gymrs_rollout_policy).  A source with kExplore
+// (ExploringActions, same header) is also told which step this is -- the work-item's first global id, the engine tick the step
+// starts from and whether four of its lanes share a Philox block: the epsilon-greedy draw is keyed by them.
 struct RandomActions {
-    static constexpr bool kPolicy = false;
+    static constexpr bool kPolicy = false, kExplore = false;
 };
 // Fit = what is folded out of every step's reward / done / truncated while they are still in registers: nothing (NoFitness: every
 // line that names it compiles away), or the per-policy counters of gymrs_rollout_policy_fitness (gymrs_rollout_policy_impl.h).
@@ -60,7 +62,9 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
     for (uint32_t k = 0; k < r.n_steps; ++k) {
         const uint64_t t = r.action_t0 + k;
         const uint64_t slot = kDiscrete ? (t >> 1) : t; // Discrete: a block serves two steps (16-bit halves)
-        if constexpr (Src::kPolicy) {
+        if constexpr (Src::kExplore) {
+            src.fill(d.st, d.act, gid, tick0 + k, aligned);
+        } else if constexpr (Src::kPolicy) {
             src.fill(d.st, d.act);
         } else if (aligned) {
             if (!kDiscrete || k == 0 || (t & 1u) == 0) {

@@ -460,6 +460,15 @@ gymrs_status gymrs_sharded_set_policy(gymrs_sharded* h, const gymrs_policy_desc*
     return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_policy(e, d, weights_host); }; });
 }
 
+// The same exploration settings on every block: the draw is keyed by GLOBAL lane ids and the blocks' ticks move together.
+gymrs_status gymrs_sharded_set_exploration(gymrs_sharded* h, const gymrs_exploration* x)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_set_exploration: handle is NULL");
+    const bool remove = x == nullptr;
+    const gymrs_exploration settings = remove ? gymrs_exploration{0, 0, 0} : *x; // by value into the workers
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_exploration(e, remove ? nullptr : &settings); }; });
+}
+
 gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps)
 {
     if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_policy: handle is NULL");

@@ -93,12 +93,51 @@ class ClosedLoopDesc(C.Structure):
 
 CLOSED_LOOP_FITNESS = 1  # GYMRS_CLOSED_LOOP_FITNESS
 CLOSED_LOOP_LANE_PARAMS = 4  # GYMRS_CLOSED_LOOP_LANE_PARAMS
+CLOSED_LOOP_EXPLORE = 16  # GYMRS_CLOSED_LOOP_EXPLORE
 
 
-def _closed_loop_desc(n_envs, n_steps, lane_params, fitness, record, flags=None) -> ClosedLoopDesc:
+class Exploration(C.Structure):
+    """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
+    _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _exploration(seed, epsilon, threshold) -> Exploration:
+    """Exactly one of ``epsilon`` (a float in [0, 1], rounded to the nearest 1 / 65536) and ``threshold`` (0 .. 65536)."""
+    if (epsilon is None) == (threshold is None):
+        raise ValueError("give exactly one of epsilon and threshold")
+    if threshold is None:
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError(f"epsilon must be in [0, 1], got {epsilon}")
+        threshold = int(round(float(epsilon) * 65536))
+    if not 0 <= int(threshold) < 2**32:
+        raise ValueError(f"threshold must be in 0 .. 65536, got {threshold}")
+    return Exploration(int(seed) & (2**64 - 1), int(threshold), 0)
+
+
+def explore_draw(seed: int, threshold: int, n_actions: int, global_id, tick):
+    """``gymrs_explore_draw`` (host only, no GPU): (explored, random_action) of the epsilon-greedy draw that takes lane
+    ``global_id`` from engine tick ``tick`` to ``tick + 1``.  ``global_id`` and ``tick`` broadcast against each other; scalars give
+    a (bool, int) pair, arrays a (bool array, uint8 array) pair.  A recorded action of row k of a launch that started at tick t0
+    was exploratory where ``explore_draw(seed, threshold, n_actions, offset + lane, t0 + k)[0]`` says so."""
+    lib = load_library()
+    x = Exploration(int(seed) & (2**64 - 1), int(threshold), 0)
+    g, t = np.broadcast_arrays(np.asarray(global_id, dtype=np.uint64), np.asarray(tick, dtype=np.uint64))
+    explored = np.empty(g.shape, np.bool_)
+    action = np.empty(g.shape, np.uint8)
+    e, a = C.c_uint8(), C.c_uint8()
+    for i in np.ndindex(g.shape):
+        _check(lib, lib.gymrs_explore_draw(C.byref(x), int(n_actions), int(g[i]), int(t[i]), C.byref(e), C.byref(a)))
+        explored[i], action[i] = bool(e.value), a.value
+    if g.shape == ():
+        return bool(explored), int(action)
+    return explored, action
+
+
+def _closed_loop_desc(n_envs, n_steps, lane_params, fitness, record, flags=None, explore=False) -> ClosedLoopDesc:
     """``record``: None, a ``Trajectory``, or a mapping with the keyword arguments of ``rollout_policy_record`` (device addresses
     ``obs``, ``actions``, ``reward``, ``done``, optionally ``truncated`` and ``lane_stride``).  The descriptor keeps it alive."""
-    f = ((CLOSED_LOOP_FITNESS if fitness else 0) | (CLOSED_LOOP_LANE_PARAMS if lane_params else 0)) if flags is None else int(flags)
+    f = ((CLOSED_LOOP_FITNESS if fitness else 0) | (CLOSED_LOOP_LANE_PARAMS if lane_params else 0) |
+         (CLOSED_LOOP_EXPLORE if explore else 0)) if flags is None else int(flags)
     traj = record
     if record is not None and not isinstance(record, Trajectory):
         stride = record.get("lane_stride")
@@ -545,14 +584,38 @@ class BatchedEngine:
 
     # -- the closed-loop calls behind one descriptor, and under per-lane physics ---------------------------
     def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
-                            flags: Optional[int] = None) -> None:
+                            flags: Optional[int] = None, explore: bool = False) -> None:
         """``gymrs_rollout_closed_loop``: ``rollout_policy`` (with ``record``: ``rollout_policy_record``; with ``fitness``:
         ``rollout_policy_fitness``) behind one descriptor.  ``lane_params`` (``GYMRS_CLOSED_LOOP_LANE_PARAMS``) lets it run while a
         parameter table is active: every lane steps with the row ``step`` would use for it, n_steps steps in one launch; without a
         table it changes nothing, so a training loop may always set it.  ``record``: a ``Trajectory`` or a mapping with the keyword
-        arguments of ``rollout_policy_record``.  ``flags`` passes a raw flags word instead of the two booleans."""
-        desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags)
+        arguments of ``rollout_policy_record``.  ``explore`` (``GYMRS_CLOSED_LOOP_EXPLORE``) plays the epsilon-greedy action of
+        ``set_exploration`` in place of the argmax.  ``flags`` passes a raw flags word instead of the three booleans."""
+        desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags, explore)
         _check(self._lib, self._lib.gymrs_rollout_closed_loop(self._h, C.byref(desc)))
+
+    # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
+    def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:
+        """Install the exploration settings (``gymrs_set_exploration``): a step explores with probability ``threshold`` / 65536
+        (``epsilon`` is rounded to that grid), drawing from a Philox stream keyed (``seed``, global lane id, engine tick).
+        ``set_exploration(None)`` removes them.  Touches no lane state, tick, statistics or fitness table; launches play them only
+        with ``rollout_closed_loop(..., explore=True)`` and ``explore_actions``."""
+        if seed is None:
+            _check(self._lib, self._lib.gymrs_set_exploration(self._h, None))
+            return
+        x = _exploration(seed, epsilon, threshold)
+        _check(self._lib, self._lib.gymrs_set_exploration(self._h, C.byref(x)))
+
+    def exploration(self) -> Tuple[int, int]:
+        """(seed, threshold) as set; raises when the engine has no exploration settings."""
+        x = Exploration()
+        _check(self._lib, self._lib.gymrs_get_exploration(self._h, C.byref(x)))
+        return int(x.seed), int(x.threshold)
+
+    def explore_actions(self, actions_dev: int) -> None:
+        """``policy_actions`` mixed with the exploration draw at the engine's current tick (one launch): ``explore_actions(buf);
+        step(buf)``, K times, is ``rollout_closed_loop(K, explore=True)``."""
+        _check(self._lib, self._lib.gymrs_explore_actions(self._h, C.c_void_p(actions_dev)))
 
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of policies [first, first + count) as an int64 array of shape (count, 4): columns reward_sum, episodes,
@@ -724,10 +787,27 @@ class ShardedEngine:
         _check(self._lib, self._lib.gymrs_sharded_rollout_policy_fitness(self._h, int(n_steps)))
 
     def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
-                            flags: Optional[int] = None) -> None:
+                            flags: Optional[int] = None, explore: bool = False) -> None:
         """``BatchedEngine.rollout_closed_loop`` on every block (``record`` must stay None: the blocks live on several devices)."""
-        desc = _closed_loop_desc(self.n_total, n_steps, lane_params, fitness, record, flags)
+        desc = _closed_loop_desc(self.n_total, n_steps, lane_params, fitness, record, flags, explore)
         _check(self._lib, self._lib.gymrs_sharded_rollout_closed_loop(self._h, C.byref(desc)))
+
+    def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:
+        """``BatchedEngine.set_exploration`` on every block: the same settings everywhere (the draw is keyed by global lane ids)."""
+        if seed is None:
+            _check(self._lib, self._lib.gymrs_sharded_set_exploration(self._h, None))
+            return
+        x = _exploration(seed, epsilon, threshold)
+        _check(self._lib, self._lib.gymrs_sharded_set_exploration(self._h, C.byref(x)))
+
+    def exploration(self) -> Tuple[int, int]:
+        """(seed, threshold) as set (every block holds the same)."""
+        return self.shards[0].exploration()
+
+    def explore_actions(self, actions_dev) -> None:
+        """``BatchedEngine.explore_actions`` on every block: ``actions_dev[r]`` is the device address of block r's buffer."""
+        for s, a in zip(self.shards, actions_dev):
+            s.explore_actions(a)
 
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of the WHOLE batch, (count, 4) int64 as ``BatchedEngine.policy_fitness``: the blocks' records summed

@@ -499,7 +499,8 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
  *   - A lane whose index is >= K (possible through the zero-copy view only) is treated as gymrs_rollout treats it: it is not
  *     stepped, pays 0 and sets no flag in every step of the launch (its record rows say so), adds nothing to any fitness
  *     record, and the next gymrs_sync returns GYMRS_EACTION naming the lowest such lane.
- *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, reserved != 0, unknown flag bits (bit 1 is not assigned),
+ *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, reserved != 0, unknown flag bits (bits 1 and 3 are not assigned;
+ *     bit 4 is GYMRS_CLOSED_LOOP_EXPLORE, "exploration" below),
  *     GYMRS_CLOSED_LOOP_FITNESS together with a record (there is no recording fitness kernel), a record that fails the buffer
  *     checks of gymrs_rollout_policy_record, n_steps > GYMRS_POLICY_FITNESS_MAX_STEPS with GYMRS_CLOSED_LOOP_FITNESS.  n_steps == 0
  *     is a no-op after these checks.
@@ -511,6 +512,50 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
 typedef struct { uint32_t n_steps; uint32_t flags; const gymrs_trajectory* record; uint64_t reserved; } gymrs_closed_loop_desc; /* 24 B */
 gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_desc* d);
 gymrs_status gymrs_sharded_rollout_closed_loop(gymrs_sharded* h, const gymrs_closed_loop_desc* d);
+/* Exploration: epsilon-greedy inside the closed-loop fused rollout, defined to the bit.
+ * The closed-loop calls above play the deterministic argmax, which is what evaluation wants; a learner that collects its batch
+ * with gymrs_rollout_closed_loop and a record must also take the action it does not already prefer.  The exploration settings live
+ * on the engine like the policy set: seed, and threshold in [0, 65536] with epsilon = threshold / 65536 exactly; reserved must be
+ * 0.  The step that takes the lane with GLOBAL id g (global_env_offset + i) from engine tick t to t + 1 -- n_actions = 2 / 3:
+ *     b        = the Philox4x32-10 block with key (seed lo, seed hi) and counter (g >> 2 lo, g >> 2 hi, t lo,
+ *                (t hi & 0xffff) | 2 << 16): the counter layout of the reset (stream 0) and action (stream 1) streams, stream 2
+ *     w        = word (g & 3) of b
+ *     explored = (w & 0xffff) < threshold
+ *     random   = ((w >> 16) * n_actions) >> 16
+ *     action   = explored ? random : the policy's action (the argmax under "closed-loop rollouts", unchanged)
+ * Four neighbouring lanes share one block per step (a work-item that owns four aligned lanes evaluates one); a
+ * global_env_offset that is not a multiple of 4 gives the same values.  The key is the engine's own tick, so K steps in one launch
+ * equal K single steps however they are split into launches, the result does not depend on how a batch is cut into engines, and
+ * a CPU can recompute every draw.  Threshold 0 is greedy: bit-identical to the call without exploration.  Threshold 65536 explores
+ * on every step (the policy's weights, non-finite ones included, then change nothing).
+ *   - gymrs_set_exploration stores the settings (x == NULL removes them); gymrs_get_exploration reads them back.  GYMRS_EINVAL:
+ *     Pendulum, threshold > 65536, reserved != 0, (get) no settings.  It needs no policy to be set, touches no lane state, tick,
+ *     statistics or fitness table, survives gymrs_set_policy and takes effect in stream order: launches enqueued before it play
+ *     the old settings.  NOT part of gymrs_engine_clone or of a snapshot (its bytes and version are unchanged).
+ *   - GYMRS_CLOSED_LOOP_EXPLORE in gymrs_closed_loop_desc.flags: gymrs_rollout_closed_loop plays the epsilon-greedy action in every
+ *     combination it has: plain, with a record (the `actions` rows hold the action TAKEN), with GYMRS_CLOSED_LOOP_FITNESS (the
+ *     counters follow the action taken), with or without GYMRS_CLOSED_LOOP_LANE_PARAMS under a table.  The flag without settings
+ *     on the engine: GYMRS_EINVAL naming gymrs_set_exploration.  Settings without the flag: the greedy launch, bit for bit --
+ *     exploration is opt-in per launch, so a learner alternates collection and greedy validation launches.  gymrs_rollout_policy,
+ *     _record and _fitness stay greedy.
+ *   - gymrs_explore_actions(e, actions_dev): the per-step counterpart, gymrs_policy_actions mixed with the draw at the engine's
+ *     current tick:  gymrs_rollout_closed_loop(K, EXPLORE)  ==  K x (gymrs_explore_actions(e, buf); gymrs_step(e, buf)).  It needs
+ *     a policy and settings (GYMRS_EINVAL otherwise) and, like gymrs_policy_actions, works while a parameter table is active.
+ *   - gymrs_explore_draw: host only, no GPU (like gymrs_policy_size): explored (0 / 1) and the random action of (global id, tick)
+ *     under the settings; either output may be NULL.  A learner that needs to know which recorded actions were exploratory
+ *     recomputes them; no trajectory row is spent on it.  GYMRS_EINVAL: NULL settings, settings gymrs_set_exploration would refuse,
+ *     n_actions outside 1 .. 256.
+ *   - gymrs_sharded_set_exploration applies the same settings to every block; gymrs_sharded_rollout_closed_loop passes the flag
+ *     through.  With the global-id key, k blocks equal one engine.
+ * Evaluation (gymrs_evaluate_policy) stays greedy. */
+#define GYMRS_CLOSED_LOOP_EXPLORE 16u /* bit 4 */
+typedef struct { uint64_t seed; uint32_t threshold; uint32_t reserved; } gymrs_exploration; /* 16 B */
+gymrs_status gymrs_set_exploration(gymrs_engine* e, const gymrs_exploration* x);
+gymrs_status gymrs_get_exploration(gymrs_engine* e, gymrs_exploration* x_out);
+gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev);
+gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, uint64_t global_id, uint64_t tick, uint8_t* explored,
+                                uint8_t* random_action);
+gymrs_status gymrs_sharded_set_exploration(gymrs_sharded* h, const gymrs_exploration* x);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

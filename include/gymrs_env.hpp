@@ -73,6 +73,15 @@ struct MountainCarObservation { // mountain_car.rs:122-128
     std::vector<double> to_vec() const { return {position, velocity}; }
 };
 
+// The epsilon-greedy draw of (global lane id, engine tick) under settings x (gymrs_explore_draw; host only, no GPU): {explored,
+// random action}.  Which actions of a recorded batch were exploratory is recomputed with it, no trajectory row is spent on them.
+inline std::pair<bool, std::uint8_t> explore_draw(const gymrs_exploration& x, std::uint32_t n_actions, std::uint64_t global_id, std::uint64_t tick)
+{
+    std::uint8_t explored = 0, action = 0;
+    check(gymrs_explore_draw(&x, n_actions, global_id, tick, &explored, &action));
+    return {explored != 0, action};
+}
+
 // ---- batched form: the shape the hot path is built for ---------------------------------------------
 class VecEnv {
 public:
@@ -233,6 +242,31 @@ public:
         const gymrs_closed_loop_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u), record, 0};
         check(gymrs_rollout_closed_loop(e_, &d));
     }
+    // epsilon-greedy exploration (gymrs_set_exploration): a step explores with probability threshold / 65536, drawing from a Philox
+    // stream keyed (seed, global lane id, engine tick); launches play it with explore = true (GYMRS_CLOSED_LOOP_EXPLORE) only
+    void set_exploration(std::uint64_t seed, std::uint32_t threshold)
+    {
+        const gymrs_exploration x{seed, threshold, 0};
+        check(gymrs_set_exploration(e_, &x));
+    }
+    void clear_exploration() { check(gymrs_set_exploration(e_, nullptr)); }
+    gymrs_exploration exploration() const
+    {
+        gymrs_exploration x{};
+        check(gymrs_get_exploration(e_, &x));
+        return x;
+    }
+    // policy_actions mixed with the draw at the engine's current tick: explore_actions + step_device, K times, is
+    // rollout_closed_loop(K, .., explore = true)
+    void explore_actions(void* actions_dev) { check(gymrs_explore_actions(e_, actions_dev)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params, bool fitness, const gymrs_trajectory* record, bool explore)
+    {
+        const gymrs_closed_loop_desc d{n_steps,
+                                       (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u) |
+                                           (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u),
+                                       record, 0};
+        check(gymrs_rollout_closed_loop(e_, &d));
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
@@ -373,6 +407,21 @@ public:
     void rollout_closed_loop(std::uint32_t n_steps, bool lane_params = false, bool fitness = false)
     {
         const gymrs_closed_loop_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u), nullptr, 0};
+        check(gymrs_sharded_rollout_closed_loop(h_, &d));
+    }
+    // VecEnv::set_exploration on every block: the same settings everywhere (the draw is keyed by global lane ids)
+    void set_exploration(std::uint64_t seed, std::uint32_t threshold)
+    {
+        const gymrs_exploration x{seed, threshold, 0};
+        check(gymrs_sharded_set_exploration(h_, &x));
+    }
+    void clear_exploration() { check(gymrs_sharded_set_exploration(h_, nullptr)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params, bool fitness, bool explore)
+    {
+        const gymrs_closed_loop_desc d{n_steps,
+                                       (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u) |
+                                           (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u),
+                                       nullptr, 0};
         check(gymrs_sharded_rollout_closed_loop(h_, &d));
     }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count) // the blocks' records, summed
