@@ -289,6 +289,20 @@ impl Engine {
         check(ffi::gymrs_rollout_closed_loop(self.raw, &d));
     }
 
+    /// `gymrs_rollout_transitions`: `rollout_closed_loop_record` (`explore`: `rollout_closed_loop_explore_record`) that also writes, per
+    /// step, the observation every ended lane showed before its re-arm into `final_obs` (`[n_steps][D][out.lane_stride]`; only the
+    /// elements of ended lane-steps are written) and, unless null, the observations the launch starts from into `start_obs`
+    /// (`[D][out.lane_stride]`).  The successor of step k is `final_obs[k]` where `done[k] | truncated[k]`, else `obs[k]`.  Engines with
+    /// `GYMRS_AUTO_RESET` only.
+    ///
+    /// # Safety
+    /// As `rollout_record`; `final_obs` and `start_obs` must be 16-byte aligned device addresses of those sizes, valid until `sync()`.
+    pub unsafe fn rollout_transitions(&mut self, n_steps: u32, lane_params: bool, explore: bool, out: &ffi::Trajectory, final_obs: *mut f32, start_obs: *mut f32) {
+        let flags = if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 } | if explore { ffi::GYMRS_CLOSED_LOOP_EXPLORE } else { 0 };
+        let d = ffi::GymrsTransitionsDesc { n_steps, flags, record: *out, final_obs, start_obs, reserved: 0 };
+        check(ffi::gymrs_rollout_transitions(self.raw, &d));
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

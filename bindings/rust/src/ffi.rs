@@ -116,6 +116,19 @@ pub struct GymrsClosedLoopDesc {
     pub reserved: u64,
 }
 
+/// `gymrs_transitions_desc`: what `gymrs_rollout_transitions` runs (include/gymrs_amd.h "transitions"), 80 bytes: the record by value,
+/// `final_obs` `[n_steps][D][record.lane_stride]` (written where a step re-armed a lane), `start_obs` `[D][record.lane_stride]` or null.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsTransitionsDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub record: Trajectory,
+    pub final_obs: *mut f32,
+    pub start_obs: *mut f32,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -233,6 +246,7 @@ extern "C" {
     pub fn gymrs_get_policy_fitness(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyFitness) -> c_int;
     pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_rollout_closed_loop(e: *mut GymrsEngine, d: *const GymrsClosedLoopDesc) -> c_int;
+    pub fn gymrs_rollout_transitions(e: *mut GymrsEngine, d: *const GymrsTransitionsDesc) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -45,6 +45,7 @@ from ._lib import library_path, load_library
 from . import sharded
 from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, EvalDesc, EVAL_COMMON_STARTS, EVAL_LANE_PARAMS
 from .engine import ClosedLoopDesc, CLOSED_LOOP_FITNESS, CLOSED_LOOP_LANE_PARAMS
+from .engine import TransitionsDesc
 from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
 
 __all__ = [
@@ -54,6 +55,6 @@ __all__ = [
     "AUTO_RESET", "TRACK_STATS", "TIME_LIMIT", "FINAL_OBS", "CARTPOLE", "MOUNTAIN_CAR", "PENDULUM",
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
     "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
-    "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS",
+    "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS", "TransitionsDesc",
     "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw",
 ]

@@ -82,6 +82,8 @@ SIGNATURES = {
     "gymrs_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     # the closed-loop calls behind one descriptor (gymrs_closed_loop_desc 24 B: {u32 n_steps, u32 flags, trajectory*, u64 reserved})
     "gymrs_rollout_closed_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # the recording closed-loop launch with per-step final observations (gymrs_transitions_desc 80 B)
+    "gymrs_rollout_transitions": (C.c_int, [C.c_void_p, C.c_void_p]),
     # epsilon-greedy exploration (gymrs_exploration 16 B: {u64 seed, u32 threshold, u32 reserved})
     "gymrs_set_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),

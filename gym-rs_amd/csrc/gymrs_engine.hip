@@ -1027,9 +1027,10 @@ static gymrs_status check_trajectory(const gymrs_engine* e, const gymrs_trajecto
 // every lane with its own row (the TableT instantiations of the policy kernels); without a table it changes nothing.
 // explore = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_EXPLORE: closed (or fitness) playing the epsilon-greedy action of the
 // engine's exploration settings (the exploring copies of the policy kernels, gymrs_explore.hip).
+// transitions = gymrs_rollout_transitions: closed with a record, and the kernel also writes these two buffers (gymrs_transitions.hip).
 static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
                                  const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false, bool lane_params = false,
-                                 bool explore = false)
+                                 bool explore = false, const TransitionArgs* transitions = nullptr)
 {
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
     if (fitness && e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
@@ -1065,7 +1066,11 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    if (explore) {
+    if (transitions) { // gymrs_rollout_transitions: one action source, a greedy launch plays threshold 0 (the greedy bits)
+        const ExploreArgs greedy{};
+        HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, explore ? e->explore : greedy,
+                                           *transitions, e->stream));
+    } else if (explore) {
         if (fitness)
             if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
         HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->explore,
@@ -1144,6 +1149,36 @@ gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_
     if (d->record)
         if (gymrs_status st = check_trajectory(e, d->record, who)) return st;
     return rollout_impl(e, d->n_steps, 0, 0, d->record, who, true, fitness, lane_params, explore);
+}
+
+// gymrs_rollout_closed_loop with a record that also keeps every step's final observations (include/gymrs_amd.h, "transitions").
+gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_desc* d)
+{
+    const char* who = "gymrs_rollout_transitions";
+    if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, std::string(who) + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (!(e->flags & GYMRS_AUTO_RESET))
+        return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no GYMRS_AUTO_RESET: nothing is re-armed, the record's obs rows already hold "
+                                                     "the final observations (gymrs_rollout_closed_loop)");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
+    if (d->flags & ~(GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
+        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_LANE_PARAMS and GYMRS_CLOSED_LOOP_EXPLORE are the only "
+                                                     "ones; GYMRS_CLOSED_LOOP_FITNESS: there is no recording fitness kernel)");
+    const bool lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0, explore = (d->flags & GYMRS_CLOSED_LOOP_EXPLORE) != 0;
+    if (explore && !e->explore_set)
+        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
+    if (e->table_k && !lane_params)
+        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table): set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags "
+                                                     "and every lane steps with its own row");
+    if (gymrs_status st = check_trajectory(e, &d->record, who)) return st;
+    if (!d->final_obs) return fail(GYMRS_EINVAL, std::string(who) + ": final_obs is required");
+    if ((reinterpret_cast<uintptr_t>(d->final_obs) | reinterpret_cast<uintptr_t>(d->start_obs)) % 16 != 0)
+        return fail(GYMRS_EINVAL, std::string(who) + ": final_obs and start_obs must be 16-byte aligned");
+    const TransitionArgs t{d->final_obs, d->start_obs};
+    return rollout_impl(e, d->n_steps, 0, 0, &d->record, who, true, false, lane_params, explore, &t);
 }
 
 gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)

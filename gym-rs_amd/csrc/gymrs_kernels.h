@@ -7,6 +7,7 @@
 //   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h)
 //   gymrs_rollout_fitness.hip  that rollout with per-policy fitness counters
 //   gymrs_explore.hip        the closed-loop kernels once more with the epsilon-greedy action source (gymrs_rollout_explore_impl.h)
+//   gymrs_transitions.hip    the recording closed-loop kernel with per-step final observations (gymrs_rollout_transitions_impl.h)
 //   gymrs_evaluate.hip       episodic policy evaluation (gymrs_evaluate.h, gymrs_evaluate_impl.h)
 //   gymrs_aux.hip            everything off the per-step path: reset, action fill, statistics, folds
 // gymrs_launch.h holds the one launch table (flag sets x lanes per work-item) the step and rollout families dispatch through;
@@ -349,4 +350,15 @@ hipError_t launch_explore_actions(gymrs_env_kind kind, const float* const* s, vo
 // launch_rollout_policy / launch_rollout_policy_fitness (fitness != NULL) playing the epsilon-greedy action of every step
 hipError_t launch_rollout_explore(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                   const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
+// ---- transitions (gymrs_rollout_transitions; gymrs_transitions.hip, gymrs_table_transitions_<env>.hip) ------------------------
+// The two buffers of a gymrs_transitions_desc as the kernels get them by value, after ExploreArgs.  Rows are RolloutArgs::rec_stride
+// lanes apart, like the record's.
+struct TransitionArgs {
+    float* final_obs; // [n_steps][obs_dim][rec_stride]: written where a step re-armed a lane, nowhere else
+    float* start_obs; // [obs_dim][rec_stride] or NULL
+};
+// launch_rollout_explore with a record (r.rec_obs != NULL, 4 lanes per work-item) that also writes t.  Engines with GYMRS_AUTO_RESET
+// only; x.threshold == 0 is the greedy launch.
+hipError_t launch_rollout_transitions(gymrs_env_kind kind, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                      const PolicyArgs& p, const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream);
 } // namespace gymrs

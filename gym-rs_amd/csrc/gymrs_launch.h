@@ -60,6 +60,24 @@ R dispatch_flag_set(uint32_t flags, R invalid, Fn&& fn)
     }
 }
 
+// The eight of them with auto-reset, for a family that is only built where lanes are re-armed (gymrs_rollout_transitions_impl.h).
+template <class R, class Fn>
+R dispatch_auto_reset_flag_set(uint32_t flags, R invalid, Fn&& fn)
+{
+    constexpr uint32_t A = GYMRS_AUTO_RESET, S = GYMRS_TRACK_STATS, T = GYMRS_TIME_LIMIT, F = GYMRS_FINAL_OBS;
+    switch (flags & (A | S | T | F)) {
+    case A: return fn(FlagSet<A>{});
+    case A | S: return fn(FlagSet<A | S>{});
+    case A | T: return fn(FlagSet<A | T>{});
+    case A | S | T: return fn(FlagSet<A | S | T>{});
+    case A | F: return fn(FlagSet<A | F>{});
+    case A | S | F: return fn(FlagSet<A | S | F>{});
+    case A | T | F: return fn(FlagSet<A | T | F>{});
+    case A | S | T | F: return fn(FlagSet<A | S | T | F>{});
+    default: return invalid;
+    }
+}
+
 // Lanes per work-item: 4 or 8.
 template <bool MINIMAL = false, class R, class Fn>
 R dispatch_lanes(int vec, R invalid, Fn&& fn)

@@ -29,9 +29,12 @@ struct RandomActions {
 struct NoFitness {
     static constexpr bool kOn = false;
 };
-template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC, class Src = RandomActions, class Fit = NoFitness>
+// Sink = where the pre-reset observation of the lanes a step re-arms goes, step by step (advance_tile): nowhere (NoFinalSink), or the
+// rows of gymrs_rollout_transitions (FinalObsRows, gymrs_rollout_transitions_impl.h), which also takes the observations the launch
+// starts from.
+template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool REC, class Src = RandomActions, class Fit = NoFitness, class Sink = NoFinalSink>
 __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, const typename Env::Consts& c,
-                                              ResetLds<Env, VEC, kBlock>& lds, const Src& src = Src(), Fit* fit = nullptr)
+                                              ResetLds<Env, VEC, kBlock>& lds, const Src& src = Src(), Fit* fit = nullptr, Sink* sink = nullptr)
 {
     constexpr int kVec = VEC;
     using R = TileRegs<Env, VEC, FLAGS>;
@@ -40,6 +43,7 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
     R d;
     load_tile<Env, VEC, FLAGS, FULL, true>(a, base, d);
     load_param_index<Env, VEC, FLAGS, FULL>(a, c, base, d); // (TableT: the index stays in registers for the whole rollout)
+    if constexpr (Sink::kOn) sink->template start<FULL>(d.st, base, a.n);
     unsigned long long resets = 0;
     double ret = 0.0, open = 0.0;
     const size_t wave_slot = (size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -94,7 +98,11 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
             a.truncate_all = (a.tick + 1 - ustart >= c.max_steps) ? 1u : 0u;
             if (a.truncate_all && R::AUTO) ustart = a.tick + 1;
         }
-        advance_tile<Env, VEC, FLAGS, FULL, true, kBlock>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x);
+        if constexpr (Sink::kOn) {
+            sink->step(k);
+            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock, Sink>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x, sink);
+        } else
+            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x);
         if constexpr (Fit::kOn) fit->template step<FULL>(out, base, a.n);
         if constexpr (REC) {
             const uint64_t row = (uint64_t)k * r.rec_stride;

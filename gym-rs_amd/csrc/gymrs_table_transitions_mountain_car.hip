@@ -1,0 +1,15 @@
+// gymrs_table_transitions_mountain_car.hip -- the transition kernels (gymrs_rollout_transitions_impl.h) of MountainCar with
+// per-lane parameter tables (TableT, gymrs_tile.h): gymrs_rollout_transitions with GYMRS_CLOSED_LOOP_LANE_PARAMS.  The eight flag
+// sets with auto-reset at 4 lanes per work-item; in a translation unit of its own so that the build compiles it in parallel with
+// the others.
+#include "gymrs_rollout_transitions_impl.h"
+
+namespace gymrs {
+
+hipError_t launch_rollout_transitions_table_mountain_car(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                                         const PolicyArgs& p, const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream)
+{
+    return rollout_transitions_env<TableT<MountainCarT>>(flags, a, r, consts, p, x, t, stream);
+}
+
+} // namespace gymrs

@@ -512,6 +512,12 @@ __device__ __forceinline__ void store_final_obs(const StepArgs& a, uint64_t base
     }
 }
 
+// Sink = where else a re-armed lane's pre-reset observation goes besides StepArgs::final_obs: nowhere (NoFinalSink: every line that
+// names it compiles away), or the per-step rows of gymrs_rollout_transitions (FinalObsRows, gymrs_rollout_transitions_impl.h).
+struct NoFinalSink {
+    static constexpr bool kOn = false;
+};
+
 // One Env::step() of a tile held in registers: physics + auto-reset of the finished lanes.  The per-step
 // kernel calls it once between load_tile and store_tile; the fused rollout kernel calls it in a loop.
 // `resets`/`ret` are the wave's statistics slot values: the per-step kernel stores the updated slot from
@@ -522,10 +528,11 @@ __device__ __forceinline__ void store_final_obs(const StepArgs& a, uint64_t base
 // lane-step: 29.6 vs 23.4 us per 2^22-lane step).  The caller loads/stores `open` (StepArgs::wave_open).
 // a.fold_step: a folding launch of a reset-logged per-step kernel (step_block): the step's done-masks stay in registers.
 // vblock: the index of the workgroup-sized tile (THREADS * VEC lanes) this is -- blockIdx.x, unless a workgroup steps several tiles.
-template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool ROLL = false, int THREADS = Env::kThreads>
+// sink (Sink::kOn): also handed the finished lanes' pre-reset observation, where store_final_obs is -- in a wave that re-arms a lane only.
+template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool ROLL = false, int THREADS = Env::kThreads, class Sink = NoFinalSink>
 __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename Env::Consts& c, uint64_t base,
                                              TileRegs<Env, VEC, FLAGS>& d, ResetLds<Env, VEC, THREADS>& lds, unsigned long long& resets,
-                                             double& ret, double& open, StepOut<VEC>& out, uint32_t vblock)
+                                             double& ret, double& open, StepOut<VEC>& out, uint32_t vblock, const Sink* sink = nullptr)
 {
     static_assert(Env::kConstReward || Env::kNeverTerminates,
                   "return tracking assumes a constant reward (return = +-length) or one shared episode clock");
@@ -686,6 +693,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
         }
         if (total != 0) { // quiet waves (MountainCar / Pendulum: nearly all) skip everything below
             if constexpr (R::FINAL) store_final_obs<Env, VEC, FLAGS, FULL>(a, base, ls, need_reset);
+            if constexpr (Sink::kOn) sink->store(base, ls, need_reset);
             if (LOGGED && a.fold_step == 0 && lane == 0) {
                 // The whole episode bookkeeping of this step for the wave's 64 * VEC lanes: 8 * VEC contiguous bytes.  (Measured at
                 // 2^20 CartPole lanes: the scattered ep_start stores cost 0.45 us per launch -- ~47k partial cache lines -- and the

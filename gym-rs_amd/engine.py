@@ -96,6 +96,12 @@ CLOSED_LOOP_LANE_PARAMS = 4  # GYMRS_CLOSED_LOOP_LANE_PARAMS
 CLOSED_LOOP_EXPLORE = 16  # GYMRS_CLOSED_LOOP_EXPLORE
 
 
+class TransitionsDesc(C.Structure):
+    """``gymrs_transitions_desc`` (include/gymrs_amd.h), 80 bytes: the record by value, then the two observation buffers."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("record", Trajectory), ("final_obs", C.c_void_p),
+                ("start_obs", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -593,6 +599,19 @@ class BatchedEngine:
         ``set_exploration`` in place of the argmax.  ``flags`` passes a raw flags word instead of the three booleans."""
         desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags, explore)
         _check(self._lib, self._lib.gymrs_rollout_closed_loop(self._h, C.byref(desc)))
+
+    def rollout_transitions(self, n_steps: int, *, record, final_obs: int, start_obs: Optional[int] = None, lane_params: bool = False,
+                            explore: bool = False, flags: Optional[int] = None) -> None:
+        """``gymrs_rollout_transitions``: ``rollout_closed_loop(n_steps, record=record, ...)`` that also writes, per step, the
+        observation every ended lane showed before its re-arm into ``final_obs`` ([n_steps][D][lane_stride] f32, device address;
+        only the elements of ended lane-steps are written) and, if given, the observations the launch starts from into
+        ``start_obs`` ([D][lane_stride]).  The successor of step k is ``where(done[k] | truncated[k], final_obs[k], obs[k])``.
+        Engines with ``AUTO_RESET`` only.  ``record``: a ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (required)."""
+        if record is None:
+            raise ValueError("rollout_transitions needs a record")
+        cl = _closed_loop_desc(self.n_envs, n_steps, lane_params, False, record, flags, explore)
+        desc = TransitionsDesc(int(n_steps), cl.flags, cl.record.contents, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None), 0)
+        _check(self._lib, self._lib.gymrs_rollout_transitions(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

@@ -556,6 +556,44 @@ gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev);
 gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, uint64_t global_id, uint64_t tick, uint8_t* explored,
                                 uint8_t* random_action);
 gymrs_status gymrs_sharded_set_exploration(gymrs_sharded* h, const gymrs_exploration* x);
+/* Transitions: a recorded closed-loop rollout that keeps what every ended episode ended in.
+ * With GYMRS_AUTO_RESET the `obs` row of a step that ends an episode holds the re-armed state; the observation the episode ended in,
+ * which a truncated step must bootstrap from, is only in the engine's GYMRS_FINAL_OBS arrays, one ending per lane.
+ * gymrs_rollout_transitions(e, d) is gymrs_rollout_closed_loop with d->n_steps = K, d->flags and &d->record that also writes that
+ * observation per step, and optionally the observations the launch starts from.  D = obs_dim (4 / 2), i = the lane.
+ *   - Everything but the two new buffers: exactly what gymrs_rollout_closed_loop leaves with the same n_steps, flags and record,
+ *     bit for bit -- the five record rows, lane state, the last step's reward / done / truncated, the engine's own
+ *     final-observation arrays (engines with GYMRS_FINAL_OBS), statistics, steps_beyond_terminated and tick.
+ *   - final_obs[(k * D + j) * record.lane_stride + i] is written if and only if step k of the launch re-armed lane i (done |
+ *     truncated; the engine has GYMRS_AUTO_RESET).  Every other element keeps the bytes it held: lanes that went on, the padding
+ *     lanes [n_envs, lane_stride), lanes whose parameter index is outside the table (they are not stepped; gymrs_sync reports
+ *     them as GYMRS_EACTION as ever).  No row is cleared: `ended = done | truncated` of the record says which elements count.
+ *   - The value written is component j of the observation the lane showed BEFORE the re-arm: the bits a per-step loop on an
+ *     engine with GYMRS_FINAL_OBS reads from gymrs_final_obs_ptrs for that lane right after that step, and the bits the record's
+ *     `obs` row would hold on an engine without auto-reset.
+ *   - start_obs (may be NULL): start_obs[j * record.lane_stride + i] = component j of lane i's observation before the first step,
+ *     what gymrs_obs_ptrs showed, so that transition 0 has its s.
+ *   - The transition of step k is (s, a, r, s', done) with s = obs[k - 1] (start_obs for k = 0), a = actions[k], r = reward[k] and
+ *     the successor s' = ended ? final_obs[k] : obs[k].
+ *   - Every flag set with GYMRS_AUTO_RESET, with or without GYMRS_FINAL_OBS on the engine; with and without a parameter table
+ *     (GYMRS_CLOSED_LOOP_LANE_PARAMS, as above), with and without GYMRS_CLOSED_LOOP_EXPLORE, any n_envs and global_env_offset.
+ *     Like every recording kernel it runs at 4 lanes per work-item.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, no policy set, an engine without GYMRS_AUTO_RESET (nothing is
+ *     re-armed there: the `obs` rows already hold the final observations), reserved != 0, any flag bit but
+ *     GYMRS_CLOSED_LOOP_LANE_PARAMS and GYMRS_CLOSED_LOOP_EXPLORE (GYMRS_CLOSED_LOOP_FITNESS: there is no recording fitness kernel),
+ *     GYMRS_CLOSED_LOOP_EXPLORE without exploration settings, an active table without GYMRS_CLOSED_LOOP_LANE_PARAMS, a record that
+ *     fails the buffer checks of gymrs_rollout_policy_record (truncated may be NULL), final_obs NULL or not 16-byte aligned,
+ *     start_obs not 16-byte aligned.  n_steps == 0 is a no-op after these checks; start_obs is not written then either.
+ * There is no sharded counterpart: a sharded batch refuses records already (its blocks live on several devices). */
+typedef struct {
+    uint32_t n_steps;
+    uint32_t flags;            /* GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE, nothing else */
+    gymrs_trajectory record;   /* by value; the rules of gymrs_rollout_policy_record (truncated may be NULL) */
+    float* final_obs;          /* [n_steps][D][record.lane_stride], required, 16-byte aligned */
+    float* start_obs;          /* [D][record.lane_stride] or NULL, 16-byte aligned */
+    uint64_t reserved;         /* 0 */
+} gymrs_transitions_desc;      /* 80 bytes */
+gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_desc* d);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

@@ -267,6 +267,17 @@ public:
                                        record, 0};
         check(gymrs_rollout_closed_loop(e_, &d));
     }
+    // gymrs_rollout_transitions: the recording closed-loop launch that also writes, per step, the pre-re-arm observation of every ended
+    // lane into final_obs ([n_steps][D][record.lane_stride], only those elements) and, unless NULL, the launch's start observations
+    // into start_obs ([D][record.lane_stride]): successor of step k = ended ? final_obs[k] : obs[k].  Engines with GYMRS_AUTO_RESET only.
+    void rollout_transitions(const gymrs_transitions_desc& d) { check(gymrs_rollout_transitions(e_, &d)); }
+    void rollout_transitions(std::uint32_t n_steps, const gymrs_trajectory& record, float* final_obs, float* start_obs = nullptr,
+                             bool lane_params = false, bool explore = false)
+    {
+        const gymrs_transitions_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u),
+                                       record, final_obs, start_obs, 0};
+        check(gymrs_rollout_transitions(e_, &d));
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
