@@ -1,6 +1,9 @@
 // gymrs_engine.hip — host side of the C ABI (include/gymrs_amd.h): owns the SoA device buffers,
 // the HIP stream and the engine tick; every entry point cites the reference interface it
 // replaces in the header.  No CPU fallback exists: without a HIP device every call fails loudly.
+// A per-step launch has ONE submission sequence, whoever submits it: prepare_step (flags, hints, StepArgs, the reset-log ring)
+// and record_step (what the engine remembers once it is submitted); the decisions in it that need no device are
+// gymrs_step_plan.h's.  The fused rollouts take a RolloutRequest that their entry points validate and fill.
 #include "gymrs_engine_priv.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -36,36 +39,14 @@ static uint64_t os_entropy()
     return ((uint64_t)rd() << 32) ^ (uint64_t)rd();
 }
 
-// Memory hints (measured, tools/size_sweep.py, profiles/r02_size_sweep.log).  Non-temporal accesses pay off
-//   * while one step's arrays (state in + out, rewards, flags) are small next to the 256 MB Infinity Cache (CartPole 2^20
-//     lanes: 6.6 vs 7.0 us): every array is read once and written once per step and the next reader is the next kernel;
-//   * and again once one step's traffic is well beyond the cache (>= ~340 MiB: CartPole 2^24 lanes 111 vs 117 us,
-//     MountainCar 2^24 lanes 52 vs 57 us): nothing survives until the next step anyway and the streaming hint spares
-//     the cache the churn.
-// In between (2^21 .. 2^23 CartPole lanes) the Infinity Cache serves part of the next step's reads and plain accesses
-// win (2^22 lanes: 25.6 vs 30.1 us).
-static uint64_t bytes_per_step(const gymrs_engine* e)
-{
-    const uint64_t bytes_per_lane = (uint64_t)e->state_dim * 8 + 10 + (e->kind == GYMRS_PENDULUM ? 8 : 0);
-    return e->n * bytes_per_lane;
-}
-
-// Round 4 (profiles/r04_hints_by_size.log, per class of access): between those two regimes it is only the stores nobody reads
-// again -- reward, done, truncated, Pendulum's cos / sin -- that should be streamed: they then leave the Infinity Cache to the state, which
-// the next step reads (CartPole 2^21 lanes 13.3 -> 12.1 us, 2^23 56.2 -> 49.0, 2^24 112.2 -> 96.0 against hinting everything, which is
-// what round 3 did from 340 MiB per step on).  Only beyond ~1 GiB per step does hinting every access win again (2^25 lanes: 231 vs 242 us).
+// The flags of a per-step launch before the take-over and the time-limit elision have had their say (hint_bits, gymrs_step_plan.h).
 static uint32_t launch_flags_of(const gymrs_engine* e)
 {
-    const uint64_t per_step = bytes_per_step(e);
-    uint32_t hint = 0;
-    switch (e->nt_mode) {
-    case 1: hint = kFlagNonTemporal; break;
-    case 2: hint = 0; break;
-    case 3: hint = kFlagNtOut; break;
-    default: hint = (per_step <= (48ull << 20) || per_step >= (1024ull << 20)) ? kFlagNonTemporal : kFlagNtOut; break;
-    }
-    return e->flags | hint | table_bit(e);
+    return e->flags | hint_bits(e->nt_mode, bytes_per_step(e->kind, e->state_dim, e->n), /*chain=*/false) | table_bit(e);
 }
+
+// Pendulum under GYMRS_TIME_LIMIT: every lane's episode clock is the host's (gymrs_step_plan.h)
+static bool has_uniform_clock(const gymrs_engine* e) { return e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT); }
 
 static StepArgs step_args(const gymrs_engine* e, const void* actions)
 {
@@ -98,7 +79,7 @@ static StepArgs step_args(const gymrs_engine* e, const void* actions)
     a.seed = e->seed;
     a.tick = e->tick;
     a.box = make_sample_box(e->lo, e->hi, e->state_dim);
-    a.truncate_all = (e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT) && e->tick + 1 - e->uniform_start >= e->max_steps) ? 1u : 0u;
+    a.truncate_all = (has_uniform_clock(e) && uniform_clock_hits(e->tick, e->uniform_start, e->max_steps)) ? 1u : 0u;
     a.skip_trunc_store = (e->kind == GYMRS_PENDULUM && e->trunc_held == (int)a.truncate_all) ? 1u : 0u;
     a.trace = e->trace;
     a.trace_wpb = (uint32_t)step_threads_of(e->kind, e->n, e->vec) / 64u;
@@ -142,9 +123,7 @@ static gymrs_status stream_op_barrier(gymrs_engine* e)
     return GYMRS_OK;
 }
 
-// ---- reset log bookkeeping (host side) ----------------------------------------------------------------------------
-// Invariant: the rows of the steps log_first_tick .. log_first_tick + log_pending - 1 (log_pending < kResetLogRows) may hold
-// bits; every other row of the ring is zero.
+// ---- reset log bookkeeping (host side; the ring's invariant and its step: gymrs_step_plan.h) -----------------------------------
 // Fold the pending rows now, with the stand-alone kernel: before anything reads ep_start or the episode counters
 // (statistics, snapshot, clone, the rollout kernel) and when the launch shape changes.
 gymrs_status fold_reset_log(gymrs_engine* e)
@@ -157,32 +136,24 @@ gymrs_status fold_reset_log(gymrs_engine* e)
     return GYMRS_OK;
 }
 
-// About to launch ONE per-step kernel at the engine's current tick: *fold = it has to be the folding variant (the ring
-// would be full after it; that launch folds the whole ring inside the kernel, its own masks included).
 // Does a launch with these flags keep its episode bookkeeping in the reset log?  (= TileRegs<CartPoleT, ..>::LOGGED)
 static bool launch_is_logged(const gymrs_engine* e, uint32_t flags)
 {
     return e->reset_log && (flags & GYMRS_TRACK_STATS) && (flags & GYMRS_AUTO_RESET) && !(flags & GYMRS_TIME_LIMIT);
 }
 
+// About to launch ONE per-step kernel at the engine's current tick: the HIP side of reset_log_step.  *fold = StepArgs::fold_step.
 static gymrs_status log_before_step(gymrs_engine* e, uint32_t flags, uint32_t* fold)
 {
     *fold = 0;
     if (!e->reset_log) return GYMRS_OK;
-    if (!launch_is_logged(e, flags)) return fold_reset_log(e); // this launch reads ep_start itself: nothing may be pending
-    if (e->log_pending != 0 && e->log_vec != e->vec) { // rows are laid out per wavefront of ONE launch shape
+    const ResetLogStep s = reset_log_step({e->log_pending, e->log_first_tick, e->log_vec}, launch_is_logged(e, flags), e->tick, e->vec);
+    if (s.fold_first)
         if (gymrs_status st = fold_reset_log(e)) return st;
-    }
-    if (e->log_pending == 0) {
-        e->log_first_tick = e->tick;
-        e->log_vec = e->vec;
-    }
-    if (e->log_pending == kResetLogRows - 1) {
-        *fold = 1;
-        e->log_pending = 0;
-    } else {
-        e->log_pending += 1;
-    }
+    e->log_pending = s.after.pending;
+    e->log_first_tick = s.after.first_tick;
+    e->log_vec = s.after.vec;
+    *fold = s.fold_step;
     return GYMRS_OK;
 }
 
@@ -233,6 +204,16 @@ static gymrs_status wait_for_age(gymrs_engine* e, bool* arrived)
     return GYMRS_OK;
 }
 
+// Is the engine's stream under a capture this library did not start?  Only a caller-provided stream can be.  1 = yes, 0 = no,
+// -1 = the query itself failed: each caller then keeps to its safe side (the elision stays on, chains stay off).
+static int stream_capturing(const gymrs_engine* e)
+{
+    if (e->own_stream) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(e->stream, &cs) != hipSuccess) return -1;
+    return cs != hipStreamCaptureStatusNone ? 1 : 0;
+}
+
 // The elision is off when GYMRS_NO_LIMIT_ELISION=1 is in the environment (every launch checks the limit, as in round 1), and
 // for launches into a stream that is being captured (what is baked into a graph cannot follow start_bound).
 static bool elision_disabled(const gymrs_engine* e)
@@ -241,15 +222,27 @@ static bool elision_disabled(const gymrs_engine* e)
         const char* v = std::getenv("GYMRS_NO_LIMIT_ELISION");
         return v && v[0] == '1';
     }();
-    if (off) return true;
-    if (!e->own_stream) { // only a caller-provided stream can be under a capture this library did not start
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(e->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return true;
-    }
-    return false;
+    return off || stream_capturing(e) == 1;
 }
 
-// The flags of ONE per-step launch at the engine's current tick.  A step takes a lane to the limit iff
+// About to submit a per-step launch: note who steps on the device.  Returns `flags`, without the hint bits when this launch is
+// the plain "install" launch after a take-over (see g_last_stepper).
+static uint32_t take_over_device(gymrs_engine* e, uint32_t flags)
+{
+    if (e->device < 0 || e->device >= kMaxDevices) return flags;
+    const gymrs_engine* prev = g_last_stepper[e->device].exchange(e, std::memory_order_relaxed);
+    if (prev == e) {
+        g_stepper_run[e->device].fetch_add(1, std::memory_order_relaxed);
+        return flags;
+    }
+    const uint32_t run = g_stepper_run[e->device].exchange(1, std::memory_order_relaxed);
+    // taking over the device from an engine that ran for a while (or first launch): install the lines
+    if ((prev == nullptr || run >= kTakeOverAfter) && e->nt_mode == 0) flags &= ~kFlagHintMask;
+    return flags;
+}
+
+// The time limit of ONE per-step launch at the engine's current tick: *io = the launch's flags, on return without
+// GYMRS_TIME_LIMIT where no lane can reach the limit.  A step takes a lane to the limit iff
 // tick + 1 - ep_start >= max_steps (advance_tile); with ep_start >= start_bound for every lane, none can while
 // tick + 1 - start_bound < max_steps.  start_bound comes from max_age_kernel, launched
 //   * once per approach, `margin` launches before the bound would expire -- under a policy whose episodes end long before
@@ -259,20 +252,8 @@ static bool elision_disabled(const gymrs_engine* e)
 //     episodes there were, the refresh behind it says so and the launches go on without the limit), then at a doubling
 //     distance up to 256 launches (a policy that keeps lanes alive up to the limit pays one 4 MB reduction and one
 //     drained queue per 256 steps).
-static gymrs_status flags_for_step(gymrs_engine* e, uint32_t* out)
+static gymrs_status elide_time_limit(gymrs_engine* e, uint32_t* io)
 {
-    uint32_t flags = launch_flags_of(e);
-    if (e->device >= 0 && e->device < kMaxDevices) {
-        const gymrs_engine* prev = g_last_stepper[e->device].exchange(e, std::memory_order_relaxed);
-        if (prev == e) {
-            g_stepper_run[e->device].fetch_add(1, std::memory_order_relaxed);
-        } else {
-            const uint32_t run = g_stepper_run[e->device].exchange(1, std::memory_order_relaxed);
-            // taking over the device from an engine that ran for a while (or first launch): install the lines, see above
-            if ((prev == nullptr || run >= kTakeOverAfter) && e->nt_mode == 0) flags &= ~kFlagHintMask;
-        }
-    }
-    *out = flags;
     if (!e->limit_elidable) return GYMRS_OK;
     if (elision_disabled(e)) {
         e->trunc_zero = false;
@@ -329,7 +310,7 @@ static gymrs_status flags_for_step(gymrs_engine* e, uint32_t* out)
         e->age_refreshes += 1;
     }
     if (!reachable) {
-        flags &= ~(uint32_t)GYMRS_TIME_LIMIT;
+        *io &= ~(uint32_t)GYMRS_TIME_LIMIT;
         if (!e->trunc_zero) { // the last launch with the limit may have left ones behind
             if (gymrs_status st = stream_op_barrier(e)) return st;
             HIP_TRY(hipMemsetAsync(e->truncated, 0, (size_t)e->n, e->stream));
@@ -340,7 +321,6 @@ static gymrs_status flags_for_step(gymrs_engine* e, uint32_t* out)
         e->trunc_zero = false;
     }
     e->last_elided = !reachable;
-    *out = flags;
     return GYMRS_OK;
 }
 
@@ -352,6 +332,23 @@ static gymrs_status dev_alloc(T** p, size_t count)
     if (err != hipSuccess) return fail(err == hipErrorOutOfMemory ? GYMRS_ENOMEM : GYMRS_EHIP, std::string("hipMalloc: ") + hipGetErrorString(err));
     *p = static_cast<T*>(q);
     return GYMRS_OK;
+}
+
+// A zeroed block of mapped, coherent host memory and the device's address of it.  On failure nothing is left allocated.
+template <class H, class D>
+static hipError_t mapped_host_block(size_t bytes, H** host, D** dev)
+{
+    void *h = nullptr, *d = nullptr;
+    hipError_t err = hipHostMalloc(&h, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (err == hipSuccess) err = hipHostGetDevicePointer(&d, h, 0);
+    if (err != hipSuccess) {
+        if (h) (void)hipHostFree(h);
+        return err;
+    }
+    std::memset(h, 0, bytes);
+    *host = static_cast<H*>(h);
+    *dev = static_cast<D*>(d);
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -645,19 +642,10 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
         const size_t at_final = (flags & GYMRS_FINAL_OBS) ? place((size_t)final_obs_stride(n_envs) * 4 * e->obs_dim) : 0;
         void* pool = nullptr;
         hipError_t perr;
-        if (n_envs <= kHostPoolMaxLanes) {
-            void* host = nullptr;
-            perr = hipHostMalloc(&host, off + 256, hipHostMallocMapped | hipHostMallocCoherent);
-            if (perr == hipSuccess) perr = hipHostGetDevicePointer(&pool, host, 0);
-            if (perr == hipSuccess) {
-                std::memset(host, 0, off + 256);
-                e->pool_host = static_cast<char*>(host);
-            } else if (host) {
-                (void)hipHostFree(host);
-            }
-        } else {
+        if (n_envs <= kHostPoolMaxLanes)
+            perr = mapped_host_block(off + 256, &e->pool_host, &pool);
+        else
             perr = hipMalloc(&pool, off + 256);
-        }
         if (perr != hipSuccess) {
             delete e;
             return fail(perr == hipErrorOutOfMemory ? GYMRS_ENOMEM : GYMRS_EHIP, std::string("hipMalloc: ") + hipGetErrorString(perr));
@@ -681,7 +669,7 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
     // workgroups of up to 16 waves
     e->n_stat_blocks = (uint32_t)((((n_envs + 255) / 256) + 15) / 16 * 16);
     chk(dev_alloc(&e->block_stats, (size_t)e->n_stat_blocks * 2));
-    // with all three flags a launch drops the time limit whenever no lane can reach it (flags_for_step)
+    // with all three flags a launch drops the time limit whenever no lane can reach it (elide_time_limit)
     constexpr uint32_t kAllThree = GYMRS_AUTO_RESET | GYMRS_TRACK_STATS | GYMRS_TIME_LIMIT;
     // CartPole only: there the launch without the limit is the reset-logged kernel (6.5 vs 6.7-6.9 us at 2^20 lanes).  For
     // MountainCar it would only spare the dense ep_start read, and under a random policy every lane is truncated in the
@@ -693,7 +681,7 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
     // byte it is credited with.  (GYMRS_DEV_ELIDE_REWARD=0|1: developer knob, forces it off / on at any size -- the tests' way to reach both paths.)
     {
         constexpr uint64_t kElideRewardFromBytes = 128ull << 20;
-        bool on = kind == GYMRS_CARTPOLE && (flags & GYMRS_AUTO_RESET) && n_envs * 42ull >= kElideRewardFromBytes; // (42 = bytes_per_step's figure for CartPole)
+        bool on = kind == GYMRS_CARTPOLE && (flags & GYMRS_AUTO_RESET) && bytes_per_step(kind, e->state_dim, n_envs) >= kElideRewardFromBytes;
         if (const char* v = std::getenv("GYMRS_DEV_ELIDE_REWARD"))
             if (kind == GYMRS_CARTPOLE && (flags & GYMRS_AUTO_RESET) && (v[0] == '0' || v[0] == '1')) on = v[0] == '1';
         e->elide_reward = on;
@@ -706,39 +694,18 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
     }
     if (e->limit_elidable) {
         chk(dev_alloc(&e->age_dev, (size_t)kStatsPartials)); // scratch of the refresh: one maximum per workgroup
-        void* host = nullptr;
-        if (st == GYMRS_OK && (hipHostMalloc(&host, 2 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                               hipHostGetDevicePointer(reinterpret_cast<void**>(&e->age_host_dev), host, 0) != hipSuccess))
+        if (st == GYMRS_OK && mapped_host_block(2 * sizeof(uint32_t), &e->age_host, &e->age_host_dev) != hipSuccess)
             st = fail(GYMRS_EHIP, "hipHostMalloc (age words)");
-        if (host) {
-            std::memset(host, 0, 2 * sizeof(uint32_t));
-            e->age_host = static_cast<volatile uint32_t*>(host);
-        }
     }
     chk(dev_alloc(&e->wave_open, (size_t)e->n_stat_blocks));
     chk(dev_alloc(&e->wave_clean, (size_t)e->n_stat_blocks));
     chk(dev_alloc(&e->err, 2));
-    {
-        void* host = nullptr;
-        if (st == GYMRS_OK && (hipHostMalloc(&host, 2 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                               hipHostGetDevicePointer(reinterpret_cast<void**>(&e->err_seen_dev), host, 0) != hipSuccess))
-            st = fail(GYMRS_EHIP, "hipHostMalloc (error flags)");
-        if (host) {
-            static_cast<uint32_t*>(host)[0] = static_cast<uint32_t*>(host)[1] = 0; // [0] invalid action seen, [1] a chain launch on the wrong XCD
-            e->err_seen = static_cast<volatile uint32_t*>(host);
-        }
-    }
+    // [0] invalid action seen, [1] a chain launch on the wrong XCD
+    if (st == GYMRS_OK && mapped_host_block(2 * sizeof(uint32_t), &e->err_seen, &e->err_seen_dev) != hipSuccess)
+        st = fail(GYMRS_EHIP, "hipHostMalloc (error flags)");
     chk(dev_alloc(&e->stats_dev, 4));
-    {
-        void* host = nullptr;
-        if (st == GYMRS_OK && (hipHostMalloc(&host, 4 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                               hipHostGetDevicePointer(reinterpret_cast<void**>(&e->stats_host_dev), host, 0) != hipSuccess))
-            st = fail(GYMRS_EHIP, "hipHostMalloc (statistics read-out)");
-        if (host) {
-            std::memset(host, 0, 4 * sizeof(double));
-            e->stats_host = static_cast<volatile double*>(host);
-        }
-    }
+    if (st == GYMRS_OK && mapped_host_block(4 * sizeof(double), &e->stats_host, &e->stats_host_dev) != hipSuccess)
+        st = fail(GYMRS_EHIP, "hipHostMalloc (statistics read-out)");
     chk(dev_alloc(&e->stats_acc, (size_t)kStatsPartials * 3));
     chk(dev_alloc(&e->stats_base, (size_t)kStatsBaseWords));
     chk(dev_alloc(&e->tick_dev, 1));
@@ -986,23 +953,60 @@ static gymrs_status prepare_open_sums(gymrs_engine* e, int vec)
     return GYMRS_OK;
 }
 
+// ---- the submission sequence of ONE per-step launch: prepare_step, submit (HIP launch or chain packet), record_step -----------
+struct StepLaunch {
+    uint32_t flags; // engine flags | hint bits | table bit
+    StepArgs args;
+};
+
+// The launch at the engine's current tick.  May put work on the stream first, in this order: the barrier that closes an open
+// chain, a refresh of the time-limit bound, the memset of `truncated`, the stand-alone fold.  chain = it gets a chain's hints.
+static gymrs_status prepare_step(gymrs_engine* e, const void* actions, bool chain, StepLaunch* l)
+{
+    l->flags = take_over_device(e, launch_flags_of(e));
+    if (gymrs_status st = elide_time_limit(e, &l->flags)) return st;
+    if (chain) l->flags = (l->flags & ~kFlagHintMask) | hint_bits(e->nt_mode, bytes_per_step(e->kind, e->state_dim, e->n), /*chain=*/true);
+    l->args = step_args(e, actions);
+    return log_before_step(e, l->flags, &l->args.fold_step);
+}
+
+// The launch has been submitted.  path: 1 a HIP launch, 2 a launch of a chain (gymrs_engine::last_path).
+static void record_step(gymrs_engine* e, const StepLaunch& l, int path)
+{
+    e->last_flags = l.flags;
+    e->last_path = path;
+    if (has_uniform_clock(e)) {
+        e->trunc_held = (int)l.args.truncate_all;
+        e->uniform_start = uniform_clock_after(e->tick, e->uniform_start, l.args.truncate_all != 0, (e->flags & GYMRS_AUTO_RESET) != 0);
+    }
+    e->tick += 1;
+    if (path == 2) e->aql_launches += 1;
+    e->n_steps_total += (double)e->n;
+}
+
+static hipError_t launch_step_through_hip_module(gymrs_engine* e, uint32_t flags, const StepArgs& a);
+
+// prepare, submit as a HIP launch on the engine's stream, record
+static gymrs_status step_through_hip(gymrs_engine* e, const void* actions)
+{
+    StepLaunch l;
+    if (gymrs_status st = prepare_step(e, actions, /*chain=*/false, &l)) return st;
+    const uint32_t flags = l.flags;
+    const StepArgs& a = l.args;
+    if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS) && !e->table_k) // (developer experiment: the chain's binary through HIP's queue)
+        HIP_TRY(launch_step_through_hip_module(e, flags, a));
+    else
+        HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
+    record_step(e, l, 1);
+    return GYMRS_OK;
+}
+
 gymrs_status gymrs_step(gymrs_engine* e, const void* actions_dev)
 {
     if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_step: NULL argument");
     HIP_TRY(hipSetDevice(e->device));
     if (gymrs_status st = prepare_open_sums(e, e->vec)) return st;
-    uint32_t flags = 0;
-    if (gymrs_status st = flags_for_step(e, &flags)) return st;
-    StepArgs a = step_args(e, actions_dev);
-    if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return st;
-    HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
-    e->last_flags = flags;
-    e->last_path = 1;
-    e->tick += 1;
-    if (e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT)) e->trunc_held = (int)a.truncate_all;
-    if (a.truncate_all && (e->flags & GYMRS_AUTO_RESET)) e->uniform_start = e->tick; // all lanes were re-armed
-    e->n_steps_total += (double)e->n;
-    return GYMRS_OK;
+    return step_through_hip(e, actions_dev);
 }
 
 // the buffer checks of the recording rollouts (gymrs_trajectory)
@@ -1019,43 +1023,45 @@ static gymrs_status check_trajectory(const gymrs_engine* e, const gymrs_trajecto
     return GYMRS_OK;
 }
 
+static gymrs_status check_fitness_steps(bool fitness, uint32_t n_steps, const char* who)
+{
+    if (!fitness || n_steps <= kMaxFitnessSteps) return GYMRS_OK;
+    return fail(GYMRS_EINVAL, std::string(who) + ": n_steps is above GYMRS_POLICY_FITNESS_MAX_STEPS (the in-register counters are 32 bits wide)");
+}
+
+// What one fused rollout launches.  The C entry points validate and fill it; rollout_impl validates nothing.
+enum class ActionSource {
+    Random,    // the Philox action stream (action_seed, action_t0): gymrs_rollout, gymrs_rollout_record
+    Policy,    // the engine's policy set (gymrs_set_policy): the closed-loop calls
+    Exploring, // the policy set's epsilon-greedy action under the engine's exploration settings (gymrs_explore.hip)
+};
+struct RolloutRequest {
+    ActionSource actions;
+    uint64_t action_seed = 0, action_t0 = 0;     // Random only
+    bool fitness = false;                        // the kernel adds to the per-policy counters (not with Random)
+    const gymrs_trajectory* record = nullptr;    // checked by check_trajectory
+    const TransitionArgs* transitions = nullptr; // with a record and a policy: the kernel also writes these two buffers (gymrs_transitions.hip)
+};
+// (Lane parameters are not part of it: a launch under an active table always plays them; check_table_opt_in guards the calls.)
+
 // The caller loop of the reference's examples (examples/cartpole.rs:15-30: random action, step, reset on
 // done, accumulate the return) fused into one launch; see rollout_kernel.
-// closed = gymrs_rollout_policy: the actions come from the engine's policy set (gymrs_set_policy) instead of the Philox stream.
-// fitness = gymrs_rollout_policy_fitness: closed, and the kernel adds to the per-policy counters (same checks, same bookkeeping).
-// lane_params = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_LANE_PARAMS: closed (or fitness) under an active parameter table,
-// every lane with its own row (the TableT instantiations of the policy kernels); without a table it changes nothing.
-// explore = gymrs_rollout_closed_loop with GYMRS_CLOSED_LOOP_EXPLORE: closed (or fitness) playing the epsilon-greedy action of the
-// engine's exploration settings (the exploring copies of the policy kernels, gymrs_explore.hip).
-// transitions = gymrs_rollout_transitions: closed with a record, and the kernel also writes these two buffers (gymrs_transitions.hip).
-static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
-                                 const gymrs_trajectory* rec, const char* who, bool closed = false, bool fitness = false, bool lane_params = false,
-                                 bool explore = false, const TransitionArgs* transitions = nullptr)
+static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, const RolloutRequest& q)
 {
-    if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
-    if (fitness && e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (closed && !e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
-    if (closed && e->table_k && !lane_params)
-        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table); policy x table is not built yet: "
-                                                     "use gymrs_policy_actions + gymrs_step");
-    if (fitness && n_steps > kMaxFitnessSteps)
-        return fail(GYMRS_EINVAL, std::string(who) + ": n_steps is above GYMRS_POLICY_FITNESS_MAX_STEPS (the in-register counters are 32 bits wide)");
     if (n_steps == 0) return GYMRS_OK;
     HIP_TRY(hipSetDevice(e->device));
     StepArgs a = step_args(e, nullptr);
     a.skip_trunc_store = 0; // the kernel stores the LAST step's flags, whatever the array holds now
     RolloutArgs r;
     std::memset(&r, 0, sizeof(r));
-    r.action_seed = action_seed;
-    r.action_t0 = action_t0;
+    r.action_seed = q.action_seed;
+    r.action_t0 = q.action_t0;
     r.uniform_start = e->uniform_start;
     r.n_steps = n_steps;
     r.n_actions = e->kind == GYMRS_CARTPOLE ? 2u : 3u;
     r.max_torque = e->max_torque;
     int vec = e->vec == 8 ? 8 : 4;
-    if (rec) {
-        if (gymrs_status st = check_trajectory(e, rec, who)) return st;
+    if (const gymrs_trajectory* rec = q.record) {
         r.rec_obs = rec->obs;
         r.rec_action = rec->actions;
         r.rec_reward = rec->reward;
@@ -1066,62 +1072,90 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, uint64_t act
     }
     if (gymrs_status st = prepare_open_sums(e, vec)) return st;
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
-    if (transitions) { // gymrs_rollout_transitions: one action source, a greedy launch plays threshold 0 (the greedy bits)
+    if (q.fitness)
+        if (gymrs_status st = policy_fitness_table(e)) return st;
+    const bool explore = q.actions == ActionSource::Exploring;
+    if (q.transitions) { // one action source: a greedy launch plays threshold 0 (the greedy bits)
         const ExploreArgs greedy{};
         HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, explore ? e->explore : greedy,
-                                           *transitions, e->stream));
+                                           *q.transitions, e->stream));
     } else if (explore) {
-        if (fitness)
-            if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
         HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->explore,
-                                       fitness ? e->fitness_dev : nullptr, e->stream));
-    } else if (fitness) {
-        if (gymrs_status st = ensure_policy_fitness(e, who)) return st;
+                                       q.fitness ? e->fitness_dev : nullptr, e->stream));
+    } else if (q.fitness) {
         HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
-    } else if (closed)
+    } else if (q.actions == ActionSource::Policy)
         HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->stream));
     else
         HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
     for (uint32_t k = 0; k < n_steps; ++k) { // the host copy of the uniform episode clock (Pendulum time limit)
-        e->tick += 1;
-        if (e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT)) {
-            const bool hit = e->tick - e->uniform_start >= e->max_steps;
+        if (has_uniform_clock(e)) {
+            const bool hit = uniform_clock_hits(e->tick, e->uniform_start, e->max_steps);
             e->trunc_held = hit ? 1 : 0; // the rollout kernel stores the last step's flags
-            if (hit && (e->flags & GYMRS_AUTO_RESET)) e->uniform_start = e->tick;
+            e->uniform_start = uniform_clock_after(e->tick, e->uniform_start, hit, (e->flags & GYMRS_AUTO_RESET) != 0);
         }
+        e->tick += 1;
     }
     e->n_steps_total += (double)e->n * (double)n_steps;
     return GYMRS_OK;
 }
 
+// The rollout calls from before the descriptors.  They have no way to opt in to a parameter table, and a call of 0 steps returns
+// before its buffers are looked at.
+static gymrs_status plain_rollout(gymrs_engine* e, uint32_t n_steps, const RolloutRequest& q, const char* who)
+{
+    if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
+    if (q.actions == ActionSource::Policy) {
+        if (q.fitness)
+            if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+        if (gymrs_status st = check_policy_set(e, who)) return st;
+        if (gymrs_status st = check_table_opt_in(e, false, who, "; policy x table is not built yet: use gymrs_policy_actions + gymrs_step")) return st;
+        if (gymrs_status st = check_fitness_steps(q.fitness, n_steps, who)) return st;
+    }
+    if (q.record && n_steps != 0)
+        if (gymrs_status st = check_trajectory(e, q.record, who)) return st;
+    return rollout_impl(e, n_steps, q);
+}
+
 gymrs_status gymrs_rollout(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0)
 {
-    return rollout_impl(e, n_steps, action_seed, action_t0, nullptr, "gymrs_rollout");
+    return plain_rollout(e, n_steps, {ActionSource::Random, action_seed, action_t0}, "gymrs_rollout");
 }
 
 gymrs_status gymrs_rollout_record(gymrs_engine* e, uint32_t n_steps, uint64_t action_seed, uint64_t action_t0,
                                   const gymrs_trajectory* out)
 {
     if (!out) return fail(GYMRS_EINVAL, "gymrs_rollout_record: trajectory is NULL");
-    return rollout_impl(e, n_steps, action_seed, action_t0, out, "gymrs_rollout_record");
+    return plain_rollout(e, n_steps, {ActionSource::Random, action_seed, action_t0, false, out}, "gymrs_rollout_record");
 }
 
-gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps)
-{
-    return rollout_impl(e, n_steps, 0, 0, nullptr, "gymrs_rollout_policy", true);
-}
+gymrs_status gymrs_rollout_policy(gymrs_engine* e, uint32_t n_steps) { return plain_rollout(e, n_steps, {ActionSource::Policy}, "gymrs_rollout_policy"); }
 
 gymrs_status gymrs_rollout_policy_fitness(gymrs_engine* e, uint32_t n_steps)
 {
-    return rollout_impl(e, n_steps, 0, 0, nullptr, "gymrs_rollout_policy_fitness", true, true);
+    return plain_rollout(e, n_steps, {ActionSource::Policy, 0, 0, true}, "gymrs_rollout_policy_fitness");
 }
 
 gymrs_status gymrs_rollout_policy_record(gymrs_engine* e, uint32_t n_steps, const gymrs_trajectory* out)
 {
     if (!e) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: NULL engine");
     if (!out) return fail(GYMRS_EINVAL, "gymrs_rollout_policy_record: trajectory is NULL");
-    return rollout_impl(e, n_steps, 0, 0, out, "gymrs_rollout_policy_record", true);
+    return plain_rollout(e, n_steps, {ActionSource::Policy, 0, 0, false, out}, "gymrs_rollout_policy_record");
+}
+
+// What the two descriptor calls check alike, in this order, between their NULL checks and their own fields.
+static gymrs_status check_closed_loop_call(const gymrs_engine* e, const char* who)
+{
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    return check_policy_set(e, who);
+}
+static ActionSource closed_loop_actions(uint32_t flags) { return (flags & GYMRS_CLOSED_LOOP_EXPLORE) ? ActionSource::Exploring : ActionSource::Policy; }
+// ... and once their flags word is known to hold known bits only
+static gymrs_status check_explore_flag(const gymrs_engine* e, uint32_t flags, const char* who)
+{
+    if (!(flags & GYMRS_CLOSED_LOOP_EXPLORE) || e->explore_set) return GYMRS_OK;
+    return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
 }
 
 // The closed-loop calls behind one descriptor with a flags word (include/gymrs_amd.h): what gymrs_rollout_policy, _record and
@@ -1131,24 +1165,19 @@ gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_
     const char* who = "gymrs_rollout_closed_loop";
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
     if (!d) return fail(GYMRS_EINVAL, std::string(who) + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_closed_loop_call(e, who)) return st;
     if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
     if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
         return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS, GYMRS_CLOSED_LOOP_LANE_PARAMS and "
                                                      "GYMRS_CLOSED_LOOP_EXPLORE are the only ones)");
-    const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0, lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0,
-               explore = (d->flags & GYMRS_CLOSED_LOOP_EXPLORE) != 0;
-    if (explore && !e->explore_set)
-        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
+    const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0;
+    if (gymrs_status st = check_explore_flag(e, d->flags, who)) return st;
     if (fitness && d->record) return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_FITNESS with a record: there is no recording fitness kernel");
-    if (e->table_k && !lane_params) // (opt-in: a plain descriptor is never played with a table behind the caller's back)
-        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table): set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags "
-                                                     "and every lane steps with its own row");
+    if (gymrs_status st = check_table_opt_in(e, (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0, who, kAdviceLaneParamsFlag)) return st;
     if (d->record)
         if (gymrs_status st = check_trajectory(e, d->record, who)) return st;
-    return rollout_impl(e, d->n_steps, 0, 0, d->record, who, true, fitness, lane_params, explore);
+    if (gymrs_status st = check_fitness_steps(fitness, d->n_steps, who)) return st;
+    return rollout_impl(e, d->n_steps, {closed_loop_actions(d->flags), 0, 0, fitness, d->record});
 }
 
 // gymrs_rollout_closed_loop with a record that also keeps every step's final observations (include/gymrs_amd.h, "transitions").
@@ -1157,9 +1186,7 @@ gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_
     const char* who = "gymrs_rollout_transitions";
     if (!e) return fail(GYMRS_EINVAL, std::string(who) + ": NULL engine");
     if (!d) return fail(GYMRS_EINVAL, std::string(who) + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_closed_loop_call(e, who)) return st;
     if (!(e->flags & GYMRS_AUTO_RESET))
         return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no GYMRS_AUTO_RESET: nothing is re-armed, the record's obs rows already hold "
                                                      "the final observations (gymrs_rollout_closed_loop)");
@@ -1167,18 +1194,14 @@ gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_
     if (d->flags & ~(GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
         return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_LANE_PARAMS and GYMRS_CLOSED_LOOP_EXPLORE are the only "
                                                      "ones; GYMRS_CLOSED_LOOP_FITNESS: there is no recording fitness kernel)");
-    const bool lane_params = (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0, explore = (d->flags & GYMRS_CLOSED_LOOP_EXPLORE) != 0;
-    if (explore && !e->explore_set)
-        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
-    if (e->table_k && !lane_params)
-        return fail(GYMRS_EINVAL, std::string(who) + ": a parameter table is active (gymrs_set_param_table): set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags "
-                                                     "and every lane steps with its own row");
+    if (gymrs_status st = check_explore_flag(e, d->flags, who)) return st;
+    if (gymrs_status st = check_table_opt_in(e, (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0, who, kAdviceLaneParamsFlag)) return st;
     if (gymrs_status st = check_trajectory(e, &d->record, who)) return st;
     if (!d->final_obs) return fail(GYMRS_EINVAL, std::string(who) + ": final_obs is required");
     if ((reinterpret_cast<uintptr_t>(d->final_obs) | reinterpret_cast<uintptr_t>(d->start_obs)) % 16 != 0)
         return fail(GYMRS_EINVAL, std::string(who) + ": final_obs and start_obs must be 16-byte aligned");
     const TransitionArgs t{d->final_obs, d->start_obs};
-    return rollout_impl(e, d->n_steps, 0, 0, &d->record, who, true, false, lane_params, explore, &t);
+    return rollout_impl(e, d->n_steps, {closed_loop_actions(d->flags), 0, 0, false, &d->record, &t});
 }
 
 gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)
@@ -1187,12 +1210,10 @@ gymrs_status gymrs_step_host(gymrs_engine* e, const void* actions_host)
     HIP_TRY(hipSetDevice(e->device));
     const size_t bytes = (size_t)e->n * action_size(e->kind);
     if (e->pool_host) { // small engine: the staging buffer is mapped host memory, the "copy" a memcpy
-        if (!e->action_staging) {
-            void* host = nullptr;
-            HIP_TRY(hipHostMalloc(&host, ((bytes + 63) & ~(size_t)63), hipHostMallocMapped | hipHostMallocCoherent));
-            e->staging_host = static_cast<char*>(host);
-            HIP_TRY(hipHostGetDevicePointer(&e->action_staging, host, 0));
-        }
+        if (!e->action_staging)
+            if (hipError_t err = mapped_host_block((bytes + 63) & ~(size_t)63, &e->staging_host, &e->action_staging))
+                return fail(GYMRS_EHIP, std::string("hipHostMalloc(&host, ((bytes + 63) & ~(size_t)63), hipHostMallocMapped | hipHostMallocCoherent): ") +
+                                            hipGetErrorString(err));
         HIP_TRY(hipStreamSynchronize(e->stream)); // a step still in flight may be reading the buffer
         std::memcpy(e->staging_host, actions_host, bytes);
         return gymrs_step(e, e->action_staging);
@@ -1214,13 +1235,17 @@ static gymrs_status build_graph(gymrs_engine* e, const char* base, uint64_t stri
     hipGraph_t graph = nullptr;
     HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     hipError_t err = hipSuccess;
+    // (a captured launch keeps the engine's own flags, time limit included: what is baked in cannot follow start_bound)
+    const uint32_t flags = launch_flags_of(e);
+    ResetLogRing ring{0, 0, e->vec}; // a replay starts on an empty ring
     for (uint32_t t = 0; t < steps && err == hipSuccess; ++t) {
         StepArgs a = step_args(e, base + (size_t)(t % n_buffers) * stride_bytes);
         a.tick = t;
         a.tick_base = e->tick_dev;
-        // (a captured launch keeps the engine's own flags, time limit included: what is baked in cannot follow start_bound)
-        a.fold_step = (launch_is_logged(e, launch_flags_of(e)) && t % kResetLogRows == kResetLogRows - 1) ? 1u : 0u; // a replay starts on an empty ring
-        err = launch_step(e->kind, e->vec, launch_flags_of(e), a, launch_consts(e), e->stream);
+        const ResetLogStep s = reset_log_step(ring, launch_is_logged(e, flags), t, e->vec);
+        a.fold_step = s.fold_step;
+        ring = s.after;
+        err = launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream);
     }
     if (err == hipSuccess) err = launch_tick_advance(e->tick_dev, steps, e->stream);
     hipError_t end = hipStreamEndCapture(e->stream, &graph);
@@ -1235,7 +1260,7 @@ static gymrs_status build_graph(gymrs_engine* e, const char* base, uint64_t stri
     e->graph_stride = stride_bytes;
     e->graph_nbuf = n_buffers;
     e->graph_steps = steps;
-    e->graph_flags = launch_flags_of(e);
+    e->graph_flags = flags;
     e->graph_vec = e->vec;
     e->graph_seed = e->seed;
     return GYMRS_OK;
@@ -1262,33 +1287,13 @@ extern "C++" std::string aql_kernel_name(const gymrs_engine* e, uint32_t flags, 
     return name;
 }
 
-// Memory hints of a chain's launches (profiles/r03_chain_hints.log; us per step, chain with plain / out / state-loads+out hints):
-// a chain lives off the lines the previous launch left in the L2s -- no write-back between its links -- so the state STORES are
-// never streamed.  What nobody reads again (reward, done, truncated, cos / sin) is: CartPole 2^20 lanes 5.44 -> 5.02, 2^21
-// 13.5 -> 12.3, Pendulum 2^20 4.76 -> 4.10, 2^21 13.4 -> 11.6.  While one step's arrays are small next to the caches the state
-// loads are streamed too (CartPole 2^20: 4.91; at 2^21 it costs 1.3 us).  Far beyond the caches everything streams, as for HIP
-// launches.  (Streaming the ACTION loads alone costs a 2^20-lane CartPole chain a full microsecond.)
-static uint32_t chain_hint_bits(const gymrs_engine* e)
-{
-    if (e->nt_mode == 1) return kFlagNonTemporal;
-    if (e->nt_mode == 2) return 0u;
-    if (e->nt_mode == 3) return kFlagNtOut;
-    const uint64_t per_step = bytes_per_step(e);
-    if (per_step >= (1024ull << 20)) return kFlagNonTemporal; // (round 4: outputs only up to 1 GiB per step, as for HIP launches -- CartPole 2^24
-                                                              // lanes 109 -> 101 us, MountainCar 2^24 50.7 -> 44.7; profiles/r04_hints_by_size.log)
-    return per_step <= (48ull << 20) ? (kFlagNtOut | kFlagNtStateLoads) : kFlagNtOut;
-}
-
 static bool aql_usable(gymrs_engine* e, uint32_t n_steps)
 {
     if (n_steps < kAqlMinChain || e->vec != 4 || e->pool_host) return false;
     if (e->flags & GYMRS_FINAL_OBS) return false; // the chain's code object holds no final-observation kernels: HIP launches
     if (e->table_k) return false;                 // nor any parameter-table kernels
     if (!aql_enabled_by_env()) return false;
-    if (!e->own_stream) { // a caller-provided stream may be under a capture: a chain cannot be captured
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(e->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
-    }
+    if (stream_capturing(e) != 0) return false; // a caller-provided stream may be under a capture: a chain cannot be captured
     if (!e->aql_tried) { // (an engine created under GYMRS_AQL=0 and stepped without it: set up on first use)
         e->aql_tried = true;
         e->aql = aql_create(e->device, &e->aql_why);
@@ -1304,47 +1309,44 @@ static bool aql_usable(gymrs_engine* e, uint32_t n_steps)
 }
 
 extern "C++" {
+// The kernel-argument block of a launch of the chain's code object, filled by hand: it must be exactly what the code object's
+// metadata says the kernel reads (no hidden arguments, no drifted layout).
+template <class Consts>
+static void fill_kern_args(StepKernArgs<Consts>* ka, const StepArgs& a, const Consts& c)
+{
+    std::memset(ka, 0, sizeof(*ka));
+    ka->s0 = a.s[0];
+    ka->s1 = a.s[1];
+    ka->s2 = a.s[2];
+    ka->s3 = a.s[3];
+    ka->action = a.action;
+    ka->n_fast = a.n_fast;
+    ka->rest = a;
+    ka->c = c;
+}
+
 template <class Consts>
 static bool aql_step(gymrs_engine* e, const AqlKernel& k, int threads, const StepArgs& a, const Consts& c, std::string* err, bool release, bool first)
 {
     StepKernArgs<Consts> ka;
-    std::memset(&ka, 0, sizeof(ka));
-    ka.s0 = a.s[0];
-    ka.s1 = a.s[1];
-    ka.s2 = a.s[2];
-    ka.s3 = a.s[3];
-    ka.action = a.action;
-    ka.n_fast = a.n_fast;
-    ka.rest = a;
-    ka.c = c;
+    fill_kern_args(&ka, a, c);
     static_assert(sizeof(ka) <= kAqlKernargSlot, "kernel arguments larger than a ring slot");
-    // the block is filled by hand: it must be exactly what the code object's metadata says the kernel reads (no hidden arguments, no
-    // drifted layout -- a kernel that read beyond sizeof(ka) would find whatever the ring slot held a lap ago)
+    // (a kernel that read beyond sizeof(ka) would find whatever the ring slot held a lap ago)
     if (k.kernarg_bytes != sizeof(ka)) {
         *err = "kernel-argument segment of the chain kernel is " + std::to_string(k.kernarg_bytes) + " bytes, the dispatcher fills " + std::to_string(sizeof(ka));
         return false;
     }
     return aql_dispatch(e->aql, k, step_grid(a.n, 4, threads * kStepTiles) * (uint32_t)threads, (uint32_t)threads, &ka, sizeof(ka), err, release, first);
 }
-} // extern "C++"
 
 // Developer experiment (gymrs_dev_set_hooks bit 3; profiles/r05_visible_through_queue.log part 6): the CHAIN'S binary -- the kernel of the embedded stand-alone
 // code object -- launched through the HIP runtime's own queue (hipModuleLaunchKernel with the hand-filled kernel-argument block).  Same packet header as a
 // HIP launch of the library's own kernel, same queue; only the code object differs.  Tells "the binary" from "the queue" where the two submissions differ.
-extern "C++" {
 template <class Consts>
 static hipError_t module_launch(hipFunction_t f, int threads, const StepArgs& a, const Consts& c, hipStream_t stream)
 {
     StepKernArgs<Consts> ka;
-    std::memset(&ka, 0, sizeof(ka));
-    ka.s0 = a.s[0];
-    ka.s1 = a.s[1];
-    ka.s2 = a.s[2];
-    ka.s3 = a.s[3];
-    ka.action = a.action;
-    ka.n_fast = a.n_fast;
-    ka.rest = a;
-    ka.c = c;
+    fill_kern_args(&ka, a, c);
     size_t bytes = sizeof(ka);
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
     return hipModuleLaunchKernel(f, step_grid(a.n, 4, threads * kStepTiles), 1, 1, (unsigned)threads, 1, 1, 0, stream, nullptr, extra);
@@ -1363,11 +1365,7 @@ static hipError_t launch_step_through_hip_module(gymrs_engine* e, uint32_t flags
     const int threads = step_threads_of(e->kind, e->n, e->vec);
     hipFunction_t f = nullptr;
     if (hipError_t err = hipModuleGetFunction(&f, mod[e->device], aql_kernel_name(e, flags, threads).c_str())) return err;
-    switch (e->kind) {
-    case GYMRS_CARTPOLE: return module_launch(f, threads, a, e->consts.cp, e->stream);
-    case GYMRS_MOUNTAIN_CAR: return module_launch(f, threads, a, e->consts.mc, e->stream);
-    default: return module_launch(f, threads, a, e->consts.pd, e->stream);
-    }
+    return visit_consts(e, [&](const auto& c) { return module_launch(f, threads, a, c, e->stream); });
 }
 
 // steps [first, n_steps) of a gymrs_step_many call as ONE chain.  *taken = false: nothing was dispatched, use HIP launches.
@@ -1410,41 +1408,29 @@ static gymrs_status step_many_aql(gymrs_engine* e, const char* base, uint64_t st
         // The host side of the step first: on an engine that elides its time limit it may have to put something on the stream (a
         // refresh of the bound, a memset, the stand-alone fold) or wait for the device -- each of which closes the open chain
         // (stream_op_barrier).  The step itself then goes into the open chain, or into a new one behind whatever that was.
-        uint32_t flags = 0;
-        if (gymrs_status st = flags_for_step(e, &flags)) return bail(st);
-        if (!visible) flags = (flags & ~kFlagHintMask) | chain_hint_bits(e); // (chain_hint_bits says why a chain has its own)
-        StepArgs a = step_args(e, base + (size_t)(t % n_buffers) * stride_bytes);
-        if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return bail(st);
+        StepLaunch l;
+        if (gymrs_status st = prepare_step(e, base + (size_t)(t % n_buffers) * stride_bytes, /*chain=*/!visible, &l)) return bail(st);
         if (!e->chain_open) { // (the host side of this step closed the chain: the step opens the next one)
             if (!aql_begin(e->aql, e->stream, &err)) return fail(GYMRS_EHIP, "AQL dispatcher: " + err);
             e->chain_open = e->chain_first = true;
         }
-        const uint32_t key = (flags & kFlagHintMask) | (flags & (GYMRS_AUTO_RESET | GYMRS_TRACK_STATS | GYMRS_TIME_LIMIT));
+        const uint32_t key = (l.flags & kFlagHintMask) | (l.flags & (GYMRS_AUTO_RESET | GYMRS_TRACK_STATS | GYMRS_TIME_LIMIT));
         if (key != last_key) {
-            const std::string name = aql_kernel_name(e, flags, threads);
+            const std::string name = aql_kernel_name(e, l.flags, threads);
             if (name.empty() || !aql_kernel(e->aql, name.c_str(), &k)) return bail(fail(GYMRS_EHIP, "AQL dispatcher: no kernel for this launch"));
             last_key = key;
         }
         // every wavefront of a chain launch checks where it runs; the chain's first launch records the table (StepArgs::xcc_table)
+        StepArgs& a = l.args;
         a.xcc_table = aql_xcc_table(e->aql);
         a.xcc_check = (e->chain_first && !poisoned) ? 2u : 1u;
         a.xcc_seq = aql_chain_number(e->aql);
         const bool first_of_chain = e->chain_first; // its packet carries the acquire that follows the hand-over (aql_dispatch)
         e->chain_first = false;
         if (no_xcc_check || visible) a.xcc_check = 0u;
-        bool ok = false;
-        switch (e->kind) {
-        case GYMRS_CARTPOLE: ok = aql_step(e, k, threads, a, e->consts.cp, &err, visible, first_of_chain); break;
-        case GYMRS_MOUNTAIN_CAR: ok = aql_step(e, k, threads, a, e->consts.mc, &err, visible, first_of_chain); break;
-        case GYMRS_PENDULUM: ok = aql_step(e, k, threads, a, e->consts.pd, &err, visible, first_of_chain); break;
-        }
-        if (!ok) return bail(fail(GYMRS_EHIP, "AQL dispatcher: " + err));
-        e->last_flags = flags;
-        e->last_path = 2;
-        e->tick += 1;
-        if (e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT)) e->trunc_held = (int)a.truncate_all;
-        if (a.truncate_all && (e->flags & GYMRS_AUTO_RESET)) e->uniform_start = e->tick;
-        e->aql_launches += 1;
+        if (!visit_consts(e, [&](const auto& c) { return aql_step(e, k, threads, a, c, &err, visible, first_of_chain); }))
+            return bail(fail(GYMRS_EHIP, "AQL dispatcher: " + err));
+        record_step(e, l, 2);
     }
     return stream_op_barrier(e);
 }
@@ -1463,20 +1449,7 @@ gymrs_status gymrs_step_many(gymrs_engine* e, const void* actions_dev, uint64_t 
     const bool graph_ok = use_graph && !(e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT));
     if (use_graph && !graph_ok) return fail(GYMRS_EINVAL, "gymrs_step_many: use_graph is not available for Pendulum with GYMRS_TIME_LIMIT");
     if (graph_ok) {
-        // a graph holds a whole number of passes over the action ring, at least 32 steps, and (reset-logged engines) a whole
-        // number of ring periods, so that a replay both starts and ends on an empty ring
-        uint32_t passes = (32 + n_buffers - 1) / n_buffers;
-        if (launch_is_logged(e, launch_flags_of(e))) {
-            uint32_t g = n_buffers, r = kResetLogRows; // gcd
-            while (r) {
-                const uint32_t tmp = g % r;
-                g = r;
-                r = tmp;
-            }
-            const uint32_t unit = kResetLogRows / g;
-            passes = (passes + unit - 1) / unit * unit;
-        }
-        const uint32_t per_graph = n_buffers * passes;
+        const uint32_t per_graph = graph_steps(n_buffers, launch_is_logged(e, launch_flags_of(e)));
         if (n_steps >= per_graph) {
             const bool hit = e->graph_exec && e->graph_actions == base && e->graph_stride == stride_bytes &&
                              e->graph_nbuf == n_buffers && e->graph_steps == per_graph && e->graph_flags == launch_flags_of(e) &&
@@ -1496,6 +1469,7 @@ gymrs_status gymrs_step_many(gymrs_engine* e, const void* actions_dev, uint64_t 
                 HIP_TRY(hipGraphLaunch(e->graph_exec, e->stream));
                 done += per_graph;
                 e->tick += per_graph;
+                e->n_steps_total += (double)e->n * (double)per_graph;
             }
             if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the replayed launches wrote the flags themselves
         }
@@ -1505,22 +1479,8 @@ gymrs_status gymrs_step_many(gymrs_engine* e, const void* actions_dev, uint64_t 
         if (gymrs_status st = step_many_aql(e, base, stride_bytes, n_buffers, done, n_steps, &taken)) return st;
         if (taken) done = n_steps;
     }
-    for (uint32_t t = done; t < n_steps; ++t) { // eager launches (and the remainder after graph replays)
-        uint32_t flags = 0;
-        if (gymrs_status st = flags_for_step(e, &flags)) return st;
-        StepArgs a = step_args(e, base + (size_t)(t % n_buffers) * stride_bytes);
-        if (gymrs_status st = log_before_step(e, flags, &a.fold_step)) return st;
-        if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS) && !e->table_k) // (developer experiment: the chain's binary through HIP's queue)
-            HIP_TRY(launch_step_through_hip_module(e, flags, a));
-        else
-            HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
-        e->last_flags = flags;
-        e->last_path = 1;
-        e->tick += 1;
-        if (e->kind == GYMRS_PENDULUM && (e->flags & GYMRS_TIME_LIMIT)) e->trunc_held = (int)a.truncate_all;
-        if (a.truncate_all && (e->flags & GYMRS_AUTO_RESET)) e->uniform_start = e->tick;
-    }
-    e->n_steps_total += (double)e->n * (double)n_steps;
+    for (uint32_t t = done; t < n_steps; ++t) // eager launches (and the remainder after graph replays)
+        if (gymrs_status st = step_through_hip(e, base + (size_t)(t % n_buffers) * stride_bytes)) return st;
     return GYMRS_OK;
 }
 

@@ -654,8 +654,7 @@ gymrs_status gymrs_fill_actions(gymrs_engine* e, void* actions_dev, uint64_t see
 gymrs_status gymrs_policy_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats)
 {
     if (!n_floats) return fail(GYMRS_EINVAL, "gymrs_policy_size: n_floats is NULL");
-    if (kind != GYMRS_CARTPOLE && kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, "gymrs_policy_size: policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (gymrs_status st = check_discrete_env(kind, "gymrs_policy_size")) return st;
     if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_policy_size: hidden must be <= 64");
     *n_floats = policy_floats(kind, hidden);
     return GYMRS_OK;
@@ -674,8 +673,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
         if (gymrs_status st = discard_policy_eval(e)) return st;
         return discard_policy_fitness(e);
     }
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, "gymrs_set_policy: policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (gymrs_status st = check_discrete_env(e->kind, "gymrs_set_policy")) return st;
     if (d->hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_set_policy: hidden must be <= 64");
     if (d->n_policies == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: n_policies must be >= 1");
     if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: lanes_per_policy must be >= 1");
@@ -714,7 +712,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
 gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
 {
     if (!e || !d_out) return fail(GYMRS_EINVAL, "gymrs_get_policy: NULL argument");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_get_policy: the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_policy_set(e, "gymrs_get_policy")) return st;
     d_out->hidden = e->policy.hidden;
     d_out->n_policies = e->policy.n_policies;
     d_out->lanes_per_policy = e->policy.lanes_per_policy;
@@ -729,7 +727,7 @@ gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* 
 gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
 {
     if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_weights_ptr: NULL argument");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_policy_weights_ptr: the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_policy_set(e, "gymrs_policy_weights_ptr")) return st;
     *dev_out = e->policy_dev;
     if (n_floats) *n_floats = (uint64_t)e->policy.stride * e->policy.n_policies;
     return GYMRS_OK;
@@ -738,7 +736,7 @@ gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t
 gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev)
 {
     if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: NULL argument");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_policy_set(e, "gymrs_policy_actions")) return st;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_policy_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->policy, e->stream));
     return GYMRS_OK;
@@ -779,7 +777,7 @@ gymrs_status gymrs_get_exploration(gymrs_engine* e, gymrs_exploration* x_out)
 gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev)
 {
     if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_explore_actions: NULL argument");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, "gymrs_explore_actions: the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_policy_set(e, "gymrs_explore_actions")) return st;
     if (!e->explore_set) return fail(GYMRS_EINVAL, "gymrs_explore_actions: the engine has no exploration settings (gymrs_set_exploration)");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_explore_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->tick, e->policy, e->explore, e->stream));
@@ -811,12 +809,9 @@ GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e)
     return GYMRS_OK;
 }
 
-// The checks the four fitness calls share, then the table: n_policies zeroed records at the first use after a gymrs_set_policy.
-GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who)
+// The table: n_policies zeroed records at the first use after a gymrs_set_policy (the caller has checked that there is a policy set).
+GYMRS_HOST_INTERNAL gymrs_status policy_fitness_table(gymrs_engine* e)
 {
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
     if (e->fitness_dev) return GYMRS_OK;
     HIP_TRY(hipSetDevice(e->device));
     const size_t bytes = (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness);
@@ -827,6 +822,14 @@ GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const ch
         HIP_TRY(err);
     }
     return GYMRS_OK;
+}
+
+// The checks the three read-out calls of the table share, then the table.
+static gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who)
+{
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
+    return policy_fitness_table(e);
 }
 } // extern "C++"
 
@@ -876,9 +879,8 @@ GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e)
 // The checks the three calls share, then the table: n_policies identity records at the first use after a gymrs_set_policy.
 static gymrs_status ensure_policy_eval(gymrs_engine* e, const char* who)
 {
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, std::string(who) + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no policy (gymrs_set_policy)");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
     if (e->eval_dev) return GYMRS_OK;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipMalloc(&e->eval_dev, (size_t)e->policy.n_policies * sizeof(gymrs_policy_eval)));
@@ -896,12 +898,11 @@ gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
     const std::string who = "gymrs_evaluate_policy";
     if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
     if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, who + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
-    if (e->table_k && !(d->flags & GYMRS_EVAL_LANE_PARAMS)) // (opt-in: a plain descriptor never plays a table engine with one set of parameters)
-        return fail(GYMRS_EINVAL, who + ": a parameter table is active (gymrs_set_param_table): set GYMRS_EVAL_LANE_PARAMS in flags and every lane "
-                                        "plays with its own row, or use gymrs_policy_actions + gymrs_step");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
+    if (gymrs_status st = check_table_opt_in(e, (d->flags & GYMRS_EVAL_LANE_PARAMS) != 0, who, // (a plain descriptor never plays a table engine with one set of parameters)
+                                             ": set GYMRS_EVAL_LANE_PARAMS in flags and every lane plays with its own row, or use gymrs_policy_actions + gymrs_step"))
+        return st;
     if (d->episodes_per_lane == 0) return fail(GYMRS_EINVAL, who + ": episodes_per_lane must be >= 1");
     if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
     if (d->flags & ~(GYMRS_EVAL_COMMON_STARTS | GYMRS_EVAL_LANE_PARAMS))

@@ -1,7 +1,11 @@
-// gymrs_engine_priv.h -- what the host-side translation units of the C ABI share: the engine object, the error convention and the few
-// helpers more than one of them needs.  gymrs_engine.hip: creation, reset, the stepping paths (HIP launches, graphs, chains), gymrs_sync;
-// gymrs_engine_io.hip: views and copies of the arrays, clone / snapshot, statistics, RCCL, the pub physics fields, the serde JSON view;
-// gymrs_probe.hip: the copy probe (measurement).  Not installed, not part of the ABI.
+// gymrs_engine_priv.h -- what the host-side translation units of the C ABI share: the engine object, the error convention, the refusals
+// more than one entry point words the same way, and the few helpers more than one of them needs.
+//   gymrs_engine.hip     creation, reset, the ONE submission sequence of a per-step launch (prepare_step / record_step, used by gymrs_step,
+//                        gymrs_step_many's eager launches and its chains; graphs bake the same launches in), the fused rollouts, gymrs_sync
+//   gymrs_engine_io.hip  views and copies of the arrays, clone / snapshot, statistics, RCCL, the policy set and its tables, the pub physics
+//                        fields, the serde JSON view
+//   gymrs_step_plan.h    the decisions of the stepping path that need no device (HIP-free, walked by tests/test_step_plan.py)
+// Not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +27,7 @@
 #include "gymrs_aql.h"
 #include "gymrs_json.h"
 #include "gymrs_kernels.h"
+#include "gymrs_step_plan.h"
 
 using namespace gymrs;
 
@@ -199,13 +204,20 @@ GYMRS_HOST_INTERNAL inline gymrs_status check_params(gymrs_env_kind kind, const 
     return GYMRS_OK;
 }
 
-GYMRS_HOST_INTERNAL inline const void* consts_ptr(const gymrs_engine* e)
+// fn(the engine's Consts): the one place that knows which member of `consts` an env kind uses.
+template <class Fn>
+inline auto visit_consts(const gymrs_engine* e, Fn&& fn)
 {
     switch (e->kind) {
-    case GYMRS_CARTPOLE: return &e->consts.cp;
-    case GYMRS_MOUNTAIN_CAR: return &e->consts.mc;
-    default: return &e->consts.pd;
+    case GYMRS_CARTPOLE: return fn(e->consts.cp);
+    case GYMRS_MOUNTAIN_CAR: return fn(e->consts.mc);
+    default: return fn(e->consts.pd);
     }
+}
+
+GYMRS_HOST_INTERNAL inline const void* consts_ptr(const gymrs_engine* e)
+{
+    return visit_consts(e, [](const auto& c) { return static_cast<const void*>(&c); });
 }
 
 // What a step or rollout launch of the engine passes as its constants: the env's Consts, or with a parameter table (the launch
@@ -216,6 +228,26 @@ GYMRS_HOST_INTERNAL inline size_t params_size(gymrs_env_kind k)
 {
     return k == GYMRS_CARTPOLE ? sizeof(gymrs_cartpole_params) : (k == GYMRS_MOUNTAIN_CAR ? sizeof(gymrs_mountain_car_params) : sizeof(gymrs_pendulum_params));
 }
+
+// The refusals the closed-loop entry points share, worded once.  `who` is the entry point's name; each entry point keeps its own
+// ORDER of checks (the tests match on which refusal wins).
+GYMRS_HOST_INTERNAL inline gymrs_status check_discrete_env(gymrs_env_kind kind, const std::string& who)
+{
+    if (kind == GYMRS_CARTPOLE || kind == GYMRS_MOUNTAIN_CAR) return GYMRS_OK;
+    return fail(GYMRS_EINVAL, who + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+}
+GYMRS_HOST_INTERNAL inline gymrs_status check_policy_set(const gymrs_engine* e, const std::string& who)
+{
+    return e->policy_dev ? GYMRS_OK : fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
+}
+// A parameter table is never played behind the caller's back: the call has to opt in.  `advice` = what the entry point tells
+// the caller to do instead, punctuation included.
+GYMRS_HOST_INTERNAL inline gymrs_status check_table_opt_in(const gymrs_engine* e, bool opted_in, const std::string& who, const char* advice)
+{
+    if (!e->table_k || opted_in) return GYMRS_OK;
+    return fail(GYMRS_EINVAL, who + ": a parameter table is active (gymrs_set_param_table)" + advice);
+}
+constexpr const char* kAdviceLaneParamsFlag = ": set GYMRS_CLOSED_LOOP_LANE_PARAMS in flags and every lane steps with its own row";
 
 // Host address of one of the pool's arrays (engines whose pool is mapped host memory).
 template <class T>
@@ -232,6 +264,6 @@ GYMRS_HOST_INTERNAL void limit_restart(gymrs_engine* e, uint64_t bound, bool tru
 GYMRS_HOST_INTERNAL std::string aql_kernel_name(const gymrs_engine* e, uint32_t flags, int threads);
 // defined in gymrs_engine_io.hip (RCCL is resolved there, at first use)
 GYMRS_HOST_INTERNAL void comm_destroy(gymrs_engine* e);
-GYMRS_HOST_INTERNAL gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who); // the fitness calls' checks + the zeroed table
+GYMRS_HOST_INTERNAL gymrs_status policy_fitness_table(gymrs_engine* e); // the per-policy counters: allocated (zeroed) at first use
 GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e);
 GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e);

@@ -10,13 +10,15 @@
 //   gymrs_transitions.hip    the recording closed-loop kernel with per-step final observations (gymrs_rollout_transitions_impl.h)
 //   gymrs_evaluate.hip       episodic policy evaluation (gymrs_evaluate.h, gymrs_evaluate_impl.h)
 //   gymrs_aux.hip            everything off the per-step path: reset, action fill, statistics, folds
-// gymrs_launch.h holds the one launch table (flag sets x lanes per work-item) the step and rollout families dispatch through;
-// gymrs_tile.h the device code they share.
+// gymrs_launch.h holds the one launch table (flag sets x lanes per work-item) the step and rollout families dispatch through, and
+// the internal launch flags; gymrs_step_plan.h the host-side decisions around a step launch that need no device (the engine's
+// alone: no kernel file includes it); gymrs_tile.h the device code the kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
+#include "gymrs_launch.h"
 #include "gymrs_physics.h"
 
 namespace gymrs {
@@ -26,16 +28,6 @@ constexpr int kBlock = GYMRS_EXP_BLOCK;
 #else
 constexpr int kBlock = 256; // work-items per workgroup of the small kernels (reset, fill, statistics) and of the rollout kernel
 #endif
-constexpr uint32_t kFlagNonTemporal = 0x100u; // internal launch flag (not an engine flag): non-temporal loads/stores
-// Hints per class of access, for the launches of a chain (gymrs_aql.h): only the stores nobody reads again (reward, done,
-// truncated, Pendulum's cos / sin), and additionally the state LOADS (the state stores stay plain: the next launch reads them
-// out of the L2).  Measured per size in profiles/r03_chain_hints.log; the engine picks (chain_hint_bits).
-constexpr uint32_t kFlagNtOut = 0x200u;
-constexpr uint32_t kFlagNtStateLoads = 0x400u;
-constexpr uint32_t kFlagHintMask = kFlagNonTemporal | kFlagNtOut | kFlagNtStateLoads;
-// Internal launch flag (not an engine flag, not a hint): the engine holds a parameter table (gymrs_set_param_table), so the
-// launch goes to the table instantiations (TableT, gymrs_table_<env>.hip) with a TableConsts instead of the env's Consts.
-constexpr uint32_t kFlagTable = 0x800u;
 
 // ---- per-lane physics parameters (gymrs_set_param_table) -------------------------------------------------------------------
 // One row of a parameter table on the device: the f32 constants make_consts derives from one gymrs_<kind>_params, without the
@@ -90,11 +82,6 @@ struct TableConsts {
     uint32_t max_steps;     // shared by every row (the time limit)
     uint32_t pad_;
 };
-// Rows of the reset log.  Measured at 2^20 CartPole lanes (128 KiB per row, no folding): a ring of <= 8 rows stays where a
-// write is cheap (6.10 us per launch; 8 steps x 40 MB is about what passes through the 256 MB Infinity Cache before a line
-// is evicted), 16 rows 6.22, >= 32 rows 6.40 (touching the next row one step ahead with a scalar load made it worse:
-// 7.1); the scattered ep_start stores it replaces: 6.65.  Must be a power of two; the folding launch is written for 8.
-constexpr uint32_t kResetLogRows = 8;
 
 // Everything one step() launch needs.  Device pointers are SoA arrays of n lanes.
 struct StepArgs {

@@ -1,7 +1,8 @@
 // gymrs_launch.h -- THE launch table of the kernel library: which (lanes per work-item, flag set) pairs a kernel family is
 // built for, and how a launch's run-time values reach the instantiation built for them.  Every family with a table goes
 // through here: the per-step kernels (gymrs_step_impl.h), the random-policy rollout (gymrs_rollout_impl.h), the closed-loop
-// rollout and its fitness variant (gymrs_rollout_policy_impl.h).
+// rollout and its fitness variant (gymrs_rollout_policy_impl.h).  The internal launch flags and the size of the reset-log ring
+// live here too: the kernels and the engine's HIP-free step plan (gymrs_step_plan.h) both need them.
 //
 // Plain host C++17, no HIP: a function here turns a run-time value into a compile-time constant (a std::integral_constant
 // handed to a generic callable, whose body names the kernel template) or refuses it with the caller's `invalid` result.
@@ -13,6 +14,22 @@
 #include "gymrs_amd.h"
 
 namespace gymrs {
+
+constexpr uint32_t kFlagNonTemporal = 0x100u; // internal launch flag (not an engine flag): non-temporal loads/stores
+// Hints per class of access, for the launches of a chain (gymrs_aql.h): only the stores nobody reads again (reward, done,
+// truncated, Pendulum's cos / sin), and additionally the state LOADS (the state stores stay plain: the next launch reads them
+// out of the L2).  Measured per size in profiles/r03_chain_hints.log; the engine picks (hint_bits, gymrs_step_plan.h).
+constexpr uint32_t kFlagNtOut = 0x200u;
+constexpr uint32_t kFlagNtStateLoads = 0x400u;
+constexpr uint32_t kFlagHintMask = kFlagNonTemporal | kFlagNtOut | kFlagNtStateLoads;
+// Internal launch flag (not an engine flag, not a hint): the engine holds a parameter table (gymrs_set_param_table), so the
+// launch goes to the table instantiations (TableT, gymrs_table_<env>.hip) with a TableConsts instead of the env's Consts.
+constexpr uint32_t kFlagTable = 0x800u;
+// Rows of the reset log.  Measured at 2^20 CartPole lanes (128 KiB per row, no folding): a ring of <= 8 rows stays where a
+// write is cheap (6.10 us per launch; 8 steps x 40 MB is about what passes through the 256 MB Infinity Cache before a line
+// is evicted), 16 rows 6.22, >= 32 rows 6.40 (touching the next row one step ahead with a scalar load made it worse:
+// 7.1); the scattered ep_start stores it replaces: 6.65.  Must be a power of two; the folding launch is written for 8.
+constexpr uint32_t kResetLogRows = 8;
 
 template <uint32_t V>
 using FlagSet = std::integral_constant<uint32_t, V>;

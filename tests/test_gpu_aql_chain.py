@@ -192,6 +192,58 @@ def test_chains_interleaved_with_hip_launches_statistics_and_copies(gymrs, twin)
         eng.close()
 
 
+@pytest.mark.parametrize("n,auto_reset", [(1000, True), (64, False)])
+def test_pendulum_episode_clock_crosses_every_submission_path(gymrs, twin, n, auto_reset):
+    """Pendulum's uniform episode clock is host bookkeeping every submission path shares: gymrs_step -> eager gymrs_step_many -> a
+    chain -> the fused rollout -> gymrs_step -> eager again, with a limit of 7 steps reached in mid-call and at the end of a call.  1000 lanes: ragged,
+    under one workgroup row; 64 lanes without auto-reset: the mapped host pool (its gymrs_step_many stays with HIP launches), and a
+    clock that never restarts."""
+    flags = gymrs.TIME_LIMIT | ((gymrs.AUTO_RESET | gymrs.TRACK_STATS) if auto_reset else 0)
+    p = gymrs.engine.default_params(2)
+    p.max_episode_steps = 7
+    nbuf, seed = 4, 5
+    eng = gymrs.BatchedEngine(2, n, flags=flags, params=p)
+    tw = TwinEngine(twin, 2, n, p, flags=flags)
+    eng.reset(seed=3)
+    tw.reset(3)
+    ring = ring_for(eng, 2, n, nbuf, seed=seed)
+    bufs = [tw.fill_actions(seed, b) for b in range(nbuf)]
+    stride = ring.stride(0) * ring.element_size()
+    truncations = []
+
+    def check(twin_actions):
+        for a in twin_actions:
+            tw.step(a)
+        want, got = tw.get_result(), eng.get_step_result()
+        assert same(eng.get_state(), tw.get_state())
+        assert same(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
+        assert len(np.unique(got[2])) == 1  # the clock is uniform
+        truncations.append(int(got[2][0]))
+
+    eng.step(ring[0].data_ptr())
+    check(bufs[:1])
+    with aql(False):
+        eng.step_many(ring.data_ptr(), stride, nbuf, 3)
+    check([bufs[t % nbuf] for t in range(3)])
+    with aql(True):
+        eng.step_many(ring.data_ptr(), stride, nbuf, 9)
+    check([bufs[t % nbuf] for t in range(9)])
+    eng.rollout(5, action_seed=seed, action_t0=2)
+    check([tw.fill_actions(seed, 2 + k) for k in range(5)])
+    eng.step(ring[1].data_ptr())
+    check(bufs[1:2])
+    with aql(False):
+        eng.step_many(ring.data_ptr(), stride, nbuf, 2)  # (to the third limit: the last step of the call is the 21st)
+    check(bufs[:2])
+    # the calls end after 1, 4, 13, 18, 19 and 21 steps; with auto-reset steps 7, 14 and 21 truncate and restart the clock, without
+    # it every step from the seventh on truncates
+    assert truncations == ([0, 0, 0, 0, 0, 1] if auto_reset else [0, 0, 1, 1, 1, 1])
+    assert extras(eng)["aql_launches"] == (9 if n > 64 else 0)
+    assert eng.stats()[3] == 21 * n
+    assert eng.tick()[0] == 1 + 21  # (the reset took tick 0)
+    eng.close()
+
+
 def test_short_calls_graphs_small_engines_and_other_launch_shapes_keep_to_hip_launches(gymrs):
     n = 5000
     with aql(True):
