@@ -312,6 +312,67 @@ impl Engine {
         check(ffi::gymrs_explore_actions(self.raw, actions_dev));
     }
 
+    /// Install the sampling settings (`gymrs_set_sampling`): a ~ softmax(logits / temperature) with `scale` = log2(e) / temperature
+    /// (finite, >= 0; 0 is the uniform policy), drawn from a Philox stream keyed (`seed`, global lane id, engine tick).  `None`
+    /// removes them.  Launches play them only through `rollout_closed_loop_sample`, `rollout_closed_loop_sample_record`,
+    /// `rollout_transitions_sample` and `sample_actions`; every other call stays greedy.
+    pub fn set_sampling(&mut self, settings: Option<(u64, f32)>) {
+        match settings {
+            Some((seed, scale)) => {
+                let x = ffi::GymrsSampling { seed, scale, reserved: 0 };
+                check(unsafe { ffi::gymrs_set_sampling(self.raw, &x) });
+            }
+            None => check(unsafe { ffi::gymrs_set_sampling(self.raw, std::ptr::null()) }),
+        }
+    }
+
+    /// `(seed, scale)` as set (`gymrs_get_sampling`); panics when the engine has no sampling settings.
+    pub fn sampling(&mut self) -> (u64, f32) {
+        let mut x = ffi::GymrsSampling { seed: 0, scale: 0.0, reserved: 0 };
+        check(unsafe { ffi::gymrs_get_sampling(self.raw, &mut x) });
+        (x.seed, x.scale)
+    }
+
+    /// `rollout_closed_loop` with `GYMRS_CLOSED_LOOP_SAMPLE`: every step plays the action drawn under `set_sampling`.
+    pub fn rollout_closed_loop_sample(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_SAMPLE
+            | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 }
+            | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_rollout_closed_loop(self.raw, &d) });
+    }
+
+    /// `rollout_closed_loop_record` with `GYMRS_CLOSED_LOOP_SAMPLE`: the `actions` rows hold the action taken; its probability is
+    /// recomputed from the `obs` rows with the weights the learner holds (`sample_draw` is the rule as code).
+    ///
+    /// # Safety
+    /// As `rollout_record`.
+    pub unsafe fn rollout_closed_loop_sample_record(&mut self, n_steps: u32, lane_params: bool, out: &ffi::Trajectory) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_SAMPLE | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: out, reserved: 0 };
+        check(ffi::gymrs_rollout_closed_loop(self.raw, &d));
+    }
+
+    /// `rollout_transitions` with `GYMRS_CLOSED_LOOP_SAMPLE`.
+    ///
+    /// # Safety
+    /// As `rollout_transitions`.
+    pub unsafe fn rollout_transitions_sample(&mut self, n_steps: u32, lane_params: bool, out: &ffi::Trajectory, final_obs: *mut f32, start_obs: *mut f32) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_SAMPLE | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 };
+        let d = ffi::GymrsTransitionsDesc { n_steps, flags, record: *out, final_obs, start_obs, reserved: 0 };
+        check(ffi::gymrs_rollout_transitions(self.raw, &d));
+    }
+
+    /// The sampled action at the engine's current tick, one u8 per lane, and (unless null) the probability of that action, one f32
+    /// per lane (`gymrs_sample_actions`): `sample_actions` + `step_device`, K times, is `rollout_closed_loop_sample(K, ..)`.
+    ///
+    /// # Safety
+    /// `actions_dev` must be a device address of at least `len()` bytes, `prob_dev` null or one of `len()` floats; both stay valid
+    /// until `sync()`.
+    pub unsafe fn sample_actions(&mut self, actions_dev: *mut c_void, prob_dev: *mut f32) {
+        check(ffi::gymrs_sample_actions(self.raw, actions_dev, prob_dev));
+    }
+
     /// The records of policies `first..first+count` (synchronising).
     pub fn policy_fitness(&mut self, first: u32, count: u32) -> Vec<ffi::GymrsPolicyFitness> {
         let mut out = vec![ffi::GymrsPolicyFitness::default(); count as usize];
@@ -416,6 +477,16 @@ pub fn explore_draw(seed: u64, threshold: u32, n_actions: u32, global_id: u64, t
     let (mut explored, mut action) = (0u8, 0u8);
     check(unsafe { ffi::gymrs_explore_draw(&x, n_actions, global_id, tick, &mut explored, &mut action) });
     (explored != 0, action)
+}
+
+/// `(action, probabilities)` of the softmax draw that takes the lane with global id `global_id` from engine tick `tick` to
+/// `tick + 1` under `(seed, scale)` from 2..=8 `logits` (`gymrs_sample_draw`; host only, no GPU).
+pub fn sample_draw(seed: u64, scale: f32, logits: &[f32], global_id: u64, tick: u64) -> (u8, Vec<f32>) {
+    let x = ffi::GymrsSampling { seed, scale, reserved: 0 };
+    let mut action = 0u8;
+    let mut probs = vec![0.0f32; logits.len()];
+    check(unsafe { ffi::gymrs_sample_draw(&x, logits.len() as u32, logits.as_ptr(), global_id, tick, &mut action, probs.as_mut_ptr()) });
+    (action, probs)
 }
 
 impl Clone for Engine {

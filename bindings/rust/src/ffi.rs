@@ -96,6 +96,19 @@ pub const GYMRS_CLOSED_LOOP_LANE_PARAMS: u32 = 4;
 /// `GYMRS_CLOSED_LOOP_EXPLORE`: every step plays the epsilon-greedy action of the engine's exploration settings (`gymrs_set_exploration`).
 pub const GYMRS_CLOSED_LOOP_EXPLORE: u32 = 16;
 
+/// `GYMRS_CLOSED_LOOP_SAMPLE`: every step plays an action drawn from the softmax of the policy's logits (`gymrs_set_sampling`).
+pub const GYMRS_CLOSED_LOOP_SAMPLE: u32 = 32;
+
+/// `gymrs_sampling`: the sampling settings of an engine (include/gymrs_amd.h "sampling"), 16 bytes.  `scale` = log2(e) / temperature,
+/// finite and >= 0; the draw is keyed (seed, global lane id, engine tick) on Philox stream 3.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct GymrsSampling {
+    pub seed: u64,
+    pub scale: f32,
+    pub reserved: u32,
+}
+
 /// `gymrs_exploration`: the exploration settings of an engine (include/gymrs_amd.h "exploration"), 16 bytes.  A step explores when the low
 /// half of its Philox word, keyed (seed, global lane id, engine tick), is below `threshold` (0..=65536: epsilon = threshold / 65536).
 #[repr(C)]
@@ -258,6 +271,18 @@ extern "C" {
         explored: *mut u8,
         random_action: *mut u8,
     ) -> c_int;
+    pub fn gymrs_set_sampling(e: *mut GymrsEngine, x: *const GymrsSampling) -> c_int;
+    pub fn gymrs_get_sampling(e: *mut GymrsEngine, x_out: *mut GymrsSampling) -> c_int;
+    pub fn gymrs_sample_actions(e: *mut GymrsEngine, actions_dev: *mut c_void, prob_dev: *mut f32) -> c_int;
+    pub fn gymrs_sample_draw(
+        x: *const GymrsSampling,
+        n_actions: u32,
+        logits: *const f32,
+        global_id: u64,
+        tick: u64,
+        action: *mut u8,
+        probs: *mut f32,
+    ) -> c_int;
     pub fn gymrs_evaluate_policy(e: *mut GymrsEngine, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_get_policy_eval(e: *mut GymrsEngine, first: u32, count: u32, host_out: *mut GymrsPolicyEval) -> c_int;
     pub fn gymrs_policy_eval_ptr(e: *mut GymrsEngine, dev_out: *mut *mut GymrsPolicyEval, n_policies: *mut u32) -> c_int;
@@ -304,6 +329,7 @@ extern "C" {
     pub fn gymrs_sharded_policy_fitness_clear(h: *mut GymrsSharded) -> c_int;
     pub fn gymrs_sharded_rollout_closed_loop(h: *mut GymrsSharded, d: *const GymrsClosedLoopDesc) -> c_int;
     pub fn gymrs_sharded_set_exploration(h: *mut GymrsSharded, x: *const GymrsExploration) -> c_int;
+    pub fn gymrs_sharded_set_sampling(h: *mut GymrsSharded, x: *const GymrsSampling) -> c_int;
     pub fn gymrs_sharded_evaluate_policy(h: *mut GymrsSharded, d: *const GymrsEvalDesc) -> c_int;
     pub fn gymrs_sharded_set_param_table(h: *mut GymrsSharded, rows: *const c_void, k: u32) -> c_int;
     pub fn gymrs_sharded_get_param_table(h: *mut GymrsSharded, rows_out: *mut c_void, capacity: u32, k: *mut u32) -> c_int;

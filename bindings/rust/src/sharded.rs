@@ -145,6 +145,26 @@ impl ShardedEngine {
         }
     }
 
+    /// `Engine::set_sampling` on every block (`gymrs_sharded_set_sampling`): the same settings everywhere, keyed by global lane ids.
+    pub fn set_sampling(&mut self, settings: Option<(u64, f32)>) {
+        match settings {
+            Some((seed, scale)) => {
+                let x = ffi::GymrsSampling { seed, scale, reserved: 0 };
+                check(unsafe { ffi::gymrs_sharded_set_sampling(self.raw, &x) });
+            }
+            None => check(unsafe { ffi::gymrs_sharded_set_sampling(self.raw, std::ptr::null()) }),
+        }
+    }
+
+    /// `rollout_closed_loop` with `GYMRS_CLOSED_LOOP_SAMPLE` on every block: k blocks equal one engine.
+    pub fn rollout_closed_loop_sample(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
+        let flags = ffi::GYMRS_CLOSED_LOOP_SAMPLE
+            | if lane_params { ffi::GYMRS_CLOSED_LOOP_LANE_PARAMS } else { 0 }
+            | if fitness { ffi::GYMRS_CLOSED_LOOP_FITNESS } else { 0 };
+        let d = ffi::GymrsClosedLoopDesc { n_steps, flags, record: std::ptr::null(), reserved: 0 };
+        check(unsafe { ffi::gymrs_sharded_rollout_closed_loop(self.raw, &d) });
+    }
+
     /// `rollout_closed_loop` with `GYMRS_CLOSED_LOOP_EXPLORE` on every block: k blocks equal one engine.
     pub fn rollout_closed_loop_explore(&mut self, n_steps: u32, lane_params: bool, fitness: bool) {
         let flags = ffi::GYMRS_CLOSED_LOOP_EXPLORE

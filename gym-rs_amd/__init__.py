@@ -47,6 +47,7 @@ from .engine import params_from_json, policy_size, PolicyFitness, PolicyEval, Ev
 from .engine import ClosedLoopDesc, CLOSED_LOOP_FITNESS, CLOSED_LOOP_LANE_PARAMS
 from .engine import TransitionsDesc
 from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
+from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -56,5 +57,5 @@ __all__ = [
     "library_path", "load_library", "shard_range", "ShardedEngine", "sharded", "params_from_json", "policy_size",
     "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
     "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS", "TransitionsDesc",
-    "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw",
+    "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw", "Sampling", "CLOSED_LOOP_SAMPLE", "sample_draw",
 ]

@@ -89,6 +89,11 @@ SIGNATURES = {
     "gymrs_get_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_explore_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_explore_draw": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    # softmax sampling (gymrs_sampling 16 B: {u64 seed, f32 scale, u32 reserved})
+    "gymrs_set_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_get_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_sample_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gymrs_sample_draw": (C.c_int, [C.c_void_p, C.c_uint32, f32p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8), f32p]),
     # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -113,6 +118,7 @@ SIGNATURES = {
     "gymrs_sharded_policy_fitness_clear": (C.c_int, [C.c_void_p]),
     "gymrs_sharded_rollout_closed_loop": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_set_exploration": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_sharded_set_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sharded_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     # per-lane physics on a sharded batch (the index in batch lane numbering)

@@ -1034,6 +1034,7 @@ enum class ActionSource {
     Random,    // the Philox action stream (action_seed, action_t0): gymrs_rollout, gymrs_rollout_record
     Policy,    // the engine's policy set (gymrs_set_policy): the closed-loop calls
     Exploring, // the policy set's epsilon-greedy action under the engine's exploration settings (gymrs_explore.hip)
+    Sampling,  // an action drawn from the softmax of the policy's logits under the engine's sampling settings (gymrs_sample.hip)
 };
 struct RolloutRequest {
     ActionSource actions;
@@ -1075,7 +1076,10 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, const Rollou
     if (q.fitness)
         if (gymrs_status st = policy_fitness_table(e)) return st;
     const bool explore = q.actions == ActionSource::Exploring;
-    if (q.transitions) { // one action source: a greedy launch plays threshold 0 (the greedy bits)
+    if (q.actions == ActionSource::Sampling) {
+        HIP_TRY(launch_rollout_sample(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->sample,
+                                      q.fitness ? e->fitness_dev : nullptr, q.transitions, e->stream));
+    } else if (q.transitions) { // one action source: a greedy launch plays threshold 0 (the greedy bits)
         const ExploreArgs greedy{};
         HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, explore ? e->explore : greedy,
                                            *q.transitions, e->stream));
@@ -1150,10 +1154,18 @@ static gymrs_status check_closed_loop_call(const gymrs_engine* e, const char* wh
     if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
     return check_policy_set(e, who);
 }
-static ActionSource closed_loop_actions(uint32_t flags) { return (flags & GYMRS_CLOSED_LOOP_EXPLORE) ? ActionSource::Exploring : ActionSource::Policy; }
+static ActionSource closed_loop_actions(uint32_t flags)
+{
+    if (flags & GYMRS_CLOSED_LOOP_SAMPLE) return ActionSource::Sampling;
+    return (flags & GYMRS_CLOSED_LOOP_EXPLORE) ? ActionSource::Exploring : ActionSource::Policy;
+}
 // ... and once their flags word is known to hold known bits only
 static gymrs_status check_explore_flag(const gymrs_engine* e, uint32_t flags, const char* who)
 {
+    if ((flags & GYMRS_CLOSED_LOOP_SAMPLE) && (flags & GYMRS_CLOSED_LOOP_EXPLORE))
+        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_SAMPLE together with GYMRS_CLOSED_LOOP_EXPLORE: a launch has one action source");
+    if ((flags & GYMRS_CLOSED_LOOP_SAMPLE) && !e->sample_set)
+        return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_SAMPLE without sampling settings on the engine (gymrs_set_sampling)");
     if (!(flags & GYMRS_CLOSED_LOOP_EXPLORE) || e->explore_set) return GYMRS_OK;
     return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_EXPLORE without exploration settings on the engine (gymrs_set_exploration)");
 }
@@ -1167,9 +1179,9 @@ gymrs_status gymrs_rollout_closed_loop(gymrs_engine* e, const gymrs_closed_loop_
     if (!d) return fail(GYMRS_EINVAL, std::string(who) + ": NULL desc");
     if (gymrs_status st = check_closed_loop_call(e, who)) return st;
     if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
-    if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
-        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS, GYMRS_CLOSED_LOOP_LANE_PARAMS and "
-                                                     "GYMRS_CLOSED_LOOP_EXPLORE are the only ones)");
+    if (d->flags & ~(GYMRS_CLOSED_LOOP_FITNESS | GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE | GYMRS_CLOSED_LOOP_SAMPLE))
+        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_FITNESS, GYMRS_CLOSED_LOOP_LANE_PARAMS, "
+                                                     "GYMRS_CLOSED_LOOP_EXPLORE and GYMRS_CLOSED_LOOP_SAMPLE are the only ones)");
     const bool fitness = (d->flags & GYMRS_CLOSED_LOOP_FITNESS) != 0;
     if (gymrs_status st = check_explore_flag(e, d->flags, who)) return st;
     if (fitness && d->record) return fail(GYMRS_EINVAL, std::string(who) + ": GYMRS_CLOSED_LOOP_FITNESS with a record: there is no recording fitness kernel");
@@ -1191,9 +1203,10 @@ gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_
         return fail(GYMRS_EINVAL, std::string(who) + ": the engine has no GYMRS_AUTO_RESET: nothing is re-armed, the record's obs rows already hold "
                                                      "the final observations (gymrs_rollout_closed_loop)");
     if (d->reserved != 0) return fail(GYMRS_EINVAL, std::string(who) + ": reserved must be 0");
-    if (d->flags & ~(GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE))
-        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_LANE_PARAMS and GYMRS_CLOSED_LOOP_EXPLORE are the only "
-                                                     "ones; GYMRS_CLOSED_LOOP_FITNESS: there is no recording fitness kernel)");
+    if (d->flags & ~(GYMRS_CLOSED_LOOP_LANE_PARAMS | GYMRS_CLOSED_LOOP_EXPLORE | GYMRS_CLOSED_LOOP_SAMPLE))
+        return fail(GYMRS_EINVAL, std::string(who) + ": unknown flag bits (GYMRS_CLOSED_LOOP_LANE_PARAMS, GYMRS_CLOSED_LOOP_EXPLORE and "
+                                                     "GYMRS_CLOSED_LOOP_SAMPLE are the only ones; GYMRS_CLOSED_LOOP_FITNESS: there is no recording "
+                                                     "fitness kernel)");
     if (gymrs_status st = check_explore_flag(e, d->flags, who)) return st;
     if (gymrs_status st = check_table_opt_in(e, (d->flags & GYMRS_CLOSED_LOOP_LANE_PARAMS) != 0, who, kAdviceLaneParamsFlag)) return st;
     if (gymrs_status st = check_trajectory(e, &d->record, who)) return st;

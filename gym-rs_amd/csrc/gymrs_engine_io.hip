@@ -3,6 +3,7 @@
 // construction, the #[derive(Serialize)] JSON view.  The engine object and the stepping paths: gymrs_engine_priv.h, gymrs_engine.hip.
 #include "gymrs_engine_priv.h"
 #include "gymrs_evaluate.h"
+#include "gymrs_sample.h"
 
 static RcclApi g_rccl;
 
@@ -793,6 +794,62 @@ gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, 
     const uint32_t w = explore_word(x->seed, global_id, tick);
     if (explored) *explored = explore_decides(w, x->threshold) ? 1 : 0;
     if (random_action) *random_action = explore_random(w, n_actions);
+    return GYMRS_OK;
+}
+
+// ---- softmax sampling: the settings, the per-step call and the host-side draw (include/gymrs_amd.h, "sampling") ------------------
+static gymrs_status check_sampling(const gymrs_sampling* x, const std::string& who)
+{
+    if (!(x->scale >= 0.0f) || x->scale > 3.402823466e+38f)
+        return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0 (scale = log2(e) / temperature; 0 is the uniform policy)");
+    if (x->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_set_sampling(gymrs_engine* e, const gymrs_sampling* x)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_sampling: NULL engine");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, "gymrs_set_sampling: sampling is for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
+    if (!x) { // (launches already enqueued carry their own copy of the settings)
+        e->sample = SampleArgs{};
+        e->sample_set = false;
+        return GYMRS_OK;
+    }
+    if (gymrs_status st = check_sampling(x, "gymrs_set_sampling")) return st;
+    e->sample = SampleArgs{x->seed, x->scale, 0};
+    e->sample_set = true;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_sampling(gymrs_engine* e, gymrs_sampling* x_out)
+{
+    if (!e || !x_out) return fail(GYMRS_EINVAL, "gymrs_get_sampling: NULL argument");
+    if (!e->sample_set) return fail(GYMRS_EINVAL, "gymrs_get_sampling: the engine has no sampling settings (gymrs_set_sampling)");
+    *x_out = gymrs_sampling{e->sample.seed, e->sample.scale, 0};
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_sample_actions(gymrs_engine* e, void* actions_dev, float* prob_dev)
+{
+    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_sample_actions: NULL argument");
+    if (gymrs_status st = check_policy_set(e, "gymrs_sample_actions")) return st;
+    if (!e->sample_set) return fail(GYMRS_EINVAL, "gymrs_sample_actions: the engine has no sampling settings (gymrs_set_sampling)");
+    if (reinterpret_cast<uintptr_t>(prob_dev) % sizeof(float) != 0) return fail(GYMRS_EINVAL, "gymrs_sample_actions: prob_dev must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_sample_actions(e->kind, e->s, actions_dev, prob_dev, e->n, e->gid0, e->tick, e->policy, e->sample, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_sample_draw(const gymrs_sampling* x, uint32_t n_actions, const float* logits, uint64_t global_id, uint64_t tick, uint8_t* action,
+                               float* probs)
+{
+    if (!x) return fail(GYMRS_EINVAL, "gymrs_sample_draw: NULL settings");
+    if (gymrs_status st = check_sampling(x, "gymrs_sample_draw")) return st;
+    if (n_actions < 2 || n_actions > kMaxSampleActions) return fail(GYMRS_EINVAL, "gymrs_sample_draw: n_actions must be in 2 .. 8");
+    if (!logits) return fail(GYMRS_EINVAL, "gymrs_sample_draw: NULL logits");
+    const uint32_t a = sample_action(logits, n_actions, x->scale, sample_word(x->seed, global_id, tick), probs);
+    if (action) *action = (uint8_t)a;
     return GYMRS_OK;
 }
 

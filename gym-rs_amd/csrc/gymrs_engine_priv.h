@@ -189,6 +189,9 @@ struct gymrs_engine {
     // stream order.  gymrs_set_policy keeps them.  Not part of clone or snapshot.
     ExploreArgs explore{};
     bool explore_set = false;
+    // The sampling settings (gymrs_set_sampling), under the same rules.
+    SampleArgs sample{};
+    bool sample_set = false;
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };

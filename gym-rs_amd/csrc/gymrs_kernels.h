@@ -7,6 +7,7 @@
 //   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h)
 //   gymrs_rollout_fitness.hip  that rollout with per-policy fitness counters
 //   gymrs_explore.hip        the closed-loop kernels once more with the epsilon-greedy action source (gymrs_rollout_explore_impl.h)
+//   gymrs_sample.hip         the closed-loop and transitions kernels with the softmax sampling source (gymrs_rollout_sample_impl.h)
 //   gymrs_transitions.hip    the recording closed-loop kernel with per-step final observations (gymrs_rollout_transitions_impl.h)
 //   gymrs_evaluate.hip       episodic policy evaluation (gymrs_evaluate.h, gymrs_evaluate_impl.h)
 //   gymrs_aux.hip            everything off the per-step path: reset, action fill, statistics, folds
@@ -311,6 +312,13 @@ struct ExploreArgs {
     uint32_t threshold; // 0 .. 65536: a step explores when the low half of its word is below it
     uint32_t pad_;
 };
+// The sampling settings of an engine (gymrs_set_sampling) as the sampling kernels get them by value, in ExploreArgs' place
+// (gymrs_sample.hip): the draw is keyed (seed, global id, engine tick) on stream 3 of gymrs_philox.h.
+struct SampleArgs {
+    uint64_t seed;
+    float scale; // log2(e) / temperature: finite, >= 0
+    uint32_t pad_;
+};
 // S: floats of one policy; 0 for an env kind that takes none (Pendulum: a Box action)
 inline uint64_t policy_floats(gymrs_env_kind kind, uint32_t hidden)
 {
@@ -348,4 +356,11 @@ struct TransitionArgs {
 // only; x.threshold == 0 is the greedy launch.
 hipError_t launch_rollout_transitions(gymrs_env_kind kind, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                       const PolicyArgs& p, const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream);
+// ---- softmax sampling (gymrs_set_sampling; gymrs_sample.hip, gymrs_sample_fitness.hip, gymrs_table_sample_<env>.hip) ----------
+// launch_policy_actions with the sampled action of engine tick `tick`; prob (may be NULL) gets the probability of every lane's action
+hipError_t launch_sample_actions(gymrs_env_kind kind, const float* const* s, void* actions, float* prob, uint64_t n, uint64_t gid0, uint64_t tick,
+                                 const PolicyArgs& p, const SampleArgs& x, hipStream_t stream);
+// launch_rollout_explore playing the sampled action of every step; t != NULL: launch_rollout_transitions (a record, no fitness)
+hipError_t launch_rollout_sample(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
+                                 const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t, hipStream_t stream);
 } // namespace gymrs

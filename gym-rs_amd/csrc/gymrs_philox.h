@@ -11,7 +11,8 @@
 // Counter layout (same in oracle/gymrs_oracle.c, which restates it independently):
 //   key     = (seed lo, seed hi)
 //   counter = (gid lo, gid hi, tick lo, (tick hi & 0xffff) | stream << 16)
-//   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests), stream 2 = epsilon-greedy exploration
+//   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests), stream 2 = epsilon-greedy exploration,
+//   stream 3 = softmax action sampling
 #pragma once
 #include "gymrs_math.h"
 
@@ -92,6 +93,12 @@ GYMRS_HD u32x4 explore_block(uint64_t seed, uint64_t gid, uint64_t tick) { retur
 GYMRS_HD uint32_t explore_word(uint64_t seed, uint64_t gid, uint64_t tick) { return pick_word(explore_block(seed, gid, tick), (uint32_t)gid & 3u); }
 GYMRS_HD bool explore_decides(uint32_t word, uint32_t threshold) { return (word & 0xffffu) < threshold; }
 GYMRS_HD uint8_t explore_random(uint32_t word, uint32_t n_actions) { return (uint8_t)(((word >> 16) * n_actions) >> 16); }
+
+// Softmax action sampling (stream 3; include/gymrs_amd.h, "sampling"): the counter layout of the exploration stream -- the step that
+// takes lane gid from engine tick t to t + 1 reads word (gid & 3) of block (gid >> 2, t).  What the word selects is in gymrs_sample.h.
+constexpr uint32_t kStreamSample = 3;
+GYMRS_HD u32x4 sample_block(uint64_t seed, uint64_t gid, uint64_t tick) { return draw4(seed, gid >> 2, tick, kStreamSample); }
+GYMRS_HD uint32_t sample_word(uint64_t seed, uint64_t gid, uint64_t tick) { return pick_word(sample_block(seed, gid, tick), (uint32_t)gid & 3u); }
 
 // u32 -> uniform f32 on [low, high): 24 random bits, u * scale + low, kept below `high` (half-open like
 // rand's Uniform::new, cartpole.rs:363).  Everything that does not depend on the random word is prepared

@@ -13,7 +13,10 @@
 //   * lanes of one wave use different policies (e.g. lanes_per_policy = 1): every lane gathers its own weights through the
 //     vector memory path from the table, which a population of small policies keeps in the L2.
 // Both give the same bits: the same operations on the same values.
+// Three action sources for rollout_block use it: PolicyActions (the argmax), ExploringActions (epsilon-greedy) and SamplingActions
+// (softmax sampling, gymrs_sample.h).
 #pragma once
+#include "gymrs_sample.h"
 #include "gymrs_tile.h"
 
 namespace gymrs {
@@ -68,6 +71,51 @@ struct PolicyWeights<VEC, false> {
     }
     __device__ __forceinline__ float operator()(int k, uint32_t i) const { return base[(uint64_t)pol[k] * stride + i]; }
 };
+
+// The logits y[a][k] of the VEC lanes of a work-item from their observations x[j].v[k] (D rows in gymrs_obs_ptrs order).  The
+// hidden layer is consumed unit by unit: A accumulators and one temporary per lane, whatever H is; its loop stays rolled (four
+// units per trip), so H = 64 costs no more code than H = 4.
+// policy_eval below keeps its own copy of this arithmetic: routed through policy_logits, 240 of the 480 existing closed-loop and
+// evaluation kernels came out with different machine code (profiles/policy_sample.md), and those kernels keep their code.
+template <class Env, int VEC, bool UNI>
+__device__ __forceinline__ void policy_logits(const PolicyWeights<VEC, UNI>& W, uint32_t H, const Vec<float, VEC> (&x)[Env::kState],
+                                              float (&y)[Env::kActions][VEC])
+{
+    constexpr int D = Env::kState, A = (int)Env::kActions;
+    static_assert(A >= 2 && sizeof(typename Env::Action) == 1, "policies are for the Discrete envs");
+    if (H == 0) { // affine: W[A][D], b[A]
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) y[a][k] = W(k, A * D + a);
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) y[a][k] = __builtin_fmaf(W(k, a * D + j), x[j].v[k], y[a][k]);
+            }
+        }
+    } else { // W1[H][D], b1[H], W2[A][H], b2[A]
+        const uint32_t o_b1 = H * D, o_w2 = o_b1 + H, o_b2 = o_w2 + A * H;
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) y[a][k] = W(k, o_b2 + a);
+        }
+        constexpr int kUnits = UNI ? 4 : 1; // gathered: one unit's 1 + D + A vector loads per lane in flight, not four units' weights
+#pragma unroll kUnits
+        for (uint32_t h = 0; h < H; ++h) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                float z = W(k, o_b1 + h);
+#pragma unroll
+                for (int j = 0; j < D; ++j) z = __builtin_fmaf(W(k, h * D + j), x[j].v[k], z);
+                const float r = (z > 0.0f) ? z : 0.0f;
+#pragma unroll
+                for (int a = 0; a < A; ++a) y[a][k] = __builtin_fmaf(W(k, o_w2 + a * H + h), r, y[a][k]);
+            }
+        }
+    }
+}
 
 // The actions of the VEC lanes of a work-item from their observations x[j].v[k] (D rows in gymrs_obs_ptrs order).  The hidden
 // layer is consumed unit by unit: A accumulators and one temporary per lane, whatever H is; its loop stays rolled (four
@@ -183,6 +231,58 @@ struct ExploringActions {
             for (int k = 0; k < VEC; ++k) act.v[k] = 0;
         }
         if (x.threshold != 0) explore_mix<VEC, (uint32_t)Env::kActions>(x, gid, tick, aligned, act);
+    }
+};
+
+// Softmax sampling (include/gymrs_amd.h, "sampling"): every lane of a work-item takes the action its draw of this step selects
+// under the weights of its logits (gymrs_sample.h: the text gymrs_sample_draw compiles).  gid, tick and aligned as in explore_mix:
+// with an aligned offset four lanes share one Philox block of stream 3.  prob (may be NULL) gets prob[action] of every lane.
+template <class Env, int VEC>
+__device__ __forceinline__ void sample_pick(const SampleArgs& x, const float (&y)[Env::kActions][VEC], uint64_t gid, uint64_t tick, bool aligned,
+                                            Vec<uint8_t, VEC>& act, Vec<float, VEC>* prob = nullptr)
+{
+    constexpr uint32_t A = (uint32_t)Env::kActions;
+    uint32_t word[VEC];
+    if (aligned) {
+#pragma unroll
+        for (int b = 0; b < VEC / 4; ++b) {
+            const u32x4 blk = sample_block(x.seed, gid + 4 * b, tick);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) word[4 * b + i] = blk.v[i];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) word[i] = sample_word(x.seed, gid + i, tick);
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        float yl[A], w[A];
+#pragma unroll
+        for (uint32_t a = 0; a < A; ++a) yl[a] = y[a][k];
+        const uint32_t greedy = sample_greedy(yl, A);
+        sample_weights(yl, A, greedy, x.scale, w);
+        const float total = sample_total(w, A);
+        const uint32_t action = sample_select(w, A, total, word[k], greedy);
+        act.v[k] = (uint8_t)action;
+        if (prob) prob->v[k] = sample_prob(w, total, greedy, action);
+    }
+}
+
+// The sampling action source of rollout_block: the policy's logits, then the pick above.  Told which step this is like
+// ExploringActions (kExplore: the same fill).
+template <class Env, int VEC, bool UNI>
+struct SamplingActions {
+    static constexpr bool kPolicy = true, kExplore = true;
+    PolicyWeights<VEC, UNI> w;
+    uint32_t hidden;
+    SampleArgs x;
+    __device__ __forceinline__ SamplingActions(const PolicyArgs& p, const uint32_t (&pol)[VEC], const SampleArgs& x_) : w(p, pol), hidden(p.hidden), x(x_) {}
+    __device__ __forceinline__ void fill(const Vec<float, VEC> (&st)[Env::kState], Vec<uint8_t, VEC>& act, uint64_t gid, uint64_t tick,
+                                         bool aligned, Vec<float, VEC>* prob = nullptr) const
+    {
+        float y[Env::kActions][VEC];
+        policy_logits<Env, VEC, UNI>(w, hidden, st, y);
+        sample_pick<Env, VEC>(x, y, gid, tick, aligned, act, prob);
     }
 };
 

@@ -469,6 +469,15 @@ gymrs_status gymrs_sharded_set_exploration(gymrs_sharded* h, const gymrs_explora
     return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_exploration(e, remove ? nullptr : &settings); }; });
 }
 
+// ... and the same sampling settings.
+gymrs_status gymrs_sharded_set_sampling(gymrs_sharded* h, const gymrs_sampling* x)
+{
+    if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_set_sampling: handle is NULL");
+    const bool remove = x == nullptr;
+    const gymrs_sampling settings = remove ? gymrs_sampling{0, 0.0f, 0} : *x; // by value into the workers
+    return h->all([=](int) { return [=](gymrs_engine*& e) { return gymrs_set_sampling(e, remove ? nullptr : &settings); }; });
+}
+
 gymrs_status gymrs_sharded_rollout_policy(gymrs_sharded* h, uint32_t n_steps)
 {
     if (!h) return fail(GYMRS_EINVAL, "gymrs_sharded_rollout_policy: handle is NULL");

@@ -94,6 +94,7 @@ class ClosedLoopDesc(C.Structure):
 CLOSED_LOOP_FITNESS = 1  # GYMRS_CLOSED_LOOP_FITNESS
 CLOSED_LOOP_LANE_PARAMS = 4  # GYMRS_CLOSED_LOOP_LANE_PARAMS
 CLOSED_LOOP_EXPLORE = 16  # GYMRS_CLOSED_LOOP_EXPLORE
+CLOSED_LOOP_SAMPLE = 32  # GYMRS_CLOSED_LOOP_SAMPLE
 
 
 class TransitionsDesc(C.Structure):
@@ -139,11 +140,44 @@ def explore_draw(seed: int, threshold: int, n_actions: int, global_id, tick):
     return explored, action
 
 
-def _closed_loop_desc(n_envs, n_steps, lane_params, fitness, record, flags=None, explore=False) -> ClosedLoopDesc:
+class Sampling(C.Structure):
+    """``gymrs_sampling`` (include/gymrs_amd.h), 16 bytes: scale = log2(e) / temperature."""
+    _fields_ = [("seed", C.c_uint64), ("scale", C.c_float), ("reserved", C.c_uint32)]
+
+
+LOG2E = 1.4426950408889634  # log2(e): the sampling rule works in base 2
+
+
+def _sampling(seed, temperature, scale) -> Sampling:
+    """Exactly one of ``temperature`` (> 0; scale = log2(e) / temperature rounded to f32) and ``scale`` (finite, >= 0)."""
+    if (temperature is None) == (scale is None):
+        raise ValueError("give exactly one of temperature and scale")
+    if scale is None:
+        if not float(temperature) > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        scale = LOG2E / float(temperature)
+    return Sampling(int(seed) & (2**64 - 1), float(scale), 0)
+
+
+def sample_draw(seed: int, scale: float, logits, global_id: int, tick: int):
+    """``gymrs_sample_draw`` (host only, no GPU): (action, probs) of the softmax draw that takes lane ``global_id`` from engine
+    tick ``tick`` to ``tick + 1`` under the f32 ``logits`` (2 .. 8 of them): the definition of include/gymrs_amd.h, "sampling", as
+    code.  ``probs`` is a float32 array, one per action."""
+    lib = load_library()
+    x = Sampling(int(seed) & (2**64 - 1), float(scale), 0)
+    y = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    probs = np.empty(y.shape, np.float32)
+    a = C.c_uint8()
+    _check(lib, lib.gymrs_sample_draw(C.byref(x), int(y.size), y.ctypes.data_as(C.POINTER(C.c_float)), int(global_id), int(tick), C.byref(a),
+                                      probs.ctypes.data_as(C.POINTER(C.c_float))))
+    return int(a.value), probs
+
+
+def _closed_loop_desc(n_envs, n_steps, lane_params, fitness, record, flags=None, explore=False, sample=False) -> ClosedLoopDesc:
     """``record``: None, a ``Trajectory``, or a mapping with the keyword arguments of ``rollout_policy_record`` (device addresses
     ``obs``, ``actions``, ``reward``, ``done``, optionally ``truncated`` and ``lane_stride``).  The descriptor keeps it alive."""
     f = ((CLOSED_LOOP_FITNESS if fitness else 0) | (CLOSED_LOOP_LANE_PARAMS if lane_params else 0) |
-         (CLOSED_LOOP_EXPLORE if explore else 0)) if flags is None else int(flags)
+         (CLOSED_LOOP_EXPLORE if explore else 0) | (CLOSED_LOOP_SAMPLE if sample else 0)) if flags is None else int(flags)
     traj = record
     if record is not None and not isinstance(record, Trajectory):
         stride = record.get("lane_stride")
@@ -590,18 +624,19 @@ class BatchedEngine:
 
     # -- the closed-loop calls behind one descriptor, and under per-lane physics ---------------------------
     def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
-                            flags: Optional[int] = None, explore: bool = False) -> None:
+                            flags: Optional[int] = None, explore: bool = False, sample: bool = False) -> None:
         """``gymrs_rollout_closed_loop``: ``rollout_policy`` (with ``record``: ``rollout_policy_record``; with ``fitness``:
         ``rollout_policy_fitness``) behind one descriptor.  ``lane_params`` (``GYMRS_CLOSED_LOOP_LANE_PARAMS``) lets it run while a
         parameter table is active: every lane steps with the row ``step`` would use for it, n_steps steps in one launch; without a
         table it changes nothing, so a training loop may always set it.  ``record``: a ``Trajectory`` or a mapping with the keyword
         arguments of ``rollout_policy_record``.  ``explore`` (``GYMRS_CLOSED_LOOP_EXPLORE``) plays the epsilon-greedy action of
-        ``set_exploration`` in place of the argmax.  ``flags`` passes a raw flags word instead of the three booleans."""
-        desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags, explore)
+        ``set_exploration`` in place of the argmax, ``sample`` (``GYMRS_CLOSED_LOOP_SAMPLE``) an action drawn from the softmax of the
+        logits under ``set_sampling``; not both.  ``flags`` passes a raw flags word instead of the booleans."""
+        desc = _closed_loop_desc(self.n_envs, n_steps, lane_params, fitness, record, flags, explore, sample)
         _check(self._lib, self._lib.gymrs_rollout_closed_loop(self._h, C.byref(desc)))
 
     def rollout_transitions(self, n_steps: int, *, record, final_obs: int, start_obs: Optional[int] = None, lane_params: bool = False,
-                            explore: bool = False, flags: Optional[int] = None) -> None:
+                            explore: bool = False, flags: Optional[int] = None, sample: bool = False) -> None:
         """``gymrs_rollout_transitions``: ``rollout_closed_loop(n_steps, record=record, ...)`` that also writes, per step, the
         observation every ended lane showed before its re-arm into ``final_obs`` ([n_steps][D][lane_stride] f32, device address;
         only the elements of ended lane-steps are written) and, if given, the observations the launch starts from into
@@ -609,7 +644,7 @@ class BatchedEngine:
         Engines with ``AUTO_RESET`` only.  ``record``: a ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (required)."""
         if record is None:
             raise ValueError("rollout_transitions needs a record")
-        cl = _closed_loop_desc(self.n_envs, n_steps, lane_params, False, record, flags, explore)
+        cl = _closed_loop_desc(self.n_envs, n_steps, lane_params, False, record, flags, explore, sample)
         desc = TransitionsDesc(int(n_steps), cl.flags, cl.record.contents, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None), 0)
         _check(self._lib, self._lib.gymrs_rollout_transitions(self._h, C.byref(desc)))
 
@@ -635,6 +670,31 @@ class BatchedEngine:
         """``policy_actions`` mixed with the exploration draw at the engine's current tick (one launch): ``explore_actions(buf);
         step(buf)``, K times, is ``rollout_closed_loop(K, explore=True)``."""
         _check(self._lib, self._lib.gymrs_explore_actions(self._h, C.c_void_p(actions_dev)))
+
+    # -- softmax sampling inside the closed-loop calls -----------------------------------------------------------
+    def set_sampling(self, seed: Optional[int] = 0, *, temperature: Optional[float] = None, scale: Optional[float] = None) -> None:
+        """Install the sampling settings (``gymrs_set_sampling``): a ~ softmax(logits / ``temperature``), drawn from a Philox stream
+        keyed (``seed``, global lane id, engine tick).  Give ``temperature`` or the kernel's own ``scale`` = log2(e) / temperature
+        (0: the uniform policy).  ``set_sampling(None)`` removes them.  Touches no lane state, tick, statistics or fitness table;
+        launches play them only with ``rollout_closed_loop(..., sample=True)``, ``rollout_transitions(..., sample=True)`` and
+        ``sample_actions``."""
+        if seed is None:
+            _check(self._lib, self._lib.gymrs_set_sampling(self._h, None))
+            return
+        x = _sampling(seed, temperature, scale)
+        _check(self._lib, self._lib.gymrs_set_sampling(self._h, C.byref(x)))
+
+    def sampling(self) -> Tuple[int, float]:
+        """(seed, scale) as set; raises when the engine has no sampling settings."""
+        x = Sampling()
+        _check(self._lib, self._lib.gymrs_get_sampling(self._h, C.byref(x)))
+        return int(x.seed), float(x.scale)
+
+    def sample_actions(self, actions_dev: int, prob: Optional[int] = None) -> None:
+        """The sampled action of every lane at the engine's current tick (one launch); ``prob`` (device address of n_envs f32, or
+        None) gets the probability of the action taken.  ``sample_actions(buf); step(buf)``, K times, is
+        ``rollout_closed_loop(K, sample=True)``."""
+        _check(self._lib, self._lib.gymrs_sample_actions(self._h, C.c_void_p(actions_dev), C.c_void_p(prob or None)))
 
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of policies [first, first + count) as an int64 array of shape (count, 4): columns reward_sum, episodes,
@@ -806,9 +866,9 @@ class ShardedEngine:
         _check(self._lib, self._lib.gymrs_sharded_rollout_policy_fitness(self._h, int(n_steps)))
 
     def rollout_closed_loop(self, n_steps: int, *, lane_params: bool = False, fitness: bool = False, record=None,
-                            flags: Optional[int] = None, explore: bool = False) -> None:
+                            flags: Optional[int] = None, explore: bool = False, sample: bool = False) -> None:
         """``BatchedEngine.rollout_closed_loop`` on every block (``record`` must stay None: the blocks live on several devices)."""
-        desc = _closed_loop_desc(self.n_total, n_steps, lane_params, fitness, record, flags, explore)
+        desc = _closed_loop_desc(self.n_total, n_steps, lane_params, fitness, record, flags, explore, sample)
         _check(self._lib, self._lib.gymrs_sharded_rollout_closed_loop(self._h, C.byref(desc)))
 
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:
@@ -827,6 +887,24 @@ class ShardedEngine:
         """``BatchedEngine.explore_actions`` on every block: ``actions_dev[r]`` is the device address of block r's buffer."""
         for s, a in zip(self.shards, actions_dev):
             s.explore_actions(a)
+
+    def set_sampling(self, seed: Optional[int] = 0, *, temperature: Optional[float] = None, scale: Optional[float] = None) -> None:
+        """``BatchedEngine.set_sampling`` on every block: the same settings everywhere (the draw is keyed by global lane ids)."""
+        if seed is None:
+            _check(self._lib, self._lib.gymrs_sharded_set_sampling(self._h, None))
+            return
+        x = _sampling(seed, temperature, scale)
+        _check(self._lib, self._lib.gymrs_sharded_set_sampling(self._h, C.byref(x)))
+
+    def sampling(self) -> Tuple[int, float]:
+        """(seed, scale) as set (every block holds the same)."""
+        return self.shards[0].sampling()
+
+    def sample_actions(self, actions_dev, prob=None) -> None:
+        """``BatchedEngine.sample_actions`` on every block: ``actions_dev[r]`` (and ``prob[r]``) are the device addresses of block
+        r's buffers."""
+        for r, (s, a) in enumerate(zip(self.shards, actions_dev)):
+            s.sample_actions(a, None if prob is None else prob[r])
 
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of the WHOLE batch, (count, 4) int64 as ``BatchedEngine.policy_fitness``: the blocks' records summed

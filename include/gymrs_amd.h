@@ -500,7 +500,7 @@ gymrs_status gymrs_sharded_policy_fitness_clear(gymrs_sharded* h);
  *     stepped, pays 0 and sets no flag in every step of the launch (its record rows say so), adds nothing to any fitness
  *     record, and the next gymrs_sync returns GYMRS_EACTION naming the lowest such lane.
  *   - GYMRS_EINVAL: NULL engine or desc, no policy set, Pendulum, reserved != 0, unknown flag bits (bits 1 and 3 are not assigned;
- *     bit 4 is GYMRS_CLOSED_LOOP_EXPLORE, "exploration" below),
+ *     bit 4 is GYMRS_CLOSED_LOOP_EXPLORE, "exploration" below; bit 5 is GYMRS_CLOSED_LOOP_SAMPLE, "sampling" below),
  *     GYMRS_CLOSED_LOOP_FITNESS together with a record (there is no recording fitness kernel), a record that fails the buffer
  *     checks of gymrs_rollout_policy_record, n_steps > GYMRS_POLICY_FITNESS_MAX_STEPS with GYMRS_CLOSED_LOOP_FITNESS.  n_steps == 0
  *     is a no-op after these checks.
@@ -556,6 +556,60 @@ gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev);
 gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, uint64_t global_id, uint64_t tick, uint8_t* explored,
                                 uint8_t* random_action);
 gymrs_status gymrs_sharded_set_exploration(gymrs_sharded* h, const gymrs_exploration* x);
+/* Sampling: a ~ softmax(logits / temperature) inside the closed-loop fused rollouts, defined to the bit.
+ * A policy-gradient learner needs the action drawn from the policy's own distribution, needs to know that distribution, and needs
+ * the draw to be reproducible.  The sampling settings live on the engine like the exploration settings: seed, and scale = log2(e) /
+ * temperature (the rule works in base 2), finite and >= 0; 0 gives the uniform policy; reserved must be 0.  For the step that takes
+ * the lane with GLOBAL id g from engine tick t to t + 1, let y[0 .. A) be the logits of "closed-loop rollouts" (unchanged) and
+ * greedy its argmax (unchanged: the first maximum, a NaN at a >= 1 never wins).  All arithmetic is f32, every operation below is a
+ * single IEEE operation, nothing is contracted or reordered:
+ *     m     = y[greedy]
+ *     d[a]  = (y[a] - m) * scale                          (one subtract, one multiply)
+ *     w[a]  = !(d[a] >= -126.0f) ? 0.0f                   (NaN, -inf and the far tail weigh nothing)
+ *           : ldexpf(P(d[a] - floorf(d[a])), (int)floorf(d[a]))
+ *     P(f)  = Horner with fmaf from c6 down to c0:  acc = c6; acc = fmaf(acc, f, c5); ... ; acc = fmaf(acc, f, c0)
+ *             c0 .. c6 = 1.0, 0x1.62e430p-1, 0x1.ebfc40p-3, 0x1.c69f6ap-5, 0x1.3c4a8ap-7, 0x1.4ca4ccp-10, 0x1.b4d1e4p-13
+ *     total = ((w[0] + w[1]) + w[2])                      (index order; A = 2: w[0] + w[1])
+ *     word  = word (g & 3) of the Philox4x32-10 block of stream 3: key (seed lo, seed hi), counter (g >> 2 lo, g >> 2 hi, t lo,
+ *             (t hi & 0xffff) | 3 << 16) -- the counter layout of streams 0 .. 2
+ *     thr   = ((float)(word >> 8) * 0x1p-24f) * total     (the first product is exact)
+ *     action  = the first a with thr < w[0] + ... + w[a]  (running f32 sum in index order); if there is none, greedy
+ *     prob[a] = w[a] / total  (one IEEE divide); if total is not > 0: prob[greedy] = 1, the others 0
+ * P(f) approximates 2^f on [0, 1): its maximum relative error against f64 exp2 over all 2^23 values f = i / 2^23, evaluated with
+ * true fmaf, is 6.7e-8 (measured: 6.704e-8, below 6.71e-8; tests/test_sample_ref.py repeats the measurement).  What follows from the rule:
+ *   - c0 == 1 makes w[greedy] == 1 exactly whenever m is finite; exact ties are equally likely; an action of weight zero is never
+ *     taken; a NaN or infinite m (all weights 0) plays the greedy action.
+ *   - f can round up to 1.0 for a denormal d; the formula still holds there.  Every w is 0 or a normal number.
+ *   - The key is the engine's own tick and the GLOBAL lane id: K steps in one launch equal K single steps however they are split
+ *     into launches, k blocks equal one engine, and a CPU can recompute every draw.
+ *   - gymrs_set_sampling stores the settings (x == NULL removes them); gymrs_get_sampling reads them back.  GYMRS_EINVAL: Pendulum,
+ *     scale NaN, infinite or negative, reserved != 0, (get) no settings.  As with gymrs_set_exploration: no policy is needed; the
+ *     settings touch no lane state, tick, statistics or fitness table, survive gymrs_set_policy, take effect in stream order and are
+ *     NOT part of gymrs_engine_clone or of a snapshot.
+ *   - GYMRS_CLOSED_LOOP_SAMPLE in the flags of gymrs_closed_loop_desc and gymrs_transitions_desc: the launch plays the sampled
+ *     action in every combination it has: plain, with a record (the `actions` rows hold the action TAKEN), with
+ *     GYMRS_CLOSED_LOOP_FITNESS (the counters follow the action taken), with or without GYMRS_CLOSED_LOOP_LANE_PARAMS under a
+ *     table, and in gymrs_rollout_transitions.  Together with GYMRS_CLOSED_LOOP_EXPLORE: GYMRS_EINVAL naming both flags.  The flag
+ *     without settings: GYMRS_EINVAL naming gymrs_set_sampling.  Settings without the flag: the greedy launch, bit for bit.
+ *     gymrs_rollout_policy, _record, _fitness and gymrs_evaluate_policy stay greedy.
+ *   - gymrs_sample_actions(e, actions_dev, prob_dev): the per-step counterpart at the engine's current tick; prob_dev (may be NULL,
+ *     else n_envs floats) gets prob[action] of every lane.  gymrs_rollout_closed_loop(K, SAMPLE)  ==  K x (gymrs_sample_actions(e,
+ *     buf, NULL); gymrs_step(e, buf)).  It needs a policy and settings (GYMRS_EINVAL otherwise) and works while a parameter table
+ *     is active.
+ *   - gymrs_sample_draw: host only, no GPU (like gymrs_explore_draw): the definition as code.  From n_actions logits it gives the
+ *     action of (global id, tick) under the settings and prob[0 .. n_actions); either output may be NULL.  GYMRS_EINVAL: NULL
+ *     settings or logits, settings gymrs_set_sampling would refuse, n_actions outside 2 .. 8.
+ *   - The fused launches write no probability row (the record layouts are pinned): a learner recomputes pi(a|s) from the `obs` rows
+ *     with the weights it already holds.
+ *   - gymrs_sharded_set_sampling applies the same settings to every block; gymrs_sharded_rollout_closed_loop passes the flag through. */
+#define GYMRS_CLOSED_LOOP_SAMPLE 32u /* bit 5 */
+typedef struct { uint64_t seed; float scale; uint32_t reserved; } gymrs_sampling; /* 16 B */
+gymrs_status gymrs_set_sampling(gymrs_engine* e, const gymrs_sampling* x);
+gymrs_status gymrs_get_sampling(gymrs_engine* e, gymrs_sampling* x_out);
+gymrs_status gymrs_sample_actions(gymrs_engine* e, void* actions_dev, float* prob_dev);
+gymrs_status gymrs_sample_draw(const gymrs_sampling* x, uint32_t n_actions, const float* logits, uint64_t global_id, uint64_t tick, uint8_t* action,
+                               float* probs);
+gymrs_status gymrs_sharded_set_sampling(gymrs_sharded* h, const gymrs_sampling* x);
 /* Transitions: a recorded closed-loop rollout that keeps what every ended episode ended in.
  * With GYMRS_AUTO_RESET the `obs` row of a step that ends an episode holds the re-armed state; the observation the episode ended in,
  * which a truncated step must bootstrap from, is only in the engine's GYMRS_FINAL_OBS arrays, one ending per lane.

@@ -82,6 +82,16 @@ inline std::pair<bool, std::uint8_t> explore_draw(const gymrs_exploration& x, st
     return {explored != 0, action};
 }
 
+// The softmax draw of (global lane id, engine tick) under settings x from n_actions logits (gymrs_sample_draw; host only, no GPU):
+// the action; probs (may be null) gets the n_actions probabilities.  The definition of include/gymrs_amd.h, "sampling", as code.
+inline std::uint8_t sample_draw(const gymrs_sampling& x, std::uint32_t n_actions, const float* logits, std::uint64_t global_id, std::uint64_t tick,
+                                float* probs = nullptr)
+{
+    std::uint8_t action = 0;
+    check(gymrs_sample_draw(&x, n_actions, logits, global_id, tick, &action, probs));
+    return action;
+}
+
 // ---- batched form: the shape the hot path is built for ---------------------------------------------
 class VecEnv {
 public:
@@ -267,6 +277,31 @@ public:
                                        record, 0};
         check(gymrs_rollout_closed_loop(e_, &d));
     }
+    // softmax sampling (gymrs_set_sampling): a ~ softmax(logits / temperature), scale = log2(e) / temperature, drawn from a Philox
+    // stream keyed (seed, global lane id, engine tick); launches play it with sample = true (GYMRS_CLOSED_LOOP_SAMPLE) only
+    void set_sampling(std::uint64_t seed, float scale)
+    {
+        const gymrs_sampling x{seed, scale, 0};
+        check(gymrs_set_sampling(e_, &x));
+    }
+    void clear_sampling() { check(gymrs_set_sampling(e_, nullptr)); }
+    gymrs_sampling sampling() const
+    {
+        gymrs_sampling x{};
+        check(gymrs_get_sampling(e_, &x));
+        return x;
+    }
+    // the sampled action at the engine's current tick (prob_dev, may be null: the probability of the action taken): sample_actions +
+    // step_device, K times, is rollout_closed_loop(K, .., sample = true)
+    void sample_actions(void* actions_dev, float* prob_dev = nullptr) { check(gymrs_sample_actions(e_, actions_dev, prob_dev)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params, bool fitness, const gymrs_trajectory* record, bool explore, bool sample)
+    {
+        const gymrs_closed_loop_desc d{n_steps,
+                                       (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u) |
+                                           (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u) | (sample ? GYMRS_CLOSED_LOOP_SAMPLE : 0u),
+                                       record, 0};
+        check(gymrs_rollout_closed_loop(e_, &d));
+    }
     // gymrs_rollout_transitions: the recording closed-loop launch that also writes, per step, the pre-re-arm observation of every ended
     // lane into final_obs ([n_steps][D][record.lane_stride], only those elements) and, unless NULL, the launch's start observations
     // into start_obs ([D][record.lane_stride]): successor of step k = ended ? final_obs[k] : obs[k].  Engines with GYMRS_AUTO_RESET only.
@@ -275,6 +310,16 @@ public:
                              bool lane_params = false, bool explore = false)
     {
         const gymrs_transitions_desc d{n_steps, (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u),
+                                       record, final_obs, start_obs, 0};
+        check(gymrs_rollout_transitions(e_, &d));
+    }
+    // ... with sample = true: the action drawn under set_sampling (GYMRS_CLOSED_LOOP_SAMPLE)
+    void rollout_transitions(std::uint32_t n_steps, const gymrs_trajectory& record, float* final_obs, float* start_obs, bool lane_params,
+                             bool explore, bool sample)
+    {
+        const gymrs_transitions_desc d{n_steps,
+                                       (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u) |
+                                           (sample ? GYMRS_CLOSED_LOOP_SAMPLE : 0u),
                                        record, final_obs, start_obs, 0};
         check(gymrs_rollout_transitions(e_, &d));
     }
@@ -427,6 +472,21 @@ public:
         check(gymrs_sharded_set_exploration(h_, &x));
     }
     void clear_exploration() { check(gymrs_sharded_set_exploration(h_, nullptr)); }
+    // VecEnv::set_sampling on every block
+    void set_sampling(std::uint64_t seed, float scale)
+    {
+        const gymrs_sampling x{seed, scale, 0};
+        check(gymrs_sharded_set_sampling(h_, &x));
+    }
+    void clear_sampling() { check(gymrs_sharded_set_sampling(h_, nullptr)); }
+    void rollout_closed_loop(std::uint32_t n_steps, bool lane_params, bool fitness, bool explore, bool sample)
+    {
+        const gymrs_closed_loop_desc d{n_steps,
+                                       (lane_params ? GYMRS_CLOSED_LOOP_LANE_PARAMS : 0u) | (fitness ? GYMRS_CLOSED_LOOP_FITNESS : 0u) |
+                                           (explore ? GYMRS_CLOSED_LOOP_EXPLORE : 0u) | (sample ? GYMRS_CLOSED_LOOP_SAMPLE : 0u),
+                                       nullptr, 0};
+        check(gymrs_sharded_rollout_closed_loop(h_, &d));
+    }
     void rollout_closed_loop(std::uint32_t n_steps, bool lane_params, bool fitness, bool explore)
     {
         const gymrs_closed_loop_desc d{n_steps,
