@@ -303,6 +303,43 @@ impl Engine {
         check(ffi::gymrs_rollout_transitions(self.raw, &d));
     }
 
+    /// Install a critic set (`gymrs_set_critic`): `n_critics` critics of `gymrs_critic_size(kind, hidden)` floats back to back; lane i
+    /// uses critic `((global_env_offset + i) / lanes_per_critic) % n_critics`.  Survives `set_policy`; not part of clone or snapshot.
+    pub fn set_critic(&mut self, weights: &[f32], hidden: u32, n_critics: u32, lanes_per_critic: u64) {
+        let mut size = 0u64;
+        check(unsafe { ffi::gymrs_critic_size(self.kind.raw(), hidden, &mut size) });
+        assert_eq!(weights.len() as u64, size * n_critics as u64);
+        let d = ffi::GymrsPolicyDesc { hidden, n_policies: n_critics, lanes_per_policy: lanes_per_critic };
+        check(unsafe { ffi::gymrs_set_critic(self.raw, &d, weights.as_ptr()) });
+    }
+
+    /// Remove the critic set.
+    pub fn clear_critic(&mut self) {
+        check(unsafe { ffi::gymrs_set_critic(self.raw, std::ptr::null(), std::ptr::null()) });
+    }
+
+    /// Zero-copy device view of the critic set and its number of floats; valid until the next `set_critic` or drop.
+    pub fn critic_weights_ptr(&mut self) -> (*mut f32, u64) {
+        let (mut p, mut n) = (std::ptr::null_mut(), 0u64);
+        check(unsafe { ffi::gymrs_critic_weights_ptr(self.raw, &mut p, &mut n) });
+        (p, n)
+    }
+
+    /// `gymrs_advantages`: GAE(lambda) advantages (and, unless null, returns and values), each `[n_steps][record.lane_stride]`, from the
+    /// rows `rollout_transitions` wrote, in one launch on the engine's stream.  `critic`: evaluate the critic set inside the kernel
+    /// (`GYMRS_ADVANTAGES_CRITIC`), else V = 0.  `final_obs` may be null (records of engines without auto-reset).  Reads and writes no
+    /// lane array.
+    ///
+    /// # Safety
+    /// Every pointer must be a 16-byte aligned device address of the size the header names, valid until `sync()`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn advantages(&mut self, n_steps: u32, critic: bool, gamma: f32, lambda: f32, record: &ffi::Trajectory, final_obs: *const f32,
+                             start_obs: *const f32, advantages: *mut f32, returns: *mut f32, values: *mut f32) {
+        let flags = if critic { ffi::GYMRS_ADVANTAGES_CRITIC } else { 0 };
+        let d = ffi::GymrsAdvantagesDesc { n_steps, flags, gamma, lambda, record: *record, final_obs, start_obs, advantages, returns, values, reserved: 0 };
+        check(ffi::gymrs_advantages(self.raw, &d));
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

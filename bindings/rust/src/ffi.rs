@@ -142,6 +142,28 @@ pub struct GymrsTransitionsDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_ADVANTAGES_CRITIC`: `gymrs_advantages` evaluates the engine's critic set (`gymrs_set_critic`) inside the kernel; without it V = 0.
+pub const GYMRS_ADVANTAGES_CRITIC: u32 = 1;
+
+/// `gymrs_advantages_desc`: what `gymrs_advantages` runs (include/gymrs_amd.h "advantages"), 112 bytes: the record by value (read: `obs`,
+/// `reward`, `done`, `truncated`), `final_obs` `[n_steps][D][record.lane_stride]` or null, `start_obs` `[D][record.lane_stride]`, and
+/// the outputs `advantages`, `returns` (or null), `values` (or null), each `[n_steps][record.lane_stride]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsAdvantagesDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub gamma: f32,
+    pub lambda: f32,
+    pub record: Trajectory,
+    pub final_obs: *const f32,
+    pub start_obs: *const f32,
+    pub advantages: *mut f32,
+    pub returns: *mut f32,
+    pub values: *mut f32,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -260,6 +282,13 @@ extern "C" {
     pub fn gymrs_policy_fitness_clear(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_rollout_closed_loop(e: *mut GymrsEngine, d: *const GymrsClosedLoopDesc) -> c_int;
     pub fn gymrs_rollout_transitions(e: *mut GymrsEngine, d: *const GymrsTransitionsDesc) -> c_int;
+    /// advantages over a transitions record: the critic set (described by a `GymrsPolicyDesc`) and the GAE(lambda) scan in one launch
+    pub fn gymrs_critic_size(kind: c_int, hidden: u32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_set_critic(e: *mut GymrsEngine, d: *const GymrsPolicyDesc, weights_host: *const f32) -> c_int;
+    pub fn gymrs_get_critic(e: *mut GymrsEngine, d_out: *mut GymrsPolicyDesc, weights_out: *mut f32, capacity_floats: u64) -> c_int;
+    pub fn gymrs_critic_weights_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_critic_value(kind: c_int, hidden: u32, weights: *const f32, obs: *const f32, v: *mut f32) -> c_int;
+    pub fn gymrs_advantages(e: *mut GymrsEngine, d: *const GymrsAdvantagesDesc) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -48,6 +48,7 @@ from .engine import ClosedLoopDesc, CLOSED_LOOP_FITNESS, CLOSED_LOOP_LANE_PARAMS
 from .engine import TransitionsDesc
 from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
 from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
+from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -58,4 +59,5 @@ __all__ = [
     "PolicyFitness", "PolicyEval", "EvalDesc", "EVAL_COMMON_STARTS", "EVAL_LANE_PARAMS",
     "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS", "TransitionsDesc",
     "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw", "Sampling", "CLOSED_LOOP_SAMPLE", "sample_draw",
+    "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
 ]

@@ -94,6 +94,13 @@ SIGNATURES = {
     "gymrs_get_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_sample_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gymrs_sample_draw": (C.c_int, [C.c_void_p, C.c_uint32, f32p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8), f32p]),
+    # advantages over a transitions record (gymrs_advantages_desc 112 B); the critic set is described by a gymrs_policy_desc
+    "gymrs_critic_size": (C.c_int, [C.c_int, C.c_uint32, u64p]),
+    "gymrs_set_critic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gymrs_get_critic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "gymrs_critic_weights_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),
+    "gymrs_critic_value": (C.c_int, [C.c_int, C.c_uint32, f32p, f32p, f32p]),
+    "gymrs_advantages": (C.c_int, [C.c_void_p, C.c_void_p]),
     # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

@@ -512,6 +512,7 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->table_dev);
     (void)hipFree(e->param_index);
     (void)hipFree(e->policy_dev);
+    (void)hipFree(e->critic_dev);
     (void)hipFree(e->fitness_dev);
     (void)hipFree(e->eval_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));

@@ -4,6 +4,7 @@
 #include "gymrs_engine_priv.h"
 #include "gymrs_evaluate.h"
 #include "gymrs_sample.h"
+#include "gymrs_advantages.h"
 
 static RcclApi g_rccl;
 
@@ -850,6 +851,157 @@ gymrs_status gymrs_sample_draw(const gymrs_sampling* x, uint32_t n_actions, cons
     if (!logits) return fail(GYMRS_EINVAL, "gymrs_sample_draw: NULL logits");
     const uint32_t a = sample_action(logits, n_actions, x->scale, sample_word(x->seed, global_id, tick), probs);
     if (action) *action = (uint8_t)a;
+    return GYMRS_OK;
+}
+
+// ---- advantages: the critic set, the host-side value and the launch (include/gymrs_amd.h, "advantages") --------------------------
+gymrs_status gymrs_critic_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats)
+{
+    if (!n_floats) return fail(GYMRS_EINVAL, "gymrs_critic_size: n_floats is NULL");
+    if (gymrs_status st = check_discrete_env(kind, "gymrs_critic_size")) return st;
+    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_critic_size: hidden must be <= 64");
+    *n_floats = critic_floats(kind, hidden);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_set_critic(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
+{
+    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_critic: NULL engine");
+    if (!d) { // remove the critic (launches already enqueued still read the buffer: wait for them)
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipFree(e->critic_dev));
+        e->critic_dev = nullptr;
+        e->critic_capacity = 0;
+        e->critic = PolicyArgs{};
+        return GYMRS_OK;
+    }
+    if (gymrs_status st = check_discrete_env(e->kind, "gymrs_set_critic")) return st;
+    if (d->hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_set_critic: hidden must be <= 64");
+    if (d->n_policies == 0) return fail(GYMRS_EINVAL, "gymrs_set_critic: n_policies (the number of critics) must be >= 1");
+    if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, "gymrs_set_critic: lanes_per_policy (lanes per critic) must be >= 1");
+    if (!weights_host) return fail(GYMRS_EINVAL, "gymrs_set_critic: weights_host is NULL");
+    const uint64_t stride = critic_floats(e->kind, d->hidden), total = stride * d->n_policies;
+    HIP_TRY(hipSetDevice(e->device));
+    if (total > e->critic_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipFree(e->critic_dev));
+        e->critic_dev = nullptr;
+        e->critic_capacity = 0;
+        e->critic = PolicyArgs{};
+        HIP_TRY(hipMalloc(&e->critic_dev, (size_t)total * sizeof(float)));
+        e->critic_capacity = total;
+    }
+    // stream-ordered: launches enqueued before this call read the old set; the host weights are consumed before the call returns
+    HIP_TRY(hipMemcpyAsync(e->critic_dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->critic.weights = e->critic_dev;
+    e->critic.lanes_per_policy = d->lanes_per_policy;
+    e->critic.n_policies = d->n_policies;
+    e->critic.hidden = d->hidden;
+    e->critic.stride = (uint32_t)stride;
+    e->critic.pad_ = 0;
+    return GYMRS_OK;
+}
+
+static gymrs_status check_critic_set(const gymrs_engine* e, const std::string& who)
+{
+    return e->critic_dev ? GYMRS_OK : fail(GYMRS_EINVAL, who + ": the engine has no critic (gymrs_set_critic)");
+}
+
+gymrs_status gymrs_get_critic(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
+{
+    if (!e || !d_out) return fail(GYMRS_EINVAL, "gymrs_get_critic: NULL argument");
+    if (gymrs_status st = check_critic_set(e, "gymrs_get_critic")) return st;
+    d_out->hidden = e->critic.hidden;
+    d_out->n_policies = e->critic.n_policies;
+    d_out->lanes_per_policy = e->critic.lanes_per_policy;
+    if (!weights_out && capacity_floats == 0) return GYMRS_OK; // a query of the description
+    const uint64_t total = (uint64_t)e->critic.stride * e->critic.n_policies;
+    if (!weights_out || capacity_floats < total) return fail(GYMRS_EINVAL, "gymrs_get_critic: capacity_floats is smaller than the critic set");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(weights_out, e->critic_dev, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
+}
+
+gymrs_status gymrs_critic_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
+{
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_critic_weights_ptr: NULL argument");
+    if (gymrs_status st = check_critic_set(e, "gymrs_critic_weights_ptr")) return st;
+    *dev_out = e->critic_dev;
+    if (n_floats) *n_floats = (uint64_t)e->critic.stride * e->critic.n_policies;
+    return GYMRS_OK;
+}
+
+namespace {
+struct HostCritic { // w(k, i) of critic_values over one critic in host memory
+    const float* w;
+    float operator()(int, uint32_t i) const { return w[i]; }
+};
+} // namespace
+
+gymrs_status gymrs_critic_value(gymrs_env_kind kind, uint32_t hidden, const float* weights, const float* obs, float* v)
+{
+    if (!weights || !obs || !v) return fail(GYMRS_EINVAL, "gymrs_critic_value: NULL argument");
+    if (gymrs_status st = check_discrete_env(kind, "gymrs_critic_value")) return st;
+    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_critic_value: hidden must be <= 64");
+    const HostCritic w{weights};
+    float out[1];
+    if (kind == GYMRS_CARTPOLE) {
+        const float x[4][1] = {{obs[0]}, {obs[1]}, {obs[2]}, {obs[3]}};
+        critic_values<4, 1, 1>(w, hidden, x, out);
+    } else {
+        const float x[2][1] = {{obs[0]}, {obs[1]}};
+        critic_values<2, 1, 1>(w, hidden, x, out);
+    }
+    *v = out[0];
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_advantages(gymrs_engine* e, const gymrs_advantages_desc* d)
+{
+    const std::string who = "gymrs_advantages";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, who + ": advantages are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (d->flags & ~GYMRS_ADVANTAGES_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_ADVANTAGES_CRITIC is the only one)");
+    const bool critic = (d->flags & GYMRS_ADVANTAGES_CRITIC) != 0;
+    if (critic && !e->critic_dev) return fail(GYMRS_EINVAL, who + ": GYMRS_ADVANTAGES_CRITIC without a critic set on the engine (gymrs_set_critic)");
+    if (!(d->gamma >= 0.0f && d->gamma <= 1.0f)) return fail(GYMRS_EINVAL, who + ": gamma must be in [0, 1]");
+    if (!(d->lambda >= 0.0f && d->lambda <= 1.0f)) return fail(GYMRS_EINVAL, who + ": lambda must be in [0, 1]");
+    const gymrs_trajectory& rec = d->record;
+    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
+    if (!rec.reward) return fail(GYMRS_EINVAL, who + ": record.reward is NULL");
+    if (!rec.done) return fail(GYMRS_EINVAL, who + ": record.done is NULL");
+    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
+    if (!d->advantages) return fail(GYMRS_EINVAL, who + ": advantages is NULL");
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(rec.obs) | reinterpret_cast<uintptr_t>(rec.reward) | reinterpret_cast<uintptr_t>(rec.done) |
+                           reinterpret_cast<uintptr_t>(rec.truncated) | reinterpret_cast<uintptr_t>(d->final_obs) |
+                           reinterpret_cast<uintptr_t>(d->start_obs) | reinterpret_cast<uintptr_t>(d->advantages) |
+                           reinterpret_cast<uintptr_t>(d->returns) | reinterpret_cast<uintptr_t>(d->values);
+    if (bits % 16 != 0) return fail(GYMRS_EINVAL, who + ": every buffer must be 16-byte aligned");
+    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
+    if (d->n_steps == 0) return GYMRS_OK;
+    AdvantageArgs a{};
+    a.obs = rec.obs;
+    a.reward = rec.reward;
+    a.done = rec.done;
+    a.truncated = rec.truncated;
+    a.final_obs = d->final_obs;
+    a.start_obs = d->start_obs;
+    a.advantages = d->advantages;
+    a.returns = d->returns;
+    a.values = d->values;
+    a.stride = rec.lane_stride;
+    a.n = e->n;
+    a.gid0 = e->gid0;
+    a.n_steps = d->n_steps;
+    a.gamma = d->gamma;
+    a.gl = d->gamma * d->lambda;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_advantages(e->kind, a, critic ? &e->critic : nullptr, e->stream));
     return GYMRS_OK;
 }
 

@@ -192,6 +192,11 @@ struct gymrs_engine {
     // The sampling settings (gymrs_set_sampling), under the same rules.
     SampleArgs sample{};
     bool sample_set = false;
+    // The critic set of gymrs_advantages (gymrs_set_critic): `critic` is a PolicyArgs whose stride is critic_floats, critic_dev the
+    // engine-owned device buffer critic.weights points to (NULL = no critic).  gymrs_set_policy keeps it.  Not part of clone or snapshot.
+    PolicyArgs critic{};
+    float* critic_dev = nullptr;
+    uint64_t critic_capacity = 0; // floats critic_dev holds
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };

@@ -363,4 +363,31 @@ hipError_t launch_sample_actions(gymrs_env_kind kind, const float* const* s, voi
 // launch_rollout_explore playing the sampled action of every step; t != NULL: launch_rollout_transitions (a record, no fitness)
 hipError_t launch_rollout_sample(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
                                  const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t, hipStream_t stream);
+// ---- advantages (gymrs_advantages; gymrs_advantages.hip) -----------------------------------------------------------------------
+// S: floats of one critic (the policy layout with one action); 0 for an env kind that takes none
+inline uint64_t critic_floats(gymrs_env_kind kind, uint32_t hidden)
+{
+    const uint64_t d = kind == GYMRS_CARTPOLE ? 4 : 2;
+    if (kind != GYMRS_CARTPOLE && kind != GYMRS_MOUNTAIN_CAR) return 0;
+    return hidden == 0 ? d + 1 : (uint64_t)hidden * (d + 2) + 1;
+}
+// A gymrs_advantages_desc as the kernel gets it by value, before the critic set (a PolicyArgs whose stride is critic_floats).
+// Rows are `stride` lanes apart (>= n, a multiple of 16), every buffer 16-byte aligned.
+struct AdvantageArgs {
+    const float* obs;         // [n_steps][obs_dim][stride]; read with a critic only
+    const float* reward;      // [n_steps][stride]
+    const uint8_t* done;      // [n_steps][stride]
+    const uint8_t* truncated; // [n_steps][stride] or NULL
+    const float* final_obs;   // [n_steps][obs_dim][stride] or NULL; read on truncated-only steps with a critic
+    const float* start_obs;   // [obs_dim][stride]; read with a critic only
+    float* advantages;        // [n_steps][stride]
+    float* returns;           // [n_steps][stride] or NULL
+    float* values;            // [n_steps][stride] or NULL
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    float gamma, gl; // gl = gamma * lambda, one multiply on the host
+    uint32_t pad_;
+};
+// critic == NULL: V = +0.0f everywhere (no observation is read)
+hipError_t launch_advantages(gymrs_env_kind kind, const AdvantageArgs& a, const PolicyArgs* critic, hipStream_t stream);
 } // namespace gymrs

@@ -103,6 +103,16 @@ class TransitionsDesc(C.Structure):
                 ("start_obs", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class AdvantagesDesc(C.Structure):
+    """``gymrs_advantages_desc`` (include/gymrs_amd.h), 112 bytes: the record by value, two observation buffers in, three rows out."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("gamma", C.c_float), ("lam", C.c_float), ("record", Trajectory),
+                ("final_obs", C.c_void_p), ("start_obs", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("values", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+ADVANTAGES_CRITIC = 1  # GYMRS_ADVANTAGES_CRITIC
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -216,6 +226,29 @@ def policy_size(kind: int, hidden: int = 0) -> int:
     n = C.c_uint64()
     _check(lib, lib.gymrs_policy_size(int(kind), int(hidden), C.byref(n)))
     return n.value
+
+
+def critic_size(kind: int, hidden: int = 0) -> int:
+    """Floats of one critic of ``gymrs_set_critic``: affine (``hidden`` = 0) ``W[D], b``, else ``W1[H][D], b1[H], W2[H], b2``: the
+    policy layout with one action (host only, no GPU).  Raises for Pendulum and ``hidden`` > 64."""
+    lib = load_library()
+    n = C.c_uint64()
+    _check(lib, lib.gymrs_critic_size(int(kind), int(hidden), C.byref(n)))
+    return n.value
+
+
+def critic_value(kind: int, hidden: int, weights, obs) -> np.float32:
+    """``gymrs_critic_value`` (host only, no GPU): V(obs) under one critic of ``critic_size(kind, hidden)`` f32 weights: the
+    definition of include/gymrs_amd.h, "advantages", as code."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    x = np.ascontiguousarray(obs, dtype=np.float32).reshape(-1)
+    if w.size != critic_size(kind, hidden) or x.size != _OBS_DIM[kind]:
+        raise ValueError(f"critic_value needs {critic_size(kind, hidden)} weights and {_OBS_DIM[kind]} observation components")
+    v = C.c_float()
+    fp = C.POINTER(C.c_float)
+    _check(lib, lib.gymrs_critic_value(int(kind), int(hidden), w.ctypes.data_as(fp), x.ctypes.data_as(fp), C.byref(v)))
+    return np.float32(v.value)
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -647,6 +680,56 @@ class BatchedEngine:
         cl = _closed_loop_desc(self.n_envs, n_steps, lane_params, False, record, flags, explore, sample)
         desc = TransitionsDesc(int(n_steps), cl.flags, cl.record.contents, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None), 0)
         _check(self._lib, self._lib.gymrs_rollout_transitions(self._h, C.byref(desc)))
+
+    # -- advantages over a transitions record: a critic evaluated inside the kernel, the GAE scan in one launch ------
+    def set_critic(self, weights, hidden: int = 0, lanes_per_critic: int = 1) -> None:
+        """Install a critic set: ``weights`` is an array of shape (n_critics, critic_size(kind, hidden)) (or one flat critic),
+        f32; lane i uses critic ((global_env_offset + i) // lanes_per_critic) % n_critics.  ``None`` removes the critic.  Touches
+        no lane state, tick or statistics, and survives ``set_policy``."""
+        if weights is None:
+            _check(self._lib, self._lib.gymrs_set_critic(self._h, None, None))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        size = critic_size(self.kind, hidden)
+        if w.size == 0 or w.size % size != 0:
+            raise ValueError(f"weights must hold a whole number (>= 1) of critics of {size} floats, got {w.size}")
+        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_critic))
+        _check(self._lib, self._lib.gymrs_set_critic(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+
+    def critic(self):
+        """(weights of shape (n_critics, critic_size), hidden, lanes_per_critic) as set (synchronising)."""
+        desc = PolicyDesc()
+        _check(self._lib, self._lib.gymrs_get_critic(self._h, C.byref(desc), None, 0))
+        size = critic_size(self.kind, desc.hidden)
+        w = np.empty((desc.n_policies, size), dtype=np.float32)
+        _check(self._lib, self._lib.gymrs_get_critic(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size))
+        return w, int(desc.hidden), int(desc.lanes_per_policy)
+
+    def critic_weights_ptr(self) -> Tuple[int, int]:
+        """(device address, number of floats) of the critic set: zero-copy; a kernel on the engine's stream may rewrite the
+        weights between two launches.  Valid until the next set_critic or close."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(self._lib, self._lib.gymrs_critic_weights_ptr(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def advantages(self, n_steps: int, *, record, start_obs: int, advantages: int, final_obs: Optional[int] = None,
+                   returns: Optional[int] = None, values: Optional[int] = None, gamma: float, lam: float, critic: bool = False,
+                   flags: Optional[int] = None) -> None:
+        """``gymrs_advantages``: GAE(lambda) advantages ([n_steps][lane_stride] f32, device address), optionally returns and
+        values, from the rows ``rollout_transitions`` wrote, in one launch on the engine's stream (no sync needed in between).
+        ``critic`` (``GYMRS_ADVANTAGES_CRITIC``) evaluates the critic set of ``set_critic`` inside the kernel; without it V = 0 and
+        ``gamma = lam = 1`` gives the reward-to-go.  ``final_obs=None`` is for records of engines without auto-reset.  ``record``: a
+        ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (its ``actions`` is not read).  Reads and writes no lane array."""
+        if record is None:
+            raise ValueError("advantages needs a record")
+        if not isinstance(record, Trajectory):
+            record = dict(record)
+            record.setdefault("actions", 0)
+        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        f = (ADVANTAGES_CRITIC if critic else 0) if flags is None else int(flags)
+        desc = AdvantagesDesc(int(n_steps), f, float(gamma), float(lam), traj, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None),
+                              C.c_void_p(advantages or None), C.c_void_p(returns or None), C.c_void_p(values or None), 0)
+        _check(self._lib, self._lib.gymrs_advantages(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

@@ -648,6 +648,76 @@ typedef struct {
     uint64_t reserved;         /* 0 */
 } gymrs_transitions_desc;      /* 80 bytes */
 gymrs_status gymrs_rollout_transitions(gymrs_engine* e, const gymrs_transitions_desc* d);
+/* Advantages: GAE(lambda) advantages, returns and values over a transitions record in ONE launch, defined to the bit.
+ * A learner that collects with gymrs_rollout_transitions turns the record into learning targets with a backward scan: K dependent
+ * rounds over [n_envs] slices when written with tensor operations, and a three-way case split per step (the episode went on / was
+ * truncated / was done) that is easy to get wrong.  gymrs_advantages(e, d) does the scan in one pass over the record, with an optional
+ * critic of the policy's shape family evaluated inside the kernel.  All arithmetic is f32, every operation below is a single IEEE
+ * operation, fmaf = the fused multiply-add with ONE rounding, nothing is contracted or reordered, every `?:` is a select (never a
+ * multiply by a mask).
+ * The critic is the policy network of "closed-loop rollouts" with a single output.  D = observation size (4 / 2), H = hidden width,
+ * 0 <= H <= 64, x[0..D) in gymrs_obs_ptrs order:
+ *     H == 0 (affine):    v = b;   for j = 0..D-1: v = fmaf(W[j], x[j], v)
+ *     H  > 0 (one layer): v = b2;  for h = 0..H-1:
+ *                             z = b1[h];  for j = 0..D-1: z = fmaf(W1[h][j], x[j], z)
+ *                             r = (z > 0.0f) ? z : 0.0f                 (compare-select: NaN and -0 give +0)
+ *                             v = fmaf(W2[h], r, v)
+ * One critic is S consecutive floats: H == 0: W[D], b (S = D + 1: 5 / 3); H > 0: W1[H][D], b1[H], W2[H], b2 (S = H*(D+2) + 1;
+ * CartPole H = 16: 97) -- the policy layout with A = 1.  gymrs_critic_size returns S (host only, no GPU; GYMRS_EINVAL for Pendulum
+ * and hidden > 64).  A critic set is n_critics critics back to back and a block size: the lane with GLOBAL id g uses critic
+ * (g / lanes_per_critic) % n_critics -- the policy's key, described by the same gymrs_policy_desc (n_policies = n_critics,
+ * lanes_per_policy = lanes_per_critic).  Without GYMRS_ADVANTAGES_CRITIC in the launch, V(x) = +0.0f for every x.
+ * The scan.  K = d->n_steps, gl = gamma * lambda (one multiply), A[K] = +0.0f; for lane i of the engine, k = K-1 down to 0, rows and
+ * columns as in gymrs_rollout_transitions (obs[k], final_obs[k] = the D components of lane i in row k):
+ *     ended   = done[k] != 0 || (truncated != NULL && truncated[k] != 0)
+ *     x_next  = (final_obs != NULL && ended) ? final_obs[k] : obs[k]
+ *     v_next  = done[k] != 0 ? +0.0f : V(x_next)
+ *     v_cur   = V(k == 0 ? start_obs : obs[k-1])
+ *     delta   = fmaf(gamma, v_next, reward[k]) - v_cur
+ *     carry   = ended ? +0.0f : A[k+1]
+ *     A[k]    = fmaf(gl, carry, delta);   R[k] = A[k] + v_cur;   values[k] = v_cur
+ * What follows from the selects: an unselected final_obs element reaches no output (that buffer is written on ended lane-steps only
+ * and otherwise holds whatever bytes it held); a NaN A[k+1] behind an episode end reaches no output; a NaN V(obs[k]) on a done step
+ * reaches no output.  final_obs == NULL is for records of engines without auto-reset, where the `obs` row already holds the final
+ * observation.  With no critic, gamma = lambda = 1, R is the reward-to-go within the episode.
+ *   - gymrs_set_critic, gymrs_get_critic and gymrs_critic_weights_ptr are gymrs_set_policy, gymrs_get_policy and
+ *     gymrs_policy_weights_ptr for the critic set: the copy happens in stream order and the call waits for its own copy; d == NULL
+ *     removes the critic; non-finite weights are legal; GYMRS_EINVAL: Pendulum, hidden > 64, zero counts, NULL weights, (get, ptr) no
+ *     critic set.  The critic touches no lane state, tick, statistics or the fitness / evaluation tables, survives gymrs_set_policy
+ *     and is NOT part of gymrs_engine_clone or of a snapshot.  Through the zero-copy view a learner on the engine's stream writes the
+ *     critic in place and the next launch reads it; valid until the next gymrs_set_critic or destroy.
+ *   - gymrs_critic_value: host only, no GPU (like gymrs_sample_draw): the definition as code.  *v = V(obs[0..D)) under one critic of
+ *     S floats.  GYMRS_EINVAL: NULL arguments, Pendulum, hidden > 64.
+ *   - gymrs_advantages runs in the engine's stream order: a gymrs_rollout_transitions enqueued just before it needs no
+ *     synchronisation in between.  It uses the engine only for the stream, the kind, n_envs, global_env_offset and the critic set: it
+ *     reads and writes no lane array -- state, flag arrays, final observations, statistics, tick, reset log, fitness / evaluation
+ *     tables and parameter index stay bit for bit.  It writes elements [k][i] for i < n_envs only: the padding lanes [n_envs,
+ *     lane_stride) keep their bytes.  A critic set without the flag plays V = 0: the critic is opt-in per launch, as exploration is.
+ *     Without the flag no observation buffer is read.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, reserved != 0, unknown flag bits, GYMRS_ADVANTAGES_CRITIC without a
+ *     critic set (naming gymrs_set_critic), gamma or lambda NaN or outside [0, 1], NULL obs / reward / done / start_obs / advantages,
+ *     any buffer not 16-byte aligned, lane_stride < n_envs or not a multiple of 16.
+ * There is no sharded counterpart: a sharded batch refuses records already (its blocks live on several devices). */
+#define GYMRS_ADVANTAGES_CRITIC 1u
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* GYMRS_ADVANTAGES_CRITIC, nothing else */
+    float gamma, lambda;        /* finite, in [0, 1] */
+    gymrs_trajectory record;    /* by value, as in gymrs_transitions_desc; READ: obs, reward, done, truncated (may be NULL);
+                                   actions is not read and may be NULL; lane_stride >= n_envs, a multiple of 16 */
+    const float* final_obs;     /* [K][D][lane_stride] or NULL, 16-byte aligned */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    float* advantages;          /* [K][lane_stride], required */
+    float* returns;             /* [K][lane_stride] or NULL */
+    float* values;              /* [K][lane_stride] or NULL */
+    uint64_t reserved;          /* 0 */
+} gymrs_advantages_desc;        /* 112 bytes */
+gymrs_status gymrs_critic_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats);
+gymrs_status gymrs_set_critic(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host);
+gymrs_status gymrs_get_critic(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats);
+gymrs_status gymrs_critic_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats);
+gymrs_status gymrs_critic_value(gymrs_env_kind kind, uint32_t hidden, const float* weights, const float* obs, float* v);
+gymrs_status gymrs_advantages(gymrs_engine* e, const gymrs_advantages_desc* d);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

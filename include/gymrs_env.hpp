@@ -323,6 +323,47 @@ public:
                                        record, final_obs, start_obs, 0};
         check(gymrs_rollout_transitions(e_, &d));
     }
+    // advantages (gymrs_advantages): the critic set -- n_critics critics of critic_size(kind, hidden) floats back to back, lane i uses
+    // critic ((global_env_offset + i) / lanes_per_critic) % n_critics -- and the GAE(lambda) scan over a transitions record in one
+    // launch on the engine's stream; critic = true (GYMRS_ADVANTAGES_CRITIC) evaluates the critic inside the kernel, else V = 0
+    static std::uint64_t critic_size(gymrs_env_kind kind, std::uint32_t hidden)
+    {
+        std::uint64_t n = 0;
+        check(gymrs_critic_size(kind, hidden, &n));
+        return n;
+    }
+    static float critic_value(gymrs_env_kind kind, std::uint32_t hidden, const float* weights, const float* obs)
+    {
+        float v = 0.0f;
+        check(gymrs_critic_value(kind, hidden, weights, obs, &v));
+        return v;
+    }
+    void set_critic(const float* weights_host, std::uint32_t hidden, std::uint32_t n_critics, std::uint64_t lanes_per_critic)
+    {
+        const gymrs_policy_desc d{hidden, n_critics, lanes_per_critic};
+        check(gymrs_set_critic(e_, &d, weights_host));
+    }
+    void clear_critic() { check(gymrs_set_critic(e_, nullptr, nullptr)); }
+    gymrs_policy_desc critic(float* weights_out = nullptr, std::uint64_t capacity_floats = 0)
+    {
+        gymrs_policy_desc d{};
+        check(gymrs_get_critic(e_, &d, weights_out, capacity_floats));
+        return d;
+    }
+    float* critic_weights_view(std::uint64_t* n_floats = nullptr)
+    {
+        float* p = nullptr;
+        check(gymrs_critic_weights_ptr(e_, &p, n_floats));
+        return p;
+    }
+    void advantages(const gymrs_advantages_desc& d) { check(gymrs_advantages(e_, &d)); }
+    void advantages(std::uint32_t n_steps, const gymrs_trajectory& record, const float* final_obs, const float* start_obs, float* advantages_out,
+                    float* returns_out, float* values_out, float gamma, float lambda, bool critic)
+    {
+        const gymrs_advantages_desc d{n_steps, critic ? GYMRS_ADVANTAGES_CRITIC : 0u, gamma, lambda, record, final_obs, start_obs, advantages_out,
+                                      returns_out, values_out, 0};
+        check(gymrs_advantages(e_, &d));
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
