@@ -340,6 +340,22 @@ impl Engine {
         check(ffi::gymrs_advantages(self.raw, &d));
     }
 
+    /// `gymrs_policy_gradient`: ADDS the fixed-point score-function gradient of the policy set over a transitions record (or, with
+    /// `critic`, the value gradient of the critic set: `GYMRS_GRADIENT_CRITIC`) to `grad` (int64 `[n_sets][S]`; the gradient is
+    /// `grad * 2^-24`) and the (lane, parameter) pairs left out to `excluded` (u64 `[n_sets]`), in one launch on the engine's stream.
+    /// `scale` = log2(e) / temperature (policy head only); `prob` may be null and must be with `critic`.  Reads and writes no lane array.
+    ///
+    /// # Safety
+    /// Every row pointer must be a 16-byte aligned device address of the size the header names, `grad` and `excluded` 8-byte aligned,
+    /// all valid until `sync()`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn policy_gradient(&mut self, n_steps: u32, critic: bool, scale: f32, record: &ffi::Trajectory, start_obs: *const f32, coef: *const f32,
+                                  prob: *mut f32, grad: *mut i64, excluded: *mut u64) {
+        let flags = if critic { ffi::GYMRS_GRADIENT_CRITIC } else { 0 };
+        let d = ffi::GymrsGradientDesc { n_steps, flags, scale, pad_: 0, record: *record, start_obs, coef, prob, grad, excluded, reserved: 0 };
+        check(ffi::gymrs_policy_gradient(self.raw, &d));
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

@@ -164,6 +164,30 @@ pub struct GymrsAdvantagesDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_GRADIENT_CRITIC`: `gymrs_policy_gradient` takes the value gradient of the critic set (`gymrs_set_critic`) instead of the
+/// score-function gradient of the policy set.
+pub const GYMRS_GRADIENT_CRITIC: u32 = 1;
+
+/// `gymrs_gradient_desc`: what `gymrs_policy_gradient` runs (include/gymrs_amd.h "gradients"), 112 bytes: the record by value (read:
+/// `obs`, and `actions` for the policy head), `start_obs` `[D][record.lane_stride]`, `coef` and `prob` (or null)
+/// `[n_steps][record.lane_stride]`, and the tables added to: `grad` int64 `[n_sets][S]` (the gradient is `grad * 2^-24`), `excluded`
+/// u64 `[n_sets]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsGradientDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub scale: f32,
+    pub pad_: u32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub coef: *const f32,
+    pub prob: *mut f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -289,6 +313,11 @@ extern "C" {
     pub fn gymrs_critic_weights_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;
     pub fn gymrs_critic_value(kind: c_int, hidden: u32, weights: *const f32, obs: *const f32, v: *mut f32) -> c_int;
     pub fn gymrs_advantages(e: *mut GymrsEngine, d: *const GymrsAdvantagesDesc) -> c_int;
+    /// gradients over a transitions record: exact fixed-point sums per set in one launch, and one lane of them on the host
+    pub fn gymrs_policy_gradient(e: *mut GymrsEngine, d: *const GymrsGradientDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_gradient_lane(kind: c_int, hidden: u32, flags: u32, scale: f32, weights: *const f32, n_steps: u32, x: *const f32, actions: *const u8,
+                               coef: *const f32, q: *mut i64, excluded: *mut u64, prob: *mut f32) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -49,6 +49,7 @@ from .engine import TransitionsDesc
 from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
 from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
+from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -60,4 +61,5 @@ __all__ = [
     "ClosedLoopDesc", "CLOSED_LOOP_FITNESS", "CLOSED_LOOP_LANE_PARAMS", "TransitionsDesc",
     "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw", "Sampling", "CLOSED_LOOP_SAMPLE", "sample_draw",
     "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
+    "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
 ]

@@ -5,6 +5,7 @@
 #include "gymrs_evaluate.h"
 #include "gymrs_sample.h"
 #include "gymrs_advantages.h"
+#include "gymrs_gradient.h"
 
 static RcclApi g_rccl;
 
@@ -1002,6 +1003,137 @@ gymrs_status gymrs_advantages(gymrs_engine* e, const gymrs_advantages_desc* d)
     a.gl = d->gamma * d->lambda;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_advantages(e->kind, a, critic ? &e->critic : nullptr, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- gradients: the host-side lane and the launch (include/gymrs_amd.h, "gradients") ------------------------------------------------
+extern "C++" {
+namespace {
+struct HostWeights { // w(k, i) of the gymrs_gradient.h templates over one network in host memory
+    const float* w;
+    float operator()(int, uint32_t i) const { return w[i]; }
+};
+
+// One lane by the shared text: the kernels' walk with VEC = 1, chunk after chunk.
+template <int D, int A, bool CRITIC>
+void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, const float* x, const uint8_t* actions, const float* coef, int64_t* q,
+                   uint64_t* excluded, float* prob)
+{
+    const HostWeights w{weights};
+    uint64_t excl = 0;
+    auto emit = [&](uint32_t s, const float (&L)[1]) {
+        long long v;
+        if (!gradient_fixed(L[0], v)) excl += 1;
+        q[s] = v;
+    };
+    const uint32_t chunks = H == 0 ? 1 : (H + kGradientChunk - 1) / kGradientChunk;
+    for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
+        const uint32_t h0 = chunk * kGradientChunk;
+        GradientAffine<D, A, 1> aff{};
+        GradientChunk<D, A, 1> chk{};
+        float db2[A][1] = {};
+        for (uint32_t k = 0; k < K; ++k) {
+            float xs[D][1], g[A][1];
+            bool on[1] = {true};
+            for (int j = 0; j < D; ++j) xs[j][0] = x[(size_t)k * D + j];
+            if constexpr (CRITIC) {
+                g[0][0] = coef[k];
+            } else {
+                float y[A][1], pa[1];
+                const float c[1] = {coef[k]};
+                const uint8_t act[1] = {actions[k]};
+                gradient_logits<D, A, 1, 1>(w, H, xs, y);
+                gradient_policy_head<A, 1>(y, act, c, scale, g, on, pa);
+                if (prob && chunk == 0) prob[k] = pa[0];
+            }
+            if (H == 0) {
+                gradient_affine_step<D, A, 1, !CRITIC>(xs, g, on, aff);
+            } else {
+                gradient_chunk_step<D, A, 1, !CRITIC>(w, H, h0, xs, g, on, chk);
+                if (chunk == 0) gradient_bias_step<A, 1, !CRITIC>(g, on, db2);
+            }
+        }
+        if (H == 0) {
+            gradient_affine_each<D, A, 1>(aff, emit);
+        } else {
+            gradient_chunk_each<D, A, 1>(H, h0, chk, emit);
+            if (chunk == 0) gradient_bias_each<D, A, 1>(H, db2, emit);
+        }
+    }
+    *excluded = excl;
+}
+} // namespace
+} // extern "C++"
+
+gymrs_status gymrs_gradient_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float scale, const float* weights, uint32_t n_steps,
+                                 const float* x, const uint8_t* actions, const float* coef, int64_t* q, uint64_t* excluded, float* prob)
+{
+    const std::string who = "gymrs_gradient_lane";
+    if (gymrs_status st = check_discrete_env(kind, who)) return st;
+    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, who + ": hidden must be <= 64");
+    if (flags & ~GYMRS_GRADIENT_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_GRADIENT_CRITIC is the only one)");
+    const bool critic = (flags & GYMRS_GRADIENT_CRITIC) != 0;
+    if (!weights || !coef || !q || !excluded || (n_steps != 0 && !x)) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!critic && n_steps != 0 && !actions) return fail(GYMRS_EINVAL, who + ": actions is NULL (the policy head reads them)");
+    if (critic && prob) return fail(GYMRS_EINVAL, who + ": prob with GYMRS_GRADIENT_CRITIC (the critic head has no probabilities)");
+    if (!critic && !(scale >= 0.0f && scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
+    if (kind == GYMRS_CARTPOLE) {
+        if (critic)
+            gradient_lane<4, 1, true>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
+        else
+            gradient_lane<4, 2, false>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
+    } else {
+        if (critic)
+            gradient_lane<2, 1, true>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
+        else
+            gradient_lane<2, 3, false>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
+    }
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_policy_gradient(gymrs_engine* e, const gymrs_gradient_desc* d)
+{
+    const std::string who = "gymrs_policy_gradient";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, who + ": gradients are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
+    if (d->reserved != 0 || d->pad_ != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (d->flags & ~GYMRS_GRADIENT_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_GRADIENT_CRITIC is the only one)");
+    const bool critic = (d->flags & GYMRS_GRADIENT_CRITIC) != 0;
+    if (critic && !e->critic_dev) return fail(GYMRS_EINVAL, who + ": GYMRS_GRADIENT_CRITIC without a critic set on the engine (gymrs_set_critic)");
+    if (!critic && !e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
+    if (!critic && !(d->scale >= 0.0f && d->scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
+    const gymrs_trajectory& rec = d->record;
+    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
+    if (!critic && !rec.actions) return fail(GYMRS_EINVAL, who + ": record.actions is NULL (the policy head reads them)");
+    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
+    if (!d->coef) return fail(GYMRS_EINVAL, who + ": coef is NULL");
+    if (!d->grad) return fail(GYMRS_EINVAL, who + ": grad is NULL");
+    if (!d->excluded) return fail(GYMRS_EINVAL, who + ": excluded is NULL");
+    if (critic && d->prob) return fail(GYMRS_EINVAL, who + ": prob with GYMRS_GRADIENT_CRITIC (the critic head has no probabilities)");
+    const uintptr_t rows = reinterpret_cast<uintptr_t>(rec.obs) | (critic ? 0 : reinterpret_cast<uintptr_t>(rec.actions)) |
+                           reinterpret_cast<uintptr_t>(d->start_obs) | reinterpret_cast<uintptr_t>(d->coef) | reinterpret_cast<uintptr_t>(d->prob);
+    if (rows % 16 != 0) return fail(GYMRS_EINVAL, who + ": every row buffer must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d->grad) | reinterpret_cast<uintptr_t>(d->excluded)) % 8 != 0)
+        return fail(GYMRS_EINVAL, who + ": grad and excluded must be 8-byte aligned");
+    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
+    if (d->n_steps == 0) return GYMRS_OK;
+    GradientArgs a{};
+    a.obs = rec.obs;
+    a.actions = critic ? nullptr : static_cast<const uint8_t*>(rec.actions);
+    a.start_obs = d->start_obs;
+    a.coef = d->coef;
+    a.prob = d->prob;
+    a.grad = reinterpret_cast<unsigned long long*>(d->grad);
+    a.excluded = reinterpret_cast<unsigned long long*>(d->excluded);
+    a.stride = rec.lane_stride;
+    a.n = e->n;
+    a.gid0 = e->gid0;
+    a.n_steps = d->n_steps;
+    a.scale = critic ? 0.0f : d->scale;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_policy_gradient(e->kind, critic, a, critic ? e->critic : e->policy, e->stream));
     return GYMRS_OK;
 }
 

@@ -390,4 +390,21 @@ struct AdvantageArgs {
 };
 // critic == NULL: V = +0.0f everywhere (no observation is read)
 hipError_t launch_advantages(gymrs_env_kind kind, const AdvantageArgs& a, const PolicyArgs* critic, hipStream_t stream);
+// ---- gradients (gymrs_policy_gradient; gymrs_gradient.hip) ---------------------------------------------------------------------
+// A gymrs_gradient_desc as the kernel gets it by value, before the set (the policy's PolicyArgs, or the critic's).  Rows are
+// `stride` lanes apart (>= n, a multiple of 16) and 16-byte aligned; grad and excluded are 8-byte aligned and ADDED to.
+struct GradientArgs {
+    const float* obs;             // [n_steps][obs_dim][stride]; rows 0 .. n_steps - 2 are read
+    const uint8_t* actions;       // [n_steps][stride]; policy head only
+    const float* start_obs;       // [obs_dim][stride]
+    const float* coef;            // [n_steps][stride]
+    float* prob;                  // [n_steps][stride] or NULL; policy head only
+    unsigned long long* grad;     // [n_sets][S], S = the set's PolicyArgs::stride
+    unsigned long long* excluded; // [n_sets]
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    float scale; // policy head only
+};
+// critic: p is the critic set (one output, `actions`, `prob` and `scale` unused), else the policy set
+hipError_t launch_policy_gradient(gymrs_env_kind kind, bool critic, const GradientArgs& a, const PolicyArgs& p, hipStream_t stream);
 } // namespace gymrs

@@ -113,6 +113,17 @@ class AdvantagesDesc(C.Structure):
 ADVANTAGES_CRITIC = 1  # GYMRS_ADVANTAGES_CRITIC
 
 
+class GradientDesc(C.Structure):
+    """``gymrs_gradient_desc`` (include/gymrs_amd.h), 112 bytes: the record by value, two rows in, one optional row out, two tables
+    added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float), ("pad_", C.c_uint32), ("record", Trajectory),
+                ("start_obs", C.c_void_p), ("coef", C.c_void_p), ("prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p),
+                ("reserved", C.c_uint64)]
+
+
+GRADIENT_CRITIC = 1  # GYMRS_GRADIENT_CRITIC
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -249,6 +260,37 @@ def critic_value(kind: int, hidden: int, weights, obs) -> np.float32:
     fp = C.POINTER(C.c_float)
     _check(lib, lib.gymrs_critic_value(int(kind), int(hidden), w.ctypes.data_as(fp), x.ctypes.data_as(fp), C.byref(v)))
     return np.float32(v.value)
+
+
+def gradient_lane(kind: int, hidden: int, weights, x, actions, coef, *, critic: bool = False, temperature: Optional[float] = None,
+                  scale: Optional[float] = None, prob: bool = False):
+    """``gymrs_gradient_lane`` (host only, no GPU): one lane's contribution to ``gymrs_policy_gradient`` -- the definition of
+    include/gymrs_amd.h, "gradients", as code.  ``weights``: ONE policy (``policy_size`` floats) or, with ``critic``, one critic
+    (``critic_size``); ``x`` [K][D] the observation every step started from, ``actions`` [K] (ignored with ``critic``), ``coef`` [K].
+    Returns (q, excluded) or, with ``prob``, (q, excluded, prob [K]): q is int64 [S], the gradient is q * 2**-24."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    size = critic_size(kind, hidden) if critic else policy_size(kind, hidden)
+    c = np.ascontiguousarray(coef, dtype=np.float32).reshape(-1)
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if w.size != size or xs.size != c.size * _OBS_DIM[kind]:
+        raise ValueError(f"gradient_lane needs {size} weights and {_OBS_DIM[kind]} observation components per step")
+    if prob and critic:
+        raise ValueError("the critic head has no probabilities")
+    a = None
+    if not critic:
+        a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(-1)
+        if a.size != c.size:
+            raise ValueError("gradient_lane needs one action per step")
+        scale = _sampling(0, temperature, scale).scale
+    q = np.zeros(size, np.int64)
+    excluded = C.c_uint64()
+    pr = np.empty(c.size, np.float32) if prob else None
+    fp = C.POINTER(C.c_float)
+    _check(lib, lib.gymrs_gradient_lane(int(kind), int(hidden), GRADIENT_CRITIC if critic else 0, float(scale or 0.0), w.ctypes.data_as(fp), int(c.size),
+                                        xs.ctypes.data_as(fp), a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None, c.ctypes.data_as(fp),
+                                        q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), pr.ctypes.data_as(fp) if prob else None))
+    return (q, excluded.value, pr) if prob else (q, excluded.value)
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -730,6 +772,32 @@ class BatchedEngine:
         desc = AdvantagesDesc(int(n_steps), f, float(gamma), float(lam), traj, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None),
                               C.c_void_p(advantages or None), C.c_void_p(returns or None), C.c_void_p(values or None), 0)
         _check(self._lib, self._lib.gymrs_advantages(self._h, C.byref(desc)))
+
+    # -- gradients over a transitions record: exact fixed-point sums per set, one launch per head -----------------
+    def policy_gradient(self, n_steps: int, *, record, start_obs: int, coef: int, grad: int, excluded: int, prob: Optional[int] = None,
+                        critic: bool = False, temperature: Optional[float] = None, scale: Optional[float] = None,
+                        flags: Optional[int] = None) -> None:
+        """``gymrs_policy_gradient``: ADDS sum over (k, i) of coef[k][i] * grad log pi(a[k][i] | x[k][i]) per policy, as int64 fixed
+        point (the gradient is ``grad`` * 2**-24), to ``grad`` (device int64 [n_policies][policy_size]) and the number of (lane,
+        parameter) pairs left out to ``excluded`` (device uint64 [n_policies]), in one launch on the engine's stream (no sync needed
+        after ``advantages``).  ``critic`` (``GYMRS_GRADIENT_CRITIC``): sum coef * grad V(x) of the critic set instead, tables
+        [n_critics][critic_size]; ``temperature`` / ``scale`` are for the policy head only (exactly one of them), ``prob`` (device
+        f32 [n_steps][lane_stride]) receives p[a].  ``record``: a ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (only
+        ``obs`` and, for the policy head, ``actions`` are read).  The caller zeroes the tables.  Reads and writes no lane array."""
+        if record is None:
+            raise ValueError("policy_gradient needs a record")
+        if not isinstance(record, Trajectory):
+            record = dict(record)
+            for name in ("actions", "reward", "done"):
+                record.setdefault(name, 0)
+        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        f = (GRADIENT_CRITIC if critic else 0) if flags is None else int(flags)
+        s = 0.0
+        if not (f & GRADIENT_CRITIC):
+            s = _sampling(0, temperature, scale).scale
+        desc = GradientDesc(int(n_steps), f, float(s), 0, traj, C.c_void_p(start_obs or None), C.c_void_p(coef or None), C.c_void_p(prob or None),
+                            C.c_void_p(grad or None), C.c_void_p(excluded or None), 0)
+        _check(self._lib, self._lib.gymrs_policy_gradient(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

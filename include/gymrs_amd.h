@@ -718,6 +718,78 @@ gymrs_status gymrs_get_critic(gymrs_engine* e, gymrs_policy_desc* d_out, float* 
 gymrs_status gymrs_critic_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats);
 gymrs_status gymrs_critic_value(gymrs_env_kind kind, uint32_t hidden, const float* weights, const float* obs, float* v);
 gymrs_status gymrs_advantages(gymrs_engine* e, const gymrs_advantages_desc* d);
+/* Gradients: the score-function gradient of the policy set, and the value gradient of the critic set, over a transitions record in
+ * ONE launch, as exact fixed-point integers.  gymrs_policy_gradient(e, d) ADDS, for every set m (policy, or critic with
+ * GYMRS_GRADIENT_CRITIC) and every parameter s of its network,
+ *     grad[m][s] += sum over the lanes i of set m of q(i, s),     q = the fixed point of  sum over k of coef[k][i] * d/d theta_s log pi(a[k][i] | x[k][i])
+ * (critic head: of sum over k of coef[k][i] * d/d phi_s V(x[k][i])).  coef is a row the learner fills: normalised advantages give
+ * REINFORCE / A2C, V - R gives the value loss, the clipped-ratio weight gives PPO (the ratio from the `prob` row below).  All
+ * arithmetic is f32, every operation below is a single IEEE operation, fmaf = the fused multiply-add with ONE rounding, nothing is
+ * contracted or reordered, every `?:` is a select.
+ * Inputs per lane-step.  Lane i of the engine has the global id g = global_env_offset + i and uses set (g / lanes_per_policy) %
+ * n_policies (the policy's key; with the flag the critic's).  For k = 0 .. K-1 in ascending order, rows and columns as in
+ * gymrs_rollout_transitions:
+ *     x = (k == 0 ? start_obs : obs[k-1])       (the observation the action was drawn from; obs[K-1] is not read)
+ *     a = actions[k];   c = coef[k]
+ * Policy head (the default).  A = number of actions, y[0..A) = the policy's logits of x as defined in "closed-loop rollouts";
+ * p[b] = the probabilities of the sampling rule ("sampling") under d->scale: greedy, w[], total, p[b] exactly as gymrs_sample_draw
+ * computes them.
+ *     beta = scale * 0x1.62e430p-1f                                  (1 / temperature for scale = log2(e) / temperature)
+ *     cb   = c * beta
+ *     g[b] = cb * ((b == a ? 1.0f : 0.0f) - p[b])                    for b = 0 .. A-1
+ *     a lane-step with a >= A contributes nothing: every accumulator below keeps its value (a select)
+ * Critic head (GYMRS_GRADIENT_CRITIC).  The network is the critic of "advantages": one output, A = 1, g[0] = c; actions and scale are
+ * not read.
+ * Backward pass.  Every parameter of every lane has its own f32 accumulator, +0.0f before k = 0, updated once per step:
+ *     H == 0:  dW[b][j] = fmaf(g[b], x[j], dW[b][j]);   db[b] = db[b] + g[b]
+ *     H  > 0:  db2[b] = db2[b] + g[b], and per unit h = 0 .. H-1, with z and r of unit h as in the forward definition:
+ *              dW2[b][h] = fmaf(g[b], r, dW2[b][h])
+ *              e  = g[0] * W2[0][h];   for b = 1 .. A-1: e = fmaf(g[b], W2[b][h], e)
+ *              dz = (z > 0.0f) ? e : 0.0f
+ *              db1[h] = db1[h] + dz;   dW1[h][j] = fmaf(dz, x[j], dW1[h][j])
+ * The table of one set has the layout of its weights (gymrs_policy_size / gymrs_critic_size): parameter s of the table is float s.
+ * Fixed point, once per (lane, parameter) after the walk, L = the lane's f32 sum:
+ *     L finite and |L| < 2^30:  q = (int64) rint((double)L * 16777216.0)      (scaling and rounding to nearest even, exact in f64)
+ *                               grad[set][s] += q   modulo 2^64
+ *     otherwise:                nothing is added, excluded[set] += 1          (one per (lane, parameter) pair left out)
+ * The gradient is grad * 2^-24.  Every lane's contribution is an integer before lanes are summed, so the table is exact: it does
+ * not depend on wave or block order, on lanes per work-item or on how the kernels cut the hidden layer; it is additive over engines
+ * (k blocks of a batch with their global_env_offset, adding into one table, equal one engine) and over launches: the call ADDS to
+ * grad and excluded, and the caller zeroes them.
+ * prob (policy head only, may be NULL): prob[k][i] = p[a], or +0.0f where a >= A, for i < n_envs: the bits gymrs_sample_draw gives
+ * for those logits.  A PPO learner takes its ratio from it; no logarithm enters the rule.
+ *   - gymrs_policy_gradient runs in the engine's stream order: a gymrs_advantages enqueued just before it needs no synchronisation
+ *     in between.  It uses the engine only for the stream, the kind, n_envs, global_env_offset and the policy (critic) set: it reads
+ *     and writes no lane array.  It reads lanes i < n_envs of every row only: the padding lanes [n_envs, lane_stride) may hold
+ *     anything, NaN included, and count for nothing; of prob they keep their bytes.  reward, done and truncated of the record are
+ *     not read and may be NULL.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, unknown flag bits, reserved != 0, no policy set (naming
+ *     gymrs_set_policy; with the flag no critic set, naming gymrs_set_critic), for the policy head scale NaN, infinite or negative,
+ *     NULL obs / start_obs / coef / grad / excluded, NULL actions for the policy head, prob with the flag, a row buffer not 16-byte
+ *     aligned, grad or excluded not 8-byte aligned, lane_stride < n_envs or not a multiple of 16.
+ *   - gymrs_gradient_lane: host only, no GPU (like gymrs_critic_value): the definition as code.  From ONE set's weights (S floats),
+ *     K = n_steps, one lane's x[K][D] (x[k] as defined above), actions[K] and coef[K] it SETS q[0..S) to the lane's contributions (0
+ *     for an excluded pair), *excluded to the number of excluded pairs and, when prob != NULL, prob[0..K).  flags and scale as in the
+ *     descriptor.  GYMRS_EINVAL: Pendulum, hidden > 64, unknown flag bits, NULL arguments, prob with the flag, a bad scale.
+ * There is no sharded counterpart: a sharded batch refuses records already. */
+#define GYMRS_GRADIENT_CRITIC 1u
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* GYMRS_GRADIENT_CRITIC, nothing else */
+    float scale;                /* policy head: log2(e) / temperature, finite, >= 0 (gymrs_sampling::scale); critic head: not read */
+    uint32_t pad_;              /* 0 */
+    gymrs_trajectory record;    /* by value; READ: obs, actions (policy head); reward, done, truncated are not read and may be NULL;
+                                   lane_stride >= n_envs, a multiple of 16 */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* coef;          /* [K][lane_stride], required, 16-byte aligned */
+    float* prob;                /* [K][lane_stride] or NULL; NULL with GYMRS_GRADIENT_CRITIC */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned, ADDED to */
+    uint64_t* excluded;         /* device uint64 [n_sets], ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_gradient_desc;          /* 112 bytes */
+gymrs_status gymrs_policy_gradient(gymrs_engine* e, const gymrs_gradient_desc* d);
+gymrs_status gymrs_gradient_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float scale, const float* weights, uint32_t n_steps,
+                                 const float* x, const uint8_t* actions, const float* coef, int64_t* q, uint64_t* excluded, float* prob);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

@@ -92,6 +92,17 @@ inline std::uint8_t sample_draw(const gymrs_sampling& x, std::uint32_t n_actions
     return action;
 }
 
+// One lane's contribution to gymrs_policy_gradient (gymrs_gradient_lane; host only, no GPU): q[0 .. S) is set, the number of
+// excluded (lane, parameter) pairs returned; prob (may be null, null with GYMRS_GRADIENT_CRITIC) gets p[a] of every step.  The
+// definition of include/gymrs_amd.h, "gradients", as code.
+inline std::uint64_t gradient_lane(gymrs_env_kind kind, std::uint32_t hidden, std::uint32_t flags, float scale, const float* weights, std::uint32_t n_steps,
+                                   const float* x, const std::uint8_t* actions, const float* coef, std::int64_t* q, float* prob = nullptr)
+{
+    std::uint64_t excluded = 0;
+    check(gymrs_gradient_lane(kind, hidden, flags, scale, weights, n_steps, x, actions, coef, q, &excluded, prob));
+    return excluded;
+}
+
 // ---- batched form: the shape the hot path is built for ---------------------------------------------
 class VecEnv {
 public:
@@ -363,6 +374,17 @@ public:
         const gymrs_advantages_desc d{n_steps, critic ? GYMRS_ADVANTAGES_CRITIC : 0u, gamma, lambda, record, final_obs, start_obs, advantages_out,
                                       returns_out, values_out, 0};
         check(gymrs_advantages(e_, &d));
+    }
+    // gradients (gymrs_policy_gradient): ADDS the fixed-point score-function gradient of the policy set over a transitions record --
+    // or, critic = true (GYMRS_GRADIENT_CRITIC), the value gradient of the critic set -- to grad (device int64 [n_sets][S]; the
+    // gradient is grad * 2^-24) and the (lane, parameter) pairs left out to excluded (device uint64 [n_sets]), in one launch on the
+    // engine's stream; scale = log2(e) / temperature (policy head only), prob may be null
+    void policy_gradient(const gymrs_gradient_desc& d) { check(gymrs_policy_gradient(e_, &d)); }
+    void policy_gradient(std::uint32_t n_steps, const gymrs_trajectory& record, const float* start_obs, const float* coef, std::int64_t* grad,
+                         std::uint64_t* excluded, float* prob, float scale, bool critic)
+    {
+        const gymrs_gradient_desc d{n_steps, critic ? GYMRS_GRADIENT_CRITIC : 0u, scale, 0u, record, start_obs, coef, prob, grad, excluded, 0};
+        check(gymrs_policy_gradient(e_, &d));
     }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
