@@ -63,8 +63,11 @@ __global__ __launch_bounds__(kBlock) void fill_actions_kernel(typename Env::Acti
 
 // ---------------------------------------------------------------------------------------------
 // Statistics read-out (off the hot path; one call per gymrs_stats / gymrs_stats_clear / all-reduce).
-//   L = sum over lanes of (ep_start - epoch) = total length of the episodes finished since the last reset()
-//       (episodes tile a lane's time axis, so the start tick of the open episode is all a lane has to keep),
+//   L = total length of the episodes finished since the last reset().  Episodes tile a lane's time axis, so the start tick of the
+//       open episode is all a lane has to keep: L = sum over lanes of (start of the open episode - epoch).  ep_start keeps the low 32
+//       bits of a start, and a lane's finished history outgrows 32 bits once the engine has run 2^32 ticks, so the sum is taken
+//       from the AGES of the open episodes, which do fit (an episode lasts at most 2^32 - 1 steps):
+//       L = n * (tick - epoch) - sum over lanes of (uint32_t)(tick - ep_start), with tick and epoch in 64 bits, modulo 2^64,
 //   E = finished episodes, R = sum of returns (Pendulum only; for the constant-reward envs return = +-length).
 // Read-only towards everything a step kernel touches: rows of the reset log that are not folded yet are counted where they lie (see_through_log).
 // Two launches, no atomics, no memset: stats_partial_kernel streams ep_start (one dwordx4 per work-item per pass) and
@@ -152,7 +155,7 @@ __device__ __forceinline__ void see_through_log(const PendingLog& lg, uint64_t l
     }
 }
 
-__global__ __launch_bounds__(kStatsThreads) void stats_partial_kernel(const uint32_t* __restrict__ ep_start, uint64_t n, uint32_t epoch,
+__global__ __launch_bounds__(kStatsThreads) void stats_partial_kernel(const uint32_t* __restrict__ ep_start, uint64_t n, uint32_t tick_ref,
                                                                       const unsigned long long* __restrict__ bs, uint32_t n_slots,
                                                                       unsigned long long* __restrict__ partials, const PendingLog lg)
 {
@@ -167,15 +170,15 @@ __global__ __launch_bounds__(kStatsThreads) void stats_partial_kernel(const uint
         const u4 x = v[i]; // plain, not non-temporal: see above
         uint32_t e4[4] = {x.x, x.y, x.z, x.w};
         if (through) see_through_log(lg, i << 2, 4u, e4, ep);
-        // each difference is taken in 32 bits (ticks wrap), the sum in 64
-        len += (unsigned long long)(uint32_t)(e4[0] - epoch) + (uint32_t)(e4[1] - epoch) + (uint32_t)(e4[2] - epoch) + (uint32_t)(e4[3] - epoch);
+        // the age of each open episode, taken in 32 bits (ticks wrap, ages stay below 2^32); the sum in 64
+        len += (unsigned long long)(uint32_t)(tick_ref - e4[0]) + (uint32_t)(tick_ref - e4[1]) + (uint32_t)(tick_ref - e4[2]) + (uint32_t)(tick_ref - e4[3]);
     }
     if ((n & 3u) != 0 && tid == 0) { // the ragged last group of up to three lanes
         uint32_t e4[4] = {0, 0, 0, 0};
         const uint32_t count = (uint32_t)(n & 3u);
         for (uint32_t j = 0; j < count; ++j) e4[j] = ep_start[(n4 << 2) + j];
         if (through) see_through_log(lg, n4 << 2, count, e4, ep);
-        for (uint32_t j = 0; j < count; ++j) len += (uint32_t)(e4[j] - epoch);
+        for (uint32_t j = 0; j < count; ++j) len += (uint32_t)(tick_ref - e4[j]);
     }
     // The per-wavefront slots are read AROUND the caches (system-scope loads): each slot has one writer -- its wavefront, in the stream's launches or in a chain
     // on the engine's own queue -- and this kernel may run on any XCD.
@@ -268,9 +271,10 @@ hipError_t launch_max_age(const uint32_t* ep_start, uint64_t n, uint32_t tick_re
 
 // mode 0: out4 = {sum_return, sum_length, n_episodes, n_steps} since the baseline; mode 1: the totals now become the baseline
 // (statistics cleared); mode 2: baseline = 0 (after reset(), which zeroed the counters itself; n_partials = 0).
+// span = n * (tick - epoch): the lane-steps since the reset; the partials' first word sums the ages of the open episodes.
 __global__ __launch_bounds__(kStatsMaxBlocks) void stats_finalize_kernel(const unsigned long long* __restrict__ partials, uint32_t n_partials,
-                                                                         unsigned long long* base, int mode, int reward_sign, double n_steps,
-                                                                         double* out4, volatile double* host_out4)
+                                                                         unsigned long long span, unsigned long long* base, int mode, int reward_sign,
+                                                                         double n_steps, double* out4, volatile double* host_out4)
 {
     unsigned long long len = 0, ep = 0;
     double ret = 0.0;
@@ -282,6 +286,7 @@ __global__ __launch_bounds__(kStatsMaxBlocks) void stats_finalize_kernel(const u
     }
     block_sum3<kStatsMaxBlocks / 64>(len, ep, ret);
     if (threadIdx.x != 0) return;
+    len = n_partials ? span - len : 0ull; // finished = all lane-steps since the reset - those of the open episodes (no partials: nothing is tracked)
     if (mode == 1) {
         base[0] = len;
         base[1] = ep;
@@ -312,10 +317,11 @@ hipError_t launch_stats(const StatsArgs& a, int mode, hipStream_t stream)
         const uint64_t want = (items + kStatsThreads - 1) / kStatsThreads;
         grid = (uint32_t)(want < 1 ? 1 : (want > (uint64_t)kStatsMaxBlocks ? (uint64_t)kStatsMaxBlocks : want));
         const PendingLog lg{a.log, a.log_row_words, a.log ? a.log_pending : 0u, a.log_first_tick, (uint32_t)(a.log_vec > 0 ? a.log_vec : 4)};
-        hipLaunchKernelGGL(stats_partial_kernel, dim3(grid), dim3(kStatsThreads), 0, stream, a.ep_start, a.n, a.epoch, a.block_stats,
+        hipLaunchKernelGGL(stats_partial_kernel, dim3(grid), dim3(kStatsThreads), 0, stream, a.ep_start, a.n, (uint32_t)a.tick, a.block_stats,
                            a.n_blocks, a.partials, lg);
     }
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(1), dim3(kStatsMaxBlocks), 0, stream, a.partials, grid, a.base, mode, a.reward_sign,
+    const unsigned long long span = (unsigned long long)a.n * (unsigned long long)(a.tick - a.epoch);
+    hipLaunchKernelGGL(stats_finalize_kernel, dim3(1), dim3(kStatsMaxBlocks), 0, stream, a.partials, grid, span, a.base, mode, a.reward_sign,
                        a.n_steps, a.out4, a.host_out4);
     return hipGetLastError();
 }

@@ -92,6 +92,7 @@ StatsArgs stats_args(const gymrs_engine* e)
     a.ep_start = e->ep_start;
     a.n = e->n;
     a.epoch = e->epoch;
+    a.tick = e->tick;
     a.block_stats = e->block_stats;
     a.n_blocks = e->n_stat_blocks;
     a.partials = e->stats_acc;
@@ -837,7 +838,7 @@ static gymrs_status reset_lanes(gymrs_engine* e, uint64_t seed, const float* lo,
     if (e->final_obs) HIP_TRY(hipMemsetAsync(e->final_obs, 0, (size_t)final_obs_stride(e->n) * 4 * e->obs_dim, e->stream)); // no episode has ended yet
     e->tick += 1;
     e->uniform_start = e->tick;
-    e->epoch = (uint32_t)e->tick; // what reset_kernel wrote into ep_start
+    e->epoch = e->tick; // what reset_kernel wrote into ep_start
     limit_restart(e, e->tick, true); // every episode starts now; reset_kernel cleared `truncated`
     // a reset discards the open episodes and starts the statistics afresh
     HIP_TRY(hipMemsetAsync(e->block_stats, 0, (size_t)e->n_stat_blocks * 2 * sizeof(unsigned long long), e->stream));

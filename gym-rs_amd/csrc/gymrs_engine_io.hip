@@ -333,7 +333,7 @@ gymrs_status gymrs_snapshot_save(gymrs_engine* e, void* host_buf, uint64_t bytes
     h.gid0 = e->gid0;
     h.flags = e->flags;
     h.state_dim = (uint32_t)e->state_dim;
-    h.epoch = e->epoch;
+    h.epoch = (uint32_t)e->epoch;
     h.n_stat_blocks = e->n_stat_blocks;
     h.max_steps = e->max_steps;
     h.open_vec = (uint32_t)e->open_vec; // lanes per work-item the open-episode sums were last updated with
@@ -1716,7 +1716,7 @@ gymrs_status gymrs_dev_peek(gymrs_engine* e, int what, void* host_out, uint64_t 
     const void* src = nullptr;
     uint64_t size = 0;
     uint32_t info[8] = {e->n_stat_blocks, e->log_row_words, e->log_pending, (uint32_t)e->log_first_tick, (uint32_t)(e->log_first_tick >> 32),
-                        (uint32_t)e->tick, (uint32_t)(e->tick >> 32), e->epoch};
+                        (uint32_t)e->tick, (uint32_t)(e->tick >> 32), (uint32_t)e->epoch};
     switch (what) {
     case 0: src = e->block_stats; size = (uint64_t)e->n_stat_blocks * 16; break;
     case 1: src = e->ep_start; size = e->n * 4; break;

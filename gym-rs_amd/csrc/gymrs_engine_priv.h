@@ -122,7 +122,7 @@ struct gymrs_engine {
     double* stats_host_dev = nullptr;      // the device's address of it
     unsigned long long* stats_acc = nullptr;  // [kStatsPartials][3] scratch of the statistics read-out
     unsigned long long* stats_base = nullptr; // [kStatsBaseWords] the statistics BASELINE {sum of start ticks, episodes, returns} of the last gymrs_stats_clear
-    uint32_t epoch = 1;                       // ep_start value written by the last reset()
+    uint64_t epoch = 1;                       // tick the last reset() wrote into ep_start (the snapshot keeps 32 bits: a reset restarts the tick at 0)
     void* action_staging = nullptr; // for gymrs_step_host
     uint64_t seed = 0, tick = 0;
     uint64_t uniform_start = 0; // Pendulum: tick at which every lane's current episode started

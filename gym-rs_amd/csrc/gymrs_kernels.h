@@ -262,10 +262,11 @@ constexpr int kStatsPartials = 256; // workgroups of the statistics read-out (= 
 struct StatsArgs {
     const uint32_t* ep_start;
     uint64_t n;
-    uint32_t epoch;    // value reset() wrote into ep_start
+    uint64_t epoch;    // the tick reset() wrote into ep_start (all 64 bits of it: ep_start keeps the low 32)
+    uint64_t tick;     // the engine tick now: no episode started after it, and an open one is younger than 2^32 steps
     const unsigned long long* block_stats;
     uint32_t n_blocks;
-    unsigned long long* partials; // [kStatsPartials][3] scratch: one {L, E, R} triple per workgroup of the read-out
+    unsigned long long* partials; // [kStatsPartials][3] scratch: one {sum of open ages, E, R} triple per workgroup of the read-out
     unsigned long long* base; // [kStatsBaseWords] {L, E, R (f64 bits)} at the last stats_clear: the BASELINE a read-out subtracts (see launch_stats)
     // the reset log's rows that are not folded yet: the read-out looks THROUGH them (read-only) instead of folding them first
     const unsigned long long* log;

@@ -876,7 +876,12 @@ gymrs_status gymrs_params_from_json(gymrs_env_kind kind, const char* json, void*
  * `rng.gen_range(0..=1)` of examples/cartpole.rs:19, generated on the device so no PCIe traffic
  * sits in a timed loop.  Philox stream 1, key = seed, counter = (global id, t). */
 gymrs_status gymrs_fill_actions(gymrs_engine* e, void* actions_dev, uint64_t seed, uint64_t t);
-/* Engine tick (number of reset()/step() calls since the last seeded reset) and current seed. */
+/* Engine tick (number of reset()/step() calls since the last seeded reset) and current seed.
+ * Tick range: the tick is a 64-bit count; gymrs_reset restarts it at 0, snapshots and clones carry it.  Every random draw of a step
+ * (re-arm, exploration, sampling) is keyed by its low 48 bits, so ticks 2^48 apart repeat draws.  The statistics are exact for any
+ * tick below 2^48: lengths are summed modulo 2^64 lane-steps, from the 64-bit tick and the ages of the open episodes.  The episode
+ * clocks keep 32 bits per lane: one episode may last at most 2^32 - 1 steps (an engine without GYMRS_TIME_LIMIT whose lane never
+ * terminates for 2^32 steps is outside that range).  tests/test_gpu_high_tick.py steps every tick-keyed path across tick 2^32. */
 gymrs_status gymrs_get_tick(gymrs_engine* e, uint64_t* tick, uint64_t* seed);
 /* Kernel tuning knobs for benchmarks; results never depend on them.  lanes_per_thread: 4 (default) or 8
  * lanes per work-item (16 was measured 4x slower everywhere and was removed in ABI 2).  memory_hint: 0 = automatic (every access non-temporal while one step's traffic is

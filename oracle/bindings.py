@@ -261,6 +261,10 @@ class Twin:
         L.twin_get_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.twin_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.twin_stats_clear.argtypes = [C.c_void_p]
+        L.twin_shift_time.argtypes = [C.c_void_p, C.c_uint64]
+        L.twin_shift_time.restype = None
+        L.twin_tick.restype = C.c_uint64
+        L.twin_tick.argtypes = [C.c_void_p]
         L.twin_invalid_count.restype = C.c_uint64
         L.twin_invalid_count.argtypes = [C.c_void_p]
         L.twin_fill_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
@@ -346,6 +350,14 @@ class TwinEngine:
 
     def stats_clear(self):
         self.lib.twin_stats_clear(self.h)
+
+    def shift_time(self, delta: int) -> None:
+        """The twin after ``delta`` more ticks in which every lane's finished history grew by ``delta`` (twin_shift_time)."""
+        assert 0 <= delta < 1 << 64
+        self.lib.twin_shift_time(self.h, delta)
+
+    def tick(self) -> int:
+        return int(self.lib.twin_tick(self.h))
 
     def invalid_count(self) -> int:
         return self.lib.twin_invalid_count(self.h)

@@ -159,6 +159,23 @@ void twin_stats_clear(twin_engine* e)
     e->n_episodes = 0;
 }
 
+// The twin as it stands after `delta` more ticks in which every lane's FINISHED history grew by `delta` steps and no
+// episode more was counted: tick (64 bits) and every episode start (mod 2^32) move forward, so each open episode keeps its
+// age, and -- where statistics are kept -- the 64-bit length sum gains n * delta (the return sum follows with the env's sign; Pendulum's is a sum of
+// rewards and stays).  The twin keeps no separate uniform episode clock for Pendulum: its lanes carry ep_start like the
+// others.  Tests use it next to a patched engine snapshot to reach ticks beyond 2^32 without stepping there.
+void twin_shift_time(twin_engine* e, uint64_t delta)
+{
+    e->tick += delta;
+    for (uint64_t i = 0; i < e->n; ++i) e->ep_start[i] += (uint32_t)delta;
+    if (!((e->flags & GYMRS_AUTO_RESET) && (e->flags & GYMRS_TRACK_STATS))) return; // no statistics are kept
+    e->sum_length += e->n * delta;
+    if (e->kind == GYMRS_CARTPOLE) e->sum_return += (double)e->n * (double)delta;
+    else if (e->kind == GYMRS_MOUNTAIN_CAR) e->sum_return -= (double)e->n * (double)delta;
+}
+
+uint64_t twin_tick(const twin_engine* e) { return e->tick; }
+
 // One engine step over host action arrays (u8, or f32 for Pendulum).
 void twin_step(twin_engine* e, const void* actions)
 {

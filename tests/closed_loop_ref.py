@@ -128,11 +128,12 @@ def final_obs_after(tw0, state, act):
     return tw0.get_obs()
 
 
-def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, reset_seed, schedule, prepare=None):
+def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, reset_seed, schedule, prepare=None, tick0=1):
     """What an engine of n lanes at global offset gid0 holds after each launch of `schedule` (steps per launch) of closed-loop
     stepping from reset(reset_seed).  `weights`: one policy set, or a list of one set per launch (a learner rewriting them between
     launches).  `prepare(state, first)` (optional) returns the start state to use in place of the reset state `state`, whose column
-    i is lane first + i of the batch; the caller applies the same function to the engine.
+    i is lane first + i of the batch; the caller applies the same function to the engine.  tick0 (default 1: the tick a reset leaves)
+    is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.
 
     Returns one SimpleNamespace per launch:
       state, obs, reward, done, truncated, stats, tick   as the engine's getters return them (twin with flags & ~F; tick counts the
@@ -156,12 +157,14 @@ def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, r
     tw.reset(reset_seed)
     if prepare is not None:
         tw.set_state(prepare(tw.get_state(), 0))
+    if tick0 != 1:
+        tw.shift_time(tick0 - 1)
     start = tw.get_state()
     final = np.zeros((d, n), np.float32)
     episodes = np.zeros(n, np.int64)
     seen = np.zeros((n_act, n), bool)
     disagree = np.zeros(n, bool)
-    tick = 1
+    tick = tick0
     out = []
     for steps, w in zip(schedule, sets):
         w = np.ascontiguousarray(w, np.float32).reshape(-1, size_of(kind, hidden))
@@ -255,8 +258,8 @@ def case(kind, shape, flags, hidden, params):
                            classes=wave_classes(n, vec, gid0, N_POLICIES, lpp))
 
 
-def run_case(c):
-    return reference(c.kind, c.n, c.gid0, c.params, c.flags, c.weights, c.hidden, c.lanes_per_policy, c.reset_seed, c.schedule, c.prepare)
+def run_case(c, tick0=1):
+    return reference(c.kind, c.n, c.gid0, c.params, c.flags, c.weights, c.hidden, c.lanes_per_policy, c.reset_seed, c.schedule, c.prepare, tick0)
 
 
 def worth_comparing(c, ref):

@@ -142,21 +142,22 @@ class Run:
     (`count=False` leaves a launch out); and, for tests/test_explore_ref.py, explored [steps][n] (bool) and greedy [steps][n]
     (the policy's action; 255 where the policy was not consulted)."""
 
-    def __init__(self, c, prepare=None, weights=None):
+    def __init__(self, c, prepare=None, weights=None, tick0=1):
         self.c = c
+        self.tick0 = tick0  # the engine tick the first step starts from (1: right after a reset; else tests/time_shift.py)
         self.weights = c.weights if weights is None else weights
         self.explore = None
         self.fitness = np.zeros((c.n_policies, 4), np.int64)
         self.gids = as_u64([c.gid0 + i for i in range(c.n)])
         self._explored, self._greedy = [], []
         self.ref = lp.TableReference(c.kind, c.n, c.gid0, c.rows, c.index, c.flags, c.reset_seed, actions=self._actions,
-                                     prepare=prepare if prepare is not None else c.prepare)
+                                     prepare=prepare if prepare is not None else c.prepare, tick0=tick0)
         self.start_state = self.ref.state.copy()
 
     def _actions(self, t, obs):
         c = self.c
         tick = self.ref.tick  # the engine tick this step starts from: the reset took it to 1
-        assert tick == 1 + t
+        assert tick == self.tick0 + t
         seed, threshold = self.explore if self.explore is not None else (0, 0)
         if threshold < EXPLORE_ONE:
             greedy = cl.policy_ref(c.kind, c.hidden, self.weights, c.lanes_per_policy, c.gid0, obs)
@@ -183,10 +184,10 @@ class Run:
                                explored=np.stack(self._explored[first:]), greedy=np.stack(self._greedy[first:]))
 
 
-def run_case(c, prepare=None, weights=None):
+def run_case(c, prepare=None, weights=None, tick0=1):
     """One SimpleNamespace per launch of c.schedule, every launch exploring under (c.seed, c.threshold); the first also has
     start_state"""
-    run = Run(c, prepare, weights)
+    run = Run(c, prepare, weights, tick0)
     out = [run.launch(steps, (c.seed, c.threshold)) for steps in c.schedule]
     out[0].start_state = run.start_state
     return out

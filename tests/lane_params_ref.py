@@ -112,7 +112,8 @@ class TableReference:
 
     actions(t, obs) -> uint8[n] gives the actions of step t (counted from 0 since the reset) for the current observations
     `obs`; the default is the random policy fill_actions(action_seed, t).  prepare(state) (optional) returns the start state to
-    use in place of the reset state; the caller applies the same function to the engine.
+    use in place of the reset state; the caller applies the same function to the engine.  tick0 (default 1: the tick a reset
+    leaves) is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.
 
     After any number of step() calls the attributes are what the engine's getters return:
       state, obs, reward, done, truncated, tick (counts the reset and every step)
@@ -123,7 +124,7 @@ class TableReference:
     records [steps] keeps obs, actions, reward, done, truncated of every step (what a recording rollout writes) and
     ended_by[2][K] counts per row the lanes that terminated / were truncated."""
 
-    def __init__(self, kind, n, gid0, rows, index, flags, reset_seed, action_seed=0, actions=None, prepare=None):
+    def __init__(self, kind, n, gid0, rows, index, flags, reset_seed, action_seed=0, actions=None, prepare=None, tick0=1):
         assert len(rows) >= 1 and all(r.max_episode_steps == rows[0].max_episode_steps for r in rows)
         self.kind, self.n, self.gid0, self.rows, self.flags = kind, n, gid0, list(rows), flags
         self.index = np.array(index, np.int64)
@@ -137,6 +138,9 @@ class TableReference:
             start = prepare(self.tws[0].get_state())
             for tw in self.tws:
                 tw.set_state(start)
+        if tick0 != 1:  # the batch as time_shift.shift_engine(eng, tick0 - 1) leaves an engine right after its reset
+            for tw in self.tws:
+                tw.shift_time(tick0 - 1)
         d = DIMS[kind][0]
         self.state = self.tws[0].get_state()  # (the reset draws do not depend on the physics: every twin holds the same)
         self.obs = self.state.copy()
@@ -145,9 +149,12 @@ class TableReference:
         self.truncated = np.zeros(n, np.uint8)
         self.final = np.zeros((d, n), np.float32)
         self.stats = np.zeros(4)
-        self.tick = 1
+        if tick0 != 1 and (flags & A) and (flags & S):  # every lane's finished history grew by the shift
+            self.stats[1] = n * (tick0 - 1)
+            self.stats[0] = self.stats[1] if kind == 0 else -self.stats[1]
+        self.tick = tick0
         self.t = 0
-        self.ep_start = np.full(n, 1, np.int64)
+        self.ep_start = np.full(n, tick0, np.int64)
         self.records = []
         self.ended_by = np.zeros((2, len(rows)), np.int64)
 

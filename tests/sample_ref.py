@@ -102,14 +102,14 @@ class Run(ex.Run):
     returns what explore_ref.Run.launch returns (explored = the action taken is not the greedy one) and prob [steps][n]: the
     probability of the action taken (1 in a greedy launch)."""
 
-    def __init__(self, c, prepare=None, weights=None):
+    def __init__(self, c, prepare=None, weights=None, tick0=1):
         self._prob = []
-        super().__init__(c, prepare, weights)
+        super().__init__(c, prepare, weights, tick0)
 
     def _actions(self, t, obs):
         c = self.c
         tick = self.ref.tick  # the engine tick this step starts from: the reset took it to 1
-        assert tick == 1 + t
+        assert tick == self.tick0 + t
         if self.explore is None:
             greedy = cl.policy_ref(c.kind, c.hidden, self.weights, c.lanes_per_policy, c.gid0, obs)
             act, prob = greedy, np.ones(c.n, np.float32)
@@ -128,9 +128,9 @@ class Run(ex.Run):
         return out
 
 
-def run_case(c, prepare=None, weights=None):
+def run_case(c, prepare=None, weights=None, tick0=1):
     """One SimpleNamespace per launch of c.schedule, every launch sampling under (c.seed, c.scale); the first also has start_state"""
-    run = Run(c, prepare, weights)
+    run = Run(c, prepare, weights, tick0)
     out = [run.launch(steps, (c.seed, c.scale)) for steps in c.schedule]
     out[0].start_state = run.start_state
     return out
@@ -143,9 +143,9 @@ class TransitionsRun:
     """transitions_ref.Run over the sampling Run: launch(steps) also returns final_obs [steps][D][n] (valid where ended), ended
     [steps][n] and start_obs [D][n]."""
 
-    def __init__(self, c):
+    def __init__(self, c, tick0=1):
         self.c = c
-        self.run = Run(c)
+        self.run = Run(c, tick0=tick0)
         self.start_state = self.run.start_state
 
     def launch(self, steps, sample=None):

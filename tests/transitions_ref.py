@@ -62,9 +62,9 @@ class Run:
     """explore_ref.Run stepped one step at a time.  launch(steps) returns what explore_ref.Run.launch returns for the whole launch,
     and with it final_obs [steps][D][n] (valid where ended), ended [steps][n] (bool) and start_obs [D][n]."""
 
-    def __init__(self, c):
+    def __init__(self, c, tick0=1):
         self.c = c
-        self.run = ex.Run(c)
+        self.run = ex.Run(c, tick0=tick0)
         self.start_state = self.run.start_state
 
     def launch(self, steps, explore=None):
@@ -83,8 +83,8 @@ class Run:
         return last
 
 
-def run_case(c):
-    run = Run(c)
+def run_case(c, tick0=1):
+    run = Run(c, tick0)
     out = [run.launch(steps) for steps in c.schedule]
     out[0].start_state = run.start_state
     return out
