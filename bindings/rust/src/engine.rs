@@ -356,6 +356,22 @@ impl Engine {
         check(ffi::gymrs_policy_gradient(self.raw, &d));
     }
 
+    /// `gymrs_ppo_gradient`: `policy_gradient` for the policy head with the coefficient computed in the kernel from the `advantages`
+    /// row and the `old_prob` row under the clip range `[clip_low, clip_high]`: ADDS the gradient of PPO's clipped objective (to
+    /// ascend) to `grad` and `excluded` and, when `counts` (u64 `[n_sets][2]`) is not null, the lane-steps seen and cut.  `prob` may be
+    /// null and may not be `old_prob`.  Reads and writes no lane array.
+    ///
+    /// # Safety
+    /// Every row pointer must be a 16-byte aligned device address of the size the header names, `grad`, `excluded` and `counts` 8-byte
+    /// aligned, all valid until `sync()`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn ppo_gradient(&mut self, n_steps: u32, scale: f32, clip_low: f32, clip_high: f32, record: &ffi::Trajectory, start_obs: *const f32,
+                               advantages: *const f32, old_prob: *const f32, prob: *mut f32, grad: *mut i64, excluded: *mut u64, counts: *mut u64) {
+        let d = ffi::GymrsPpoDesc { n_steps, flags: 0, scale, clip_low, clip_high, pad_: 0, record: *record, start_obs, advantages, old_prob, prob,
+                                    grad, excluded, counts, reserved: 0 };
+        check(ffi::gymrs_ppo_gradient(self.raw, &d));
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

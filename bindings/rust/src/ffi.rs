@@ -188,6 +188,29 @@ pub struct GymrsGradientDesc {
     pub reserved: u64,
 }
 
+/// `gymrs_ppo_desc`: what `gymrs_ppo_gradient` runs (include/gymrs_amd.h "clipped surrogate"), 136 bytes: `gymrs_gradient_desc` for the
+/// policy head with the clip range, the `advantages` and `old_prob` rows in place of `coef`, and `counts` u64 `[n_sets][2]` (or null):
+/// the lane-steps seen and the lane-steps cut, added to.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsPpoDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub scale: f32,
+    pub clip_low: f32,
+    pub clip_high: f32,
+    pub pad_: u32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub advantages: *const f32,
+    pub old_prob: *const f32,
+    pub prob: *mut f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub counts: *mut u64,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -318,6 +341,12 @@ extern "C" {
     #[allow(clippy::too_many_arguments)]
     pub fn gymrs_gradient_lane(kind: c_int, hidden: u32, flags: u32, scale: f32, weights: *const f32, n_steps: u32, x: *const f32, actions: *const u8,
                                coef: *const f32, q: *mut i64, excluded: *mut u64, prob: *mut f32) -> c_int;
+    /// the clipped surrogate (PPO) over a transitions record in one launch, and one lane of it on the host
+    pub fn gymrs_ppo_gradient(e: *mut GymrsEngine, d: *const GymrsPpoDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_ppo_lane(kind: c_int, hidden: u32, scale: f32, clip_low: f32, clip_high: f32, weights: *const f32, n_steps: u32, x: *const f32,
+                          actions: *const u8, advantages: *const f32, old_prob: *const f32, q: *mut i64, excluded: *mut u64, counts: *mut u64,
+                          prob: *mut f32) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -50,6 +50,7 @@ from .engine import Exploration, CLOSED_LOOP_EXPLORE, explore_draw
 from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
+from .engine import PpoDesc, ppo_lane
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -62,4 +63,5 @@ __all__ = [
     "Exploration", "CLOSED_LOOP_EXPLORE", "explore_draw", "Sampling", "CLOSED_LOOP_SAMPLE", "sample_draw",
     "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
+    "PpoDesc", "ppo_lane",
 ]

@@ -105,6 +105,10 @@ SIGNATURES = {
     "gymrs_policy_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_gradient_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p,
                                       C.POINTER(C.c_int64), u64p, f32p]),
+    # the clipped surrogate over a transitions record (gymrs_ppo_desc 136 B) and the host-only lane
+    "gymrs_ppo_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_ppo_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p, f32p,
+                                 C.POINTER(C.c_int64), u64p, u64p, f32p]),
     # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

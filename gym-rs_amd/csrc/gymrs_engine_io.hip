@@ -1014,11 +1014,19 @@ struct HostWeights { // w(k, i) of the gymrs_gradient.h templates over one netwo
     float operator()(int, uint32_t i) const { return w[i]; }
 };
 
+// What "clipped surrogate" adds to a lane: coef is then the advantages row
+struct PpoLane {
+    const float* old_prob;
+    float clip_low, clip_high;
+    uint64_t* counts; // [2], SET
+};
+
 // One lane by the shared text: the kernels' walk with VEC = 1, chunk after chunk.
 template <int D, int A, bool CRITIC>
 void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, const float* x, const uint8_t* actions, const float* coef, int64_t* q,
-                   uint64_t* excluded, float* prob)
+                   uint64_t* excluded, float* prob, const PpoLane* ppo = nullptr)
 {
+    uint64_t seen = 0, ncut = 0;
     const HostWeights w{weights};
     uint64_t excl = 0;
     auto emit = [&](uint32_t s, const float (&L)[1]) {
@@ -1043,7 +1051,17 @@ void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, co
                 const float c[1] = {coef[k]};
                 const uint8_t act[1] = {actions[k]};
                 gradient_logits<D, A, 1, 1>(w, H, xs, y);
-                gradient_policy_head<A, 1>(y, act, c, scale, g, on, pa);
+                if (ppo) {
+                    const float po[1] = {ppo->old_prob[k]};
+                    bool cut[1];
+                    gradient_ppo_head<A, 1>(y, act, c, po, scale, ppo->clip_low, ppo->clip_high, g, on, pa, cut);
+                    if (chunk == 0) {
+                        seen += on[0] ? 1 : 0;
+                        ncut += cut[0] ? 1 : 0;
+                    }
+                } else {
+                    gradient_policy_head<A, 1>(y, act, c, scale, g, on, pa);
+                }
                 if (prob && chunk == 0) prob[k] = pa[0];
             }
             if (H == 0) {
@@ -1061,6 +1079,16 @@ void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, co
         }
     }
     *excluded = excl;
+    if (ppo && ppo->counts) {
+        ppo->counts[0] = seen;
+        ppo->counts[1] = ncut;
+    }
+}
+
+// 0 <= low <= 1 <= high, finite (false for a NaN)
+bool ppo_bounds_ok(float low, float high)
+{
+    return low >= 0.0f && low <= 1.0f && high >= 1.0f && high <= std::numeric_limits<float>::max();
 }
 } // namespace
 } // extern "C++"
@@ -1134,6 +1162,76 @@ gymrs_status gymrs_policy_gradient(gymrs_engine* e, const gymrs_gradient_desc* d
     a.scale = critic ? 0.0f : d->scale;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_policy_gradient(e->kind, critic, a, critic ? e->critic : e->policy, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- clipped surrogate: the host-side lane and the launch (include/gymrs_amd.h, "clipped surrogate") -------------------------------
+gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
+                            const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
+                            uint64_t counts[2], float* prob)
+{
+    const std::string who = "gymrs_ppo_lane";
+    if (gymrs_status st = check_discrete_env(kind, who)) return st;
+    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, who + ": hidden must be <= 64");
+    if (!weights || !advantages || !old_prob || !q || !excluded || (n_steps != 0 && (!x || !actions))) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (prob && prob == old_prob) return fail(GYMRS_EINVAL, who + ": prob and old_prob may not alias");
+    if (!(scale >= 0.0f && scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
+    if (!ppo_bounds_ok(clip_low, clip_high)) return fail(GYMRS_EINVAL, who + ": clip bounds must be finite with 0 <= clip_low <= 1 <= clip_high");
+    const PpoLane ppo{old_prob, clip_low, clip_high, counts};
+    if (kind == GYMRS_CARTPOLE)
+        gradient_lane<4, 2, false>(hidden, scale, weights, n_steps, x, actions, advantages, q, excluded, prob, &ppo);
+    else
+        gradient_lane<2, 3, false>(hidden, scale, weights, n_steps, x, actions, advantages, q, excluded, prob, &ppo);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d)
+{
+    const std::string who = "gymrs_ppo_gradient";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
+        return fail(GYMRS_EINVAL, who + ": gradients are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
+    if (d->reserved != 0 || d->pad_ != 0) return fail(GYMRS_EINVAL, who + ": reserved and pad_ must be 0");
+    if (d->flags != 0) return fail(GYMRS_EINVAL, who + ": unknown flag bits (flags must be 0)");
+    if (!e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
+    if (!(d->scale >= 0.0f && d->scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
+    if (!ppo_bounds_ok(d->clip_low, d->clip_high)) return fail(GYMRS_EINVAL, who + ": clip bounds must be finite with 0 <= clip_low <= 1 <= clip_high");
+    const gymrs_trajectory& rec = d->record;
+    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
+    if (!rec.actions) return fail(GYMRS_EINVAL, who + ": record.actions is NULL (the policy head reads them)");
+    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
+    if (!d->advantages) return fail(GYMRS_EINVAL, who + ": advantages is NULL");
+    if (!d->old_prob) return fail(GYMRS_EINVAL, who + ": old_prob is NULL");
+    if (!d->grad) return fail(GYMRS_EINVAL, who + ": grad is NULL");
+    if (!d->excluded) return fail(GYMRS_EINVAL, who + ": excluded is NULL");
+    if (d->prob == d->old_prob) return fail(GYMRS_EINVAL, who + ": prob and old_prob may not alias");
+    const uintptr_t rows = reinterpret_cast<uintptr_t>(rec.obs) | reinterpret_cast<uintptr_t>(rec.actions) | reinterpret_cast<uintptr_t>(d->start_obs) |
+                           reinterpret_cast<uintptr_t>(d->advantages) | reinterpret_cast<uintptr_t>(d->old_prob) | reinterpret_cast<uintptr_t>(d->prob);
+    if (rows % 16 != 0) return fail(GYMRS_EINVAL, who + ": every row buffer must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d->grad) | reinterpret_cast<uintptr_t>(d->excluded) | reinterpret_cast<uintptr_t>(d->counts)) % 8 != 0)
+        return fail(GYMRS_EINVAL, who + ": grad, excluded and counts must be 8-byte aligned");
+    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
+    if (d->n_steps == 0) return GYMRS_OK;
+    PpoArgs a{};
+    a.g.obs = rec.obs;
+    a.g.actions = static_cast<const uint8_t*>(rec.actions);
+    a.g.start_obs = d->start_obs;
+    a.g.coef = d->advantages;
+    a.g.prob = d->prob;
+    a.g.grad = reinterpret_cast<unsigned long long*>(d->grad);
+    a.g.excluded = reinterpret_cast<unsigned long long*>(d->excluded);
+    a.g.stride = rec.lane_stride;
+    a.g.n = e->n;
+    a.g.gid0 = e->gid0;
+    a.g.n_steps = d->n_steps;
+    a.g.scale = d->scale;
+    a.old_prob = d->old_prob;
+    a.counts = reinterpret_cast<unsigned long long*>(d->counts);
+    a.clip_low = d->clip_low;
+    a.clip_high = d->clip_high;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_ppo_gradient(e->kind, a, e->policy, e->stream));
     return GYMRS_OK;
 }
 

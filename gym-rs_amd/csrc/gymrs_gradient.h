@@ -9,6 +9,9 @@
 // table of one set has the same layout.  The accumulators of a hidden layer do not fit in registers, so its units are taken
 // kGradientChunk at a time: a chunk owns the sums of dW1, db1 and dW2 of its units (db2 belongs to chunk 0), and every sum is the
 // same sequence of operations whichever chunk size is chosen.
+//
+// "clipped surrogate" (gymrs_ppo_gradient, gymrs_ppo_lane) is the policy head with its coefficient computed here: ppo_coefficient,
+// gradient_ppo_head.
 #pragma once
 #include "gymrs_sample.h"
 
@@ -78,6 +81,46 @@ GYMRS_HD void gradient_policy_head(const float (&y)[A][VEC], const uint8_t (&act
             pa[k] = hit ? p : pa[k];
         }
         on[k] = act[k] < (uint8_t)A;
+    }
+}
+
+// The coefficient of "clipped surrogate": one divide, the compares (false on NaN), a select, one multiply.  cut = the lane-step is
+// outside the clip range on the side its advantage pushes to: it adds nothing.
+GYMRS_HD float ppo_coefficient(float adv, float po, float pa, float clip_low, float clip_high, bool& cut)
+{
+    const float ratio = pa / po;
+    cut = (adv > 0.0f && ratio > clip_high) || (adv < 0.0f && ratio < clip_low);
+    return cut ? 0.0f : adv * ratio;
+}
+
+// The policy head of "clipped surrogate": gradient_policy_head with c = ppo_coefficient(adv, po, pa), which needs pa before g.
+// cut[k] is set for a lane-step with `on` only: one that is not `on` is not counted.
+template <int A, int VEC>
+GYMRS_HD void gradient_ppo_head(const float (&y)[A][VEC], const uint8_t (&act)[VEC], const float (&adv)[VEC], const float (&po)[VEC], float scale,
+                                float clip_low, float clip_high, float (&g)[A][VEC], bool (&on)[VEC], float (&pa)[VEC], bool (&cut)[VEC])
+{
+    const float beta = scale * 0x1.62e430p-1f;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        float yl[A], wt[A], p[A];
+#pragma unroll
+        for (int b = 0; b < A; ++b) yl[b] = y[b][k];
+        const uint32_t greedy = sample_greedy(yl, A);
+        sample_weights(yl, A, greedy, scale, wt);
+        const float total = sample_total(wt, A);
+        pa[k] = 0.0f;
+#pragma unroll
+        for (int b = 0; b < A; ++b) {
+            p[b] = sample_prob(wt, total, greedy, (uint32_t)b);
+            pa[k] = (act[k] == (uint8_t)b) ? p[b] : pa[k];
+        }
+        on[k] = act[k] < (uint8_t)A;
+        bool out;
+        const float c = ppo_coefficient(adv[k], po[k], pa[k], clip_low, clip_high, out);
+        const float cb = c * beta;
+#pragma unroll
+        for (int b = 0; b < A; ++b) g[b][k] = cb * ((act[k] == (uint8_t)b ? 1.0f : 0.0f) - p[b]);
+        cut[k] = on[k] && out;
     }
 }
 

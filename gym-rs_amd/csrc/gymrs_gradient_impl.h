@@ -12,6 +12,10 @@
 // `prob`.  After the walk every sum becomes its fixed-point integer (gradient_fixed) and is added to the table: a wave whose lanes
 // share one set sums in integers first (wave_sum_u64) and issues one atomic per parameter, a gathered wave one per lane and
 // parameter.  Integer adds commute: the table does not depend on the order.
+//
+// gymrs_ppo_gradient ("clipped surrogate") is the policy head with PPO = true: the coefficient of a lane-step comes from the
+// advantages row (in the `coef` slot), one more row (old_prob) and the p[a] the head already holds, and chunk 0 counts the lane-steps
+// and the cut ones per set.  The eight kernels above are compiled without any of it (if constexpr).
 #pragma once
 #include "gymrs_gradient.h"
 #include "gymrs_policy.h"
@@ -60,11 +64,37 @@ struct GradientSink {
             for (int k = 0; k < VEC; ++k) atomic_add_nonzero(excluded + pol[k], (unsigned long long)excl[k]);
         }
     }
+    // counts[set][0] += the lane-steps seen, counts[set][1] += the cut ones: per lane at most K < 2^32 each, the wave's sum in 64 bits
+    __device__ __forceinline__ void count(unsigned long long* counts, const uint32_t (&seen)[VEC], const uint32_t (&cut)[VEC])
+    {
+        if constexpr (UNI) {
+            unsigned long long s = 0, c = 0;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                s += live[k] ? seen[k] : 0u;
+                c += live[k] ? cut[k] : 0u;
+            }
+            const unsigned long long ts = wave_sum_u64(s), tc = wave_sum_u64(c);
+            if ((threadIdx.x & 63u) == 0) {
+                atomic_add_nonzero(counts + (uint64_t)pol[0] * 2, ts);
+                atomic_add_nonzero(counts + (uint64_t)pol[0] * 2 + 1, tc);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                atomic_add_nonzero(counts + (uint64_t)pol[k] * 2, live[k] ? (unsigned long long)seen[k] : 0ull);
+                atomic_add_nonzero(counts + (uint64_t)pol[k] * 2 + 1, live[k] ? (unsigned long long)cut[k] : 0ull);
+            }
+        }
+    }
 };
 
-template <class Env, bool CRITIC, bool HID, bool UNI, bool FULL>
-__device__ __forceinline__ void gradient_block(const GradientArgs& a, const PolicyArgs& p, const uint32_t (&pol)[4], uint64_t base)
+// PPO: x != NULL holds what "clipped surrogate" adds to the policy head (a.coef is its advantages row)
+template <class Env, bool CRITIC, bool HID, bool UNI, bool FULL, bool PPO>
+__device__ __forceinline__ void gradient_block(const GradientArgs& a, const PolicyArgs& p, const uint32_t (&pol)[4], uint64_t base,
+                                               [[maybe_unused]] const PpoArgs* x_)
 {
+    static_assert(!(PPO && CRITIC), "the clipped surrogate is a policy head");
     constexpr int VEC = 4, D = Env::kState, A = CRITIC ? 1 : (int)Env::kActions;
     constexpr bool NT = !HID; // an affine launch reads every row once; the chunks of a hidden one read them again
     constexpr bool MASK = !CRITIC;
@@ -80,15 +110,19 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
 
     Vec<float, VEC> x[D], cf;
     Vec<uint8_t, VEC> ac{};
+    [[maybe_unused]] Vec<float, VEC> op{};
+    [[maybe_unused]] uint32_t seen[VEC] = {}, ncut[VEC] = {};
 #pragma unroll
     for (int j = 0; j < D; ++j) x[j] = load_vec<float, VEC, NT>(a.start_obs + (uint64_t)j * stride, base, n, FULL, 0.0f);
     cf = load_vec<float, VEC, NT>(a.coef, base, n, FULL, 0.0f);
     if constexpr (!CRITIC) ac = load_vec<uint8_t, VEC, NT>(a.actions, base, n, FULL, uint8_t(0));
+    if constexpr (PPO) op = load_vec<float, VEC, NT>(x_->old_prob, base, n, FULL, 0.0f);
 
     for (uint32_t k = 0; k < K; ++k) {
         // row k + 1 (its observation is obs[k]), before the arithmetic of row k
         Vec<float, VEC> xn[D], cn{};
         Vec<uint8_t, VEC> an{};
+        [[maybe_unused]] Vec<float, VEC> opn{};
 #pragma unroll
         for (int j = 0; j < D; ++j) xn[j] = Vec<float, VEC>{};
         if (k + 1 < K) {
@@ -96,6 +130,7 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
             for (int j = 0; j < D; ++j) xn[j] = load_vec<float, VEC, NT>(a.obs + ((uint64_t)k * D + j) * stride, base, n, FULL, 0.0f);
             cn = load_vec<float, VEC, NT>(a.coef + (uint64_t)(k + 1) * stride, base, n, FULL, 0.0f);
             if constexpr (!CRITIC) an = load_vec<uint8_t, VEC, NT>(a.actions + (uint64_t)(k + 1) * stride, base, n, FULL, uint8_t(0));
+            if constexpr (PPO) opn = load_vec<float, VEC, NT>(x_->old_prob + (uint64_t)(k + 1) * stride, base, n, FULL, 0.0f);
         }
 
         float xs[D][VEC], g[A][VEC];
@@ -119,7 +154,20 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
             }
             // gathered: one unit's weights per lane in flight, not four units' (policy_logits)
             gradient_logits<D, A, VEC, UNI ? 4 : 1>(w, H, xs, y);
-            gradient_policy_head<A, VEC>(y, act, c, a.scale, g, on, pa);
+            if constexpr (PPO) {
+                float po[VEC];
+                bool cut[VEC];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) po[i] = op.v[i];
+                gradient_ppo_head<A, VEC>(y, act, c, po, a.scale, x_->clip_low, x_->clip_high, g, on, pa, cut);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    seen[i] += on[i] ? 1u : 0u;
+                    ncut[i] += cut[i] ? 1u : 0u;
+                }
+            } else {
+                gradient_policy_head<A, VEC>(y, act, c, a.scale, g, on, pa);
+            }
             if (a.prob && first) {
                 Vec<float, VEC> pr;
 #pragma unroll
@@ -137,6 +185,7 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
         for (int j = 0; j < D; ++j) x[j] = xn[j];
         cf = cn;
         ac = an;
+        if constexpr (PPO) op = opn;
     }
 
     GradientSink<VEC, UNI> sink;
@@ -155,6 +204,9 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
         gradient_affine_each<D, A, VEC>(aff, sink);
     }
     sink.finish(a.excluded);
+    if constexpr (PPO) {
+        if (x_->counts && first) sink.count(x_->counts, seen, ncut); // wave-uniform
+    }
 }
 
 template <class Env, bool CRITIC, bool HID>
@@ -168,14 +220,38 @@ __global__ __launch_bounds__(kBlock) void gradient_kernel(const GradientArgs a, 
     policy_select<VEC>(p, a.gid0 + base, pol, uniform);
     if (uniform) {
         if (full)
-            gradient_block<Env, CRITIC, HID, true, true>(a, p, pol, base);
+            gradient_block<Env, CRITIC, HID, true, true, false>(a, p, pol, base, nullptr);
         else
-            gradient_block<Env, CRITIC, HID, true, false>(a, p, pol, base);
+            gradient_block<Env, CRITIC, HID, true, false, false>(a, p, pol, base, nullptr);
     } else {
         if (full)
-            gradient_block<Env, CRITIC, HID, false, true>(a, p, pol, base);
+            gradient_block<Env, CRITIC, HID, false, true, false>(a, p, pol, base, nullptr);
         else
-            gradient_block<Env, CRITIC, HID, false, false>(a, p, pol, base);
+            gradient_block<Env, CRITIC, HID, false, false, false>(a, p, pol, base, nullptr);
+    }
+}
+
+// The same four copies of the clipped surrogate's policy head
+template <class Env, bool HID>
+__global__ __launch_bounds__(kBlock) void gradient_ppo_kernel(const PpoArgs x, const PolicyArgs p)
+{
+    const GradientArgs& a = x.g;
+    constexpr int VEC = 4, LPB = kBlock * VEC;
+    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;
+    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; // wave-uniform, see step_kernel
+    uint32_t pol[VEC] = {0, 0, 0, 0};
+    bool uniform = true;
+    policy_select<VEC>(p, a.gid0 + base, pol, uniform);
+    if (uniform) {
+        if (full)
+            gradient_block<Env, false, HID, true, true, true>(a, p, pol, base, &x);
+        else
+            gradient_block<Env, false, HID, true, false, true>(a, p, pol, base, &x);
+    } else {
+        if (full)
+            gradient_block<Env, false, HID, false, true, true>(a, p, pol, base, &x);
+        else
+            gradient_block<Env, false, HID, false, false, true>(a, p, pol, base, &x);
     }
 }
 
@@ -191,6 +267,21 @@ static hipError_t gradient_env(const GradientArgs& a, const PolicyArgs& p, hipSt
     } else {
         const uint32_t chunks = (p.hidden + kGradientChunk - 1) / kGradientChunk;
         hipLaunchKernelGGL((gradient_kernel<Env, CRITIC, true>), dim3(blocks, chunks), dim3(kBlock), 0, stream, a, p);
+    }
+    return hipGetLastError();
+}
+
+// The same for gymrs_ppo_gradient (gymrs_gradient_ppo.hip); its checks are gymrs_ppo_gradient's.
+template <class Env>
+static hipError_t gradient_ppo_env(const PpoArgs& a, const PolicyArgs& p, hipStream_t stream)
+{
+    launch_begin();
+    const uint32_t blocks = step_grid(a.g.n, 4);
+    if (p.hidden == 0) {
+        hipLaunchKernelGGL((gradient_ppo_kernel<Env, false>), dim3(blocks), dim3(kBlock), 0, stream, a, p);
+    } else {
+        const uint32_t chunks = (p.hidden + kGradientChunk - 1) / kGradientChunk;
+        hipLaunchKernelGGL((gradient_ppo_kernel<Env, true>), dim3(blocks, chunks), dim3(kBlock), 0, stream, a, p);
     }
     return hipGetLastError();
 }

@@ -408,4 +408,14 @@ struct GradientArgs {
 };
 // critic: p is the critic set (one output, `actions`, `prob` and `scale` unused), else the policy set
 hipError_t launch_policy_gradient(gymrs_env_kind kind, bool critic, const GradientArgs& a, const PolicyArgs& p, hipStream_t stream);
+// ---- clipped surrogate (gymrs_ppo_gradient; gymrs_gradient_ppo.hip) ------------------------------------------------------------
+// A gymrs_ppo_desc as the kernel gets it: the policy head's GradientArgs with the advantages row in the `coef` slot, and what the
+// coefficient is computed from.  counts is 8-byte aligned and ADDED to; old_prob is a row like coef.
+struct PpoArgs {
+    GradientArgs g;
+    const float* old_prob;      // [n_steps][stride]
+    unsigned long long* counts; // [n_sets][2] or NULL
+    float clip_low, clip_high;
+};
+hipError_t launch_ppo_gradient(gymrs_env_kind kind, const PpoArgs& a, const PolicyArgs& p, hipStream_t stream);
 } // namespace gymrs

@@ -124,6 +124,14 @@ class GradientDesc(C.Structure):
 GRADIENT_CRITIC = 1  # GYMRS_GRADIENT_CRITIC
 
 
+class PpoDesc(C.Structure):
+    """``gymrs_ppo_desc`` (include/gymrs_amd.h), 136 bytes: the record by value, three rows in, one optional row out, two tables and
+    an optional pair of counters per set added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float), ("clip_low", C.c_float), ("clip_high", C.c_float),
+                ("pad_", C.c_uint32), ("record", Trajectory), ("start_obs", C.c_void_p), ("advantages", C.c_void_p), ("old_prob", C.c_void_p),
+                ("prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -291,6 +299,48 @@ def gradient_lane(kind: int, hidden: int, weights, x, actions, coef, *, critic: 
                                         xs.ctypes.data_as(fp), a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None, c.ctypes.data_as(fp),
                                         q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), pr.ctypes.data_as(fp) if prob else None))
     return (q, excluded.value, pr) if prob else (q, excluded.value)
+
+
+def _clip_bounds(clip, clip_low, clip_high):
+    """(clip_low, clip_high) as f32: either ``clip`` (epsilon: 1 - clip and 1 + clip rounded to f32) or both bounds."""
+    if (clip_low is None) != (clip_high is None):
+        raise ValueError("give clip_low and clip_high together")
+    if clip_low is None:
+        if clip is None:
+            raise ValueError("give clip, or clip_low and clip_high")
+        return float(np.float32(1.0 - float(clip))), float(np.float32(1.0 + float(clip)))
+    return float(np.float32(clip_low)), float(np.float32(clip_high))
+
+
+def ppo_lane(kind: int, hidden: int, weights, x, actions, advantages, old_prob, *, clip: Optional[float] = 0.2, clip_low: Optional[float] = None,
+             clip_high: Optional[float] = None, temperature: Optional[float] = None, scale: Optional[float] = None, prob: bool = False):
+    """``gymrs_ppo_lane`` (host only, no GPU): one lane's contribution to ``gymrs_ppo_gradient`` -- the definition of
+    include/gymrs_amd.h, "clipped surrogate", as code.  ``weights``: ONE policy; ``x`` [K][D], ``actions`` [K], ``advantages`` [K],
+    ``old_prob`` [K].  Returns (q, excluded, counts) or, with ``prob``, (q, excluded, counts, prob [K]): q is int64 [S], counts is
+    uint64 [2] = (lane-steps with an action in range, those that were cut)."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    size = policy_size(kind, hidden)
+    adv = np.ascontiguousarray(advantages, dtype=np.float32).reshape(-1)
+    po = np.ascontiguousarray(old_prob, dtype=np.float32).reshape(-1)
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(-1)
+    if w.size != size or xs.size != adv.size * _OBS_DIM[kind]:
+        raise ValueError(f"ppo_lane needs {size} weights and {_OBS_DIM[kind]} observation components per step")
+    if a.size != adv.size or po.size != adv.size:
+        raise ValueError("ppo_lane needs one action and one old probability per step")
+    low, high = _clip_bounds(clip, clip_low, clip_high)
+    s = _sampling(0, temperature, scale).scale
+    q = np.zeros(size, np.int64)
+    excluded = C.c_uint64()
+    counts = np.zeros(2, np.uint64)
+    pr = np.empty(adv.size, np.float32) if prob else None
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint64)
+    _check(lib, lib.gymrs_ppo_lane(int(kind), int(hidden), float(s), low, high, w.ctypes.data_as(fp), int(adv.size), xs.ctypes.data_as(fp),
+                                   a.ctypes.data_as(C.POINTER(C.c_uint8)), adv.ctypes.data_as(fp), po.ctypes.data_as(fp),
+                                   q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), counts.ctypes.data_as(up),
+                                   pr.ctypes.data_as(fp) if prob else None))
+    return (q, excluded.value, counts, pr) if prob else (q, excluded.value, counts)
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -798,6 +848,32 @@ class BatchedEngine:
         desc = GradientDesc(int(n_steps), f, float(s), 0, traj, C.c_void_p(start_obs or None), C.c_void_p(coef or None), C.c_void_p(prob or None),
                             C.c_void_p(grad or None), C.c_void_p(excluded or None), 0)
         _check(self._lib, self._lib.gymrs_policy_gradient(self._h, C.byref(desc)))
+
+    # -- the clipped surrogate over a transitions record: one launch per PPO epoch --------------------------------
+    def ppo_gradient(self, n_steps: int, *, record, start_obs: int, advantages: int, old_prob: int, grad: int, excluded: int,
+                     counts: Optional[int] = None, prob: Optional[int] = None, clip: Optional[float] = 0.2, clip_low: Optional[float] = None,
+                     clip_high: Optional[float] = None, temperature: Optional[float] = None, scale: Optional[float] = None,
+                     flags: int = 0) -> None:
+        """``gymrs_ppo_gradient``: ``policy_gradient`` with the policy head whose coefficient is computed in the kernel from the
+        ``advantages`` row and the ``old_prob`` row (the ``prob`` row of the policy the record was drawn from): ratio = p[a] /
+        old_prob, cut where the advantage pushes it out of [clip_low, clip_high], else advantage * ratio.  ADDS the gradient of PPO's
+        clipped objective (to ascend) per policy to ``grad`` and ``excluded`` as ``policy_gradient`` does, and, with ``counts`` (device
+        uint64 [n_policies][2]), the lane-steps seen and the lane-steps cut.  ``clip`` (epsilon) becomes ``np.float32(1 - clip)`` and
+        ``np.float32(1 + clip)``; ``clip_low`` / ``clip_high`` give the bounds themselves.  ``prob`` receives the new p[a] and may
+        not be ``old_prob``.  Exactly one of ``temperature`` / ``scale``.  Reads and writes no lane array."""
+        if record is None:
+            raise ValueError("ppo_gradient needs a record")
+        if not isinstance(record, Trajectory):
+            record = dict(record)
+            for name in ("actions", "reward", "done"):
+                record.setdefault(name, 0)
+        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        low, high = _clip_bounds(clip, clip_low, clip_high)
+        s = _sampling(0, temperature, scale).scale
+        desc = PpoDesc(int(n_steps), int(flags), float(s), low, high, 0, traj, C.c_void_p(start_obs or None), C.c_void_p(advantages or None),
+                       C.c_void_p(old_prob or None), C.c_void_p(prob or None), C.c_void_p(grad or None), C.c_void_p(excluded or None),
+                       C.c_void_p(counts or None), 0)
+        _check(self._lib, self._lib.gymrs_ppo_gradient(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

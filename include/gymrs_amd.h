@@ -790,6 +790,64 @@ typedef struct {
 gymrs_status gymrs_policy_gradient(gymrs_engine* e, const gymrs_gradient_desc* d);
 gymrs_status gymrs_gradient_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float scale, const float* weights, uint32_t n_steps,
                                  const float* x, const uint8_t* actions, const float* coef, int64_t* q, uint64_t* excluded, float* prob);
+/* Clipped surrogate: PPO's gradient over a transitions record in ONE launch per epoch.  gymrs_ppo_gradient(e, d) is
+ * gymrs_policy_gradient with the policy head, with one difference: the coefficient of a lane-step is not read from a row, it is
+ * computed from an advantage row and an old-probability row.  Everything else is as "gradients" defines it: x, a, the logits, p[],
+ * beta, the accumulators, the backward pass, the fixed point, excluded, the set key (the policy's) and additivity.
+ * For lane i and step k, with pa = p[a] (the value "gradients" writes to prob; +0.0f where a >= A):
+ *     adv   = advantages[k][i];   po = old_prob[k][i]
+ *     ratio = pa / po                                                                  (one IEEE divide)
+ *     cut   = (adv > 0.0f && ratio > clip_high) || (adv < 0.0f && ratio < clip_low)    (compares: false on NaN)
+ *     c     = cut ? +0.0f : adv * ratio                                                (a select, one multiply)
+ *     cb    = c * beta;   g[b] = cb * ((b == a ? 1.0f : 0.0f) - p[b])                  (unchanged from here on)
+ * The table receives the gradient of  sum over k of min(ratio * adv, clip(ratio, clip_low, clip_high) * adv),  the objective to
+ * ASCEND: the learner adds it.  The bounds are the caller's floats (1 - epsilon and 1 + epsilon as the caller rounds them): the
+ * library does no arithmetic on an epsilon.  What follows from the rule:
+ *   - a lane-step with a >= A contributes nothing (as in "gradients") and is not counted below;
+ *   - a c that is not finite, or one that takes a sum past 2^30, puts that lane's pairs into excluded, as such a coef does in
+ *     "gradients": a NaN po or adv gives c = NaN; po = 0 gives ratio = +inf (pa > 0), which a positive adv cuts and any other adv
+ *     turns into c = -inf or NaN; po = +inf gives ratio = +0, which a negative adv cuts (clip_low > 0) and a positive one
+ *     multiplies to c = +0: a finite value, nothing is excluded; a negative po is arithmetic like any other (ratio < 0);
+ *   - the compares are strict: ratio == clip_high (ratio == clip_low) is not cut; adv == 0 (either sign) is never cut;
+ *   - by definition the call equals gymrs_policy_gradient with coef[k][i] = c, integer for integer.
+ * counts (may be NULL): device uint64 [n_sets][2], ADDED to, exact: counts[set][0] += 1 per lane-step with a < A, counts[set][1] +=
+ * 1 per such lane-step with cut.  The clip fraction of a set is counts[set][1] / counts[set][0].
+ * prob (may be NULL) behaves exactly as in gymrs_policy_gradient and receives the new p[a]; old_prob and prob may not alias.
+ *   - Like gymrs_advantages and gymrs_policy_gradient the call runs in the engine's stream order and uses the engine only for the
+ *     stream, the kind, n_envs, global_env_offset and the policy set: it reads and writes no lane array.  It reads lanes i < n_envs
+ *     of every row only: the padding lanes may hold anything, NaN included, and count for nothing; of prob they keep their bytes.
+ *     reward, done and truncated of the record are not read and may be NULL.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: everything gymrs_policy_gradient refuses for the policy head (NULL engine or desc, Pendulum,
+ *     reserved != 0, no policy set (naming gymrs_set_policy), scale NaN, infinite or negative, NULL obs / actions / start_obs / grad
+ *     / excluded, a row buffer not 16-byte aligned, grad or excluded not 8-byte aligned, lane_stride < n_envs or not a multiple of
+ *     16), and: flags != 0 or pad_ != 0, NULL or misaligned advantages or old_prob, prob == old_prob, bounds that are NaN, infinite
+ *     or outside 0 <= clip_low <= 1 <= clip_high, counts not 8-byte aligned.
+ *   - gymrs_ppo_lane: host only, no GPU: the definition as code, as gymrs_gradient_lane is for "gradients".  From ONE policy's
+ *     weights, K = n_steps, one lane's x[K][D], actions[K], advantages[K] and old_prob[K] it SETS q[0..S), *excluded, counts[0..2)
+ *     (when counts != NULL) and prob[0..K) (when prob != NULL).  GYMRS_EINVAL: Pendulum, hidden > 64, NULL arguments, prob ==
+ *     old_prob, a bad scale, bad bounds.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* 0, reserved */
+    float scale;                /* log2(e) / temperature, finite, >= 0, as gymrs_gradient_desc */
+    float clip_low;             /* 0 <= clip_low <= 1, e.g. (float)(1 - 0.2) */
+    float clip_high;            /* 1 <= clip_high, finite, e.g. (float)(1 + 0.2) */
+    uint32_t pad_;              /* 0 */
+    gymrs_trajectory record;    /* by value; READ: obs, actions; lane_stride >= n_envs, a multiple of 16 */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* advantages;    /* [K][lane_stride], required, 16-byte aligned */
+    const float* old_prob;      /* [K][lane_stride], required, 16-byte aligned: the prob row of the policy the record was drawn from */
+    float* prob;                /* [K][lane_stride] or NULL; not old_prob */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned, ADDED to */
+    uint64_t* excluded;         /* device uint64 [n_sets], ADDED to */
+    uint64_t* counts;           /* device uint64 [n_sets][2] or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_ppo_desc;               /* 136 bytes */
+gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d);
+gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
+                            const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
+                            uint64_t counts[2], float* prob);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

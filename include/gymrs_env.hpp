@@ -103,6 +103,18 @@ inline std::uint64_t gradient_lane(gymrs_env_kind kind, std::uint32_t hidden, st
     return excluded;
 }
 
+// One lane's contribution to gymrs_ppo_gradient (gymrs_ppo_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
+// (lane, parameter) pairs returned; counts (may be null) gets the lane-steps seen and cut, prob (may be null) p[a] of every step.
+// The definition of include/gymrs_amd.h, "clipped surrogate", as code.
+inline std::uint64_t ppo_lane(gymrs_env_kind kind, std::uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights,
+                              std::uint32_t n_steps, const float* x, const std::uint8_t* actions, const float* advantages, const float* old_prob,
+                              std::int64_t* q, std::uint64_t* counts = nullptr, float* prob = nullptr)
+{
+    std::uint64_t excluded = 0;
+    check(gymrs_ppo_lane(kind, hidden, scale, clip_low, clip_high, weights, n_steps, x, actions, advantages, old_prob, q, &excluded, counts, prob));
+    return excluded;
+}
+
 // ---- batched form: the shape the hot path is built for ---------------------------------------------
 class VecEnv {
 public:
@@ -385,6 +397,16 @@ public:
     {
         const gymrs_gradient_desc d{n_steps, critic ? GYMRS_GRADIENT_CRITIC : 0u, scale, 0u, record, start_obs, coef, prob, grad, excluded, 0};
         check(gymrs_policy_gradient(e_, &d));
+    }
+    // the clipped surrogate (gymrs_ppo_gradient): policy_gradient's policy head with the coefficient computed in the kernel from the
+    // advantages row and the old-probability row under the clip range [clip_low, clip_high] (the caller's floats); ADDS PPO's
+    // gradient (to ascend) to grad and excluded and, when counts (device uint64 [n_sets][2]) is not null, the lane-steps seen and cut
+    void ppo_gradient(const gymrs_ppo_desc& d) { check(gymrs_ppo_gradient(e_, &d)); }
+    void ppo_gradient(std::uint32_t n_steps, const gymrs_trajectory& record, const float* start_obs, const float* advantages, const float* old_prob,
+                      std::int64_t* grad, std::uint64_t* excluded, std::uint64_t* counts, float* prob, float scale, float clip_low, float clip_high)
+    {
+        const gymrs_ppo_desc d{n_steps, 0u, scale, clip_low, clip_high, 0u, record, start_obs, advantages, old_prob, prob, grad, excluded, counts, 0};
+        check(gymrs_ppo_gradient(e_, &d));
     }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {

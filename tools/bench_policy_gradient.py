@@ -49,7 +49,7 @@ def kernel_resources(lib: Path) -> dict:
         for co in sorted(Path(tmp).glob("lib.so.*amdgcn*")):
             notes = subprocess.run([str(llvm / "llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout
             for block in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-                name = re.search(r"\.name:\s+(\S*gradient_kernel\S*)", block)
+                name = re.search(r"\.name:\s+(\S*gradient_(?:ppo_)?kernel\S*)", block)  # gymrs_policy_gradient's and gymrs_ppo_gradient's
                 if not name:
                     continue
                 field = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", block).group(1))  # noqa: E731
