@@ -28,6 +28,7 @@ HIP_SOURCES = [CSRC / "gymrs_step_cartpole.hip", CSRC / "gymrs_step_mountain_car
                CSRC / "gymrs_table_explore_mountain_car.hip", CSRC / "gymrs_transitions.hip", CSRC / "gymrs_table_transitions_cartpole.hip",
                CSRC / "gymrs_table_transitions_mountain_car.hip", CSRC / "gymrs_sample.hip", CSRC / "gymrs_sample_fitness.hip",
                CSRC / "gymrs_table_sample_cartpole.hip", CSRC / "gymrs_table_sample_mountain_car.hip", CSRC / "gymrs_advantages.hip", CSRC / "gymrs_gradient.hip", CSRC / "gymrs_gradient_ppo.hip", CSRC / "gymrs_evaluate.hip", CSRC / "gymrs_aux.hip", CSRC / "gymrs_engine.hip", CSRC / "gymrs_engine_io.hip",
+               CSRC / "gymrs_engine_learn.hip",
                CSRC / "gymrs_aql.hip", CSRC / "gymrs_sharded.hip"]
 # The per-step kernels once more as a stand-alone gfx950 code object (device-only compile), embedded into the library by
 # gymrs_aql.hip (.incbin) and loaded through HSA by the engine's own AQL dispatcher.

@@ -512,8 +512,8 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->err);
     (void)hipFree(e->table_dev);
     (void)hipFree(e->param_index);
-    (void)hipFree(e->policy_dev);
-    (void)hipFree(e->critic_dev);
+    (void)hipFree(e->policy.dev);
+    (void)hipFree(e->critic.dev);
     (void)hipFree(e->fitness_dev);
     (void)hipFree(e->eval_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));
@@ -1079,19 +1079,19 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, const Rollou
         if (gymrs_status st = policy_fitness_table(e)) return st;
     const bool explore = q.actions == ActionSource::Exploring;
     if (q.actions == ActionSource::Sampling) {
-        HIP_TRY(launch_rollout_sample(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->sample,
+        HIP_TRY(launch_rollout_sample(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->sample,
                                       q.fitness ? e->fitness_dev : nullptr, q.transitions, e->stream));
     } else if (q.transitions) { // one action source: a greedy launch plays threshold 0 (the greedy bits)
         const ExploreArgs greedy{};
-        HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, explore ? e->explore : greedy,
+        HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, explore ? e->explore : greedy,
                                            *q.transitions, e->stream));
     } else if (explore) {
-        HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->explore,
+        HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->explore,
                                        q.fitness ? e->fitness_dev : nullptr, e->stream));
     } else if (q.fitness) {
-        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->fitness_dev, e->stream));
+        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->fitness_dev, e->stream));
     } else if (q.actions == ActionSource::Policy)
-        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy, e->stream));
+        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->stream));
     else
         HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags

@@ -1,11 +1,8 @@
 // gymrs_engine_io.hip -- the parts of the C ABI (include/gymrs_amd.h) that look at an engine or copy it rather than step it: views and copies of the
 // SoA arrays, clone / snapshot (Env: Clone + Serialize, core.rs:25), episode statistics and their RCCL all-reduce, the pub physics fields after
-// construction, the #[derive(Serialize)] JSON view.  The engine object and the stepping paths: gymrs_engine_priv.h, gymrs_engine.hip.
+// construction, the #[derive(Serialize)] JSON view.  The engine object and the stepping paths: gymrs_engine_priv.h, gymrs_engine.hip; the
+// learner surface (policy and critic sets, advantages, gradients, the per-policy tables): gymrs_engine_learn.hip.
 #include "gymrs_engine_priv.h"
-#include "gymrs_evaluate.h"
-#include "gymrs_sample.h"
-#include "gymrs_advantages.h"
-#include "gymrs_gradient.h"
 
 static RcclApi g_rccl;
 
@@ -651,743 +648,6 @@ gymrs_status gymrs_fill_actions(gymrs_engine* e, void* actions_dev, uint64_t see
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_fill_actions(e->kind, actions_dev, e->n, e->gid0, seed, t, e->max_torque, e->stream));
     return GYMRS_OK;
-}
-
-// ---- closed-loop rollouts: the policy set --------------------------------------------------------------------------------
-gymrs_status gymrs_policy_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats)
-{
-    if (!n_floats) return fail(GYMRS_EINVAL, "gymrs_policy_size: n_floats is NULL");
-    if (gymrs_status st = check_discrete_env(kind, "gymrs_policy_size")) return st;
-    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_policy_size: hidden must be <= 64");
-    *n_floats = policy_floats(kind, hidden);
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
-{
-    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_policy: NULL engine");
-    if (!d) { // remove the policy (launches already enqueued still read the buffer: wait for them)
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipFree(e->policy_dev));
-        e->policy_dev = nullptr;
-        e->policy_capacity = 0;
-        e->policy = PolicyArgs{};
-        if (gymrs_status st = discard_policy_eval(e)) return st;
-        return discard_policy_fitness(e);
-    }
-    if (gymrs_status st = check_discrete_env(e->kind, "gymrs_set_policy")) return st;
-    if (d->hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_set_policy: hidden must be <= 64");
-    if (d->n_policies == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: n_policies must be >= 1");
-    if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, "gymrs_set_policy: lanes_per_policy must be >= 1");
-    if (!weights_host) return fail(GYMRS_EINVAL, "gymrs_set_policy: weights_host is NULL");
-    const uint64_t stride = policy_floats(e->kind, d->hidden), total = stride * d->n_policies;
-    HIP_TRY(hipSetDevice(e->device));
-    // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
-    // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
-    if (e->fitness_dev && d->n_policies == e->policy.n_policies) {
-        HIP_TRY(hipMemsetAsync(e->fitness_dev, 0, (size_t)d->n_policies * sizeof(gymrs_policy_fitness), e->stream));
-    } else if (gymrs_status st = discard_policy_fitness(e)) {
-        return st;
-    }
-    if (gymrs_status st = discard_policy_eval(e)) return st; // the episodic records belong to the set they were played with
-    if (total > e->policy_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipFree(e->policy_dev));
-        e->policy_dev = nullptr;
-        e->policy_capacity = 0;
-        e->policy = PolicyArgs{};
-        HIP_TRY(hipMalloc(&e->policy_dev, (size_t)total * sizeof(float)));
-        e->policy_capacity = total;
-    }
-    // stream-ordered: launches enqueued before this call read the old set; the host weights are consumed before the call returns
-    HIP_TRY(hipMemcpyAsync(e->policy_dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->policy.weights = e->policy_dev;
-    e->policy.lanes_per_policy = d->lanes_per_policy;
-    e->policy.n_policies = d->n_policies;
-    e->policy.hidden = d->hidden;
-    e->policy.stride = (uint32_t)stride;
-    e->policy.pad_ = 0;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
-{
-    if (!e || !d_out) return fail(GYMRS_EINVAL, "gymrs_get_policy: NULL argument");
-    if (gymrs_status st = check_policy_set(e, "gymrs_get_policy")) return st;
-    d_out->hidden = e->policy.hidden;
-    d_out->n_policies = e->policy.n_policies;
-    d_out->lanes_per_policy = e->policy.lanes_per_policy;
-    if (!weights_out && capacity_floats == 0) return GYMRS_OK; // a query of the description
-    const uint64_t total = (uint64_t)e->policy.stride * e->policy.n_policies;
-    if (!weights_out || capacity_floats < total) return fail(GYMRS_EINVAL, "gymrs_get_policy: capacity_floats is smaller than the policy set");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(weights_out, e->policy_dev, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    return stream_sync_checked(e);
-}
-
-gymrs_status gymrs_policy_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
-{
-    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_weights_ptr: NULL argument");
-    if (gymrs_status st = check_policy_set(e, "gymrs_policy_weights_ptr")) return st;
-    *dev_out = e->policy_dev;
-    if (n_floats) *n_floats = (uint64_t)e->policy.stride * e->policy.n_policies;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_policy_actions(gymrs_engine* e, void* actions_dev)
-{
-    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_policy_actions: NULL argument");
-    if (gymrs_status st = check_policy_set(e, "gymrs_policy_actions")) return st;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_policy_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->policy, e->stream));
-    return GYMRS_OK;
-}
-
-// ---- epsilon-greedy exploration: the settings, the per-step call and the host-side draw ------------------------------------------
-static gymrs_status check_exploration(const gymrs_exploration* x, const std::string& who)
-{
-    if (x->threshold > kExploreOne) return fail(GYMRS_EINVAL, who + ": threshold must be <= 65536 (epsilon = threshold / 65536)");
-    if (x->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_set_exploration(gymrs_engine* e, const gymrs_exploration* x)
-{
-    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_exploration: NULL engine");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, "gymrs_set_exploration: exploration is for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!x) { // (launches already enqueued carry their own copy of the settings)
-        e->explore = ExploreArgs{};
-        e->explore_set = false;
-        return GYMRS_OK;
-    }
-    if (gymrs_status st = check_exploration(x, "gymrs_set_exploration")) return st;
-    e->explore = ExploreArgs{x->seed, x->threshold, 0};
-    e->explore_set = true;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_get_exploration(gymrs_engine* e, gymrs_exploration* x_out)
-{
-    if (!e || !x_out) return fail(GYMRS_EINVAL, "gymrs_get_exploration: NULL argument");
-    if (!e->explore_set) return fail(GYMRS_EINVAL, "gymrs_get_exploration: the engine has no exploration settings (gymrs_set_exploration)");
-    *x_out = gymrs_exploration{e->explore.seed, e->explore.threshold, 0};
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_explore_actions(gymrs_engine* e, void* actions_dev)
-{
-    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_explore_actions: NULL argument");
-    if (gymrs_status st = check_policy_set(e, "gymrs_explore_actions")) return st;
-    if (!e->explore_set) return fail(GYMRS_EINVAL, "gymrs_explore_actions: the engine has no exploration settings (gymrs_set_exploration)");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_explore_actions(e->kind, e->s, actions_dev, e->n, e->gid0, e->tick, e->policy, e->explore, e->stream));
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_explore_draw(const gymrs_exploration* x, uint32_t n_actions, uint64_t global_id, uint64_t tick, uint8_t* explored,
-                                uint8_t* random_action)
-{
-    if (!x) return fail(GYMRS_EINVAL, "gymrs_explore_draw: NULL settings");
-    if (gymrs_status st = check_exploration(x, "gymrs_explore_draw")) return st;
-    if (n_actions == 0 || n_actions > 256) return fail(GYMRS_EINVAL, "gymrs_explore_draw: n_actions must be in 1 .. 256");
-    const uint32_t w = explore_word(x->seed, global_id, tick);
-    if (explored) *explored = explore_decides(w, x->threshold) ? 1 : 0;
-    if (random_action) *random_action = explore_random(w, n_actions);
-    return GYMRS_OK;
-}
-
-// ---- softmax sampling: the settings, the per-step call and the host-side draw (include/gymrs_amd.h, "sampling") ------------------
-static gymrs_status check_sampling(const gymrs_sampling* x, const std::string& who)
-{
-    if (!(x->scale >= 0.0f) || x->scale > 3.402823466e+38f)
-        return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0 (scale = log2(e) / temperature; 0 is the uniform policy)");
-    if (x->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_set_sampling(gymrs_engine* e, const gymrs_sampling* x)
-{
-    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_sampling: NULL engine");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, "gymrs_set_sampling: sampling is for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
-    if (!x) { // (launches already enqueued carry their own copy of the settings)
-        e->sample = SampleArgs{};
-        e->sample_set = false;
-        return GYMRS_OK;
-    }
-    if (gymrs_status st = check_sampling(x, "gymrs_set_sampling")) return st;
-    e->sample = SampleArgs{x->seed, x->scale, 0};
-    e->sample_set = true;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_get_sampling(gymrs_engine* e, gymrs_sampling* x_out)
-{
-    if (!e || !x_out) return fail(GYMRS_EINVAL, "gymrs_get_sampling: NULL argument");
-    if (!e->sample_set) return fail(GYMRS_EINVAL, "gymrs_get_sampling: the engine has no sampling settings (gymrs_set_sampling)");
-    *x_out = gymrs_sampling{e->sample.seed, e->sample.scale, 0};
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_sample_actions(gymrs_engine* e, void* actions_dev, float* prob_dev)
-{
-    if (!e || !actions_dev) return fail(GYMRS_EINVAL, "gymrs_sample_actions: NULL argument");
-    if (gymrs_status st = check_policy_set(e, "gymrs_sample_actions")) return st;
-    if (!e->sample_set) return fail(GYMRS_EINVAL, "gymrs_sample_actions: the engine has no sampling settings (gymrs_set_sampling)");
-    if (reinterpret_cast<uintptr_t>(prob_dev) % sizeof(float) != 0) return fail(GYMRS_EINVAL, "gymrs_sample_actions: prob_dev must be 4-byte aligned");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_sample_actions(e->kind, e->s, actions_dev, prob_dev, e->n, e->gid0, e->tick, e->policy, e->sample, e->stream));
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_sample_draw(const gymrs_sampling* x, uint32_t n_actions, const float* logits, uint64_t global_id, uint64_t tick, uint8_t* action,
-                               float* probs)
-{
-    if (!x) return fail(GYMRS_EINVAL, "gymrs_sample_draw: NULL settings");
-    if (gymrs_status st = check_sampling(x, "gymrs_sample_draw")) return st;
-    if (n_actions < 2 || n_actions > kMaxSampleActions) return fail(GYMRS_EINVAL, "gymrs_sample_draw: n_actions must be in 2 .. 8");
-    if (!logits) return fail(GYMRS_EINVAL, "gymrs_sample_draw: NULL logits");
-    const uint32_t a = sample_action(logits, n_actions, x->scale, sample_word(x->seed, global_id, tick), probs);
-    if (action) *action = (uint8_t)a;
-    return GYMRS_OK;
-}
-
-// ---- advantages: the critic set, the host-side value and the launch (include/gymrs_amd.h, "advantages") --------------------------
-gymrs_status gymrs_critic_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n_floats)
-{
-    if (!n_floats) return fail(GYMRS_EINVAL, "gymrs_critic_size: n_floats is NULL");
-    if (gymrs_status st = check_discrete_env(kind, "gymrs_critic_size")) return st;
-    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_critic_size: hidden must be <= 64");
-    *n_floats = critic_floats(kind, hidden);
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_set_critic(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
-{
-    if (!e) return fail(GYMRS_EINVAL, "gymrs_set_critic: NULL engine");
-    if (!d) { // remove the critic (launches already enqueued still read the buffer: wait for them)
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipFree(e->critic_dev));
-        e->critic_dev = nullptr;
-        e->critic_capacity = 0;
-        e->critic = PolicyArgs{};
-        return GYMRS_OK;
-    }
-    if (gymrs_status st = check_discrete_env(e->kind, "gymrs_set_critic")) return st;
-    if (d->hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_set_critic: hidden must be <= 64");
-    if (d->n_policies == 0) return fail(GYMRS_EINVAL, "gymrs_set_critic: n_policies (the number of critics) must be >= 1");
-    if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, "gymrs_set_critic: lanes_per_policy (lanes per critic) must be >= 1");
-    if (!weights_host) return fail(GYMRS_EINVAL, "gymrs_set_critic: weights_host is NULL");
-    const uint64_t stride = critic_floats(e->kind, d->hidden), total = stride * d->n_policies;
-    HIP_TRY(hipSetDevice(e->device));
-    if (total > e->critic_capacity) { // a larger set: a new buffer (launches in flight still read the old one: wait for them)
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipFree(e->critic_dev));
-        e->critic_dev = nullptr;
-        e->critic_capacity = 0;
-        e->critic = PolicyArgs{};
-        HIP_TRY(hipMalloc(&e->critic_dev, (size_t)total * sizeof(float)));
-        e->critic_capacity = total;
-    }
-    // stream-ordered: launches enqueued before this call read the old set; the host weights are consumed before the call returns
-    HIP_TRY(hipMemcpyAsync(e->critic_dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->critic.weights = e->critic_dev;
-    e->critic.lanes_per_policy = d->lanes_per_policy;
-    e->critic.n_policies = d->n_policies;
-    e->critic.hidden = d->hidden;
-    e->critic.stride = (uint32_t)stride;
-    e->critic.pad_ = 0;
-    return GYMRS_OK;
-}
-
-static gymrs_status check_critic_set(const gymrs_engine* e, const std::string& who)
-{
-    return e->critic_dev ? GYMRS_OK : fail(GYMRS_EINVAL, who + ": the engine has no critic (gymrs_set_critic)");
-}
-
-gymrs_status gymrs_get_critic(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
-{
-    if (!e || !d_out) return fail(GYMRS_EINVAL, "gymrs_get_critic: NULL argument");
-    if (gymrs_status st = check_critic_set(e, "gymrs_get_critic")) return st;
-    d_out->hidden = e->critic.hidden;
-    d_out->n_policies = e->critic.n_policies;
-    d_out->lanes_per_policy = e->critic.lanes_per_policy;
-    if (!weights_out && capacity_floats == 0) return GYMRS_OK; // a query of the description
-    const uint64_t total = (uint64_t)e->critic.stride * e->critic.n_policies;
-    if (!weights_out || capacity_floats < total) return fail(GYMRS_EINVAL, "gymrs_get_critic: capacity_floats is smaller than the critic set");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(weights_out, e->critic_dev, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    return stream_sync_checked(e);
-}
-
-gymrs_status gymrs_critic_weights_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
-{
-    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_critic_weights_ptr: NULL argument");
-    if (gymrs_status st = check_critic_set(e, "gymrs_critic_weights_ptr")) return st;
-    *dev_out = e->critic_dev;
-    if (n_floats) *n_floats = (uint64_t)e->critic.stride * e->critic.n_policies;
-    return GYMRS_OK;
-}
-
-namespace {
-struct HostCritic { // w(k, i) of critic_values over one critic in host memory
-    const float* w;
-    float operator()(int, uint32_t i) const { return w[i]; }
-};
-} // namespace
-
-gymrs_status gymrs_critic_value(gymrs_env_kind kind, uint32_t hidden, const float* weights, const float* obs, float* v)
-{
-    if (!weights || !obs || !v) return fail(GYMRS_EINVAL, "gymrs_critic_value: NULL argument");
-    if (gymrs_status st = check_discrete_env(kind, "gymrs_critic_value")) return st;
-    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, "gymrs_critic_value: hidden must be <= 64");
-    const HostCritic w{weights};
-    float out[1];
-    if (kind == GYMRS_CARTPOLE) {
-        const float x[4][1] = {{obs[0]}, {obs[1]}, {obs[2]}, {obs[3]}};
-        critic_values<4, 1, 1>(w, hidden, x, out);
-    } else {
-        const float x[2][1] = {{obs[0]}, {obs[1]}};
-        critic_values<2, 1, 1>(w, hidden, x, out);
-    }
-    *v = out[0];
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_advantages(gymrs_engine* e, const gymrs_advantages_desc* d)
-{
-    const std::string who = "gymrs_advantages";
-    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
-    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, who + ": advantages are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
-    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    if (d->flags & ~GYMRS_ADVANTAGES_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_ADVANTAGES_CRITIC is the only one)");
-    const bool critic = (d->flags & GYMRS_ADVANTAGES_CRITIC) != 0;
-    if (critic && !e->critic_dev) return fail(GYMRS_EINVAL, who + ": GYMRS_ADVANTAGES_CRITIC without a critic set on the engine (gymrs_set_critic)");
-    if (!(d->gamma >= 0.0f && d->gamma <= 1.0f)) return fail(GYMRS_EINVAL, who + ": gamma must be in [0, 1]");
-    if (!(d->lambda >= 0.0f && d->lambda <= 1.0f)) return fail(GYMRS_EINVAL, who + ": lambda must be in [0, 1]");
-    const gymrs_trajectory& rec = d->record;
-    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
-    if (!rec.reward) return fail(GYMRS_EINVAL, who + ": record.reward is NULL");
-    if (!rec.done) return fail(GYMRS_EINVAL, who + ": record.done is NULL");
-    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
-    if (!d->advantages) return fail(GYMRS_EINVAL, who + ": advantages is NULL");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(rec.obs) | reinterpret_cast<uintptr_t>(rec.reward) | reinterpret_cast<uintptr_t>(rec.done) |
-                           reinterpret_cast<uintptr_t>(rec.truncated) | reinterpret_cast<uintptr_t>(d->final_obs) |
-                           reinterpret_cast<uintptr_t>(d->start_obs) | reinterpret_cast<uintptr_t>(d->advantages) |
-                           reinterpret_cast<uintptr_t>(d->returns) | reinterpret_cast<uintptr_t>(d->values);
-    if (bits % 16 != 0) return fail(GYMRS_EINVAL, who + ": every buffer must be 16-byte aligned");
-    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
-    if (d->n_steps == 0) return GYMRS_OK;
-    AdvantageArgs a{};
-    a.obs = rec.obs;
-    a.reward = rec.reward;
-    a.done = rec.done;
-    a.truncated = rec.truncated;
-    a.final_obs = d->final_obs;
-    a.start_obs = d->start_obs;
-    a.advantages = d->advantages;
-    a.returns = d->returns;
-    a.values = d->values;
-    a.stride = rec.lane_stride;
-    a.n = e->n;
-    a.gid0 = e->gid0;
-    a.n_steps = d->n_steps;
-    a.gamma = d->gamma;
-    a.gl = d->gamma * d->lambda;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_advantages(e->kind, a, critic ? &e->critic : nullptr, e->stream));
-    return GYMRS_OK;
-}
-
-// ---- gradients: the host-side lane and the launch (include/gymrs_amd.h, "gradients") ------------------------------------------------
-extern "C++" {
-namespace {
-struct HostWeights { // w(k, i) of the gymrs_gradient.h templates over one network in host memory
-    const float* w;
-    float operator()(int, uint32_t i) const { return w[i]; }
-};
-
-// What "clipped surrogate" adds to a lane: coef is then the advantages row
-struct PpoLane {
-    const float* old_prob;
-    float clip_low, clip_high;
-    uint64_t* counts; // [2], SET
-};
-
-// One lane by the shared text: the kernels' walk with VEC = 1, chunk after chunk.
-template <int D, int A, bool CRITIC>
-void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, const float* x, const uint8_t* actions, const float* coef, int64_t* q,
-                   uint64_t* excluded, float* prob, const PpoLane* ppo = nullptr)
-{
-    uint64_t seen = 0, ncut = 0;
-    const HostWeights w{weights};
-    uint64_t excl = 0;
-    auto emit = [&](uint32_t s, const float (&L)[1]) {
-        long long v;
-        if (!gradient_fixed(L[0], v)) excl += 1;
-        q[s] = v;
-    };
-    const uint32_t chunks = H == 0 ? 1 : (H + kGradientChunk - 1) / kGradientChunk;
-    for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
-        const uint32_t h0 = chunk * kGradientChunk;
-        GradientAffine<D, A, 1> aff{};
-        GradientChunk<D, A, 1> chk{};
-        float db2[A][1] = {};
-        for (uint32_t k = 0; k < K; ++k) {
-            float xs[D][1], g[A][1];
-            bool on[1] = {true};
-            for (int j = 0; j < D; ++j) xs[j][0] = x[(size_t)k * D + j];
-            if constexpr (CRITIC) {
-                g[0][0] = coef[k];
-            } else {
-                float y[A][1], pa[1];
-                const float c[1] = {coef[k]};
-                const uint8_t act[1] = {actions[k]};
-                gradient_logits<D, A, 1, 1>(w, H, xs, y);
-                if (ppo) {
-                    const float po[1] = {ppo->old_prob[k]};
-                    bool cut[1];
-                    gradient_ppo_head<A, 1>(y, act, c, po, scale, ppo->clip_low, ppo->clip_high, g, on, pa, cut);
-                    if (chunk == 0) {
-                        seen += on[0] ? 1 : 0;
-                        ncut += cut[0] ? 1 : 0;
-                    }
-                } else {
-                    gradient_policy_head<A, 1>(y, act, c, scale, g, on, pa);
-                }
-                if (prob && chunk == 0) prob[k] = pa[0];
-            }
-            if (H == 0) {
-                gradient_affine_step<D, A, 1, !CRITIC>(xs, g, on, aff);
-            } else {
-                gradient_chunk_step<D, A, 1, !CRITIC>(w, H, h0, xs, g, on, chk);
-                if (chunk == 0) gradient_bias_step<A, 1, !CRITIC>(g, on, db2);
-            }
-        }
-        if (H == 0) {
-            gradient_affine_each<D, A, 1>(aff, emit);
-        } else {
-            gradient_chunk_each<D, A, 1>(H, h0, chk, emit);
-            if (chunk == 0) gradient_bias_each<D, A, 1>(H, db2, emit);
-        }
-    }
-    *excluded = excl;
-    if (ppo && ppo->counts) {
-        ppo->counts[0] = seen;
-        ppo->counts[1] = ncut;
-    }
-}
-
-// 0 <= low <= 1 <= high, finite (false for a NaN)
-bool ppo_bounds_ok(float low, float high)
-{
-    return low >= 0.0f && low <= 1.0f && high >= 1.0f && high <= std::numeric_limits<float>::max();
-}
-} // namespace
-} // extern "C++"
-
-gymrs_status gymrs_gradient_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float scale, const float* weights, uint32_t n_steps,
-                                 const float* x, const uint8_t* actions, const float* coef, int64_t* q, uint64_t* excluded, float* prob)
-{
-    const std::string who = "gymrs_gradient_lane";
-    if (gymrs_status st = check_discrete_env(kind, who)) return st;
-    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, who + ": hidden must be <= 64");
-    if (flags & ~GYMRS_GRADIENT_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_GRADIENT_CRITIC is the only one)");
-    const bool critic = (flags & GYMRS_GRADIENT_CRITIC) != 0;
-    if (!weights || !coef || !q || !excluded || (n_steps != 0 && !x)) return fail(GYMRS_EINVAL, who + ": NULL argument");
-    if (!critic && n_steps != 0 && !actions) return fail(GYMRS_EINVAL, who + ": actions is NULL (the policy head reads them)");
-    if (critic && prob) return fail(GYMRS_EINVAL, who + ": prob with GYMRS_GRADIENT_CRITIC (the critic head has no probabilities)");
-    if (!critic && !(scale >= 0.0f && scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
-    if (kind == GYMRS_CARTPOLE) {
-        if (critic)
-            gradient_lane<4, 1, true>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
-        else
-            gradient_lane<4, 2, false>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
-    } else {
-        if (critic)
-            gradient_lane<2, 1, true>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
-        else
-            gradient_lane<2, 3, false>(hidden, scale, weights, n_steps, x, actions, coef, q, excluded, prob);
-    }
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_policy_gradient(gymrs_engine* e, const gymrs_gradient_desc* d)
-{
-    const std::string who = "gymrs_policy_gradient";
-    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
-    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, who + ": gradients are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
-    if (d->reserved != 0 || d->pad_ != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    if (d->flags & ~GYMRS_GRADIENT_CRITIC) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_GRADIENT_CRITIC is the only one)");
-    const bool critic = (d->flags & GYMRS_GRADIENT_CRITIC) != 0;
-    if (critic && !e->critic_dev) return fail(GYMRS_EINVAL, who + ": GYMRS_GRADIENT_CRITIC without a critic set on the engine (gymrs_set_critic)");
-    if (!critic && !e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
-    if (!critic && !(d->scale >= 0.0f && d->scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
-    const gymrs_trajectory& rec = d->record;
-    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
-    if (!critic && !rec.actions) return fail(GYMRS_EINVAL, who + ": record.actions is NULL (the policy head reads them)");
-    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
-    if (!d->coef) return fail(GYMRS_EINVAL, who + ": coef is NULL");
-    if (!d->grad) return fail(GYMRS_EINVAL, who + ": grad is NULL");
-    if (!d->excluded) return fail(GYMRS_EINVAL, who + ": excluded is NULL");
-    if (critic && d->prob) return fail(GYMRS_EINVAL, who + ": prob with GYMRS_GRADIENT_CRITIC (the critic head has no probabilities)");
-    const uintptr_t rows = reinterpret_cast<uintptr_t>(rec.obs) | (critic ? 0 : reinterpret_cast<uintptr_t>(rec.actions)) |
-                           reinterpret_cast<uintptr_t>(d->start_obs) | reinterpret_cast<uintptr_t>(d->coef) | reinterpret_cast<uintptr_t>(d->prob);
-    if (rows % 16 != 0) return fail(GYMRS_EINVAL, who + ": every row buffer must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d->grad) | reinterpret_cast<uintptr_t>(d->excluded)) % 8 != 0)
-        return fail(GYMRS_EINVAL, who + ": grad and excluded must be 8-byte aligned");
-    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
-    if (d->n_steps == 0) return GYMRS_OK;
-    GradientArgs a{};
-    a.obs = rec.obs;
-    a.actions = critic ? nullptr : static_cast<const uint8_t*>(rec.actions);
-    a.start_obs = d->start_obs;
-    a.coef = d->coef;
-    a.prob = d->prob;
-    a.grad = reinterpret_cast<unsigned long long*>(d->grad);
-    a.excluded = reinterpret_cast<unsigned long long*>(d->excluded);
-    a.stride = rec.lane_stride;
-    a.n = e->n;
-    a.gid0 = e->gid0;
-    a.n_steps = d->n_steps;
-    a.scale = critic ? 0.0f : d->scale;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_policy_gradient(e->kind, critic, a, critic ? e->critic : e->policy, e->stream));
-    return GYMRS_OK;
-}
-
-// ---- clipped surrogate: the host-side lane and the launch (include/gymrs_amd.h, "clipped surrogate") -------------------------------
-gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
-                            const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
-                            uint64_t counts[2], float* prob)
-{
-    const std::string who = "gymrs_ppo_lane";
-    if (gymrs_status st = check_discrete_env(kind, who)) return st;
-    if (hidden > kMaxPolicyHidden) return fail(GYMRS_EINVAL, who + ": hidden must be <= 64");
-    if (!weights || !advantages || !old_prob || !q || !excluded || (n_steps != 0 && (!x || !actions))) return fail(GYMRS_EINVAL, who + ": NULL argument");
-    if (prob && prob == old_prob) return fail(GYMRS_EINVAL, who + ": prob and old_prob may not alias");
-    if (!(scale >= 0.0f && scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
-    if (!ppo_bounds_ok(clip_low, clip_high)) return fail(GYMRS_EINVAL, who + ": clip bounds must be finite with 0 <= clip_low <= 1 <= clip_high");
-    const PpoLane ppo{old_prob, clip_low, clip_high, counts};
-    if (kind == GYMRS_CARTPOLE)
-        gradient_lane<4, 2, false>(hidden, scale, weights, n_steps, x, actions, advantages, q, excluded, prob, &ppo);
-    else
-        gradient_lane<2, 3, false>(hidden, scale, weights, n_steps, x, actions, advantages, q, excluded, prob, &ppo);
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d)
-{
-    const std::string who = "gymrs_ppo_gradient";
-    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
-    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
-    if (e->kind != GYMRS_CARTPOLE && e->kind != GYMRS_MOUNTAIN_CAR)
-        return fail(GYMRS_EINVAL, who + ": gradients are for the Discrete envs (CartPole, MountainCar); Pendulum takes no policy and records no transitions");
-    if (d->reserved != 0 || d->pad_ != 0) return fail(GYMRS_EINVAL, who + ": reserved and pad_ must be 0");
-    if (d->flags != 0) return fail(GYMRS_EINVAL, who + ": unknown flag bits (flags must be 0)");
-    if (!e->policy_dev) return fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
-    if (!(d->scale >= 0.0f && d->scale <= std::numeric_limits<float>::max())) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
-    if (!ppo_bounds_ok(d->clip_low, d->clip_high)) return fail(GYMRS_EINVAL, who + ": clip bounds must be finite with 0 <= clip_low <= 1 <= clip_high");
-    const gymrs_trajectory& rec = d->record;
-    if (!rec.obs) return fail(GYMRS_EINVAL, who + ": record.obs is NULL");
-    if (!rec.actions) return fail(GYMRS_EINVAL, who + ": record.actions is NULL (the policy head reads them)");
-    if (!d->start_obs) return fail(GYMRS_EINVAL, who + ": start_obs is NULL");
-    if (!d->advantages) return fail(GYMRS_EINVAL, who + ": advantages is NULL");
-    if (!d->old_prob) return fail(GYMRS_EINVAL, who + ": old_prob is NULL");
-    if (!d->grad) return fail(GYMRS_EINVAL, who + ": grad is NULL");
-    if (!d->excluded) return fail(GYMRS_EINVAL, who + ": excluded is NULL");
-    if (d->prob == d->old_prob) return fail(GYMRS_EINVAL, who + ": prob and old_prob may not alias");
-    const uintptr_t rows = reinterpret_cast<uintptr_t>(rec.obs) | reinterpret_cast<uintptr_t>(rec.actions) | reinterpret_cast<uintptr_t>(d->start_obs) |
-                           reinterpret_cast<uintptr_t>(d->advantages) | reinterpret_cast<uintptr_t>(d->old_prob) | reinterpret_cast<uintptr_t>(d->prob);
-    if (rows % 16 != 0) return fail(GYMRS_EINVAL, who + ": every row buffer must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(d->grad) | reinterpret_cast<uintptr_t>(d->excluded) | reinterpret_cast<uintptr_t>(d->counts)) % 8 != 0)
-        return fail(GYMRS_EINVAL, who + ": grad, excluded and counts must be 8-byte aligned");
-    if (rec.lane_stride < e->n || rec.lane_stride % 16 != 0) return fail(GYMRS_EINVAL, who + ": lane_stride must be >= n_envs and a multiple of 16");
-    if (d->n_steps == 0) return GYMRS_OK;
-    PpoArgs a{};
-    a.g.obs = rec.obs;
-    a.g.actions = static_cast<const uint8_t*>(rec.actions);
-    a.g.start_obs = d->start_obs;
-    a.g.coef = d->advantages;
-    a.g.prob = d->prob;
-    a.g.grad = reinterpret_cast<unsigned long long*>(d->grad);
-    a.g.excluded = reinterpret_cast<unsigned long long*>(d->excluded);
-    a.g.stride = rec.lane_stride;
-    a.g.n = e->n;
-    a.g.gid0 = e->gid0;
-    a.g.n_steps = d->n_steps;
-    a.g.scale = d->scale;
-    a.old_prob = d->old_prob;
-    a.counts = reinterpret_cast<unsigned long long*>(d->counts);
-    a.clip_low = d->clip_low;
-    a.clip_high = d->clip_high;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(launch_ppo_gradient(e->kind, a, e->policy, e->stream));
-    return GYMRS_OK;
-}
-
-// ---- per-policy fitness: the table behind gymrs_rollout_policy_fitness -----------------------------------------------------
-extern "C++" {
-// A gymrs_set_policy that removes the policy or changes n_policies: the table goes (launches already enqueued still add to it: wait for them).
-GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e)
-{
-    if (!e->fitness_dev) return GYMRS_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipFree(e->fitness_dev));
-    e->fitness_dev = nullptr;
-    return GYMRS_OK;
-}
-
-// The table: n_policies zeroed records at the first use after a gymrs_set_policy (the caller has checked that there is a policy set).
-GYMRS_HOST_INTERNAL gymrs_status policy_fitness_table(gymrs_engine* e)
-{
-    if (e->fitness_dev) return GYMRS_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t bytes = (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness);
-    HIP_TRY(hipMalloc(&e->fitness_dev, bytes));
-    if (hipError_t err = hipMemsetAsync(e->fitness_dev, 0, bytes, e->stream)) {
-        (void)hipFree(e->fitness_dev);
-        e->fitness_dev = nullptr;
-        HIP_TRY(err);
-    }
-    return GYMRS_OK;
-}
-
-// The checks the three read-out calls of the table share, then the table.
-static gymrs_status ensure_policy_fitness(gymrs_engine* e, const char* who)
-{
-    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
-    if (gymrs_status st = check_policy_set(e, who)) return st;
-    return policy_fitness_table(e);
-}
-} // extern "C++"
-
-gymrs_status gymrs_policy_fitness_ptr(gymrs_engine* e, gymrs_policy_fitness** dev_out, uint32_t* n_policies)
-{
-    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_fitness_ptr: NULL argument");
-    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_policy_fitness_ptr")) return st;
-    *dev_out = e->fitness_dev;
-    if (n_policies) *n_policies = e->policy.n_policies;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_get_policy_fitness(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_fitness* host_out)
-{
-    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_policy_fitness: NULL argument");
-    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_get_policy_fitness")) return st;
-    if ((uint64_t)first + count > e->policy.n_policies) return fail(GYMRS_EINVAL, "gymrs_get_policy_fitness: first + count is beyond n_policies");
-    if (count == 0) return stream_sync_checked(e);
-    HIP_TRY(hipMemcpyAsync(host_out, e->fitness_dev + first, (size_t)count * sizeof(gymrs_policy_fitness), hipMemcpyDeviceToHost, e->stream));
-    return stream_sync_checked(e);
-}
-
-gymrs_status gymrs_policy_fitness_clear(gymrs_engine* e)
-{
-    if (!e) return fail(GYMRS_EINVAL, "gymrs_policy_fitness_clear: NULL engine");
-    const bool fresh = e->fitness_dev == nullptr; // (a table that comes into being here is already zero)
-    if (gymrs_status st = ensure_policy_fitness(e, "gymrs_policy_fitness_clear")) return st;
-    if (fresh) return GYMRS_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemsetAsync(e->fitness_dev, 0, (size_t)e->policy.n_policies * sizeof(gymrs_policy_fitness), e->stream));
-    return GYMRS_OK;
-}
-
-// ---- episodic policy evaluation: gymrs_evaluate_policy and its table ------------------------------------------------------------
-extern "C++" {
-// Every gymrs_set_policy: the table goes (launches already enqueued still add to it: wait for them).
-GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e)
-{
-    if (!e->eval_dev) return GYMRS_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipFree(e->eval_dev));
-    e->eval_dev = nullptr;
-    return GYMRS_OK;
-}
-
-// The checks the three calls share, then the table: n_policies identity records at the first use after a gymrs_set_policy.
-static gymrs_status ensure_policy_eval(gymrs_engine* e, const char* who)
-{
-    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
-    if (gymrs_status st = check_policy_set(e, who)) return st;
-    if (e->eval_dev) return GYMRS_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMalloc(&e->eval_dev, (size_t)e->policy.n_policies * sizeof(gymrs_policy_eval)));
-    if (hipError_t err = launch_policy_eval_identity(e->eval_dev, e->policy.n_policies, e->stream)) {
-        (void)hipFree(e->eval_dev);
-        e->eval_dev = nullptr;
-        HIP_TRY(err);
-    }
-    return GYMRS_OK;
-}
-} // extern "C++"
-
-gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
-{
-    const std::string who = "gymrs_evaluate_policy";
-    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
-    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
-    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
-    if (gymrs_status st = check_policy_set(e, who)) return st;
-    if (gymrs_status st = check_table_opt_in(e, (d->flags & GYMRS_EVAL_LANE_PARAMS) != 0, who, // (a plain descriptor never plays a table engine with one set of parameters)
-                                             ": set GYMRS_EVAL_LANE_PARAMS in flags and every lane plays with its own row, or use gymrs_policy_actions + gymrs_step"))
-        return st;
-    if (d->episodes_per_lane == 0) return fail(GYMRS_EINVAL, who + ": episodes_per_lane must be >= 1");
-    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
-    if (d->flags & ~(GYMRS_EVAL_COMMON_STARTS | GYMRS_EVAL_LANE_PARAMS))
-        return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_EVAL_COMMON_STARTS and GYMRS_EVAL_LANE_PARAMS are the only ones)");
-    if (reinterpret_cast<uintptr_t>(d->lengths_dev) % alignof(uint32_t) != 0) return fail(GYMRS_EINVAL, who + ": lengths_dev must be 4-byte aligned");
-    const uint32_t dflt = e->kind == GYMRS_CARTPOLE ? e->consts.cp.max_steps : e->consts.mc.max_steps; // the params' max_episode_steps (500 / 200 by default; a table: the limit its rows share)
-    const uint32_t m = d->max_episode_steps ? d->max_episode_steps : dflt;
-    if ((uint64_t)d->episodes_per_lane * m > kMaxEvalSteps)
-        return fail(GYMRS_EINVAL, who + ": episodes_per_lane * max_episode_steps is above GYMRS_POLICY_EVAL_MAX_STEPS (it bounds the launch's running "
-                                        "time and keeps a lane's step count in 32 bits); split the evaluation");
-    if (gymrs_status st = ensure_policy_eval(e, "gymrs_evaluate_policy")) return st;
-    HIP_TRY(hipSetDevice(e->device));
-    // the latest call's results: identities first, in stream order, then this launch's episodes
-    HIP_TRY(launch_policy_eval_identity(e->eval_dev, e->policy.n_policies, e->stream));
-    EvalArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.n = e->n;
-    a.gid0 = e->gid0;
-    a.seed = d->seed;
-    a.episodes = d->episodes_per_lane;
-    a.max_steps = m;
-    a.flags = d->flags & GYMRS_EVAL_COMMON_STARTS; // (GYMRS_EVAL_LANE_PARAMS chooses the kernel; without a table it changes nothing)
-    a.lengths = d->lengths_dev;
-    a.table = e->eval_dev;
-    a.box = make_sample_box(e->dflt_lo, e->dflt_hi, e->state_dim); // gymrs_reset without bounds
-    HIP_TRY(launch_evaluate_policy(e->kind, e->table_k ? kFlagTable : 0u, a, launch_consts(e), e->policy, e->stream));
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_policy_eval_ptr(gymrs_engine* e, gymrs_policy_eval** dev_out, uint32_t* n_policies)
-{
-    if (!e || !dev_out) return fail(GYMRS_EINVAL, "gymrs_policy_eval_ptr: NULL argument");
-    if (gymrs_status st = ensure_policy_eval(e, "gymrs_policy_eval_ptr")) return st;
-    *dev_out = e->eval_dev;
-    if (n_policies) *n_policies = e->policy.n_policies;
-    return GYMRS_OK;
-}
-
-gymrs_status gymrs_get_policy_eval(gymrs_engine* e, uint32_t first, uint32_t count, gymrs_policy_eval* host_out)
-{
-    if (!e || !host_out) return fail(GYMRS_EINVAL, "gymrs_get_policy_eval: NULL argument");
-    if (gymrs_status st = ensure_policy_eval(e, "gymrs_get_policy_eval")) return st;
-    if ((uint64_t)first + count > e->policy.n_policies) return fail(GYMRS_EINVAL, "gymrs_get_policy_eval: first + count is beyond n_policies");
-    if (count == 0) return stream_sync_checked(e);
-    HIP_TRY(hipMemcpyAsync(host_out, e->eval_dev + first, (size_t)count * sizeof(gymrs_policy_eval), hipMemcpyDeviceToHost, e->stream));
-    return stream_sync_checked(e);
 }
 
 // ---- the pub physics fields after construction -------------------------------------------------------------------

@@ -2,8 +2,10 @@
 // more than one entry point words the same way, and the few helpers more than one of them needs.
 //   gymrs_engine.hip     creation, reset, the ONE submission sequence of a per-step launch (prepare_step / record_step, used by gymrs_step,
 //                        gymrs_step_many's eager launches and its chains; graphs bake the same launches in), the fused rollouts, gymrs_sync
-//   gymrs_engine_io.hip  views and copies of the arrays, clone / snapshot, statistics, RCCL, the policy set and its tables, the pub physics
-//                        fields, the serde JSON view
+//   gymrs_engine_io.hip  views and copies of the arrays, clone / snapshot, statistics, RCCL, the pub physics fields and tables, the serde
+//                        JSON view, developer hooks
+//   gymrs_engine_learn.hip  the learner surface: the policy and critic sets, exploration and sampling, advantages, gradients, the clipped
+//                        surrogate, the host-only lanes, the fitness and evaluation tables
 //   gymrs_step_plan.h    the decisions of the stepping path that need no device (HIP-free, walked by tests/test_step_plan.py)
 // Not installed, not part of the ABI.
 #pragma once
@@ -56,6 +58,14 @@ struct RcclApi {
     const char* (*GetErrorString)(int) = nullptr;
     int (*GroupStart)() = nullptr; // several devices driven by ONE thread (gymrs_allreduce_stats_multi): RCCL's calls are collective per
     int (*GroupEnd)() = nullptr;   // communicator, so one thread may only issue them for all of its devices inside a group
+};
+
+// A set of small networks on the device (gymrs_set_policy, gymrs_set_critic): `args` is what the kernels get by value, `dev` the engine-owned
+// buffer args.weights points to (NULL = no set), `capacity` the floats dev holds.  The functions over it: gymrs_engine_learn.hip.
+struct WeightSet {
+    PolicyArgs args{};
+    float* dev = nullptr;
+    uint64_t capacity = 0;
 };
 
 struct gymrs_engine {
@@ -173,16 +183,14 @@ struct gymrs_engine {
     uint16_t* param_index = nullptr;         // [n] the row of every lane, allocated on first use
     std::vector<unsigned char> table_params; // the table_k rows as the caller set them (f64 gymrs_<kind>_params, back to back)
     TableConsts tconsts{};                   // the by-value constants of a table launch
-    // The policy set of the closed-loop calls (gymrs_set_policy): `policy` is what the policy kernels get by value, policy_dev the
-    // engine-owned device buffer policy.weights points to (NULL = no policy).  Not part of clone or snapshot.
-    PolicyArgs policy{};
-    float* policy_dev = nullptr;
-    uint64_t policy_capacity = 0; // floats policy_dev holds
-    // The per-policy counters of gymrs_rollout_policy_fitness: policy.n_policies records, allocated (zeroed) at the first fitness
+    // The policy set of the closed-loop calls (gymrs_set_policy) and the critic set of gymrs_advantages (gymrs_set_critic: the stride of
+    // its args is critic_floats; gymrs_set_policy keeps it).  Not part of clone or snapshot.
+    WeightSet policy, critic;
+    // The per-policy counters of gymrs_rollout_policy_fitness: policy.args.n_policies records, allocated (zeroed) at the first fitness
     // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
     // stays the same).  Not part of clone or snapshot.
     gymrs_policy_fitness* fitness_dev = nullptr;
-    // The per-policy episodic records of gymrs_evaluate_policy: policy.n_policies records holding the latest call's results, allocated
+    // The per-policy episodic records of gymrs_evaluate_policy: policy.args.n_policies records holding the latest call's results, allocated
     // (as identities) at first use after a gymrs_set_policy; every gymrs_set_policy frees it.  Not part of clone or snapshot.
     gymrs_policy_eval* eval_dev = nullptr;
     // The exploration settings (gymrs_set_exploration): what the exploring kernels get by value, so a change takes effect in
@@ -192,11 +200,6 @@ struct gymrs_engine {
     // The sampling settings (gymrs_set_sampling), under the same rules.
     SampleArgs sample{};
     bool sample_set = false;
-    // The critic set of gymrs_advantages (gymrs_set_critic): `critic` is a PolicyArgs whose stride is critic_floats, critic_dev the
-    // engine-owned device buffer critic.weights points to (NULL = no critic).  gymrs_set_policy keeps it.  Not part of clone or snapshot.
-    PolicyArgs critic{};
-    float* critic_dev = nullptr;
-    uint64_t critic_capacity = 0; // floats critic_dev holds
     uint64_t limit_elided_launches = 0; // for the serde view's engine extras (tests, diagnostics)
     uint64_t age_refreshes = 0, age_waits = 0, age_wait_ns = 0;
 };
@@ -244,10 +247,12 @@ GYMRS_HOST_INTERNAL inline gymrs_status check_discrete_env(gymrs_env_kind kind, 
     if (kind == GYMRS_CARTPOLE || kind == GYMRS_MOUNTAIN_CAR) return GYMRS_OK;
     return fail(GYMRS_EINVAL, who + ": policies are for the Discrete envs (CartPole, MountainCar); Pendulum takes a Box action");
 }
-GYMRS_HOST_INTERNAL inline gymrs_status check_policy_set(const gymrs_engine* e, const std::string& who)
+// `noun`: "policy" or "critic", which is also how its setter ends
+GYMRS_HOST_INTERNAL inline gymrs_status check_weight_set(const WeightSet& set, const std::string& noun, const std::string& who)
 {
-    return e->policy_dev ? GYMRS_OK : fail(GYMRS_EINVAL, who + ": the engine has no policy (gymrs_set_policy)");
+    return set.dev ? GYMRS_OK : fail(GYMRS_EINVAL, who + ": the engine has no " + noun + " (gymrs_set_" + noun + ")");
 }
+GYMRS_HOST_INTERNAL inline gymrs_status check_policy_set(const gymrs_engine* e, const std::string& who) { return check_weight_set(e->policy, "policy", who); }
 // A parameter table is never played behind the caller's back: the call has to opt in.  `advice` = what the entry point tells
 // the caller to do instead, punctuation included.
 GYMRS_HOST_INTERNAL inline gymrs_status check_table_opt_in(const gymrs_engine* e, bool opted_in, const std::string& who, const char* advice)
@@ -272,6 +277,5 @@ GYMRS_HOST_INTERNAL void limit_restart(gymrs_engine* e, uint64_t bound, bool tru
 GYMRS_HOST_INTERNAL std::string aql_kernel_name(const gymrs_engine* e, uint32_t flags, int threads);
 // defined in gymrs_engine_io.hip (RCCL is resolved there, at first use)
 GYMRS_HOST_INTERNAL void comm_destroy(gymrs_engine* e);
+// defined in gymrs_engine_learn.hip
 GYMRS_HOST_INTERNAL gymrs_status policy_fitness_table(gymrs_engine* e); // the per-policy counters: allocated (zeroed) at first use
-GYMRS_HOST_INTERNAL gymrs_status discard_policy_fitness(gymrs_engine* e);
-GYMRS_HOST_INTERNAL gymrs_status discard_policy_eval(gymrs_engine* e);

@@ -1,5 +1,5 @@
 // gymrs_evaluate.h -- launch interface of the episodic policy evaluation (gymrs_evaluate_policy, include/gymrs_amd.h "episodic
-// policy evaluation"): between the engine (gymrs_engine_io.hip) and its kernels (gymrs_evaluate_impl.h).
+// policy evaluation"): between the engine (gymrs_engine_learn.hip) and its kernels (gymrs_evaluate_impl.h).
 #pragma once
 #include "gymrs_kernels.h"
 

@@ -1,4 +1,4 @@
-// gymrs_kernels.h — launch interface between the engine (gymrs_engine.hip, gymrs_engine_io.hip) and the gfx950 kernels.  Plain
+// gymrs_kernels.h — launch interface between the engine (gymrs_engine.hip, gymrs_engine_io.hip, gymrs_engine_learn.hip) and the gfx950 kernels.  Plain
 // structs passed by value as kernel arguments (uniform -> SGPRs).  The kernel files:
 //   gymrs_step_<env>.hip     the per-step kernel table of one env type (gymrs_step_impl.h), one translation unit each
 //   gymrs_table_<env>.hip    the per-step, rollout and evaluation kernels of one env type with a parameter table (TableT)

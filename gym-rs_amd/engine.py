@@ -363,6 +363,64 @@ def _check(lib, status: int) -> None:
     raise GymrsError(status, msg)
 
 
+def _set_weights(lib, setter, handle, kind, weights, hidden, lanes, size_of, plural) -> None:
+    """``gymrs_set_policy`` / ``gymrs_set_critic`` / ``gymrs_sharded_set_policy``: ``weights`` (None removes the set) holds a whole
+    number of networks of ``size_of(kind, hidden)`` floats."""
+    if weights is None:
+        _check(lib, setter(handle, None, None))
+        return
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    size = size_of(kind, hidden)
+    if w.size == 0 or w.size % size != 0:
+        raise ValueError(f"weights must hold a whole number (>= 1) of {plural} of {size} floats, got {w.size}")
+    desc = PolicyDesc(int(hidden), w.size // size, int(lanes))
+    _check(lib, setter(handle, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+
+
+def _describe(lib, getter, handle) -> PolicyDesc:
+    """``gymrs_get_policy`` / ``gymrs_get_critic`` as a query of the description."""
+    desc = PolicyDesc()
+    _check(lib, getter(handle, C.byref(desc), None, 0))
+    return desc
+
+
+def _get_weights(lib, getter, handle, kind, size_of):
+    """``gymrs_get_policy`` / ``gymrs_get_critic``: (weights of shape (n, size), hidden, lanes per network) (synchronising)."""
+    desc = _describe(lib, getter, handle)
+    w = np.empty((desc.n_policies, size_of(kind, desc.hidden)), dtype=np.float32)
+    _check(lib, getter(handle, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size))
+    return w, int(desc.hidden), int(desc.lanes_per_policy)
+
+
+def _view(lib, fn, handle, count_type=C.c_uint64) -> Tuple[int, int]:
+    """(device address, count) of a ``gymrs_*_ptr`` call."""
+    p, n = C.c_void_p(), count_type()
+    _check(lib, fn(handle, C.byref(p), C.byref(n)))
+    return p.value, n.value
+
+
+def _record(who, n_envs, n_steps, record, unread=()) -> Trajectory:
+    """The by-value record of a descriptor from ``record``, a ``Trajectory`` or a mapping as in ``rollout_closed_loop`` that may
+    leave out the names the call does not read (``unread``)."""
+    if record is None:
+        raise ValueError(f"{who} needs a record")
+    if not isinstance(record, Trajectory):
+        record = dict(record)
+        for name in unread:
+            record.setdefault(name, 0)
+    return _closed_loop_desc(n_envs, n_steps, False, False, record).record.contents
+
+
+def _policy_records(lib, getter, handle, policy_handle, first, count, columns) -> np.ndarray:
+    """Records of policies [first, first + count) as int64 rows (synchronising); ``count`` defaults to the rest of the set the engine
+    ``policy_handle`` holds."""
+    if count is None:
+        count = int(_describe(lib, lib.gymrs_get_policy, policy_handle).n_policies) - int(first)
+    out = np.zeros((max(int(count), 0), columns), dtype=np.int64)
+    _check(lib, getter(handle, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def shard_range(n_total: int, world_size: int, rank: int) -> Tuple[int, int]:
     """Contiguous lane shard of rank ``rank``: (global offset, count).  Lanes are independent, so
     the batch shards trivially; the global id keeps Philox draws identical for any world size."""
@@ -698,31 +756,16 @@ class BatchedEngine:
         """Install a policy set: ``weights`` is an array of shape (n_policies, policy_size(kind, hidden)) (or one flat policy),
         f32, laid out as include/gymrs_amd.h says; lane i uses policy ((global_env_offset + i) // lanes_per_policy) % n_policies.
         ``None`` removes the policy.  Touches no lane state, tick or statistics."""
-        if weights is None:
-            _check(self._lib, self._lib.gymrs_set_policy(self._h, None, None))
-            return
-        w = np.ascontiguousarray(weights, dtype=np.float32)
-        size = policy_size(self.kind, hidden)
-        if w.size == 0 or w.size % size != 0:
-            raise ValueError(f"weights must hold a whole number (>= 1) of policies of {size} floats, got {w.size}")
-        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_policy))
-        _check(self._lib, self._lib.gymrs_set_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+        _set_weights(self._lib, self._lib.gymrs_set_policy, self._h, self.kind, weights, hidden, lanes_per_policy, policy_size, "policies")
 
     def get_policy(self):
         """(weights of shape (n_policies, policy_size), hidden, lanes_per_policy) as set (synchronising)."""
-        desc = PolicyDesc()
-        _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
-        size = policy_size(self.kind, desc.hidden)
-        w = np.empty((desc.n_policies, size), dtype=np.float32)
-        _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size))
-        return w, int(desc.hidden), int(desc.lanes_per_policy)
+        return _get_weights(self._lib, self._lib.gymrs_get_policy, self._h, self.kind, policy_size)
 
     def policy_weights_ptr(self) -> Tuple[int, int]:
         """(device address, number of floats) of the policy set: zero-copy; a kernel on the engine's stream may rewrite the
         weights between two launches.  Valid until the next set_policy or close."""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(self._lib, self._lib.gymrs_policy_weights_ptr(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return _view(self._lib, self._lib.gymrs_policy_weights_ptr, self._h)
 
     def policy_actions(self, actions_dev: int) -> None:
         """Write the policy's uint8 action for every lane's current observation to ``actions_dev`` (one launch)."""
@@ -778,31 +821,16 @@ class BatchedEngine:
         """Install a critic set: ``weights`` is an array of shape (n_critics, critic_size(kind, hidden)) (or one flat critic),
         f32; lane i uses critic ((global_env_offset + i) // lanes_per_critic) % n_critics.  ``None`` removes the critic.  Touches
         no lane state, tick or statistics, and survives ``set_policy``."""
-        if weights is None:
-            _check(self._lib, self._lib.gymrs_set_critic(self._h, None, None))
-            return
-        w = np.ascontiguousarray(weights, dtype=np.float32)
-        size = critic_size(self.kind, hidden)
-        if w.size == 0 or w.size % size != 0:
-            raise ValueError(f"weights must hold a whole number (>= 1) of critics of {size} floats, got {w.size}")
-        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_critic))
-        _check(self._lib, self._lib.gymrs_set_critic(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+        _set_weights(self._lib, self._lib.gymrs_set_critic, self._h, self.kind, weights, hidden, lanes_per_critic, critic_size, "critics")
 
     def critic(self):
         """(weights of shape (n_critics, critic_size), hidden, lanes_per_critic) as set (synchronising)."""
-        desc = PolicyDesc()
-        _check(self._lib, self._lib.gymrs_get_critic(self._h, C.byref(desc), None, 0))
-        size = critic_size(self.kind, desc.hidden)
-        w = np.empty((desc.n_policies, size), dtype=np.float32)
-        _check(self._lib, self._lib.gymrs_get_critic(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p), w.size))
-        return w, int(desc.hidden), int(desc.lanes_per_policy)
+        return _get_weights(self._lib, self._lib.gymrs_get_critic, self._h, self.kind, critic_size)
 
     def critic_weights_ptr(self) -> Tuple[int, int]:
         """(device address, number of floats) of the critic set: zero-copy; a kernel on the engine's stream may rewrite the
         weights between two launches.  Valid until the next set_critic or close."""
-        p, n = C.c_void_p(), C.c_uint64()
-        _check(self._lib, self._lib.gymrs_critic_weights_ptr(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return _view(self._lib, self._lib.gymrs_critic_weights_ptr, self._h)
 
     def advantages(self, n_steps: int, *, record, start_obs: int, advantages: int, final_obs: Optional[int] = None,
                    returns: Optional[int] = None, values: Optional[int] = None, gamma: float, lam: float, critic: bool = False,
@@ -812,12 +840,7 @@ class BatchedEngine:
         ``critic`` (``GYMRS_ADVANTAGES_CRITIC``) evaluates the critic set of ``set_critic`` inside the kernel; without it V = 0 and
         ``gamma = lam = 1`` gives the reward-to-go.  ``final_obs=None`` is for records of engines without auto-reset.  ``record``: a
         ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (its ``actions`` is not read).  Reads and writes no lane array."""
-        if record is None:
-            raise ValueError("advantages needs a record")
-        if not isinstance(record, Trajectory):
-            record = dict(record)
-            record.setdefault("actions", 0)
-        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        traj = _record("advantages", self.n_envs, n_steps, record, unread=("actions",))
         f = (ADVANTAGES_CRITIC if critic else 0) if flags is None else int(flags)
         desc = AdvantagesDesc(int(n_steps), f, float(gamma), float(lam), traj, C.c_void_p(final_obs or None), C.c_void_p(start_obs or None),
                               C.c_void_p(advantages or None), C.c_void_p(returns or None), C.c_void_p(values or None), 0)
@@ -834,13 +857,7 @@ class BatchedEngine:
         [n_critics][critic_size]; ``temperature`` / ``scale`` are for the policy head only (exactly one of them), ``prob`` (device
         f32 [n_steps][lane_stride]) receives p[a].  ``record``: a ``Trajectory`` or a mapping as in ``rollout_closed_loop`` (only
         ``obs`` and, for the policy head, ``actions`` are read).  The caller zeroes the tables.  Reads and writes no lane array."""
-        if record is None:
-            raise ValueError("policy_gradient needs a record")
-        if not isinstance(record, Trajectory):
-            record = dict(record)
-            for name in ("actions", "reward", "done"):
-                record.setdefault(name, 0)
-        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        traj = _record("policy_gradient", self.n_envs, n_steps, record, unread=("actions", "reward", "done"))
         f = (GRADIENT_CRITIC if critic else 0) if flags is None else int(flags)
         s = 0.0
         if not (f & GRADIENT_CRITIC):
@@ -861,13 +878,7 @@ class BatchedEngine:
         uint64 [n_policies][2]), the lane-steps seen and the lane-steps cut.  ``clip`` (epsilon) becomes ``np.float32(1 - clip)`` and
         ``np.float32(1 + clip)``; ``clip_low`` / ``clip_high`` give the bounds themselves.  ``prob`` receives the new p[a] and may
         not be ``old_prob``.  Exactly one of ``temperature`` / ``scale``.  Reads and writes no lane array."""
-        if record is None:
-            raise ValueError("ppo_gradient needs a record")
-        if not isinstance(record, Trajectory):
-            record = dict(record)
-            for name in ("actions", "reward", "done"):
-                record.setdefault(name, 0)
-        traj = _closed_loop_desc(self.n_envs, n_steps, False, False, record).record.contents
+        traj = _record("ppo_gradient", self.n_envs, n_steps, record, unread=("actions", "reward", "done"))
         low, high = _clip_bounds(clip, clip_low, clip_high)
         s = _sampling(0, temperature, scale).scale
         desc = PpoDesc(int(n_steps), int(flags), float(s), low, high, 0, traj, C.c_void_p(start_obs or None), C.c_void_p(advantages or None),
@@ -926,20 +937,12 @@ class BatchedEngine:
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of policies [first, first + count) as an int64 array of shape (count, 4): columns reward_sum, episodes,
         done, truncated (synchronising).  ``count`` defaults to the rest of the set."""
-        if count is None:
-            desc = PolicyDesc()
-            _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
-            count = int(desc.n_policies) - int(first)
-        out = np.zeros((max(int(count), 0), 4), dtype=np.int64)
-        _check(self._lib, self._lib.gymrs_get_policy_fitness(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _policy_records(self._lib, self._lib.gymrs_get_policy_fitness, self._h, self._h, first, count, 4)
 
     def policy_fitness_ptr(self) -> Tuple[int, int]:
         """(device address, n_policies) of the records (``PolicyFitness``, 32 bytes each): zero-copy, under the stream rules of
         the other views.  Valid until the next set_policy or close."""
-        p, n = C.c_void_p(), C.c_uint32()
-        _check(self._lib, self._lib.gymrs_policy_fitness_ptr(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return _view(self._lib, self._lib.gymrs_policy_fitness_ptr, self._h, C.c_uint32)
 
     def policy_fitness_clear(self) -> None:
         """Zero the records (in stream order)."""
@@ -963,20 +966,12 @@ class BatchedEngine:
         """The episodic records of policies [first, first + count) as an int64 array of shape (count, 8): columns return_sum,
         return_sq_sum, episodes, done, truncated, steps, return_min, return_max (synchronising; return_sq_sum is the uint64's
         bits).  ``count`` defaults to the rest of the set."""
-        if count is None:
-            desc = PolicyDesc()
-            _check(self._lib, self._lib.gymrs_get_policy(self._h, C.byref(desc), None, 0))
-            count = int(desc.n_policies) - int(first)
-        out = np.zeros((max(int(count), 0), 8), dtype=np.int64)
-        _check(self._lib, self._lib.gymrs_get_policy_eval(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _policy_records(self._lib, self._lib.gymrs_get_policy_eval, self._h, self._h, first, count, 8)
 
     def policy_eval_ptr(self) -> Tuple[int, int]:
         """(device address, n_policies) of the episodic records (``PolicyEval``, 64 bytes each): zero-copy, under the stream
         rules of the other views.  Valid until the next set_policy or close."""
-        p, n = C.c_void_p(), C.c_uint32()
-        _check(self._lib, self._lib.gymrs_policy_eval_ptr(self._h, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return _view(self._lib, self._lib.gymrs_policy_eval_ptr, self._h, C.c_uint32)
 
     def tick(self) -> Tuple[int, int]:
         t, s = C.c_uint64(), C.c_uint64()
@@ -1074,15 +1069,7 @@ class ShardedEngine:
     # -- closed-loop rollouts and per-policy fitness on every block (the policy set is keyed by global lane ids) --
     def set_policy(self, weights, hidden: int = 0, lanes_per_policy: int = 1) -> None:
         """``BatchedEngine.set_policy`` on every block: the same set everywhere.  ``None`` removes the policy."""
-        if weights is None:
-            _check(self._lib, self._lib.gymrs_sharded_set_policy(self._h, None, None))
-            return
-        w = np.ascontiguousarray(weights, dtype=np.float32)
-        size = policy_size(self.kind, hidden)
-        if w.size == 0 or w.size % size != 0:
-            raise ValueError(f"weights must hold a whole number (>= 1) of policies of {size} floats, got {w.size}")
-        desc = PolicyDesc(int(hidden), w.size // size, int(lanes_per_policy))
-        _check(self._lib, self._lib.gymrs_sharded_set_policy(self._h, C.byref(desc), w.ctypes.data_as(C.c_void_p)))
+        _set_weights(self._lib, self._lib.gymrs_sharded_set_policy, self._h, self.kind, weights, hidden, lanes_per_policy, policy_size, "policies")
 
     def rollout_policy(self, n_steps: int) -> None:
         """``BatchedEngine.rollout_policy`` on every block."""
@@ -1136,13 +1123,8 @@ class ShardedEngine:
     def policy_fitness(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The records of the WHOLE batch, (count, 4) int64 as ``BatchedEngine.policy_fitness``: the blocks' records summed
         (exact; synchronising)."""
-        if count is None:  # (every block holds the same set: block 0's description is the batch's)
-            desc = PolicyDesc()
-            _check(self._lib, self._lib.gymrs_get_policy(self.shards[0]._h, C.byref(desc), None, 0))
-            count = int(desc.n_policies) - int(first)
-        out = np.zeros((max(int(count), 0), 4), dtype=np.int64)
-        _check(self._lib, self._lib.gymrs_sharded_get_policy_fitness(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
-        return out
+        # (every block holds the same set: block 0's description is the batch's)
+        return _policy_records(self._lib, self._lib.gymrs_sharded_get_policy_fitness, self._h, self.shards[0]._h, first, count, 4)
 
     def policy_fitness_ptr(self):
         """[(device address, n_policies)] per block: each block's own records (``shards[r].policy_fitness_ptr()``); their sum
@@ -1162,13 +1144,7 @@ class ShardedEngine:
     def policy_eval(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The episodic records of the WHOLE batch, (count, 8) int64 as ``BatchedEngine.policy_eval``: the blocks' records merged
         (sums added, min of mins, max of maxes; synchronising)."""
-        if count is None:
-            desc = PolicyDesc()
-            _check(self._lib, self._lib.gymrs_get_policy(self.shards[0]._h, C.byref(desc), None, 0))
-            count = int(desc.n_policies) - int(first)
-        out = np.zeros((max(int(count), 0), 8), dtype=np.int64)
-        _check(self._lib, self._lib.gymrs_sharded_get_policy_eval(self._h, int(first), int(count), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _policy_records(self._lib, self._lib.gymrs_sharded_get_policy_eval, self._h, self.shards[0]._h, first, count, 8)
 
     def policy_eval_ptr(self):
         """[(device address, n_policies)] per block: each block's own records (``shards[r].policy_eval_ptr()``)."""
