@@ -1077,23 +1077,15 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, const Rollou
     if (gymrs_status st = fold_reset_log(e)) return st; // the rollout kernel carries ep_start and the counters itself
     if (q.fitness)
         if (gymrs_status st = policy_fitness_table(e)) return st;
-    const bool explore = q.actions == ActionSource::Exploring;
-    if (q.actions == ActionSource::Sampling) {
-        HIP_TRY(launch_rollout_sample(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->sample,
-                                      q.fitness ? e->fitness_dev : nullptr, q.transitions, e->stream));
-    } else if (q.transitions) { // one action source: a greedy launch plays threshold 0 (the greedy bits)
-        const ExploreArgs greedy{};
-        HIP_TRY(launch_rollout_transitions(e->kind, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, explore ? e->explore : greedy,
-                                           *q.transitions, e->stream));
-    } else if (explore) {
-        HIP_TRY(launch_rollout_explore(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->explore,
-                                       q.fitness ? e->fitness_dev : nullptr, e->stream));
-    } else if (q.fitness) {
-        HIP_TRY(launch_rollout_policy_fitness(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->fitness_dev, e->stream));
-    } else if (q.actions == ActionSource::Policy)
-        HIP_TRY(launch_rollout_policy(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, e->stream));
-    else
+    if (q.actions == ActionSource::Random)
         HIP_TRY(launch_rollout(e->kind, vec, e->flags | table_bit(e), a, r, launch_consts(e), e->stream));
+    else {
+        const ClosedLoopSource source = q.actions == ActionSource::Sampling    ? ClosedLoopSource::sampling
+                                        : q.actions == ActionSource::Exploring ? ClosedLoopSource::exploring
+                                                                               : ClosedLoopSource::policy;
+        HIP_TRY(launch_closed_loop(e->kind, {vec, e->flags | table_bit(e), a, r, launch_consts(e), e->policy.args, source, e->explore, e->sample,
+                                             q.fitness ? e->fitness_dev : nullptr, q.transitions, e->stream}));
+    }
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
     for (uint32_t k = 0; k < n_steps; ++k) { // the host copy of the uniform episode clock (Pendulum time limit)
         if (has_uniform_clock(e)) {

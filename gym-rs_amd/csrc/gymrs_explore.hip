@@ -55,27 +55,7 @@ hipError_t launch_explore_actions(gymrs_env_kind kind, const float* const* s, vo
     });
 }
 
-hipError_t launch_rollout_explore_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                          const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
-hipError_t launch_rollout_explore_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                 const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
-hipError_t launch_rollout_explore_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                     const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
-
-hipError_t launch_rollout_explore(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                  const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    if (a.n == 0 || r.n_steps == 0) return hipSuccess;
-    if (fitness && (r.rec_obs || r.n_steps > kMaxFitnessSteps)) return hipErrorInvalidValue;
-    if (flags & kFlagTable) {
-        switch (kind) {
-        case GYMRS_CARTPOLE: return launch_rollout_explore_table_cartpole(vec, flags, a, r, consts, p, x, fitness, stream);
-        case GYMRS_MOUNTAIN_CAR: return launch_rollout_explore_table_mountain_car(vec, flags, a, r, consts, p, x, fitness, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (fitness) return launch_rollout_explore_fitness(kind, vec, flags, a, r, consts, p, x, fitness, stream);
-    return dispatch_policy_env(kind, [&](auto env) { return rollout_explore_vec<typename decltype(env)::type>(vec, flags, a, r, consts, p, x, stream); });
-}
+hipError_t closed_loop_explore_cartpole(const ClosedLoopLaunch& l) { return closed_loop_unit<CartPoleT, ClosedLoopFamily::explore>(l); }
+hipError_t closed_loop_explore_mountain_car(const ClosedLoopLaunch& l) { return closed_loop_unit<MountainCarT, ClosedLoopFamily::explore>(l); }
 
 } // namespace gymrs

@@ -5,12 +5,7 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_explore_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                          const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    return dispatch_policy_env(kind, [&](auto env) {
-        return rollout_explore_fitness_vec<typename decltype(env)::type>(vec, flags, a, r, consts, p, x, fitness, stream);
-    });
-}
+hipError_t closed_loop_explore_fitness_cartpole(const ClosedLoopLaunch& l) { return closed_loop_unit<CartPoleT, ClosedLoopFamily::explore_fitness>(l); }
+hipError_t closed_loop_explore_fitness_mountain_car(const ClosedLoopLaunch& l) { return closed_loop_unit<MountainCarT, ClosedLoopFamily::explore_fitness>(l); }
 
 } // namespace gymrs

@@ -4,7 +4,7 @@
 //   gymrs_table_<env>.hip    the per-step, rollout and evaluation kernels of one env type with a parameter table (TableT)
 //   gymrs_step_aql.hip       the per-step kernels once more, as the code object of the engine's own AQL dispatcher
 //   gymrs_rollout.hip        the fused random-policy rollout (gymrs_rollout_impl.h)
-//   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h)
+//   gymrs_rollout_policy.hip the closed-loop kernels: policy actions, the fused rollout under a policy (gymrs_policy.h); launch_closed_loop
 //   gymrs_rollout_fitness.hip  that rollout with per-policy fitness counters
 //   gymrs_explore.hip        the closed-loop kernels once more with the epsilon-greedy action source (gymrs_rollout_explore_impl.h)
 //   gymrs_sample.hip         the closed-loop and transitions kernels with the softmax sampling source (gymrs_rollout_sample_impl.h)
@@ -330,40 +330,46 @@ inline uint64_t policy_floats(gymrs_env_kind kind, uint32_t hidden)
 // actions[i] = policy(observation of lane i) for the n lanes whose observation rows are s[0 .. obs_dim)
 hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, void* actions, uint64_t n, uint64_t gid0, const PolicyArgs& p,
                                  hipStream_t stream);
-// launch_rollout with the policy as the action source (r.action_seed / action_t0 / n_actions are not read)
-hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                 const PolicyArgs& p, hipStream_t stream);
-// launch_rollout_policy (non-recording) that also adds every step's reward / done / truncated of every lane to the record of
-// the lane's policy in fitness[n_policies] (gymrs_rollout_fitness.hip): integer atomics, once per wave and launch.  The
-// in-register accumulators are 32 bits wide: r.n_steps <= kMaxFitnessSteps (GYMRS_POLICY_FITNESS_MAX_STEPS).
-constexpr uint32_t kMaxFitnessSteps = GYMRS_POLICY_FITNESS_MAX_STEPS;
-hipError_t launch_rollout_policy_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                         const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream);
-// ---- epsilon-greedy exploration (gymrs_set_exploration; gymrs_explore.hip, gymrs_table_explore_<env>.hip) ----------------------
+// ---- epsilon-greedy exploration (gymrs_set_exploration; gymrs_explore.hip) ----------------------------------------------------
 // launch_policy_actions mixed with the exploration draw of engine tick `tick`
 hipError_t launch_explore_actions(gymrs_env_kind kind, const float* const* s, void* actions, uint64_t n, uint64_t gid0, uint64_t tick,
                                   const PolicyArgs& p, const ExploreArgs& x, hipStream_t stream);
-// launch_rollout_policy / launch_rollout_policy_fitness (fitness != NULL) playing the epsilon-greedy action of every step
-hipError_t launch_rollout_explore(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                  const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
-// ---- transitions (gymrs_rollout_transitions; gymrs_transitions.hip, gymrs_table_transitions_<env>.hip) ------------------------
-// The two buffers of a gymrs_transitions_desc as the kernels get them by value, after ExploreArgs.  Rows are RolloutArgs::rec_stride
-// lanes apart, like the record's.
+// ---- softmax sampling (gymrs_set_sampling; gymrs_sample.hip) -------------------------------------------------------------------
+// launch_policy_actions with the sampled action of engine tick `tick`; prob (may be NULL) gets the probability of every lane's action
+hipError_t launch_sample_actions(gymrs_env_kind kind, const float* const* s, void* actions, float* prob, uint64_t n, uint64_t gid0, uint64_t tick,
+                                 const PolicyArgs& p, const SampleArgs& x, hipStream_t stream);
+// ---- the closed-loop fused rollouts (gymrs_rollout_closed_loop, gymrs_rollout_transitions and the calls from before them) -----
+// The two buffers of a gymrs_transitions_desc as the transitions kernels get them by value, after the source's arguments.  Rows are
+// RolloutArgs::rec_stride lanes apart, like the record's.
 struct TransitionArgs {
     float* final_obs; // [n_steps][obs_dim][rec_stride]: written where a step re-armed a lane, nowhere else
     float* start_obs; // [obs_dim][rec_stride] or NULL
 };
-// launch_rollout_explore with a record (r.rec_obs != NULL, 4 lanes per work-item) that also writes t.  Engines with GYMRS_AUTO_RESET
-// only; x.threshold == 0 is the greedy launch.
-hipError_t launch_rollout_transitions(gymrs_env_kind kind, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                      const PolicyArgs& p, const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream);
-// ---- softmax sampling (gymrs_set_sampling; gymrs_sample.hip, gymrs_sample_fitness.hip, gymrs_table_sample_<env>.hip) ----------
-// launch_policy_actions with the sampled action of engine tick `tick`; prob (may be NULL) gets the probability of every lane's action
-hipError_t launch_sample_actions(gymrs_env_kind kind, const float* const* s, void* actions, float* prob, uint64_t n, uint64_t gid0, uint64_t tick,
-                                 const PolicyArgs& p, const SampleArgs& x, hipStream_t stream);
-// launch_rollout_explore playing the sampled action of every step; t != NULL: launch_rollout_transitions (a record, no fitness)
-hipError_t launch_rollout_sample(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                 const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t, hipStream_t stream);
+constexpr uint32_t kMaxFitnessSteps = GYMRS_POLICY_FITNESS_MAX_STEPS;
+// One closed-loop launch: launch_rollout with the policy set as the action source (r.action_seed / action_t0 / n_actions are not
+// read).  Which of the eight kernel families it reaches, and which combinations reach none, is dispatch_closed_loop's decision
+// (gymrs_launch.h) over source, fitness != NULL, r.rec_obs != NULL, transitions != NULL, vec and flags.
+struct ClosedLoopLaunch {
+    int vec;        // lanes per work-item: 4 or 8, 4 with a record
+    uint32_t flags; // the engine's flags, with kFlagTable: `consts` is a TableConsts and the TableT instantiations play
+    StepArgs a;
+    RolloutArgs r;
+    const void* consts;
+    PolicyArgs p;
+    ClosedLoopSource source;
+    ExploreArgs explore; // read when source is exploring (the transitions kernel of a greedy launch gets threshold 0: the greedy bits)
+    SampleArgs sample;   // read when source is sampling
+    // != NULL: the kernel also adds every step's reward / done / truncated of every lane to the record of the lane's policy in
+    // fitness[n_policies]: integer atomics, once per wave and launch.  The in-register accumulators are 32 bits wide:
+    // r.n_steps <= kMaxFitnessSteps.
+    gymrs_policy_fitness* fitness;
+    const TransitionArgs* transitions; // != NULL: a record that also keeps final and start observations; engines with GYMRS_AUTO_RESET only
+    hipStream_t stream;
+};
+// hipErrorInvalidValue for what dispatch_closed_loop refuses, for n_steps > kMaxFitnessSteps with fitness, and for transitions
+// without final_obs or with rec_stride < n (every store is addressed inside a row of rec_stride lanes: the caller's
+// check_trajectory is what makes that safe).  No lanes or no steps: nothing is launched.
+hipError_t launch_closed_loop(gymrs_env_kind kind, const ClosedLoopLaunch& l);
 // ---- advantages (gymrs_advantages; gymrs_advantages.hip) -----------------------------------------------------------------------
 // S: floats of one critic (the policy layout with one action); 0 for an env kind that takes none
 inline uint64_t critic_floats(gymrs_env_kind kind, uint32_t hidden)

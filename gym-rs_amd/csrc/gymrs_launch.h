@@ -1,8 +1,10 @@
 // gymrs_launch.h -- THE launch table of the kernel library: which (lanes per work-item, flag set) pairs a kernel family is
 // built for, and how a launch's run-time values reach the instantiation built for them.  Every family with a table goes
-// through here: the per-step kernels (gymrs_step_impl.h), the random-policy rollout (gymrs_rollout_impl.h), the closed-loop
-// rollout and its fitness variant (gymrs_rollout_policy_impl.h).  The internal launch flags and the size of the reset-log ring
-// live here too: the kernels and the engine's HIP-free step plan (gymrs_step_plan.h) both need them.
+// through here: the per-step kernels (gymrs_step_impl.h), the random-policy rollout (gymrs_rollout_impl.h) and the eight
+// closed-loop rollout families (gymrs_rollout_policy_impl.h and the headers on top of it), whose routing decision -- which family
+// a request reaches, and which requests reach none -- is dispatch_closed_loop at the end of this file.  The internal launch flags
+// and the size of the reset-log ring live here too: the kernels and the engine's HIP-free step plan (gymrs_step_plan.h) both need
+// them.
 //
 // Plain host C++17, no HIP: a function here turns a run-time value into a compile-time constant (a std::integral_constant
 // handed to a generic callable, whose body names the kernel template) or refuses it with the caller's `invalid` result.
@@ -122,6 +124,72 @@ R dispatch_recording(bool record, R invalid, Fn&& fn)
 {
     if (record) return detail::reach<VEC == 4, std::true_type>(invalid, fn);
     return detail::reach<true, std::false_type>(invalid, fn);
+}
+
+// ---- the closed-loop fused rollouts: eight kernel families (gymrs_rollout_policy_impl.h and the three headers on top of it), one
+// routing decision.  Where a request's actions come from ...
+enum class ClosedLoopSource {
+    policy,    // the greedy action of the engine's policy set
+    exploring, // its epsilon-greedy action (ExploreArgs)
+    sampling,  // an action drawn from the softmax of its logits (SampleArgs)
+};
+// ... and the kernel it reaches: rollout_<name>_kernel.
+enum class ClosedLoopFamily {
+    policy,
+    policy_fitness,
+    explore,
+    explore_fitness,
+    sample,
+    sample_fitness,
+    transitions,
+    sample_transitions,
+};
+constexpr int kClosedLoopFamilies = 8;
+template <ClosedLoopFamily V>
+using Family = std::integral_constant<ClosedLoopFamily, V>;
+
+namespace detail {
+// fn(Family<..>): GREEDY, EXPLORING or SAMPLING by the source.
+template <ClosedLoopFamily GREEDY, ClosedLoopFamily EXPLORING, ClosedLoopFamily SAMPLING, class R, class Fn>
+R dispatch_source(ClosedLoopSource source, R invalid, Fn&& fn)
+{
+    switch (source) {
+    case ClosedLoopSource::policy: return fn(Family<GREEDY>{});
+    case ClosedLoopSource::exploring: return fn(Family<EXPLORING>{});
+    case ClosedLoopSource::sampling: return fn(Family<SAMPLING>{});
+    default: return invalid;
+    }
+}
+} // namespace detail
+
+// fn(Family<FAMILY>, Lanes<VEC>, FlagSet<FLAGS>, std::bool_constant<REC>) for a closed-loop request, or `invalid`:
+//   * the fitness counters go with neither a record nor transitions (no such kernel is built);
+//   * transitions need a record and auto-reset (without it nothing is re-armed); they run at 4 lanes per work-item whatever `vec`
+//     says, in the eight flag sets with auto-reset.  Greedy and exploring requests share the transitions family (a greedy launch
+//     plays threshold 0), sampling has its own;
+//   * fitness: the source's fitness family, the ten flag sets at 4 or 8 lanes, REC = false;
+//   * otherwise the source's plain family, the ten flag sets at 4 or 8 lanes; a record at 4 lanes only.
+template <class R, class Fn>
+R dispatch_closed_loop(ClosedLoopSource source, bool fitness, bool record, bool transitions, int vec, uint32_t flags, R invalid, Fn&& fn)
+{
+    using F = ClosedLoopFamily;
+    if (fitness && (record || transitions)) return invalid;
+    if (transitions) {
+        if (!record || !(flags & GYMRS_AUTO_RESET)) return invalid;
+        return dispatch_auto_reset_flag_set(flags, invalid, [&](auto flag_set) {
+            return detail::dispatch_source<F::transitions, F::transitions, F::sample_transitions>(
+                source, invalid, [&](auto family) { return fn(family, Lanes<4>{}, flag_set, std::true_type{}); });
+        });
+    }
+    return dispatch_table(vec, flags, invalid, [&](auto lanes, auto flag_set) {
+        if (fitness)
+            return detail::dispatch_source<F::policy_fitness, F::explore_fitness, F::sample_fitness>(
+                source, invalid, [&](auto family) { return fn(family, lanes, flag_set, std::false_type{}); });
+        return dispatch_recording<decltype(lanes)::value>(record, invalid, [&](auto rec) {
+            return detail::dispatch_source<F::policy, F::explore, F::sample>(source, invalid,
+                                                                             [&](auto family) { return fn(family, lanes, flag_set, rec); });
+        });
+    });
 }
 
 } // namespace gymrs

@@ -4,26 +4,7 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_policy_fitness_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                        const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream);
-hipError_t launch_rollout_policy_fitness_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                            const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream);
-
-hipError_t launch_rollout_policy_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                         const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    if (a.n == 0 || r.n_steps == 0) return hipSuccess;
-    if (r.rec_obs || !fitness || r.n_steps > kMaxFitnessSteps) return hipErrorInvalidValue;
-    if (flags & kFlagTable) {
-        switch (kind) {
-        case GYMRS_CARTPOLE: return launch_rollout_policy_fitness_table_cartpole(vec, flags, a, r, consts, p, fitness, stream);
-        case GYMRS_MOUNTAIN_CAR: return launch_rollout_policy_fitness_table_mountain_car(vec, flags, a, r, consts, p, fitness, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    return dispatch_policy_env(kind, [&](auto env) {
-        return rollout_policy_fitness_vec<typename decltype(env)::type>(vec, flags, a, r, consts, p, fitness, stream);
-    });
-}
+hipError_t closed_loop_rollout_fitness_cartpole(const ClosedLoopLaunch& l) { return closed_loop_unit<CartPoleT, ClosedLoopFamily::policy_fitness>(l); }
+hipError_t closed_loop_rollout_fitness_mountain_car(const ClosedLoopLaunch& l) { return closed_loop_unit<MountainCarT, ClosedLoopFamily::policy_fitness>(l); }
 
 } // namespace gymrs

@@ -1,7 +1,8 @@
 // gymrs_rollout_policy.hip -- the closed-loop kernels (gymrs_policy.h) and their launches: policy_actions_kernel (the per-step
 // counterpart: observations -> actions) and rollout_policy_kernel (gymrs_rollout_policy_impl.h), the fused multi-step kernel with
 // the policy as its action source, for CartPole and MountainCar (the Discrete envs) with uniform constants.  The parameter-table
-// instantiations (kFlagTable) live in one translation unit per env type, gymrs_table_policy_<env>.hip.
+// instantiations (kFlagTable) live in one translation unit per env type, gymrs_table_policy_<env>.hip.  Also launch_closed_loop: the
+// one entry the engine calls for every closed-loop rollout, whichever translation unit holds its kernel.
 #include "gymrs_rollout_policy_impl.h"
 
 namespace gymrs {
@@ -53,23 +54,54 @@ hipError_t launch_policy_actions(gymrs_env_kind kind, const float* const* s, voi
     });
 }
 
-hipError_t launch_rollout_policy_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                const PolicyArgs& p, hipStream_t stream);
-hipError_t launch_rollout_policy_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                    const PolicyArgs& p, hipStream_t stream);
+// ---- launch_closed_loop: the one way from a closed-loop request to its kernel.  The kernels are spread over translation units so
+// that the build compiles them in parallel; every unit exports closed_loop_unit (gymrs_rollout_policy_impl.h) once per env type
+// under the name of its file.
+using ClosedLoopUnit = hipError_t(const ClosedLoopLaunch&);
+ClosedLoopUnit closed_loop_rollout_policy_cartpole, closed_loop_rollout_policy_mountain_car, closed_loop_rollout_fitness_cartpole,
+    closed_loop_rollout_fitness_mountain_car, closed_loop_explore_cartpole, closed_loop_explore_mountain_car, closed_loop_explore_fitness_cartpole,
+    closed_loop_explore_fitness_mountain_car, closed_loop_sample_cartpole, closed_loop_sample_mountain_car, closed_loop_sample_fitness_cartpole,
+    closed_loop_sample_fitness_mountain_car, closed_loop_transitions_cartpole, closed_loop_transitions_mountain_car,
+    closed_loop_table_policy_cartpole, closed_loop_table_policy_mountain_car, closed_loop_table_explore_cartpole,
+    closed_loop_table_explore_mountain_car, closed_loop_table_sample_cartpole, closed_loop_table_sample_mountain_car,
+    closed_loop_table_transitions_cartpole, closed_loop_table_transitions_mountain_car;
 
-hipError_t launch_rollout_policy(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                 const PolicyArgs& p, hipStream_t stream)
+hipError_t closed_loop_rollout_policy_cartpole(const ClosedLoopLaunch& l) { return closed_loop_unit<CartPoleT, ClosedLoopFamily::policy>(l); }
+hipError_t closed_loop_rollout_policy_mountain_car(const ClosedLoopLaunch& l) { return closed_loop_unit<MountainCarT, ClosedLoopFamily::policy>(l); }
+
+// The unit that holds a family: [family][kFlagTable set][CartPole, MountainCar].  A table unit holds a source's plain and fitness
+// families (and the sampling one its transitions family) where the uniform envs have a unit each.
+static ClosedLoopUnit* const kClosedLoopUnits[kClosedLoopFamilies][2][2] = {
+    /* policy             */ {{closed_loop_rollout_policy_cartpole, closed_loop_rollout_policy_mountain_car},
+                              {closed_loop_table_policy_cartpole, closed_loop_table_policy_mountain_car}},
+    /* policy_fitness     */ {{closed_loop_rollout_fitness_cartpole, closed_loop_rollout_fitness_mountain_car},
+                              {closed_loop_table_policy_cartpole, closed_loop_table_policy_mountain_car}},
+    /* explore            */ {{closed_loop_explore_cartpole, closed_loop_explore_mountain_car},
+                              {closed_loop_table_explore_cartpole, closed_loop_table_explore_mountain_car}},
+    /* explore_fitness    */ {{closed_loop_explore_fitness_cartpole, closed_loop_explore_fitness_mountain_car},
+                              {closed_loop_table_explore_cartpole, closed_loop_table_explore_mountain_car}},
+    /* sample             */ {{closed_loop_sample_cartpole, closed_loop_sample_mountain_car},
+                              {closed_loop_table_sample_cartpole, closed_loop_table_sample_mountain_car}},
+    /* sample_fitness     */ {{closed_loop_sample_fitness_cartpole, closed_loop_sample_fitness_mountain_car},
+                              {closed_loop_table_sample_cartpole, closed_loop_table_sample_mountain_car}},
+    /* transitions        */ {{closed_loop_transitions_cartpole, closed_loop_transitions_mountain_car},
+                              {closed_loop_table_transitions_cartpole, closed_loop_table_transitions_mountain_car}},
+    /* sample_transitions */ {{closed_loop_sample_cartpole, closed_loop_sample_mountain_car},
+                              {closed_loop_table_sample_cartpole, closed_loop_table_sample_mountain_car}},
+};
+
+hipError_t launch_closed_loop(gymrs_env_kind kind, const ClosedLoopLaunch& l)
 {
-    if (a.n == 0 || r.n_steps == 0) return hipSuccess;
-    if (flags & kFlagTable) {
-        switch (kind) {
-        case GYMRS_CARTPOLE: return launch_rollout_policy_table_cartpole(vec, flags, a, r, consts, p, stream);
-        case GYMRS_MOUNTAIN_CAR: return launch_rollout_policy_table_mountain_car(vec, flags, a, r, consts, p, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    return dispatch_policy_env(kind, [&](auto env) { return rollout_policy_vec<typename decltype(env)::type>(vec, flags, a, r, consts, p, stream); });
+    if (l.a.n == 0 || l.r.n_steps == 0) return hipSuccess;
+    if (kind != GYMRS_CARTPOLE && kind != GYMRS_MOUNTAIN_CAR) return hipErrorInvalidValue;
+    if (l.fitness && l.r.n_steps > kMaxFitnessSteps) return hipErrorInvalidValue;
+    // transitions: every store is addressed inside a row of rec_stride lanes (the caller's check_trajectory is what makes that safe)
+    if (l.transitions && (!l.transitions->final_obs || l.r.rec_stride < l.a.n)) return hipErrorInvalidValue;
+    const int table = (l.flags & kFlagTable) ? 1 : 0, env = kind == GYMRS_CARTPOLE ? 0 : 1;
+    ClosedLoopUnit* const unit = dispatch_closed_loop(l.source, l.fitness != nullptr, l.r.rec_obs != nullptr, l.transitions != nullptr, l.vec, l.flags,
+                                                      static_cast<ClosedLoopUnit*>(nullptr),
+                                                      [&](auto family, auto, auto, auto) { return kClosedLoopUnits[(int)decltype(family)::value][table][env]; });
+    return unit ? unit(l) : hipErrorInvalidValue;
 }
 
 } // namespace gymrs

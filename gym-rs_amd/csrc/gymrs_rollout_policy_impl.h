@@ -1,8 +1,9 @@
 // gymrs_rollout_policy_impl.h -- the closed-loop fused kernels, gfx950: rollout_policy_kernel (rollout_block of
 // gymrs_rollout_impl.h with the policy of gymrs_policy.h as its action source), rollout_policy_fitness_kernel (the same with the
-// per-policy counters of include/gymrs_amd.h, "per-policy fitness") and their launches for one env type.  Included by
-// gymrs_rollout_policy.hip and gymrs_rollout_fitness.hip (the uniform envs) and by gymrs_table_policy_<env>.hip (TableT: per-lane
-// parameter tables, gymrs_rollout_closed_loop).
+// per-policy counters of include/gymrs_amd.h, "per-policy fitness"), the one entry text of all eight closed-loop kernels
+// (GYMRS_CLOSED_LOOP_ENTRY) and the one launch of a translation unit (closed_loop_unit).  Included by gymrs_rollout_policy.hip and
+// gymrs_rollout_fitness.hip (the uniform envs) and by gymrs_table_policy_<env>.hip (TableT: per-lane parameter tables,
+// gymrs_rollout_closed_loop).
 #pragma once
 #include "gymrs_policy.h"
 #include "gymrs_rollout_impl.h"
@@ -26,35 +27,54 @@ struct PolicyWaves<TableT<MountainCarT>, VEC, FIT> {
     static constexpr int value = VEC == 4 ? 3 : (FIT ? 1 : 2); // one step above: up to 164 B (VEC = 4), 140 B (VEC = 8 with counters)
 };
 
-// gymrs_rollout_policy / _record: rollout_block with the policy as its action source.  FULL / ragged and uniform / gathered
-// weights are both chosen per wave, wave-uniformly.  The register budget: PolicyWaves above.
-// (rollout_policy_fitness_kernel, below, repeats this body with a Fit hook: moved into one shared inline
-// function, the four kernel-argument pointer loads of the state rows leave the two weight branches for the kernel's entry and
-// every instantiation comes out with other register spills.)
+// The body of every closed-loop kernel (the eight rollout_*_kernel of this header and of gymrs_rollout_explore_impl.h,
+// gymrs_rollout_transitions_impl.h and gymrs_rollout_sample_impl.h; the last one #undef's it): rollout_block under an action source
+// built from the policy set.  FULL / ragged and uniform / gathered weights are both chosen per wave, wave-uniformly.
+//
+// A macro and not a function, because the kernels must keep their machine code.  Tried on gymrs_table_explore_mountain_car.hip (50
+// kernels), disassembly compared line by line with the separate bodies': as a __device__ __forceinline__ function template taking
+// the kernel arguments by const&, 7.3e5 differing lines (other SGPR allocation from the first kernel on, other code length: the
+// kernel-argument pointer loads of the state rows leave the two weight branches for the kernel's entry, and every instantiation
+// comes out with other register spills); taking them by value, 8.0e5; as text expanded inside each __global__ function, none.
+//
+// Expects in scope: the kernel parameters a (StepArgs), r (RolloutArgs), c (Env::Consts), p (PolicyArgs) and whatever SOURCE_ARGS,
+// HOOK and BLOCK_ARGS name; Env, VEC and FLAGS (template parameters or constants of the kernel).
+// Declares: LPB, lds, base, pol, uniform, full; then per weight branch UNI, `src` -- a SOURCE<Env, VEC, UNI> built from SOURCE_ARGS
+// (parenthesised) -- and what HOOK says (GYMRS_FITNESS_HOOK, below: a Fit hook `fit` that depends on UNI; or nothing), and calls
+// rollout_block<Env, VEC, FLAGS, FULL, REC> with BLOCK_ARGS (parenthesised).  A Sink (the transitions kernels') does not depend on
+// the branch: the kernel declares it before the expansion.
+#define GYMRS_CLOSED_LOOP_ENTRY(SOURCE, SOURCE_ARGS, REC, HOOK, BLOCK_ARGS)                                                                        \
+    constexpr int LPB = kBlock * VEC;                                                                                                               \
+    __shared__ ResetLds<Env, VEC, kBlock> lds;                                                                                                      \
+    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;                                                                 \
+    uint32_t pol[VEC];                                                                                                                              \
+    bool uniform;                                                                                                                                   \
+    policy_select<VEC>(p, a.gid0 + base, pol, uniform);                                                                                             \
+    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; /* wave-uniform, see step_kernel */     \
+    if (uniform) {                                                                                                                                  \
+        constexpr bool UNI = true;                                                                                                                  \
+        const SOURCE<Env, VEC, UNI> src SOURCE_ARGS;                                                                                                \
+        HOOK                                                                                                                                        \
+        if (full)                                                                                                                                   \
+            rollout_block<Env, VEC, FLAGS, true, REC> BLOCK_ARGS;                                                                                   \
+        else                                                                                                                                        \
+            rollout_block<Env, VEC, FLAGS, false, REC> BLOCK_ARGS;                                                                                  \
+    } else {                                                                                                                                        \
+        constexpr bool UNI = false;                                                                                                                 \
+        const SOURCE<Env, VEC, UNI> src SOURCE_ARGS;                                                                                                \
+        HOOK                                                                                                                                        \
+        if (full)                                                                                                                                   \
+            rollout_block<Env, VEC, FLAGS, true, REC> BLOCK_ARGS;                                                                                   \
+        else                                                                                                                                        \
+            rollout_block<Env, VEC, FLAGS, false, REC> BLOCK_ARGS;                                                                                  \
+    }
+
+// gymrs_rollout_policy / _record: the policy's greedy action.  The register budget: PolicyWaves above.
 template <class Env, int VEC, uint32_t FLAGS, bool REC>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PolicyWaves<Env, VEC, false>::value, PolicyWaves<Env, VEC, false>::value))) void rollout_policy_kernel(
     const StepArgs a, const RolloutArgs r, const typename Env::Consts c, const PolicyArgs p)
 {
-    constexpr int LPB = kBlock * VEC;
-    __shared__ ResetLds<Env, VEC, kBlock> lds;
-    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;
-    uint32_t pol[VEC];
-    bool uniform;
-    policy_select<VEC>(p, a.gid0 + base, pol, uniform);
-    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; // wave-uniform, see step_kernel
-    if (uniform) {
-        const PolicyActions<Env, VEC, true> src(p, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, REC>(a, r, c, lds, src);
-        else
-            rollout_block<Env, VEC, FLAGS, false, REC>(a, r, c, lds, src);
-    } else {
-        const PolicyActions<Env, VEC, false> src(p, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, REC>(a, r, c, lds, src);
-        else
-            rollout_block<Env, VEC, FLAGS, false, REC>(a, r, c, lds, src);
-    }
+    GYMRS_CLOSED_LOOP_ENTRY(PolicyActions, (p, pol), REC, /* no hook */, (a, r, c, lds, src))
 }
 
 // ---- per-policy fitness: the counters live in registers for the K steps of a launch (no memory traffic per step) and reach the
@@ -160,64 +180,51 @@ struct PolicyFitness<VEC, TLIM, false> {
     }
 };
 
-// rollout_policy_kernel's body (above, where a note says why the two are not one function) with the hook
-// above.  No recording variant.
+// The same with the hook above: the counters follow the action taken.  No recording variant.
+#define GYMRS_FITNESS_HOOK PolicyFitness<VEC, (FLAGS & GYMRS_TIME_LIMIT) != 0, UNI> fit(fitness, pol);
 template <class Env, int VEC, uint32_t FLAGS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PolicyWaves<Env, VEC, true>::value, PolicyWaves<Env, VEC, true>::value))) void rollout_policy_fitness_kernel(
     const StepArgs a, const RolloutArgs r, const typename Env::Consts c, const PolicyArgs p, gymrs_policy_fitness* const fitness)
 {
-    constexpr int LPB = kBlock * VEC;
-    constexpr bool TLIM = (FLAGS & GYMRS_TIME_LIMIT) != 0;
-    __shared__ ResetLds<Env, VEC, kBlock> lds;
-    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;
-    uint32_t pol[VEC];
-    bool uniform;
-    policy_select<VEC>(p, a.gid0 + base, pol, uniform);
-    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; // wave-uniform, see step_kernel
-    if (uniform) {
-        const PolicyActions<Env, VEC, true> src(p, pol);
-        PolicyFitness<VEC, TLIM, true> fit(fitness, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, false>(a, r, c, lds, src, &fit);
-        else
-            rollout_block<Env, VEC, FLAGS, false, false>(a, r, c, lds, src, &fit);
-    } else {
-        const PolicyActions<Env, VEC, false> src(p, pol);
-        PolicyFitness<VEC, TLIM, false> fit(fitness, pol);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, false>(a, r, c, lds, src, &fit);
-        else
-            rollout_block<Env, VEC, FLAGS, false, false>(a, r, c, lds, src, &fit);
-    }
+    GYMRS_CLOSED_LOOP_ENTRY(PolicyActions, (p, pol), false, GYMRS_FITNESS_HOOK, (a, r, c, lds, src, &fit))
 }
 
-// The launches: lanes per work-item x flag set (gymrs_launch.h) x recording, for one env type.
-template <class Env>
-static hipError_t rollout_policy_vec(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                     hipStream_t stream)
+// ---- the launches (host side).  One closed-loop launch of kernel `kernel` (any of the eight: they share their first four
+// parameters; `extra`: the rest) at VEC lanes per work-item.
+template <class Env, int VEC, class Kernel, class... Extra>
+static hipError_t closed_loop_submit(Kernel kernel, const ClosedLoopLaunch& l, const Extra&... extra)
 {
-    return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
-        constexpr int VEC = decltype(lanes)::value;
-        return dispatch_recording<VEC>(r.rec_obs != nullptr, hipErrorInvalidValue, [&](auto rec) {
-            launch_begin();
-            hipLaunchKernelGGL((rollout_policy_kernel<Env, VEC, decltype(flag_set)::value, decltype(rec)::value>), dim3(step_grid(a.n, VEC)),
-                               dim3(kBlock), 0, stream, a, r, *static_cast<const typename Env::Consts*>(consts), p);
-            return hipGetLastError();
-        });
-    });
+    launch_begin();
+    hipLaunchKernelGGL(kernel, dim3(step_grid(l.a.n, VEC)), dim3(kBlock), 0, l.stream, l.a, l.r, *static_cast<const typename Env::Consts*>(l.consts),
+                       l.p, extra...);
+    return hipGetLastError();
 }
 
-template <class Env>
-static hipError_t rollout_policy_fitness_vec(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                             const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream)
+// The kernel of a family tag (gymrs_launch.h) and its launch: one overload per family, next to its kernel.
+template <class Env, int VEC, uint32_t FLAGS, bool REC>
+static hipError_t closed_loop_kernel(Family<ClosedLoopFamily::policy>, const ClosedLoopLaunch& l)
 {
-    return dispatch_table(vec, flags, hipErrorInvalidValue, [&](auto lanes, auto flag_set) {
-        constexpr int VEC = decltype(lanes)::value;
-        launch_begin();
-        hipLaunchKernelGGL((rollout_policy_fitness_kernel<Env, VEC, decltype(flag_set)::value>), dim3(step_grid(a.n, VEC)), dim3(kBlock), 0, stream,
-                           a, r, *static_cast<const typename Env::Consts*>(consts), p, fitness);
-        return hipGetLastError();
-    });
+    return closed_loop_submit<Env, VEC>(rollout_policy_kernel<Env, VEC, FLAGS, REC>, l);
+}
+template <class Env, int VEC, uint32_t FLAGS, bool REC>
+static hipError_t closed_loop_kernel(Family<ClosedLoopFamily::policy_fitness>, const ClosedLoopLaunch& l)
+{
+    return closed_loop_submit<Env, VEC>(rollout_policy_fitness_kernel<Env, VEC, FLAGS>, l, l.fitness);
+}
+
+// What a translation unit exports, once per env type it is built for (the one signature launch_closed_loop's table holds,
+// gymrs_rollout_policy.hip): the launch of `l` in the instantiation dispatch_closed_loop (gymrs_launch.h) picks for it.  BUILT: the
+// families this unit instantiates; a request for another one is the table's mistake and launches nothing.
+template <class Env, ClosedLoopFamily... BUILT>
+static hipError_t closed_loop_unit(const ClosedLoopLaunch& l)
+{
+    return dispatch_closed_loop(l.source, l.fitness != nullptr, l.r.rec_obs != nullptr, l.transitions != nullptr, l.vec, l.flags, hipErrorInvalidValue,
+                                [&](auto family, auto lanes, auto flag_set, auto rec) {
+                                    if constexpr (((decltype(family)::value == BUILT) || ...))
+                                        return closed_loop_kernel<Env, decltype(lanes)::value, decltype(flag_set)::value, decltype(rec)::value>(family, l);
+                                    else
+                                        return hipErrorInvalidValue;
+                                });
 }
 
 } // namespace gymrs

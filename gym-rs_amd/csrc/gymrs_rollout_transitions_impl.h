@@ -68,40 +68,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Transiti
 {
     constexpr int VEC = 4; // the record's rule
     static_assert((FLAGS & GYMRS_AUTO_RESET) != 0, "without auto-reset nothing is re-armed: the record's obs rows are the final observations");
-    constexpr int LPB = kBlock * VEC;
-    __shared__ ResetLds<Env, VEC, kBlock> lds;
-    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * VEC;
-    uint32_t pol[VEC];
-    bool uniform;
-    policy_select<VEC>(p, a.gid0 + base, pol, uniform);
-    const bool full = (uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= a.n; // wave-uniform, see step_kernel
     FinalObsRows<Env, VEC> sink(t, r);
-    if (uniform) {
-        const ExploringActions<Env, VEC, true> src(p, pol, x);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, true>(a, r, c, lds, src, static_cast<NoFitness*>(nullptr), &sink);
-        else
-            rollout_block<Env, VEC, FLAGS, false, true>(a, r, c, lds, src, static_cast<NoFitness*>(nullptr), &sink);
-    } else {
-        const ExploringActions<Env, VEC, false> src(p, pol, x);
-        if (full)
-            rollout_block<Env, VEC, FLAGS, true, true>(a, r, c, lds, src, static_cast<NoFitness*>(nullptr), &sink);
-        else
-            rollout_block<Env, VEC, FLAGS, false, true>(a, r, c, lds, src, static_cast<NoFitness*>(nullptr), &sink);
-    }
+    GYMRS_CLOSED_LOOP_ENTRY(ExploringActions, (p, pol, x), true, /* no hook */, (a, r, c, lds, src, static_cast<NoFitness*>(nullptr), &sink))
 }
-
-// The launch: the eight flag sets with GYMRS_AUTO_RESET (gymrs_launch.h), 4 lanes per work-item, for one env type.
-template <class Env>
-static hipError_t rollout_transitions_env(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                          const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream)
+template <class Env, int VEC, uint32_t FLAGS, bool REC>
+static hipError_t closed_loop_kernel(Family<ClosedLoopFamily::transitions>, const ClosedLoopLaunch& l)
 {
-    return dispatch_auto_reset_flag_set(flags, hipErrorInvalidValue, [&](auto flag_set) {
-        launch_begin();
-        hipLaunchKernelGGL((rollout_transitions_kernel<Env, decltype(flag_set)::value>), dim3(step_grid(a.n, 4)), dim3(kBlock), 0, stream, a, r,
-                           *static_cast<const typename Env::Consts*>(consts), p, x, t);
-        return hipGetLastError();
-    });
+    static_assert(VEC == 4 && REC, "the record's rule");
+    return closed_loop_submit<Env, VEC>(rollout_transitions_kernel<Env, FLAGS>, l, l.source == ClosedLoopSource::exploring ? l.explore : ExploreArgs{},
+                                        *l.transitions);
 }
 
 } // namespace gymrs

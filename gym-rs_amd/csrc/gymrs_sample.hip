@@ -61,31 +61,13 @@ hipError_t launch_sample_actions(gymrs_env_kind kind, const float* const* s, voi
     });
 }
 
-hipError_t launch_rollout_sample_fitness(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                         const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream);
-hipError_t launch_rollout_sample_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t,
-                                                hipStream_t stream);
-hipError_t launch_rollout_sample_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                    const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t,
-                                                    hipStream_t stream);
-
-hipError_t launch_rollout_sample(gymrs_env_kind kind, int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                 const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t, hipStream_t stream)
+hipError_t closed_loop_sample_cartpole(const ClosedLoopLaunch& l)
 {
-    if (a.n == 0 || r.n_steps == 0) return hipSuccess;
-    if (fitness && (t || r.rec_obs || r.n_steps > kMaxFitnessSteps)) return hipErrorInvalidValue;
-    // transitions: every store is addressed inside a row of rec_stride lanes (the caller's check_trajectory is what makes that safe)
-    if (t && (!r.rec_obs || !t->final_obs || r.rec_stride < a.n || !(flags & GYMRS_AUTO_RESET))) return hipErrorInvalidValue;
-    if (flags & kFlagTable) {
-        switch (kind) {
-        case GYMRS_CARTPOLE: return launch_rollout_sample_table_cartpole(vec, flags, a, r, consts, p, x, fitness, t, stream);
-        case GYMRS_MOUNTAIN_CAR: return launch_rollout_sample_table_mountain_car(vec, flags, a, r, consts, p, x, fitness, t, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (fitness) return launch_rollout_sample_fitness(kind, vec, flags, a, r, consts, p, x, fitness, stream);
-    return dispatch_policy_env(kind, [&](auto env) { return rollout_sample_env<typename decltype(env)::type>(vec, flags, a, r, consts, p, x, t, stream); });
+    return closed_loop_unit<CartPoleT, ClosedLoopFamily::sample, ClosedLoopFamily::sample_transitions>(l);
+}
+hipError_t closed_loop_sample_mountain_car(const ClosedLoopLaunch& l)
+{
+    return closed_loop_unit<MountainCarT, ClosedLoopFamily::sample, ClosedLoopFamily::sample_transitions>(l);
 }
 
 } // namespace gymrs

@@ -6,10 +6,9 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_explore_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                           const PolicyArgs& p, const ExploreArgs& x, gymrs_policy_fitness* fitness, hipStream_t stream)
+hipError_t closed_loop_table_explore_mountain_car(const ClosedLoopLaunch& l)
 {
-    return rollout_explore_env<TableT<MountainCarT>>(vec, flags, a, r, consts, p, x, fitness, stream);
+    return closed_loop_unit<TableT<MountainCarT>, ClosedLoopFamily::explore, ClosedLoopFamily::explore_fitness>(l);
 }
 
 } // namespace gymrs

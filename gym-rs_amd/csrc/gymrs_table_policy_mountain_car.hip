@@ -6,16 +6,9 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_policy_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                        const PolicyArgs& p, hipStream_t stream)
+hipError_t closed_loop_table_policy_mountain_car(const ClosedLoopLaunch& l)
 {
-    return rollout_policy_vec<TableT<MountainCarT>>(vec, flags, a, r, consts, p, stream);
-}
-
-hipError_t launch_rollout_policy_fitness_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                                const PolicyArgs& p, gymrs_policy_fitness* fitness, hipStream_t stream)
-{
-    return rollout_policy_fitness_vec<TableT<MountainCarT>>(vec, flags, a, r, consts, p, fitness, stream);
+    return closed_loop_unit<TableT<MountainCarT>, ClosedLoopFamily::policy, ClosedLoopFamily::policy_fitness>(l);
 }
 
 } // namespace gymrs

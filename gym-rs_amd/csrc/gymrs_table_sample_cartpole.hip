@@ -6,12 +6,9 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_sample_table_cartpole(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                          const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t,
-                                          hipStream_t stream)
+hipError_t closed_loop_table_sample_cartpole(const ClosedLoopLaunch& l)
 {
-    if (fitness) return rollout_sample_fitness_vec<TableT<CartPoleT>>(vec, flags, a, r, consts, p, x, fitness, stream);
-    return rollout_sample_env<TableT<CartPoleT>>(vec, flags, a, r, consts, p, x, t, stream);
+    return closed_loop_unit<TableT<CartPoleT>, ClosedLoopFamily::sample, ClosedLoopFamily::sample_fitness, ClosedLoopFamily::sample_transitions>(l);
 }
 
 } // namespace gymrs

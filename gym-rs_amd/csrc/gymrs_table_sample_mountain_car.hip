@@ -6,12 +6,9 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_sample_table_mountain_car(int vec, uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                          const PolicyArgs& p, const SampleArgs& x, gymrs_policy_fitness* fitness, const TransitionArgs* t,
-                                          hipStream_t stream)
+hipError_t closed_loop_table_sample_mountain_car(const ClosedLoopLaunch& l)
 {
-    if (fitness) return rollout_sample_fitness_vec<TableT<MountainCarT>>(vec, flags, a, r, consts, p, x, fitness, stream);
-    return rollout_sample_env<TableT<MountainCarT>>(vec, flags, a, r, consts, p, x, t, stream);
+    return closed_loop_unit<TableT<MountainCarT>, ClosedLoopFamily::sample, ClosedLoopFamily::sample_fitness, ClosedLoopFamily::sample_transitions>(l);
 }
 
 } // namespace gymrs

@@ -5,10 +5,6 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_transitions_table_cartpole(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts, const PolicyArgs& p,
-                                                     const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream)
-{
-    return rollout_transitions_env<TableT<CartPoleT>>(flags, a, r, consts, p, x, t, stream);
-}
+hipError_t closed_loop_table_transitions_cartpole(const ClosedLoopLaunch& l) { return closed_loop_unit<TableT<CartPoleT>, ClosedLoopFamily::transitions>(l); }
 
 } // namespace gymrs

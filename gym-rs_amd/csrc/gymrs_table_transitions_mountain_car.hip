@@ -6,10 +6,6 @@
 
 namespace gymrs {
 
-hipError_t launch_rollout_transitions_table_mountain_car(uint32_t flags, const StepArgs& a, const RolloutArgs& r, const void* consts,
-                                                         const PolicyArgs& p, const ExploreArgs& x, const TransitionArgs& t, hipStream_t stream)
-{
-    return rollout_transitions_env<TableT<MountainCarT>>(flags, a, r, consts, p, x, t, stream);
-}
+hipError_t closed_loop_table_transitions_mountain_car(const ClosedLoopLaunch& l) { return closed_loop_unit<TableT<MountainCarT>, ClosedLoopFamily::transitions>(l); }
 
 } // namespace gymrs
