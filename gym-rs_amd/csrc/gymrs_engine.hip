@@ -866,9 +866,10 @@ gymrs_status gymrs_reset(gymrs_engine* e, int has_seed, uint64_t seed, const flo
         for (int j = 0; j < sampled; ++j) {
             lo[j] = bounds[j];
             hi[j] = bounds[d + j];
-            // rand's Uniform::new panics unless low < high and both are finite [RECALLED]
-            if (!(lo[j] < hi[j]) || !std::isfinite(lo[j]) || !std::isfinite(hi[j]))
-                return fail(GYMRS_EINVAL, "gymrs_reset: bounds need finite low < high");
+            // rand's Uniform::new panics unless low < high and both are finite, and on a range that overflows [RECALLED]; a width
+            // whose 2^-24 share is not a normal float would draw one value for every lane (sample_range_ok)
+            if (!sample_range_ok(lo[j], hi[j]))
+                return fail(GYMRS_EINVAL, "gymrs_reset: bounds need finite low < high, a finite f32 width high - low, and a width of at least 2^-102");
         }
     }
     const uint64_t s = has_seed ? seed : os_entropy();
@@ -925,6 +926,8 @@ gymrs_status gymrs_reset_pcg64(gymrs_engine* e, int has_seed, uint64_t seed, con
             lo[j] = (float)low;
             hi[j] = (float)high;
             if (!(lo[j] < hi[j])) return fail(GYMRS_EINVAL, "gymrs_reset_pcg64: bounds collapse in f32");
+            if (!sample_range_ok(lo[j], hi[j])) // gymrs_reset's rule, for the box the re-arms draw from
+                return fail(GYMRS_EINVAL, "gymrs_reset_pcg64: the f32 box of the re-arms needs finite low < high, a finite f32 width high - low, and a width of at least 2^-102");
         }
     }
     const uint64_t s = has_seed ? seed : os_entropy();

@@ -126,10 +126,23 @@ inline SampleBox make_sample_box(const float* lo, const float* hi, int dims)
     return b;
 }
 
+// What a caller's box must satisfy per sampled component before make_sample_box may take it (gymrs_reset and the f32 box
+// gymrs_reset_pcg64 keeps for the re-arms check it): finite low < high, a finite f32 width high - low ([-3e38, 3e38) gives
+// scale24 = inf, and then every draw is high_prev or NaN), and a normal scale24 = (high - low) * 2^-24 (zero or subnormal for
+// widths below 2^-102: [0, 1e-45) draws `low` every time).
+inline bool sample_range_ok(float lo, float hi)
+{
+    if (!(lo < hi) || !__builtin_isfinite(lo) || !__builtin_isfinite(hi)) return false;
+    const float width = hi - lo;
+    return __builtin_isfinite(width) && width >= 0x1p-102f; // 2^-102 * 2^-24 = 2^-126, the smallest normal float (the product is exact)
+}
+
 GYMRS_HD float uniform_in_box(uint32_t r, const SampleBox& b, int j)
 {
     const float v = fmaf_((float)(r >> 8), b.scale24[j], b.lo[j]);
-    return v < b.hi_prev[j] ? v : b.hi_prev[j]; // v is never NaN: both operands of the min are finite
+    // v is never NaN for a box that passed sample_range_ok: scale24 and low are finite, and at most 2^24 * scale24 = high - low
+    // is added to low.  (With scale24 = inf word 0 would give 0 * inf = NaN, and the select would fall through to high_prev.)
+    return v < b.hi_prev[j] ? v : b.hi_prev[j];
 }
 
 GYMRS_HD float uniform_between(uint32_t r, float low, float high)

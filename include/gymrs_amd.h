@@ -138,7 +138,12 @@ gymrs_status gymrs_get_stream(gymrs_engine* e, void** hip_stream);
 /* ---- Env::reset(seed, return_info, options) (core.rs:45-50) -------------------------------- */
 /* has_seed = 0 re-seeds from OS entropy (seeding.rs:22); the same seed always gives the same
  * states.  bounds_low_high = obs_dim lows then obs_dim highs replacing the default
- * sampling box (`options`, cartpole.rs:352-364, mountain_car.rs:175-190), or NULL.
+ * sampling box (`options`, cartpole.rs:352-364, mountain_car.rs:175-190), or NULL.  The box stays in force for
+ * every GYMRS_AUTO_RESET re-arm until the next reset (NULL returns to the default box); clones and snapshots carry it.
+ * Every sampled component (MountainCar: the position only) needs finite low < high, a finite f32 width high - low
+ * ([-1.5e38, 1.5e38) is accepted, [-2e38, 2e38) is not) and a width of at least 2^-102, so that the step of a draw,
+ * width * 2^-24, is a normal float: GYMRS_EINVAL otherwise, and the engine keeps the box it had.  The same rule holds
+ * for the f32 box gymrs_reset_pcg64 keeps for the re-arms.
  * *seed_used (may be NULL) receives the seed number, like rand_random's second return value
  * (seeding.rs:21-26). */
 gymrs_status gymrs_reset(gymrs_engine* e, int has_seed, uint64_t seed, const float* bounds_low_high,

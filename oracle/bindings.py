@@ -274,6 +274,8 @@ class Twin:
         L.twin_uniform_between.argtypes = [C.c_uint32, C.c_float, C.c_float]
         L.twin_uniform_in_box.restype = C.c_float
         L.twin_uniform_in_box.argtypes = [C.c_uint32, C.c_float, C.c_float]
+        L.twin_sample_range_ok.restype = C.c_int
+        L.twin_sample_range_ok.argtypes = [C.c_float, C.c_float]
         L.twin_clipf.restype = C.c_float
         L.twin_clipf.argtypes = [C.c_float] * 3
         L.twin_angle_normalize.restype = C.c_float
@@ -292,6 +294,10 @@ class Twin:
         o = (C.c_uint32 * 4)()
         self.lib.twin_philox(c, k, o)
         return list(o)
+
+    def sample_range_ok(self, lo: float, hi: float) -> bool:
+        """The library's own host-side check of one sampled component [lo, hi) of a reset box (gymrs_philox.h)."""
+        return bool(self.lib.twin_sample_range_ok(float(np.float32(lo)), float(np.float32(hi))))
 
 
 class TwinEngine:

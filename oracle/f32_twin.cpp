@@ -317,6 +317,7 @@ float twin_uniform_in_box(uint32_t r, float lo, float hi)
     const SampleBox b = make_sample_box(&lo, &hi, 1);
     return uniform_in_box(r, b, 0);
 }
+int twin_sample_range_ok(float lo, float hi) { return sample_range_ok(lo, hi) ? 1 : 0; } // the library's own check of a reset box
 float twin_clipf(float v, float l, float r) { return clipf(v, l, r); }
 float twin_angle_normalize(float x) { return angle_normalize(x); }
 

@@ -128,12 +128,13 @@ def final_obs_after(tw0, state, act):
     return tw0.get_obs()
 
 
-def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, reset_seed, schedule, prepare=None, tick0=1):
+def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, reset_seed, schedule, prepare=None, tick0=1, bounds=None):
     """What an engine of n lanes at global offset gid0 holds after each launch of `schedule` (steps per launch) of closed-loop
     stepping from reset(reset_seed).  `weights`: one policy set, or a list of one set per launch (a learner rewriting them between
     launches).  `prepare(state, first)` (optional) returns the start state to use in place of the reset state `state`, whose column
     i is lane first + i of the batch; the caller applies the same function to the engine.  tick0 (default 1: the tick a reset leaves)
-    is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.
+    is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.  bounds (default None: the env's own box)
+    is the `options` of the reset, lows then highs: every re-arm draws from it too.
 
     Returns one SimpleNamespace per launch:
       state, obs, reward, done, truncated, stats, tick   as the engine's getters return them (twin with flags & ~F; tick counts the
@@ -154,7 +155,7 @@ def reference(kind, n, gid0, params, flags, weights, hidden, lanes_per_policy, r
     assert len(sets) == len(schedule)
     tw = TwinEngine(_twin, kind, n, params, flags=flags & ~F, gid0=gid0)
     tw0 = TwinEngine(_twin, kind, n, params, flags=0)
-    tw.reset(reset_seed)
+    tw.reset(reset_seed, bounds)
     if prepare is not None:
         tw.set_state(prepare(tw.get_state(), 0))
     if tick0 != 1:
@@ -247,19 +248,20 @@ def mountain_car_prepare(state, first):
     return state
 
 
-def case(kind, shape, flags, hidden, params):
+def case(kind, shape, flags, hidden, params, bounds=None):
     """The arguments of `reference` for one case of the matrix; `params` = the engine's default parameters of `kind` (edited here)."""
     n, vec, gid0, lpp = SHAPES[shape]
     params.max_episode_steps = MAX_EPISODE_STEPS
     w = make_weights(kind, hidden, N_POLICIES, SEEDS[kind, hidden, shape])
     prepare = mountain_car_prepare if kind == 1 else None
     return SimpleNamespace(kind=kind, n=n, vec=vec, gid0=gid0, params=params, flags=flags, weights=w, hidden=hidden, lanes_per_policy=lpp,
-                           reset_seed=RESET_SEED, schedule=SCHEDULE, prepare=prepare,
+                           reset_seed=RESET_SEED, schedule=SCHEDULE, prepare=prepare, bounds=bounds,
                            classes=wave_classes(n, vec, gid0, N_POLICIES, lpp))
 
 
 def run_case(c, tick0=1):
-    return reference(c.kind, c.n, c.gid0, c.params, c.flags, c.weights, c.hidden, c.lanes_per_policy, c.reset_seed, c.schedule, c.prepare, tick0)
+    return reference(c.kind, c.n, c.gid0, c.params, c.flags, c.weights, c.hidden, c.lanes_per_policy, c.reset_seed, c.schedule, c.prepare, tick0,
+                     getattr(c, "bounds", None))
 
 
 def worth_comparing(c, ref):

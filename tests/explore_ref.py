@@ -115,7 +115,7 @@ def matrix():
     return out
 
 
-def case(kind, flags, table, gid0=0, policy_set=(3, 512), hidden=0, schedule=SPLITS[0], n=N, threshold=THRESHOLD, seed=SEED):
+def case(kind, flags, table, gid0=0, policy_set=(3, 512), hidden=0, schedule=SPLITS[0], n=N, threshold=THRESHOLD, seed=SEED, bounds=None):
     n_policies, lpp = policy_set
     k = TABLE_ROWS if table else 1
     rows = lp.make_rows(kind, k, lp.ROWS_SEED + kind, MAX_EPISODE_STEPS) if table else [lp.default_row(kind, MAX_EPISODE_STEPS)]
@@ -123,7 +123,7 @@ def case(kind, flags, table, gid0=0, policy_set=(3, 512), hidden=0, schedule=SPL
     w = cl.make_weights(kind, hidden, n_policies, WEIGHTS_SEED)
     prepare = (lambda state: cl.mountain_car_prepare(state, 0)) if kind == 1 else None
     return SimpleNamespace(kind=kind, n=n, gid0=gid0, flags=flags, table=table, rows=rows, index=index, weights=w, hidden=hidden,
-                           n_policies=n_policies, lanes_per_policy=lpp, reset_seed=RESET_SEED, schedule=tuple(schedule), prepare=prepare,
+                           n_policies=n_policies, lanes_per_policy=lpp, reset_seed=RESET_SEED, schedule=tuple(schedule), prepare=prepare, bounds=bounds,
                            seed=seed, threshold=threshold, policies=pf.policies_of(n, gid0, lpp, n_policies),
                            classes={vec: cl.wave_classes(n, vec, gid0, n_policies, lpp) for vec in (4, 8)})
 
@@ -151,7 +151,8 @@ class Run:
         self.gids = as_u64([c.gid0 + i for i in range(c.n)])
         self._explored, self._greedy = [], []
         self.ref = lp.TableReference(c.kind, c.n, c.gid0, c.rows, c.index, c.flags, c.reset_seed, actions=self._actions,
-                                     prepare=prepare if prepare is not None else c.prepare, tick0=tick0)
+                                     prepare=prepare if prepare is not None else c.prepare, tick0=tick0,
+                                     bounds=getattr(c, "bounds", None))
         self.start_state = self.ref.state.copy()
 
     def _actions(self, t, obs):

@@ -113,7 +113,8 @@ class TableReference:
     actions(t, obs) -> uint8[n] gives the actions of step t (counted from 0 since the reset) for the current observations
     `obs`; the default is the random policy fill_actions(action_seed, t).  prepare(state) (optional) returns the start state to
     use in place of the reset state; the caller applies the same function to the engine.  tick0 (default 1: the tick a reset
-    leaves) is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.
+    leaves) is the engine tick the first step starts from: tick0 - 1 is the shift of tests/time_shift.py.  bounds (default None: the
+    env's own box) is the `options` of the reset, lows then highs: every re-arm draws from it too.
 
     After any number of step() calls the attributes are what the engine's getters return:
       state, obs, reward, done, truncated, tick (counts the reset and every step)
@@ -124,7 +125,7 @@ class TableReference:
     records [steps] keeps obs, actions, reward, done, truncated of every step (what a recording rollout writes) and
     ended_by[2][K] counts per row the lanes that terminated / were truncated."""
 
-    def __init__(self, kind, n, gid0, rows, index, flags, reset_seed, action_seed=0, actions=None, prepare=None, tick0=1):
+    def __init__(self, kind, n, gid0, rows, index, flags, reset_seed, action_seed=0, actions=None, prepare=None, tick0=1, bounds=None):
         assert len(rows) >= 1 and all(r.max_episode_steps == rows[0].max_episode_steps for r in rows)
         self.kind, self.n, self.gid0, self.rows, self.flags = kind, n, gid0, list(rows), flags
         self.index = np.array(index, np.int64)
@@ -133,7 +134,7 @@ class TableReference:
         self.tws = [TwinEngine(twin(), kind, n, row, flags=flags & ~F, gid0=gid0) for row in rows]
         self.tws0 = [TwinEngine(twin(), kind, n, row, flags=0) for row in rows]
         for tw in self.tws:
-            tw.reset(reset_seed)
+            tw.reset(reset_seed, bounds)
         if prepare is not None:
             start = prepare(self.tws[0].get_state())
             for tw in self.tws:

@@ -83,8 +83,8 @@ def sample_actions(kind, hidden, weights, lanes_per_policy, gid0, obs, seed, sca
 
 
 # ---- the cases of tests/test_gpu_sample.py: explore_ref's shapes, axes and matrix ---------------------------------------------------
-def case(kind, flags, table, gid0=0, policy_set=(3, 512), hidden=0, schedule=SPLITS[0], n=N, scale=SCALE, seed=SEED, weights=None):
-    c = ex.case(kind, flags, table, gid0, policy_set, hidden, schedule, n, seed=seed)
+def case(kind, flags, table, gid0=0, policy_set=(3, 512), hidden=0, schedule=SPLITS[0], n=N, scale=SCALE, seed=SEED, weights=None, bounds=None):
+    c = ex.case(kind, flags, table, gid0, policy_set, hidden, schedule, n, seed=seed, bounds=bounds)
     c.scale = float(np.float32(scale))
     del c.threshold
     if weights is not None:

@@ -38,7 +38,7 @@ def make_engine(gymrs, c, vec, explore=True, prepare=None):
     if c.table:
         eng.set_param_table(rows)
         eng.set_param_index(c.index)
-    eng.reset(seed=c.reset_seed)
+    eng.reset(seed=c.reset_seed, options=getattr(c, "bounds", None))
     prepare = prepare if prepare is not None else c.prepare
     if prepare is not None:
         eng.set_state(prepare(eng.get_state()))

@@ -69,7 +69,7 @@ class Pair:
     """An engine and its twin, reset with the same seed and moved `delta` ticks forward; the action counter t starts at the shifted
     tick.  With F the final-observation rows are tracked as tests/closed_loop_ref.py documents."""
 
-    def __init__(self, gymrs, twin, kind, n, flags, delta, vec=4, gid0=12345, limit=LIMIT, seed=3, start=None):
+    def __init__(self, gymrs, twin, kind, n, flags, delta, vec=4, gid0=12345, limit=LIMIT, seed=3, start=None, bounds=None):
         self.kind, self.n, self.flags, self.gymrs = kind, n, flags, gymrs
         p = gymrs.engine.default_params(kind)
         p.max_episode_steps = limit
@@ -77,13 +77,14 @@ class Pair:
         self.eng = gymrs.BatchedEngine(kind, n, global_env_offset=gid0, flags=flags, params=p, lanes_per_thread=vec)
         self.tw = TwinEngine(twin, kind, n, p, flags=flags & ~F, gid0=gid0)
         self.tw0 = TwinEngine(twin, kind, n, p, flags=0) if flags & F else None
-        self.eng.reset(seed=seed)
-        self.tw.reset(seed)
+        self.eng.reset(seed=seed, options=bounds)  # (bounds: tests/test_gpu_reset_box.py)
+        self.tw.reset(seed, bounds)
         if start is not None:
             self.eng.set_state(start)
             self.tw.set_state(start)
-        ts.shift_engine(self.eng, delta)
-        self.tw.shift_time(delta)
+        if delta:
+            ts.shift_engine(self.eng, delta)
+            self.tw.shift_time(delta)
         self.t = self.tw.tick()
         self.final = np.zeros((self.eng.obs_dim, n), np.float32)
         self.buf = torch.empty(n, dtype=torch.float32 if kind == 2 else torch.uint8, device=DEV)

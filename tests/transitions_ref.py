@@ -32,7 +32,7 @@ def seed_of(kind, hidden, shape, table, explore):
     return SEEDS.get((kind, hidden, shape, table, explore), clt.seed_of(kind, hidden, shape))
 
 
-def case(kind, shape, flags, hidden, table, explore):
+def case(kind, shape, flags, hidden, table, explore, bounds=None):
     n, vec, gid0, lpp = SHAPES[shape]
     assert vec == 4 and flags & A
     k = K if table else 1
@@ -43,7 +43,7 @@ def case(kind, shape, flags, hidden, table, explore):
     classes = cl.wave_classes(n, 4, gid0, cl.N_POLICIES, lpp)
     return SimpleNamespace(kind=kind, n=n, vec=4, gid0=gid0, flags=flags, table=table, explore=explore, rows=rows, index=index, weights=w,
                            hidden=hidden, n_policies=cl.N_POLICIES, lanes_per_policy=lpp, reset_seed=cl.RESET_SEED, schedule=SCHEDULE,
-                           prepare=prepare, seed=SEED, threshold=THRESHOLD, policies=pf.policies_of(n, gid0, lpp, cl.N_POLICIES),
+                           prepare=prepare, bounds=bounds, seed=SEED, threshold=THRESHOLD, policies=pf.policies_of(n, gid0, lpp, cl.N_POLICIES),
                            classes={4: classes, 8: classes})
 
 
