@@ -1090,6 +1090,13 @@ static gymrs_status rollout_impl(gymrs_engine* e, uint32_t n_steps, const Rollou
                                              q.fitness ? e->fitness_dev : nullptr, q.transitions, e->stream}));
     }
     if (e->flags & GYMRS_TIME_LIMIT) e->trunc_zero = false; // the kernel stored the last step's flags
+    // ... and every lane's reward, without looking at the reward-elision words (step_block) or updating them.  Without a table every lane
+    // of a fused launch is stepped and earns the constant, so words that say "clean" stay true.  Under a table a lane whose index is out of
+    // it is not stepped and is paid 0.0: what the words say is no longer known, and the next per-step launch starts from "rewrite everything".
+    if (e->table_k) {
+        HIP_TRY(hipMemsetAsync(e->wave_clean, 0, (size_t)e->n_stat_blocks * sizeof(uint32_t), e->stream));
+        e->clean_shape = 0;
+    }
     for (uint32_t k = 0; k < n_steps; ++k) { // the host copy of the uniform episode clock (Pendulum time limit)
         if (has_uniform_clock(e)) {
             const bool hit = uniform_clock_hits(e->tick, e->uniform_start, e->max_steps);

@@ -100,7 +100,11 @@ struct gymrs_engine {
     uint32_t* ep_start = nullptr;
     float* final_obs = nullptr; // GYMRS_FINAL_OBS: obs_dim rows of final_obs_stride(n) lanes (StepArgs::final_obs), else NULL
     uint32_t* wave_clean = nullptr; // per-wavefront: its part of `reward` holds the env's constant reward (see step_block)
-    int clean_shape = 0;           // lanes per workgroup row the flags were written with (vec * threads); 0 = all clear
+    int clean_shape = 0;           // lanes per work-item the words were written with; 0 = all clear
+    // Who clears the words (and sets clean_shape = 0): gymrs_reset, gymrs_snapshot_load, a per-step or fused launch of another shape
+    // (prepare_wave_flags), and -- host-side, in rollout_impl -- every fused launch under a parameter table: the rollout kernels store every
+    // reward and never touch the words, and under a table they may have paid a rejected lane 0.0.  (The kernels were left alone: without a
+    // table no launch changed.)  tests/test_gpu_elided_stores.py leaves the array dirty across each of these.
     bool elide_reward = false;     // CartPole with GYMRS_AUTO_RESET from kElideRewardFromBytes per step on: the constant reward store is elided like MountainCar's
     double* wave_open = nullptr; // per-wavefront sum of the rewards of the open episodes (Pendulum + TRACK_STATS)
     int open_vec = 0;            // lanes per work-item of the launch that last updated wave_open (0 = none yet)

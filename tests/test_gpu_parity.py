@@ -683,7 +683,8 @@ def test_pendulum_flags_follow_the_twin_on_every_step(gymrs, twin, auto):
 
 def test_mountain_car_reward_array_stays_right_around_invalid_actions(gymrs, twin):
     """MountainCar's constant reward is not rewritten while the array already holds it; a step with an invalid
-    action pays 0 on that lane (lane untouched), and the step after must put -1 back."""
+    action pays 0 on that lane (lane untouched), and the step after must put -1 back.  (The last paragraph steps with a clean array:
+    tests/test_gpu_elided_stores.py leaves it dirty across the shape change and the snapshot load.)"""
     n = 5000
     flags = gymrs.AUTO_RESET | gymrs.TRACK_STATS
     eng = gymrs.BatchedEngine(1, n, flags=flags)
@@ -776,7 +777,8 @@ def test_cartpole_reward_elision_changes_nothing_but_the_stores(gymrs, twin, eli
 
 def test_cartpole_reward_array_stays_right_around_invalid_actions_when_elided(gymrs, elide_reward_forced):
     """The elided store's flag must fall when a step pays something else (an invalid action pays 0 and leaves the lane alone), and the next
-    step must put 1.0 back; a change of launch shape and a snapshot load start from "rewrite everything"."""
+    step must put 1.0 back; a change of launch shape and a snapshot load start from "rewrite everything" (with the array left dirty
+    across them: tests/test_gpu_elided_stores.py)."""
     n = 5000
     flags = gymrs.AUTO_RESET | gymrs.TRACK_STATS
     elide_reward_forced("1")
