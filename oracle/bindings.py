@@ -265,6 +265,10 @@ class Twin:
         L.twin_shift_time.restype = None
         L.twin_tick.restype = C.c_uint64
         L.twin_tick.argtypes = [C.c_void_p]
+        L.twin_get_clocks.restype = None
+        L.twin_get_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twin_set_clocks.restype = None
+        L.twin_set_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.twin_invalid_count.restype = C.c_uint64
         L.twin_invalid_count.argtypes = [C.c_void_p]
         L.twin_fill_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
@@ -364,6 +368,20 @@ class TwinEngine:
 
     def tick(self) -> int:
         return int(self.lib.twin_tick(self.h))
+
+    def get_clocks(self):
+        """(ep_start uint32[n], beyond uint8[n]): the tick every lane's open episode started at, and CartPole's
+        steps_beyond_terminated -- what a step reads beside the state (twin_get_clocks)."""
+        start = np.empty(self.n, np.uint32)
+        beyond = np.empty(self.n, np.uint8)
+        self.lib.twin_get_clocks(self.h, start.ctypes.data, beyond.ctypes.data)
+        return start, beyond
+
+    def set_clocks(self, ep_start, beyond) -> None:
+        start = np.ascontiguousarray(ep_start, np.uint32)
+        b = np.ascontiguousarray(beyond, np.uint8)
+        assert start.shape == (self.n,) and b.shape == (self.n,)
+        self.lib.twin_set_clocks(self.h, start.ctypes.data, b.ctypes.data)
 
     def invalid_count(self) -> int:
         return self.lib.twin_invalid_count(self.h)

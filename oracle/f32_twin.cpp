@@ -176,6 +176,21 @@ void twin_shift_time(twin_engine* e, uint64_t delta)
 
 uint64_t twin_tick(const twin_engine* e) { return e->tick; }
 
+// The episode bookkeeping a step reads beside the state: the tick every lane's open episode started at (mod 2^32) and
+// CartPole's steps_beyond_terminated.  tests/lane_params_ref.py keeps one twin per parameter row; with these two calls a lane
+// that changes its row takes its episode along.  Either pointer may be NULL.
+void twin_get_clocks(const twin_engine* e, uint32_t* ep_start, uint8_t* beyond)
+{
+    if (ep_start) std::memcpy(ep_start, e->ep_start.data(), e->n * sizeof(uint32_t));
+    if (beyond) std::memcpy(beyond, e->beyond.data(), e->n);
+}
+
+void twin_set_clocks(twin_engine* e, const uint32_t* ep_start, const uint8_t* beyond)
+{
+    if (ep_start) std::memcpy(e->ep_start.data(), ep_start, e->n * sizeof(uint32_t));
+    if (beyond) std::memcpy(e->beyond.data(), beyond, e->n);
+}
+
 // One engine step over host action arrays (u8, or f32 for Pendulum).
 void twin_step(twin_engine* e, const void* actions)
 {

@@ -74,7 +74,7 @@ class Run:
     the per-policy records accumulated over the launches so far -- and of what shows that a comparison there means something:
     episodes [n] ended so far, actions_seen [A][n], disagree [n] (two policies of the set, asked alone, chose differently),
     told_apart = the fraction of lanes whose state would differ had they been stepped with their neighbour's row.
-    set_index(index): the index rewritten between two launches (TableReference.set_index says for which flag sets)."""
+    set_index(index): the index rewritten between two launches (TableReference.set_index)."""
 
     def __init__(self, c, prepare=None):
         self.c = c

@@ -142,9 +142,10 @@ class TableReference:
         if tick0 != 1:  # the batch as time_shift.shift_engine(eng, tick0 - 1) leaves an engine right after its reset
             for tw in self.tws:
                 tw.shift_time(tick0 - 1)
-        d = DIMS[kind][0]
+        d = TwinEngine._OBS_DIM[kind]  # (Pendulum, which takes no table, runs here as one row: its observation is not its state)
+        self.reset_seed, self.bounds = reset_seed, bounds
         self.state = self.tws[0].get_state()  # (the reset draws do not depend on the physics: every twin holds the same)
-        self.obs = self.state.copy()
+        self.obs = self.tws[0].get_obs()
         self.reward = np.zeros(n, np.float32)
         self.done = np.zeros(n, np.uint8)
         self.truncated = np.zeros(n, np.uint8)
@@ -172,19 +173,63 @@ class TableReference:
         """The state every lane would have now had it stepped with row row_of_lane[i] all along (the twins are all there)"""
         return self._gather([tw.get_state() for tw in self.tws], np.asarray(row_of_lane, np.int64))
 
-    def set_index(self, index):
-        """The index rewritten between two steps: every lane goes on from its own state with its new row.  The twins keep their
-        episode clocks and CartPole's steps_beyond_terminated per twin, out of reach from here, so this is for flag sets that
-        read neither: auto-reset on, no time limit."""
-        assert (self.flags & A) and not (self.flags & T)
+    def rehome(self):
+        """Every twin takes every lane as its own twin (index[i]) holds it: state, episode clock and CartPole's
+        steps_beyond_terminated (TwinEngine.get_clocks).  After it a lane may go on under any row."""
+        clocks = [tw.get_clocks() for tw in self.tws]
+        start, beyond = (self._gather([c[j] for c in clocks]) for j in range(2))
         for tw in self.tws:
             tw.set_state(self.state)
+            tw.set_clocks(start, beyond)
+
+    def set_index(self, index):
+        """The index rewritten between two steps: every lane goes on from its own state, episode clock and
+        steps_beyond_terminated with its new row (under every flag set: rehome)."""
+        self.rehome()
         self.index = np.array(index, np.int64)
         assert self.index.shape == (self.n,) and self.index.min() >= 0 and self.index.max() < len(self.rows)
 
+    def set_rows(self, rows, index=None):
+        """As many other rows (gymrs_set_params / gymrs_set_param_table between two steps: only the constants change), and
+        optionally another index with them"""
+        assert len(rows) == len(self.rows) and all(r.max_episode_steps == rows[0].max_episode_steps for r in rows)
+        self.set_index(self.index if index is None else index)
+        self.rows = list(rows)
+        for tw, tw0, row in zip(self.tws, self.tws0, self.rows):
+            tw.set_params(row)
+            tw0.set_params(row)
+
+    def set_state(self, state):
+        """gymrs_set_state of every lane: the state and nothing else (clocks, flags and final observations stay)"""
+        for tw in self.tws:
+            tw.set_state(state)
+        self.state = self.tws[0].get_state()
+        self.obs = self.tws[0].get_obs()
+
+    def stats_clear(self):
+        """gymrs_stats_clear: the totals so far become the baseline; open episodes go on and count in full when they end"""
+        for tw in self.tws:
+            tw.stats_clear()
+        self.stats = np.zeros(4)
+
+    def rebox(self, bounds):
+        """The same engine with another box for its coming re-arms (what a clone that lost the box would be): twins reset with
+        the box and put back to this tick, these states and these clocks.  CartPole / MountainCar (Pendulum's twin keeps a
+        return per lane that cannot be put back)."""
+        assert self.kind != 2
+        self.rehome()
+        clocks = self.tws[0].get_clocks()
+        for tw in self.tws:
+            tw.reset(self.reset_seed, bounds)
+            if self.tick != 1:
+                tw.shift_time(self.tick - 1)
+            tw.set_state(self.state)
+            tw.set_clocks(*clocks)
+        self.bounds = bounds
+
     def step(self, count=1):
         for _ in range(count):
-            act = np.ascontiguousarray(self.actions(self.t, self.obs), np.uint8)
+            act = np.ascontiguousarray(self.actions(self.t, self.obs), np.float32 if self.kind == 2 else np.uint8)
             assert act.shape == (self.n,)
             finals = []
             results = []
@@ -202,7 +247,9 @@ class TableReference:
             if self.flags & A:
                 self.final[:, ended] = self._gather(finals)[:, ended]
             self.stats[3] += self.n
-            if (self.flags & A) and (self.flags & S):
+            if self.kind == 2:  # one row: the twin's own statistics (a float sum of rewards, not a length)
+                self.stats = self.tws[0].stats()
+            elif (self.flags & A) and (self.flags & S):
                 length = (self.tick - self.ep_start[ended]).sum()
                 self.stats[0] += length if self.kind == 0 else -length
                 self.stats[1] += length

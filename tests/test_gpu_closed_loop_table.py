@@ -210,7 +210,7 @@ class DeviceColumn:
 @pytest.mark.parametrize("kind", [0, 1])
 def test_index_rewritten_between_two_launches(gymrs, kind, flags, shape):
     """A write through param_index_ptr on the engine's stream takes effect in the next launch: every lane goes on from its own state
-    with its new row.  (Flag sets without the time limit: TableReference.set_index says why.)"""
+    with its new row.  (Flag sets without the time limit; tests/test_gpu_sequences.py rewrites the index under the others.)"""
     c = ref.case(kind, shape, flags, 8)
     first, second = lp.REWRITE_STEPS
     new = lp.make_index(c.n, ref.K, lp.INDEX_SEED + 10 + kind)

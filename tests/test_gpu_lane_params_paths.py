@@ -265,7 +265,7 @@ class DeviceColumn:
 @pytest.mark.parametrize("kind", [0, 1])
 def test_index_rewritten_between_rollouts(gymrs, kind, flags, vec):
     """A write through param_index_ptr on the engine's stream takes effect in the next fused launch: every lane goes on from its own
-    state with its new row.  (Flag sets without the time limit: TableReference.set_index says why.)"""
+    state with its new row.  (Flag sets without the time limit; tests/test_gpu_sequences.py rewrites the index under the others.)"""
     c = ref.matrix_case(kind, flags, ref.OFFSETS[0], stages=())
     r = ref.matrix_reference(c)
     eng = table_engine(gymrs, c, vec)

@@ -184,6 +184,38 @@ def test_time_limit_truncation_twin(twin, gymrs):
     assert s[2] == 64 * 3 and s[1] == 64 * 21 and s[0] == -64 * 21
 
 
+def test_twin_clocks_move_a_lane_between_twins(twin, gymrs):
+    """get_clocks / set_clocks: the tick every open episode started at and CartPole's steps_beyond_terminated.  A second twin that
+    takes state and clocks from a first goes on exactly as the first does -- the truncation falls on the same step, and without
+    auto-reset a lane beyond termination is paid 0 -- and a twin that takes the state alone does not."""
+    P = gymrs.engine.default_params(0)
+    P.max_episode_steps = 20
+    for flags in (gymrs.TIME_LIMIT | gymrs.AUTO_RESET, 0):
+        a, b, c = (TwinEngine(twin, 0, 64, P, flags=flags, gid0=5) for _ in range(3))
+        for te, action_seed in ((a, 1), (b, 7), (c, 7)):  # the same seed and tick (the re-arm draws are keyed by them), other actions
+            te.reset(3)
+            for t in range(25):
+                te.step(te.fill_actions(action_seed, t))
+        start, beyond = a.get_clocks()
+        assert start.dtype == np.uint32 and beyond.dtype == np.uint8 and start.shape == beyond.shape == (64,)
+        assert len(set(start.tolist())) > 1 if flags else (beyond.any() and not beyond.all())
+        assert not all(np.array_equal(x, y) for x, y in zip(c.get_clocks(), (start, beyond)))  # (the other twins went their own way)
+        for te in (b, c):
+            te.set_state(a.get_state())
+        b.set_clocks(start, beyond)
+        assert all(np.array_equal(x, y) for x, y in zip(b.get_clocks(), (start, beyond)))
+        differs = False
+        for t in range(8):
+            act = a.fill_actions(2, t)
+            for te in (a, b, c):
+                te.step(act)
+            for x, y, z in zip(a.get_result(), b.get_result(), c.get_result()):
+                assert np.array_equal(x, y), (flags, t)
+                differs |= not np.array_equal(x, z)
+            assert np.array_equal(a.get_state().view(np.uint32), b.get_state().view(np.uint32)), (flags, t)
+        assert differs, flags
+
+
 def _f64_flags_of_f32_state(kind, st32, P):
     """The reference's own termination compares (f64) applied to an f32 state: cartpole.rs:450-453, mountain_car.rs:422."""
     s = st32.astype(np.float64)
