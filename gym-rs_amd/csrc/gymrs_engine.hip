@@ -69,6 +69,7 @@ static StepArgs step_args(const gymrs_engine* e, const void* actions)
     a.reset_log_row_words = e->log_row_words;
     a.fold_step = 0;
     a.elide_reward = e->elide_reward ? 1u : 0u;
+    a.div_in_range = (e->kind == GYMRS_CARTPOLE && div_in_range_ok(e->consts.cp)) ? 1u : 0u; // (a table launch never reads it: TableT divides with `/`)
     a.err = e->err;
     a.err_seen = e->err_seen_dev;
     a.n = e->n;

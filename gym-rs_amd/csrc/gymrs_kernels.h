@@ -114,6 +114,8 @@ struct StepArgs {
     uint32_t reset_log_row_words;
     uint32_t fold_step;            // this launch folds the ring (wave-uniform branch in step_block)
     uint32_t elide_reward;         // constant-reward envs whose kernel does not elide the reward store unconditionally (CartPole): != 0 = this engine elides it (step_block)
+    uint32_t div_in_range;         // CartPole's per-step kernel: != 0 = the host has bounded the division's `den` inside [0.25, 2) (div_in_range_ok, gymrs_physics.h), the
+                                   // fast path may divide scale-free (CartPoleT::advance_fast_tile).  It fills what was a 4-byte hole: no other member moves.
     uint32_t* err;      // [0] number of invalid actions seen, [1] lowest offending lane (0xffffffff = none)
     uint32_t* err_seen; // mapped host words: [0] a wave that saw an invalid action sets it to 1: gymrs_sync looks there first and
                         // fetches err[] only then (no device-to-host copy per synchronisation); [1] a wave of a CHAIN launch that found
@@ -145,6 +147,8 @@ struct StepArgs {
 
 static_assert(offsetof(StepArgs, final_obs) == offsetof(StepArgs, beyond) && sizeof(float*) == sizeof(uint8_t*) && sizeof(StepArgs) == 296,
               "GYMRS_FINAL_OBS shares the slot of `beyond`: the layout of StepArgs must not move");
+static_assert(offsetof(StepArgs, elide_reward) == 136 && offsetof(StepArgs, div_in_range) == 140 && offsetof(StepArgs, err) == 144,
+              "div_in_range sits in the padding behind elide_reward: KernArgView::fetch and the AQL dispatcher address StepArgs by offset");
 // Lanes between two rows of the final-observation arrays: n rounded up to 16, so that every row starts aligned for a vector store.
 __host__ __device__ inline uint64_t final_obs_stride(uint64_t n) { return (n + 15) & ~15ull; }
 

@@ -30,6 +30,59 @@ GYMRS_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
 GYMRS_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
 GYMRS_HD float fabsf_(float f) { return u2f(f2u(f) & 0x7fffffffu); }
 
+// ---- division without scaling and fix-up, for operands PROVEN to need neither ---------------------------------------------
+// An IEEE f32 division on gfx950 is 11 VALU instructions: two v_div_scale, v_rcp, the refinement below, v_div_fmas (coupled to
+// VCC) and v_div_fixup.  The scales, the fmas' rescaling and the fix-up only act on operands with extreme exponents (and on
+// zeros, infinities, NaNs).  Inside the window below none of them acts, and the refinement alone -- a reciprocal good to one ulp,
+// one Newton step on it, the quotient, two residual corrections -- ends on the correctly rounded quotient: the bits of `/`.
+//
+// THE WINDOW (a condition, not a measurement: tests/test_div_in_range.py shows 0 mismatches against `/` on it with the
+// emulation below, the reciprocal taken correctly rounded and one ulp off either way):
+//   den   in one of the binades [0.25, 0.5), [0.5, 1), [1, 2), at least 2^-12 (relative) away from both of the binade's ends: biased
+//         exponent kDivDenExpLo .. kDivDenExpHi = 125 .. 127, mantissa field kDivDenManLo .. kDivDenManHi
+//                                                                  -- proven on the HOST from the constants (div_in_range_ok, gymrs_physics.h)
+//   |num| in [2^-40, 2^41), i.e. biased exponent kDivNumExpLo .. kDivNumExpHi = 87 .. 167   -- tested on the DEVICE (div_num_in_window)
+// Outside it the sequence is WRONG in places: num = -0 gives +0; a denormal, huge, infinite or NaN num; and a den one ulp below a
+// power of two, whose reciprocal sits one ulp above one -- "one ulp off" then crosses into the binade below, where an ulp is half the
+// size, and a numerator that is a power of two comes out one ulp wrong (the emulation found exactly these).  Callers divide with
+// `/` there.  The CPU twin always divides with `/`.
+constexpr uint32_t kDivDenExpLo = 125u, kDivDenExpHi = 127u, kDivDenManLo = 0x000800u, kDivDenManHi = 0x7ff800u;
+constexpr uint32_t kDivNumExpLo = 87u, kDivNumExpHi = 167u;
+GYMRS_HD bool div_den_in_window(float den)
+{
+    const uint32_t u = f2u(den), e = u >> 23, m = u & 0x7fffffu; // (a negative den has e >= 256)
+    return e >= kDivDenExpLo && e <= kDivDenExpHi && m >= kDivDenManLo && m <= kDivDenManHi;
+}
+
+// `num` may take the scale-free division: its exponent field lies in the window.  Zeros and denormals (field 0), infinities and
+// NaNs (255) and everything too small or too large fail.  div_window_key maps the window onto 0 .. kDivWindowKeyMax whatever
+// the sign (the shift drops it), so that several numerators are tested with one compare of the largest key.
+constexpr uint32_t kDivWindowKeyMax = ((kDivNumExpHi - kDivNumExpLo + 1u) << 24) - 1u;
+GYMRS_HD uint32_t div_window_key(float num) { return (f2u(num) << 1) - (kDivNumExpLo << 24); }
+GYMRS_HD bool div_num_in_window(float num) { return div_window_key(num) <= kDivWindowKeyMax; }
+
+// The refinement from a reciprocal estimate r0 of den (8 VALU with the reciprocal; none touches VCC).
+GYMRS_HD float div_refine(float num, float den, float r0)
+{
+    const float e = fmaf_(-den, r0, 1.0f);
+    const float r = fmaf_(e, r0, r0);
+    float q = num * r;
+    float t = fmaf_(-den, q, num);
+    q = fmaf_(t, r, q);
+    t = fmaf_(-den, q, num);
+    return fmaf_(t, r, q);
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ float div_in_range(float num, float den) { return div_refine(num, den, __builtin_amdgcn_rcpf(den)); }
+#endif
+// Host emulation of div_in_range: v_rcp_f32 (1 ulp) modelled as the correctly rounded reciprocal moved by `ulps` (-1, 0, +1) units
+// in the last place.
+inline float div_in_range_emulated(float num, float den, int ulps)
+{
+    const float r0 = u2f(f2u(1.0f / den) + (uint32_t)ulps); // (den > 0: the bit pattern orders like the value)
+    return div_refine(num, den, r0);
+}
+
 // |r| <= pi/4 (+2%).  Near-minimax fits (least squares on Chebyshev nodes in z = r*r):
 //   sin r = r + r*z*(S1 + z*(S2 + z*S3))          approximation error 1.3e-8 relative
 //   cos r = 1 - z/2 + z*z*(C1 + z*(C2 + z*C3))    approximation error 8.4e-9 absolute

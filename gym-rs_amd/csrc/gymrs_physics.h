@@ -92,19 +92,51 @@ inline CartPoleConsts make_consts(const gymrs_cartpole_params& p)
 // One step of the dynamics + termination test.  Returns done.  (cartpole.rs:408-453)
 // SC selects how sin/cos are evaluated (gymrs_math.h); every choice gives the same bits on its domain.
 // INTEG: -1 = read c.integrator at run time, 0 = Euler, 1 = semi-implicit (lets a kernel hoist the choice).
-template <class SC = SinCosGeneral, int INTEG = -1>
-GYMRS_HD bool cartpole_advance(const CartPoleConsts& c, float& x, float& x_dot, float& theta, float& theta_dot,
-                               uint32_t action)
+// The step in two halves around its one division, so that a kernel may choose HOW it divides (CartPoleT::advance_fast_tile,
+// gymrs_tile.h): cartpole_pre gives the quotient's operands, cartpole_post takes the quotient.  cartpole_advance is the two
+// with `/` in between: the same operations in the same order, whoever calls them.
+template <class SC>
+GYMRS_HD void cartpole_pre(const CartPoleConsts& c, float theta, float theta_dot, uint32_t action, float& costheta, float& temp, float& num,
+                           float& den)
 {
     const float force = (action == 1u) ? c.force_over_tm : -c.force_over_tm; // :414-418, already / total_mass
-    float sintheta, costheta;
+    float sintheta;
     SC::eval(theta, &sintheta, &costheta); // :420-421
     // :423-424  temp = (force + polemass_length * theta_dot^2 * sintheta) / total_mass
-    const float temp = fmaf_(c.pml_over_tm, (theta_dot * theta_dot) * sintheta, force);
+    temp = fmaf_(c.pml_over_tm, (theta_dot * theta_dot) * sintheta, force);
     // :425-428  thetaacc = (g*sin - cos*temp) / (length * (4/3 - masspole*cos^2/total_mass))
-    const float num = fmaf_(-costheta, temp, c.gravity * sintheta);
-    const float den = fmaf_(-c.len_mp_over_tm, costheta * costheta, c.len_43);
-    const float thetaacc = num / den;
+    num = fmaf_(-costheta, temp, c.gravity * sintheta);
+    den = fmaf_(-c.len_mp_over_tm, costheta * costheta, c.len_43);
+}
+
+// The interval of `den` while |theta| <= pi/4 (the kernels' fast path: cos from sincos_poly, no reduction), bounded on the host
+// from the constants: cos in [sqrt(1/2) (1 - eps), 1 + eps] with eps = 1e-3, a thousand times the polynomial's and the roundings'
+// error, and the ends moved outwards by 1e-6 relative for the fma's own rounding.
+inline void div_den_interval(const CartPoleConsts& c, double& lo, double& hi)
+{
+    const double eps = 1e-3, c2_lo = 0.5 * (1.0 - eps) * (1.0 - eps), c2_hi = (1.0 + eps) * (1.0 + eps);
+    const double a = (double)c.len_43 - (double)c.len_mp_over_tm * c2_lo, b = (double)c.len_43 - (double)c.len_mp_over_tm * c2_hi;
+    lo = (a < b ? a : b);
+    hi = (a < b ? b : a);
+    lo -= 1e-6 * (lo < 0 ? -lo : lo);
+    hi += 1e-6 * (hi < 0 ? -hi : hi);
+}
+// The host guard of the scale-free division (gymrs_math.h): true only if every `den` of the fast path lies inside ONE binade of
+// the window, clear of its ends (div_den_in_window holds for both ends of the interval, with the same exponent).  Default
+// parameters: 0.62 .. 0.65, inside [0.5, 1).  A NaN or an infinity among the constants fails every compare: refused.
+inline bool div_in_range_ok(const CartPoleConsts& c)
+{
+    double lo, hi;
+    div_den_interval(c, lo, hi);
+    if (!(lo > 0.0 && hi < 4.0 && lo <= hi)) return false;
+    const float flo = (float)lo, fhi = (float)hi; // (rounding moves an end by 6e-8 relative; the window's margin to the binade's ends is 2.4e-4)
+    return div_den_in_window(flo) && div_den_in_window(fhi) && (f2u(flo) >> 23) == (f2u(fhi) >> 23);
+}
+
+template <int INTEG = -1>
+GYMRS_HD bool cartpole_post(const CartPoleConsts& c, float& x, float& x_dot, float& theta, float& theta_dot, float costheta, float temp,
+                            float thetaacc)
+{
     // :429  xacc = temp - polemass_length * thetaacc * costheta / total_mass
     const float xacc = fmaf_(-c.pml_over_tm, thetaacc * costheta, temp);
     if (INTEG == 0 || (INTEG < 0 && c.integrator == 0)) { // :431-435 Euler: x and theta advance with the OLD velocities
@@ -120,6 +152,15 @@ GYMRS_HD bool cartpole_advance(const CartPoleConsts& c, float& x, float& x_dot, 
     }
     // :450-453 strict compares; a NaN counts as "> threshold" in OrderedFloat's order (Q10)
     return !(fabsf_(x) <= c.x_thr) || !(fabsf_(theta) <= c.theta_thr);
+}
+
+template <class SC = SinCosGeneral, int INTEG = -1>
+GYMRS_HD bool cartpole_advance(const CartPoleConsts& c, float& x, float& x_dot, float& theta, float& theta_dot,
+                               uint32_t action)
+{
+    float costheta, temp, num, den;
+    cartpole_pre<SC>(c, theta, theta_dot, action, costheta, temp, num, den);
+    return cartpole_post<INTEG>(c, x, x_dot, theta, theta_dot, costheta, temp, num / den);
 }
 
 // :455-464 — reward with steps_beyond_terminated (`beyond` = is_some()).

@@ -18,7 +18,9 @@
 //   * The physics of the 4 lanes of a work-item runs as ONE basic block whenever the whole wave is on
 //     the common path (valid actions, angle in the polynomial's range), so the 4 independent dependency
 //     chains interleave; the general per-lane code is the wave-uniform fallback.  Both give the same
-//     bits.  (Packed v_pk_*_f32 math was measured to run at half rate on this part: no gain, not used.)
+//     bits.  (The compiler pairs the lanes' arithmetic into packed v_pk_*_f32 instructions there -- some 56 of them in CartPole's
+//     kernel.  They are NOT half rate: profiles/r06_instruction_cost.log prices one at 5.3-5.6 issue cycles against 3.1-3.4 for a
+//     scalar form, 0.8-0.85 of the two instructions it replaces.)
 //   * auto-reset: about 1 lane in 22 finishes per step, so ~95 % of the 256-lane waves hold a finished
 //     lane.  A wave __ballot done-mask + mbcnt ranks compact them into the wave's own LDS segment and the
 //     wave evaluates ONE Philox4x32-10 block per finished lane (one pass of ~11 active lanes) instead of
@@ -26,7 +28,8 @@
 //     stores them with its vector store.  Everything stays inside one wavefront: no s_barrier (a
 //     workgroup-level variant with one Philox pass per workgroup measured the same on CartPole and 10 %
 //     slower on MountainCar: its barrier re-couples the waves), no speculative evaluation (Philox in the
-//     load shadow measured no better: v_mad_u64_u32 is quarter rate and the shadow is not free).
+//     load shadow measured no better: the shadow is not free.  v_mad_u64_u32 is not the reason: it issues in 5.7 cycles with the
+//     SIMD full, profiles/r06_instruction_cost.log -- "quarter rate" was its 10.5-cycle latency with one wave per SIMD).
 //     Quiet waves (MountainCar, Pendulum: nearly all) skip the whole path.
 //   * Episode bookkeeping: what a step has to remember is the tick each lane's open episode started at (episodes tile a
 //     lane's time axis, so the sum of finished lengths is sum(ep_start) - n*epoch, evaluated when statistics are read)

@@ -208,6 +208,47 @@ struct CartPoleT {
         done = cartpole_advance<SinCosSmall, INTEG>(c, st[0], st[1], st[2], st[3], a);
         reward = 1.0f;
     }
+    // The per-step kernel's fast path of a whole work-item (advance_tile; `div_ok` = StepArgs::div_in_range, the host's guard):
+    // the same operations as VEC x advance_fast, with the VEC divisions scale-free (div_in_range, gymrs_math.h: 8 VALU instead
+    // of 11, none coupled to VCC) when the host has bounded `den` and every numerator of the WAVE lies in the window -- one
+    // key per lane, one compare per work-item.  Any other wave (a zero, a denormal, a NaN, an infinity, a huge theta_dot
+    // somewhere in it) divides with `/`: a wave-uniform branch around the quotients alone.  The same bits either way.
+    static constexpr bool kDivInRange = true;
+    // MASKS: also hand out the wave's done-masks dm[] (advance_tile's SPLIT), taken straight from the termination compares.
+    template <int INTEG, int VEC, bool MASKS>
+    __device__ static void advance_fast_tile(const Consts& c, float (&ls)[kState][VEC], const Action (&la)[VEC], float (&rw)[VEC], bool (&dn)[VEC],
+                                             unsigned long long (&dm)[VEC], bool div_ok)
+    {
+        float cs[VEC], temp[VEC], num[VEC], den[VEC], acc[VEC];
+        uint32_t key = 0;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            cartpole_pre<SinCosSmall>(c, ls[2][k], ls[3][k], la[k], cs[k], temp[k], num[k], den[k]);
+            const uint32_t kk = div_window_key(num[k]);
+            key = key > kk ? key : kk;
+        }
+        if (div_ok && __all(key <= kDivWindowKeyMax)) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[k] = div_in_range(num[k], den[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) acc[k] = num[k] / den[k];
+        }
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            dn[k] = cartpole_post<INTEG>(c, ls[0][k], ls[1][k], ls[2][k], ls[3][k], cs[k], temp[k], acc[k]);
+            rw[k] = 1.0f;
+        }
+        if constexpr (!MASKS) return;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            // cartpole_post's termination test (cartpole.rs:450-453) once more, as ballots OF THE COMPARES: each v_cmp leaves its lane mask in
+            // an SGPR pair, and dm[k] -- bit i = work-item i's lane k is done -- is their scalar OR: the wave's done-mask without a VALU
+            // instruction beyond the two compares.  The lanes read their own bit back as a predicate (no instruction either).
+            dm[k] = __ballot(!(fabsf_(ls[0][k]) <= c.x_thr)) | __ballot(!(fabsf_(ls[2][k]) <= c.theta_thr));
+            dn[k] = __builtin_amdgcn_inverse_ballot_w64(dm[k]);
+        }
+    }
     __device__ static void sample(const u32x4& r, const SampleBox& b, float* st) { cartpole_sample(r, b, st[0], st[1], st[2], st[3]); }
 };
 
@@ -226,6 +267,7 @@ struct MountainCarT {
     static constexpr bool kHasObsExtra = false;
     static constexpr bool kNeverTerminates = false;
     static constexpr int kThreads = 256; // (512 measured 1-2 % slower for this short kernel)
+    static constexpr bool kDivInRange = false; // (no division in the step)
     static constexpr bool kLoadsAheadOfArguments = false; // (round 6: -4 % / level at 2^20 lanes, but +3 .. +4 % from 2^22 on, in either order of the new structure)
     __device__ static bool valid(Action a) { return a < 3; } // Discrete(3)
     __device__ static void advance(const Consts& c, float* st, Action a, float& reward, bool& done)
@@ -263,6 +305,7 @@ struct PendulumT { // spec-derived, not in the reference
     // kernel argument (StepArgs::truncate_all) instead of a per-lane compare against a dense ep_start read.
     static constexpr bool kNeverTerminates = true;
     static constexpr int kThreads = 256;
+    static constexpr bool kDivInRange = false; // (no division in the step)
     static constexpr bool kLoadsAheadOfArguments = true; // step_kernel_body (round 6): 2^20 lanes -9 % on four boxes; its BASELINE size 2^22: -2 .. -5 % on three boxes (both ring sizes), +6 % once
     __device__ static bool valid(Action) { return true; } // a Box action is clipped, never rejected
     __device__ static void advance(const Consts& c, float* st, Action a, float& reward, bool& done)
@@ -292,6 +335,7 @@ template <class Base>
 struct TableT : Base {
     static_assert(!Base::kNeverTerminates, "no Pendulum tables: max_torque also drives the random-policy actions");
     static constexpr bool kTable = true;
+    static constexpr bool kDivInRange = false; // per-lane constants: no host bound on `den`, the lanes divide with `/`
     using LaneConsts = typename Base::Consts;
     using Consts = TableConsts;
     __device__ static int variant(const Consts& c) { return Base::kVariants == 1 || c.integrator == 0 ? 0 : 1; }
@@ -557,6 +601,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
     }
     float rw[kVec];
     bool dn[kVec], tr[kVec], need_reset[kVec];
+    [[maybe_unused]] unsigned long long dm[kVec]; // SPLIT (below): the fast path's done-masks
 #ifdef GYMRS_TRACE_TIMES
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     GYMRS_STAMP(2); // all loads have landed
@@ -589,6 +634,44 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
         }
         fast = fast && top < c.k;
     }
+    // The step's flags: done / truncated / who re-arms.  SPLIT (the per-step kernel of the uniform CartPole under auto-reset): each
+    // branch of the physics evaluates them ITSELF, so that on the common path the lane masks the termination compares leave in
+    // SGPR pairs ARE out.masks -- merged with the general path as wave-uniform words, not through the byte-packed `done` word
+    // (from which the re-arm code then re-derived them: an and / bfe and two compares per lane).  Every other instantiation
+    // evaluates them once, behind the merge, as it always did.
+#ifdef GYMRS_EXP_NO_SPLIT // (developer builds: the per-part A/B of profiles/cartpole_fastpath_ab.log)
+    constexpr bool SPLIT = false;
+#else
+    constexpr bool SPLIT = Env::kDivInRange && !ROLL && AUTO;
+#endif
+    Vec<uint8_t, kVec>&done = out.done, &trunc = out.trunc;
+    auto step_flags = [&](auto all_stepped) { // all_stepped: the fast path -- a full tile, every action valid
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) {
+            const bool stepped = decltype(all_stepped)::value || ((FULL || (base + k < a.n)) && Env::valid(la[k]) && lane_index_ok(c, d, k));
+            if (Env::kHasBeyond && !AUTO) { // cartpole.rs:455-464
+                bool b = d.beyond.v[k] != 0;
+                const float r = cartpole_reward(dn[k], b);
+                if (stepped) {
+                    rw[k] = r;
+                    d.beyond.v[k] = b ? 1 : 0;
+                }
+            }
+            if (Env::kNeverTerminates)
+                tr[k] = TLIM && stepped && a.truncate_all != 0;
+            else
+                tr[k] = TLIM && stepped && (tick_next - d.ep_start.v[k]) >= c.max_steps;
+            done.v[k] = dn[k] ? 1 : 0;
+            trunc.v[k] = tr[k] ? 1 : 0;
+            need_reset[k] = AUTO && (dn[k] || tr[k]);
+            if constexpr (SPLIT) {
+                if constexpr (decltype(all_stepped)::value)
+                    out.masks[k] = TLIM ? (dm[k] | __ballot(tr[k])) : dm[k];
+                else
+                    out.masks[k] = __ballot(need_reset[k]);
+            }
+        }
+    };
     out.reward_is_const = true; // the fast path pays the constant on every lane
 #pragma unroll
     for (int k = 0; k < kVec; ++k) out.masks[k] = 0;
@@ -599,7 +682,13 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
             else
                 advance_fast_rows<Env, VEC, 1>(lc, ls, la, rw, dn);
         } else {
-            if (Env::kVariants == 1 || Env::variant(c) == 0)
+            if constexpr (Env::kDivInRange && !ROLL) { // (the per-step kernels of the uniform CartPole: CartPoleT::advance_fast_tile)
+                if (Env::variant(c) == 0)
+                    Env::template advance_fast_tile<0, VEC, SPLIT>(c, ls, la, rw, dn, dm, a.div_in_range != 0u);
+                else
+                    Env::template advance_fast_tile<1, VEC, SPLIT>(c, ls, la, rw, dn, dm, a.div_in_range != 0u);
+                if constexpr (SPLIT) step_flags(std::true_type{});
+            } else if (Env::kVariants == 1 || Env::variant(c) == 0)
                 advance_fast_all<Env, VEC, 0>(c, ls, la, rw, dn);
             else
                 advance_fast_all<Env, VEC, 1>(c, ls, la, rw, dn);
@@ -635,27 +724,29 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
             *a.err_seen = 1u;
         }
         out.reward_is_const = __all(n_bad == 0); // an invalid action leaves the lane untouched and pays 0
+        if constexpr (SPLIT) step_flags(std::false_type{});
     }
     GYMRS_STAMP(3); // physics done
-    Vec<uint8_t, kVec>&done = out.done, &trunc = out.trunc;
+    if constexpr (!SPLIT) { // (step_flags' loop, spelled out: routed through the lambda, MountainCar's and Pendulum's kernels come out as different machine code)
 #pragma unroll
-    for (int k = 0; k < kVec; ++k) {
-        const bool stepped = (FULL || (base + k < a.n)) && Env::valid(la[k]) && lane_index_ok(c, d, k);
-        if (Env::kHasBeyond && !AUTO) { // cartpole.rs:455-464
-            bool b = d.beyond.v[k] != 0;
-            const float r = cartpole_reward(dn[k], b);
-            if (stepped) {
-                rw[k] = r;
-                d.beyond.v[k] = b ? 1 : 0;
+        for (int k = 0; k < kVec; ++k) {
+            const bool stepped = (FULL || (base + k < a.n)) && Env::valid(la[k]) && lane_index_ok(c, d, k);
+            if (Env::kHasBeyond && !AUTO) { // cartpole.rs:455-464
+                bool b = d.beyond.v[k] != 0;
+                const float r = cartpole_reward(dn[k], b);
+                if (stepped) {
+                    rw[k] = r;
+                    d.beyond.v[k] = b ? 1 : 0;
+                }
             }
+            if (Env::kNeverTerminates)
+                tr[k] = TLIM && stepped && a.truncate_all != 0;
+            else
+                tr[k] = TLIM && stepped && (tick_next - d.ep_start.v[k]) >= c.max_steps;
+            done.v[k] = dn[k] ? 1 : 0;
+            trunc.v[k] = tr[k] ? 1 : 0;
+            need_reset[k] = AUTO && (dn[k] || tr[k]);
         }
-        if (Env::kNeverTerminates)
-            tr[k] = TLIM && stepped && a.truncate_all != 0;
-        else
-            tr[k] = TLIM && stepped && (tick_next - d.ep_start.v[k]) >= c.max_steps;
-        done.v[k] = dn[k] ? 1 : 0;
-        trunc.v[k] = tr[k] ? 1 : 0;
-        need_reset[k] = AUTO && (dn[k] || tr[k]);
     }
     if (STATS && !Env::kConstReward) { // this step's rewards join the wave's open-episode sum (lanes not stepped have 0)
         float rs = 0.0f;
@@ -682,8 +773,14 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
         uint32_t total = 0; // finished lanes of this wave (wave-uniform)
 #pragma unroll
         for (int k = 0; k < kVec; ++k) {
-            const unsigned long long m = __ballot(need_reset[k]);
-            out.masks[k] = m;
+            unsigned long long m;
+            if constexpr (SPLIT) { // the branch's own ballot, handed back to the lanes as a predicate: an SGPR pair either way, no VALU
+                m = out.masks[k];
+                need_reset[k] = __builtin_amdgcn_inverse_ballot_w64(m);
+            } else {
+                m = __ballot(need_reset[k]);
+                out.masks[k] = m;
+            }
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             slot[k] = total + rank;
             if (need_reset[k]) {
