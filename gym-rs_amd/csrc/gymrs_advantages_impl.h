@@ -15,13 +15,6 @@
 
 namespace gymrs {
 
-// Read-once rows and write-once outputs with the non-temporal hint (1) or plain (0).  Developer builds (tools/devbuild.py
-// -DGYMRS_EXP_ADVANTAGES_NT=0) give the other library; both were measured at 2^20 lanes x 64 steps (profiles/advantages.md).
-#ifndef GYMRS_EXP_ADVANTAGES_NT
-#define GYMRS_EXP_ADVANTAGES_NT 1
-#endif
-constexpr bool kAdvantagesNT = GYMRS_EXP_ADVANTAGES_NT != 0;
-
 // The critic's weights through the policy's accessors: PolicyWeights<VEC, UNI> is w(k, i).
 template <class Env, int VEC, bool UNI>
 __device__ __forceinline__ void critic_eval(const PolicyWeights<VEC, UNI>& w, uint32_t H, const Vec<float, VEC> (&x)[Env::kState], float (&v)[VEC])
@@ -40,7 +33,7 @@ template <class Env, bool CRITIC, bool UNI, bool FULL>
 __device__ __forceinline__ void advantages_block(const AdvantageArgs& a, const PolicyArgs& p, const uint32_t (&pol)[4], uint64_t base)
 {
     constexpr int VEC = 4, D = Env::kState;
-    constexpr bool NT = kAdvantagesNT;
+    constexpr bool NT = true; // read-once rows and write-once outputs carry the non-temporal hint (plain measured slower: profiles/advantages.md)
     const uint64_t stride = a.stride, n = a.n;
     const PolicyWeights<VEC, UNI> w(p, pol);
     const bool has_trunc = a.truncated != nullptr, has_final = a.final_obs != nullptr; // wave-uniform
@@ -111,9 +104,9 @@ __device__ __forceinline__ void advantages_block(const AdvantageArgs& a, const P
             carry[i] = adv.v[i];
             v_obs[i] = v_cur[i];
         }
-        store_vec<float, VEC, NT ? 1 : 0>(a.advantages + (uint64_t)k * stride, base, n, FULL, adv);
-        if (a.returns) store_vec<float, VEC, NT ? 1 : 0>(a.returns + (uint64_t)k * stride, base, n, FULL, ret);
-        if (a.values) store_vec<float, VEC, NT ? 1 : 0>(a.values + (uint64_t)k * stride, base, n, FULL, val);
+        store_vec<float, VEC, NT>(a.advantages + (uint64_t)k * stride, base, n, FULL, adv);
+        if (a.returns) store_vec<float, VEC, NT>(a.returns + (uint64_t)k * stride, base, n, FULL, ret);
+        if (a.values) store_vec<float, VEC, NT>(a.values + (uint64_t)k * stride, base, n, FULL, val);
         if (k == 0) break;
         rew = rew_p;
         dn = dn_p;

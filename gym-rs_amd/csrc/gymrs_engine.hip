@@ -622,8 +622,7 @@ gymrs_status gymrs_engine_create(gymrs_env_kind kind, uint64_t n_envs, uint64_t 
     // lane i of every array maps to the same memory channel / cache set and a wave's 5 loads and 6 stores
     // pile onto it (measured: 7.7 us per launch at 2^20 lanes against 7.1 us per 2^20 at 1.5 * 2^20).
     {
-        size_t skew = 4352; // 4 KiB + 256 B
-        if (const char* env = std::getenv("GYMRS_ARRAY_SKEW")) skew = (size_t)std::strtoull(env, nullptr, 10) & ~(size_t)255;
+        constexpr size_t skew = 4352; // 4 KiB + 256 B (other skews: profiles/r04_array_skew.log)
         size_t off = 0;
         int index = 0;
         auto place = [&](size_t bytes) {
@@ -990,19 +989,12 @@ static void record_step(gymrs_engine* e, const StepLaunch& l, int path)
     e->n_steps_total += (double)e->n;
 }
 
-static hipError_t launch_step_through_hip_module(gymrs_engine* e, uint32_t flags, const StepArgs& a);
-
 // prepare, submit as a HIP launch on the engine's stream, record
 static gymrs_status step_through_hip(gymrs_engine* e, const void* actions)
 {
     StepLaunch l;
     if (gymrs_status st = prepare_step(e, actions, /*chain=*/false, &l)) return st;
-    const uint32_t flags = l.flags;
-    const StepArgs& a = l.args;
-    if ((e->dev_hooks & 8u) && !(e->flags & GYMRS_FINAL_OBS) && !e->table_k) // (developer experiment: the chain's binary through HIP's queue)
-        HIP_TRY(launch_step_through_hip_module(e, flags, a));
-    else
-        HIP_TRY(launch_step(e->kind, e->vec, flags, a, launch_consts(e), e->stream));
+    HIP_TRY(launch_step(e->kind, e->vec, l.flags, l.args, launch_consts(e), e->stream));
     record_step(e, l, 1);
     return GYMRS_OK;
 }
@@ -1354,37 +1346,9 @@ static bool aql_step(gymrs_engine* e, const AqlKernel& k, int threads, const Ste
         *err = "kernel-argument segment of the chain kernel is " + std::to_string(k.kernarg_bytes) + " bytes, the dispatcher fills " + std::to_string(sizeof(ka));
         return false;
     }
-    return aql_dispatch(e->aql, k, step_grid(a.n, 4, threads * kStepTiles) * (uint32_t)threads, (uint32_t)threads, &ka, sizeof(ka), err, release, first);
-}
-
-// Developer experiment (gymrs_dev_set_hooks bit 3; profiles/r05_visible_through_queue.log part 6): the CHAIN'S binary -- the kernel of the embedded stand-alone
-// code object -- launched through the HIP runtime's own queue (hipModuleLaunchKernel with the hand-filled kernel-argument block).  Same packet header as a
-// HIP launch of the library's own kernel, same queue; only the code object differs.  Tells "the binary" from "the queue" where the two submissions differ.
-template <class Consts>
-static hipError_t module_launch(hipFunction_t f, int threads, const StepArgs& a, const Consts& c, hipStream_t stream)
-{
-    StepKernArgs<Consts> ka;
-    fill_kern_args(&ka, a, c);
-    size_t bytes = sizeof(ka);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ka, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    return hipModuleLaunchKernel(f, step_grid(a.n, 4, threads * kStepTiles), 1, 1, (unsigned)threads, 1, 1, 0, stream, nullptr, extra);
+    return aql_dispatch(e->aql, k, step_grid(a.n, 4, threads) * (uint32_t)threads, (uint32_t)threads, &ka, sizeof(ka), err, release, first);
 }
 } // extern "C++"
-
-static hipError_t launch_step_through_hip_module(gymrs_engine* e, uint32_t flags, const StepArgs& a)
-{
-    static hipModule_t mod[kMaxDevices] = {};
-    if (e->device < 0 || e->device >= kMaxDevices || e->vec != 4) return hipErrorInvalidValue;
-    if (!mod[e->device]) {
-        size_t bytes = 0;
-        const void* blob = aql_code_blob(&bytes);
-        if (hipError_t err = hipModuleLoadData(&mod[e->device], blob)) return err;
-    }
-    const int threads = step_threads_of(e->kind, e->n, e->vec);
-    hipFunction_t f = nullptr;
-    if (hipError_t err = hipModuleGetFunction(&f, mod[e->device], aql_kernel_name(e, flags, threads).c_str())) return err;
-    return visit_consts(e, [&](const auto& c) { return module_launch(f, threads, a, c, e->stream); });
-}
 
 // steps [first, n_steps) of a gymrs_step_many call as ONE chain.  *taken = false: nothing was dispatched, use HIP launches.
 static gymrs_status step_many_aql(gymrs_engine* e, const char* base, uint64_t stride_bytes, uint32_t n_buffers, uint32_t first, uint32_t n_steps,
@@ -1397,10 +1361,9 @@ static gymrs_status step_many_aql(gymrs_engine* e, const char* base, uint64_t st
         if (gymrs_status st = fold_reset_log(e)) return st;
     }
     // (test hook, tests/test_gpu_aql_chain.py: a table nobody's XCC matches -- and no recording launch -- stands in for a deal that changed
-    // in mid-chain; the memset sits on the stream ahead of the hand-over into the chain)
-    // (test / developer hooks, set through gymrs_dev_set_hooks -- not in the header, not read from the environment on the stepping path)
-    const bool no_xcc_check = (e->dev_hooks & 2u) != 0; // A/B runs only: what the check costs
-    const bool poisoned = (e->dev_hooks & 1u) != 0;     // tests/test_gpu_aql_chain.py: a table nobody's XCC matches
+    // in mid-chain; the memset sits on the stream ahead of the hand-over into the chain; set through gymrs_dev_set_hooks -- not in the header, not
+    // read from the environment on the stepping path)
+    const bool poisoned = (e->dev_hooks & 1u) != 0;
     if (poisoned) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(aql_xcc_table(e->aql)), 0x11, 8 * kXccTableStride, e->stream));
     if (!aql_begin(e->aql, e->stream, &err)) { // nothing dispatched, no host state touched: this engine goes back to HIP launches for good
         e->aql_why = "aql_begin: " + err;
@@ -1412,8 +1375,7 @@ static gymrs_status step_many_aql(gymrs_engine* e, const char* base, uint64_t st
     *taken = true;
     // GYMRS_AQL=2: every launch RELEASES (HIP's header) and uses HIP launches' hints: nothing rests on lines staying in an XCD's L2, so no XCD check either
     const bool visible = aql_mode_by_env() == 2;
-    int threads = step_threads_of(e->kind, e->n, e->vec);
-    if ((e->dev_hooks & 4u) && e->kind == GYMRS_CARTPOLE) threads = kBlock; // (developer hook: 256 work-items per workgroup for CartPole chains)
+    const int threads = step_threads_of(e->kind, e->n, e->vec);
     uint32_t last_key = ~0u;
     AqlKernel k;
     auto bail = [e](gymrs_status st) { // close the chain (what was dispatched still runs and hands the stream back), keep the error
@@ -1445,7 +1407,7 @@ static gymrs_status step_many_aql(gymrs_engine* e, const char* base, uint64_t st
         a.xcc_seq = aql_chain_number(e->aql);
         const bool first_of_chain = e->chain_first; // its packet carries the acquire that follows the hand-over (aql_dispatch)
         e->chain_first = false;
-        if (no_xcc_check || visible) a.xcc_check = 0u;
+        if (visible) a.xcc_check = 0u;
         if (!visit_consts(e, [&](const auto& c) { return aql_step(e, k, threads, a, c, &err, visible, first_of_chain); }))
             return bail(fail(GYMRS_EHIP, "AQL dispatcher: " + err));
         record_step(e, l, 2);

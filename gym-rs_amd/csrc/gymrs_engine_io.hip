@@ -1051,12 +1051,13 @@ gymrs_status gymrs_params_from_json(gymrs_env_kind kind, const char* text, void*
 }
 
 // Test / developer hooks (NOT in the header; tests and A/B tools bind it by name): bit 0 the next chains find a poisoned XCD table (stands in for a
-// workgroup deal that changed under the engine), bit 1 no XCD check (what it costs), bit 2 CartPole chains with 256 work-items per workgroup, bit 3 HIP
-// launches of gymrs_step_many start the CHAIN'S binary (the embedded code object) through hipModuleLaunchKernel, bit 4 gymrs_allreduce_stats_multi takes
-// its grouped RCCL branch even for one shard, bit 5 that branch treats RCCL as unavailable (the host-sum fall-back of a failed first contact).  Until round 4 these were environment variables read on every gymrs_step_many.
+// workgroup deal that changed under the engine), bit 4 gymrs_allreduce_stats_multi takes its grouped RCCL branch even for one shard, bit 5 that branch
+// treats RCCL as unavailable (the host-sum fall-back of a failed first contact).  Bits 1 to 3 belonged to experiments that are over (tools/README.md): they
+// and every other bit are refused, so that a tool from those days fails instead of measuring the product.
 gymrs_status gymrs_dev_set_hooks(gymrs_engine* e, uint32_t bits)
 {
     if (!e) return fail(GYMRS_EINVAL, "gymrs_dev_set_hooks: engine is NULL");
+    if (bits & ~(1u | 16u | 32u)) return fail(GYMRS_EINVAL, "gymrs_dev_set_hooks: only the bits 1, 16 and 32 exist");
     e->dev_hooks = bits;
     return GYMRS_OK;
 }

@@ -18,7 +18,7 @@ __device__ __forceinline__ void explore_actions_block(const float* const (&s)[4]
     const ExploringActions<Env, 4, UNI> src(p, pol, x);
     Vec<uint8_t, 4> act;
     src.fill(obs, act, gid, tick, (gid & 3u) == 0); // (base is a multiple of 4: the offset decides, wave-uniformly)
-    store_vec<uint8_t, 4, 0>(actions, base, n, full, act);
+    store_vec<uint8_t, 4, false>(actions, base, n, full, act);
 }
 
 template <class Env>

@@ -172,7 +172,7 @@ __device__ __forceinline__ void gradient_block(const GradientArgs& a, const Poli
                 Vec<float, VEC> pr;
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) pr.v[i] = pa[i];
-                store_vec<float, VEC, 1>(a.prob + (uint64_t)k * stride, base, n, FULL, pr);
+                store_vec<float, VEC, true>(a.prob + (uint64_t)k * stride, base, n, FULL, pr);
             }
         }
         if constexpr (HID) {

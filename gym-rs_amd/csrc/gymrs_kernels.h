@@ -24,11 +24,7 @@
 
 namespace gymrs {
 
-#ifdef GYMRS_EXP_BLOCK // (developer builds, HIP launches only: the workgroup size of every kernel that uses kBlock; profiles/r04_wave_variants.log)
-constexpr int kBlock = GYMRS_EXP_BLOCK;
-#else
 constexpr int kBlock = 256; // work-items per workgroup of the small kernels (reset, fill, statistics) and of the rollout kernel
-#endif
 
 // ---- per-lane physics parameters (gymrs_set_param_table) -------------------------------------------------------------------
 // One row of a parameter table on the device: the f32 constants make_consts derives from one gymrs_<kind>_params, without the
@@ -211,10 +207,7 @@ struct ResetArgs {
 // ... and only while the launch is at most two generations of waves: from 2^22 lanes on a CU refills better in units of 4 waves (round 4,
 // profiles/r04_wave_variants.log: 2^22 lanes 25.7 -> 24.8 us, 2^23 48.7 -> 47.4; 2^21 12.0 vs 12.2 the other way).
 constexpr int kCartPoleThreads = 512;
-#ifndef GYMRS_EXP_BIG_BELOW // (developer builds: where the 512-work-item window of CartPole ends; profiles/r05_cartpole_2p21.log)
-#define GYMRS_EXP_BIG_BELOW 2048
-#endif
-constexpr uint64_t kBigGroupsFrom = 512, kBigGroupsBelow = GYMRS_EXP_BIG_BELOW;
+constexpr uint64_t kBigGroupsFrom = 512, kBigGroupsBelow = 2048; // (where the window ends: profiles/r05_cartpole_2p21.log)
 inline bool step_uses_big_groups(uint64_t n, int threads, int vec)
 {
     return n >= (uint64_t)threads * vec * kBigGroupsFrom && n < (uint64_t)threads * vec * kBigGroupsBelow;
@@ -225,14 +218,6 @@ inline int step_threads_of(gymrs_env_kind kind, uint64_t n, int vec)
 }
 
 constexpr uint32_t kXccTableStride = 32; // words between two entries of StepArgs::xcc_table: one 128-byte line per entry
-
-// Tiles (of `threads` * `vec` lanes) a workgroup of the per-step kernel steps one after the other: 1; developer builds (GYMRS_EXP_TILES,
-// tools/devbuild.py) may ask for more (profiles/r04_two_tiles_per_workgroup.log).
-#ifdef GYMRS_EXP_TILES
-constexpr int kStepTiles = GYMRS_EXP_TILES;
-#else
-constexpr int kStepTiles = 1;
-#endif
 
 // Number of workgroups of `threads` work-items for n lanes at `vec` lanes per work-item (4 or 8).
 inline uint32_t step_grid(uint64_t n, int vec, int threads = kBlock)

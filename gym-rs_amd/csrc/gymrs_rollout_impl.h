@@ -100,9 +100,9 @@ __device__ __forceinline__ void rollout_block(StepArgs a, const RolloutArgs& r, 
         }
         if constexpr (Sink::kOn) {
             sink->step(k);
-            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock, Sink>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x, sink);
+            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock, Sink>(a, c, base, d, lds, resets, ret, open, out, sink);
         } else
-            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock>(a, c, base, d, lds, resets, ret, open, out, blockIdx.x);
+            advance_tile<Env, VEC, FLAGS, FULL, true, kBlock>(a, c, base, d, lds, resets, ret, open, out);
         if constexpr (Fit::kOn) fit->template step<FULL>(out, base, a.n);
         if constexpr (REC) {
             const uint64_t row = (uint64_t)k * r.rec_stride;

@@ -18,7 +18,7 @@ __device__ __forceinline__ void policy_actions_block(const float* const (&s)[4],
     const PolicyWeights<4, UNI> w(p, pol);
     Vec<uint8_t, 4> act;
     policy_eval<Env, 4, UNI>(w, p.hidden, x, act);
-    store_vec<uint8_t, 4, 0>(actions, base, n, full, act);
+    store_vec<uint8_t, 4, false>(actions, base, n, full, act);
 }
 
 template <class Env>

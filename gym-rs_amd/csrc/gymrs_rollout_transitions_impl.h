@@ -31,7 +31,7 @@ struct FinalObsRows {
     {
         if (start_obs) { // wave-uniform
 #pragma unroll
-            for (int j = 0; j < Env::kState; ++j) store_vec<float, VEC, 1>(start_obs + j * stride, base, n, FULL, st[j]);
+            for (int j = 0; j < Env::kState; ++j) store_vec<float, VEC, true>(start_obs + j * stride, base, n, FULL, st[j]);
         }
     }
     __device__ __forceinline__ void step(uint32_t k) { row = final_obs + (uint64_t)k * Env::kState * stride; }

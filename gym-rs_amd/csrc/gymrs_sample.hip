@@ -19,8 +19,8 @@ __device__ __forceinline__ void sample_actions_block(const float* const (&s)[4],
     Vec<uint8_t, 4> act;
     Vec<float, 4> pr;
     src.fill(obs, act, gid, tick, (gid & 3u) == 0, PROB ? &pr : nullptr); // (base is a multiple of 4: the offset decides, wave-uniformly)
-    store_vec<uint8_t, 4, 0>(actions, base, n, full, act);
-    if constexpr (PROB) store_vec<float, 4, 0>(prob, base, n, full, pr);
+    store_vec<uint8_t, 4, false>(actions, base, n, full, act);
+    if constexpr (PROB) store_vec<float, 4, false>(prob, base, n, full, pr);
 }
 
 template <class Env, bool PROB>

@@ -64,18 +64,16 @@ __device__ __forceinline__ uint32_t select_by_mask(unsigned long long m, uint32_
 // 6.66 us (scattered stores, round 1) -> 6.47 us on the same box.  The folding launch is the SAME kernel taking a
 // wave-uniform branch on a kernel argument, not a second instantiation: alternating two kernels (each with its own copy of
 // the physics and reset code) cost MountainCar's 4 us launches up to 1.3 us each.
-// vblock = the index of the workgroup-sized tile (THREADS * VEC lanes): blockIdx.x, unless the workgroup steps several tiles
-// (step_kernel_body, TILES > 1).  `d` holds the tile's loads (issued, not necessarily landed).
+// `d` holds the loads of the workgroup's tile (THREADS * VEC lanes; issued, not necessarily landed).
 template <class Env, int VEC, uint32_t FLAGS, int THREADS, bool FULL>
-__device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env::Consts& c, ResetLds<Env, VEC, THREADS>& lds, uint32_t vblock,
-                                                  TileRegs<Env, VEC, FLAGS>& d)
+__device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env::Consts& c, ResetLds<Env, VEC, THREADS>& lds, TileRegs<Env, VEC, FLAGS>& d)
 {
     constexpr int kVec = VEC;
     constexpr int LPB = THREADS * kVec;
     constexpr bool AUTO = (FLAGS & GYMRS_AUTO_RESET) != 0;
     constexpr bool STATS = AUTO && (FLAGS & GYMRS_TRACK_STATS);
     constexpr bool LOGGED = TileRegs<Env, VEC, FLAGS>::LOGGED; // bookkeeping through the reset log: no statistics slot to load
-    const uint64_t base = (uint64_t)vblock * LPB + (uint64_t)threadIdx.x * kVec;
+    const uint64_t base = (uint64_t)blockIdx.x * LPB + (uint64_t)threadIdx.x * kVec;
     // A replayed HIP graph keeps the tick on the device.  Resolved here, BEHIND the state loads: ahead of them
     // the branch makes every wave wait for the whole kernel-argument fetch before it issues its first load.
     if (a.tick_base) a.tick += *a.tick_base;
@@ -86,7 +84,7 @@ __device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env
     // has exactly one writer per launch.)
     unsigned long long old_resets = 0;
     double old_ret = 0.0, open = 0.0;
-    const size_t wave_slot = (size_t)vblock * (THREADS / 64) + (threadIdx.x >> 6); // = the global wave index
+    const size_t wave_slot = (size_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6); // = the global wave index
     if (STATS && !LOGGED) {
         const unsigned long long* bs = a.block_stats + wave_slot * 2;
         old_resets = bs[0];
@@ -127,23 +125,16 @@ __device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env
     // MountainCar's 3.1 us chain step 0.3 us: profiles/r04_xcd_check_cost.log); a workgroup that finds itself elsewhere reads whatever memory
     // holds -- an older chain's tag -- and reports.  Both reads sit HERE, behind every load of the step: the wave waits for memory anyway
     // (s_getreg is a slow scalar instruction; at the end of the kernel it kept every wave resident 0.25 us longer).
-#ifndef GYMRS_EXP_XCC_PARTS // (developer builds, A/B runs: 1 the table fetch, 2 the s_getreg, 4 the compare / record at the end; 0 = no check)
-#define GYMRS_EXP_XCC_PARTS 7
-#endif
     uint32_t xcc_want = 0, xcc_id = 0;
-    const bool xcc_asks = a.xcc_check != 0u && (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64u && vblock == blockIdx.x * (uint32_t)kStepTiles;
-#if GYMRS_EXP_XCC_PARTS & 1
+    const bool xcc_asks = a.xcc_check != 0u && (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64u;
     if (xcc_asks && a.xcc_check == 1u) xcc_want = a.xcc_table[(blockIdx.x & 7u) * kXccTableStride];
-#endif
-#if GYMRS_EXP_XCC_PARTS & 2
     if (xcc_asks) {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
         xcc_id = (a.xcc_seq << 8) | ((xcc_id & 0xfu) + 1u); // tagged with the chain's number: an entry of an earlier chain never matches
     }
-#endif
     GYMRS_STAMP(1);
     StepOut<VEC> out;
-    advance_tile<Env, VEC, FLAGS, FULL, false, THREADS>(a, c, base, d, lds, old_resets, old_ret, open, out, vblock);
+    advance_tile<Env, VEC, FLAGS, FULL, false, THREADS>(a, c, base, d, lds, old_resets, old_ret, open, out);
     store_tile<Env, VEC, FLAGS, FULL>(a, base, d, out, elide && clean != 0 && out.reward_is_const);
     if (fold) {
         const uint32_t lane = threadIdx.x & 63u;
@@ -172,7 +163,6 @@ __device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env
     }
     if (elide && (clean != 0) != out.reward_is_const && (threadIdx.x & 63u) == 0) a.wave_clean[wave_slot] = out.reward_is_const ? 1u : 0u;
     if (STATS && !Env::kConstReward && (threadIdx.x & 63u) == 0) a.wave_open[wave_slot] = open;
-#if GYMRS_EXP_XCC_PARTS & 4
     if (xcc_asks) { // (see above) the first launch of a chain records, every later one compares
         if (a.xcc_check == 2u) {
             if (blockIdx.x < 8u && threadIdx.x == 0) a.xcc_table[blockIdx.x * kXccTableStride] = xcc_id; // (plain: stays in this XCD's L2)
@@ -180,18 +170,17 @@ __device__ __forceinline__ void step_block_loaded(StepArgs a, const typename Env
             a.err_seen[1] = blockIdx.x + 1u;
         }
     }
-#endif
     GYMRS_STAMP(6);
 }
 
 template <class Env, int VEC, uint32_t FLAGS, int THREADS, bool FULL>
-__device__ __forceinline__ void step_block(const StepArgs& a, const typename Env::Consts& c, ResetLds<Env, VEC, THREADS>& lds, uint32_t vblock)
+__device__ __forceinline__ void step_block(const StepArgs& a, const typename Env::Consts& c, ResetLds<Env, VEC, THREADS>& lds)
 {
     GYMRS_STAMP(0);
     TileRegs<Env, VEC, FLAGS> d;
-    load_tile<Env, VEC, FLAGS, FULL>(a, (uint64_t)vblock * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
-    load_param_index<Env, VEC, FLAGS, FULL>(a, c, (uint64_t)vblock * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
-    step_block_loaded<Env, VEC, FLAGS, THREADS, FULL>(a, c, lds, vblock, d);
+    load_tile<Env, VEC, FLAGS, FULL>(a, (uint64_t)blockIdx.x * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
+    load_param_index<Env, VEC, FLAGS, FULL>(a, c, (uint64_t)blockIdx.x * (THREADS * VEC) + (uint64_t)threadIdx.x * VEC, d);
+    step_block_loaded<Env, VEC, FLAGS, THREADS, FULL>(a, c, lds, d);
 }
 
 // VEC lanes per work-item: 4 (4096 waves for 2^20 lanes, 4 waves per SIMD) or 8 (2 waves per SIMD; a tuning knob: measured
@@ -234,7 +223,7 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
     // straddles n (and the empty ones behind it) takes the guarded per-lane code.  n_fast (a preloaded scalar
     // argument) is n -- or 0 when the caller's action buffer is not aligned for the vector load, which sends
     // every wavefront through the guarded code (per-lane action loads); the real n travels in StepArgs.
-    if constexpr (kStepTiles == 1 && Env::kLoadsAheadOfArguments) {
+    if constexpr (Env::kLoadsAheadOfArguments) {
         StepArgs a;
         typename Env::Consts c;
         if ((uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= n_fast) {
@@ -263,7 +252,7 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
             if (Env::kHasBeyond && !R::AUTO) d.beyond = load_vec<uint8_t, VEC, R::NT_SL>(a.beyond, base, a.n, true, uint8_t(0));
             if (R::TLIM && !Env::kNeverTerminates) d.ep_start = load_vec<uint32_t, VEC, false>(a.ep_start, base, a.n, true, 0u);
             load_param_index<Env, VEC, FLAGS, true>(a, c, base, d);
-            step_block_loaded<Env, VEC, FLAGS, THREADS, true>(a, c, lds, blockIdx.x, d);
+            step_block_loaded<Env, VEC, FLAGS, THREADS, true>(a, c, lds, d);
         } else {
             KernArgView<Env>::fetch(a, c);
             a.s[0] = s0;
@@ -271,7 +260,7 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
             a.s[2] = s2;
             a.s[3] = s3;
             a.action = action;
-            step_block<Env, VEC, FLAGS, THREADS, false>(a, c, lds, blockIdx.x);
+            step_block<Env, VEC, FLAGS, THREADS, false>(a, c, lds);
         }
     } else {
         const typename Env::Consts& c = c_by_value;
@@ -281,43 +270,14 @@ __device__ __forceinline__ void step_kernel_body(float* s0, float* s1, float* s2
         a.s[2] = s2;
         a.s[3] = s3;
         a.action = action;
-        if constexpr (kStepTiles == 1) {
-            if ((uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= n_fast)
-                step_block<Env, VEC, FLAGS, THREADS, true>(a, c, lds, blockIdx.x);
-            else
-                step_block<Env, VEC, FLAGS, THREADS, false>(a, c, lds, blockIdx.x);
-        } else {
-            // (developer builds, GYMRS_EXP_TILES) a workgroup steps kStepTiles consecutive tiles, the loads of tile j + 1 issued before the
-            // arithmetic of tile j: more bytes in flight per resident wave where a launch is several generations of waves
-            const uint32_t vb0 = blockIdx.x * (uint32_t)kStepTiles;
-            if ((uint64_t)(vb0 + kStepTiles - 1) * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= n_fast) {
-                TileRegs<Env, VEC, FLAGS> d[2];
-                load_tile<Env, VEC, FLAGS, true>(a, (uint64_t)vb0 * LPB + (uint64_t)threadIdx.x * VEC, d[0]);
-                load_param_index<Env, VEC, FLAGS, true>(a, c, (uint64_t)vb0 * LPB + (uint64_t)threadIdx.x * VEC, d[0]);
-#pragma unroll
-                for (int j = 0; j < kStepTiles; ++j) {
-                    if (j + 1 < kStepTiles) {
-                        load_tile<Env, VEC, FLAGS, true>(a, (uint64_t)(vb0 + j + 1) * LPB + (uint64_t)threadIdx.x * VEC, d[(j + 1) & 1]);
-                        load_param_index<Env, VEC, FLAGS, true>(a, c, (uint64_t)(vb0 + j + 1) * LPB + (uint64_t)threadIdx.x * VEC, d[(j + 1) & 1]);
-                    }
-                    step_block_loaded<Env, VEC, FLAGS, THREADS, true>(a, c, lds, vb0 + j, d[j & 1]);
-                }
-            } else {
-                for (int j = 0; j < kStepTiles; ++j)
-                    if ((uint64_t)(vb0 + j) * LPB < rest.n) step_block<Env, VEC, FLAGS, THREADS, false>(a, c, lds, vb0 + j);
-            }
-        }
+        if ((uint64_t)blockIdx.x * LPB + (uint64_t)((threadIdx.x >> 6) + 1) * (64 * VEC) <= n_fast)
+            step_block<Env, VEC, FLAGS, THREADS, true>(a, c, lds);
+        else
+            step_block<Env, VEC, FLAGS, THREADS, false>(a, c, lds);
     }
 }
 
-#ifndef GYMRS_EXP_WAVES // (developer builds: the occupancy the register allocator aims for)
-#define GYMRS_EXP_WAVES(VEC_) (16 / (VEC_) < 1 ? 1 : 16 / (VEC_))
-#endif
-#ifndef GYMRS_EXP_WAVES_MIN
-#define GYMRS_EXP_WAVES_MIN 1
-#endif
-#define GYMRS_STEP_KERNEL_ATTRS(THREADS_, VEC_) \
-    __global__ __launch_bounds__(THREADS_) __attribute__((amdgpu_waves_per_eu(GYMRS_EXP_WAVES_MIN, GYMRS_EXP_WAVES(VEC_))))
+#define GYMRS_STEP_KERNEL_ATTRS(THREADS_, VEC_) __global__ __launch_bounds__(THREADS_) __attribute__((amdgpu_waves_per_eu(1, 16 / (VEC_))))
 
 template <class Env, int VEC, uint32_t FLAGS, int THREADS>
 GYMRS_STEP_KERNEL_ATTRS(THREADS, VEC) void step_kernel(float* s0, float* s1, float* s2, float* s3, const void* action, uint64_t n_fast,
@@ -326,10 +286,8 @@ GYMRS_STEP_KERNEL_ATTRS(THREADS, VEC) void step_kernel(float* s0, float* s1, flo
     step_kernel_body<Env, VEC, FLAGS, THREADS>(s0, s1, s2, s3, action, n_fast, rest, c);
 }
 
-#ifndef GYMRS_EXP_BLOCK
 static_assert(CartPoleT::kThreads == kCartPoleThreads && MountainCarT::kThreads == kBlock && PendulumT::kThreads == kBlock,
               "step_threads_of (gymrs_kernels.h) must pick what launch_one picks");
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // launch tables
@@ -339,12 +297,12 @@ static hipError_t launch_one(const StepArgs& a, const void* consts, hipStream_t 
     launch_begin(); // (gymrs_kernels.h: the thread's last-error word may hold somebody else's error)
     if constexpr (Env::kThreads != kBlock) {
         if (step_uses_big_groups(a.n, Env::kThreads, VEC)) { // >= 2 big workgroups per CU, at most two generations of waves
-            hipLaunchKernelGGL((step_kernel<Env, VEC, FLAGS, Env::kThreads>), dim3(step_grid(a.n, VEC, Env::kThreads * kStepTiles)), dim3(Env::kThreads), 0,
-                               stream, a.s[0], a.s[1], a.s[2], a.s[3], a.action, a.n_fast, a, *static_cast<const typename Env::Consts*>(consts));
+            hipLaunchKernelGGL((step_kernel<Env, VEC, FLAGS, Env::kThreads>), dim3(step_grid(a.n, VEC, Env::kThreads)), dim3(Env::kThreads), 0, stream, a.s[0],
+                               a.s[1], a.s[2], a.s[3], a.action, a.n_fast, a, *static_cast<const typename Env::Consts*>(consts));
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((step_kernel<Env, VEC, FLAGS, kBlock>), dim3(step_grid(a.n, VEC, kBlock * kStepTiles)), dim3(kBlock), 0, stream, a.s[0], a.s[1],
+    hipLaunchKernelGGL((step_kernel<Env, VEC, FLAGS, kBlock>), dim3(step_grid(a.n, VEC, kBlock)), dim3(kBlock), 0, stream, a.s[0], a.s[1],
                        a.s[2], a.s[3], a.action, a.n_fast, a, *static_cast<const typename Env::Consts*>(consts));
     return hipGetLastError();
 }

@@ -121,8 +121,7 @@ __device__ __forceinline__ Vec<T, V> load_vec(const T* __restrict__ p, uint64_t 
     return r;
 }
 
-// POL: 0 plain, 1 non-temporal, 2 (developer builds, GYMRS_EXP_SC1) written through at agent scope (`sc1`)
-template <class T, int V, int POL>
+template <class T, int V, bool NT>
 __device__ __forceinline__ void store_vec(T* __restrict__ p, uint64_t base, uint64_t n, bool full, const Vec<T, V>& r)
 {
     typedef T vt __attribute__((ext_vector_type(V)));
@@ -130,15 +129,7 @@ __device__ __forceinline__ void store_vec(T* __restrict__ p, uint64_t base, uint
         vt x;
 #pragma unroll
         for (int k = 0; k < V; ++k) x[k] = r.v[k];
-        if constexpr (POL == 2) {
-            static_assert(sizeof(vt) == 4 || sizeof(vt) == 16, "sc1 stores: 4 lanes per work-item only");
-            if constexpr (sizeof(vt) == 16) {
-                typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(reinterpret_cast<vt*>(p + base)), "v"(__builtin_bit_cast(u4, x)) : "memory");
-            }
-            else
-                asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" ::"v"(reinterpret_cast<vt*>(p + base)), "v"(__builtin_bit_cast(uint32_t, x)) : "memory");
-        } else if constexpr (POL == 1)
+        if constexpr (NT)
             __builtin_nontemporal_store(x, reinterpret_cast<vt*>(p + base));
         else
             *reinterpret_cast<vt*>(p + base) = x;
@@ -179,11 +170,7 @@ struct CartPoleT {
     static constexpr bool kConstReward = true;    // under auto-reset every step pays 1.0 (cartpole.rs:455-459)
     static constexpr float kReward = 1.0f;
     static constexpr bool kElideConstReward = false; // not unconditionally: per engine, StepArgs::elide_reward (from 128 MiB per step on; at 2^20 lanes the flag load and the 4 B per lane are a wash)
-#ifdef GYMRS_EXP_NO_RESET_LOG // (developer builds: ablation)
-    static constexpr bool kUseResetLog = false;
-#else
     static constexpr bool kUseResetLog = true;       // measured: 6.67 -> 6.44 us per 2^20-lane step (1 lane in 22 re-arms per step)
-#endif
     static constexpr bool kHasBeyond = true;
     static constexpr bool kHasObsExtra = false;
     static constexpr bool kNeverTerminates = false;
@@ -371,21 +358,8 @@ struct TileRegs {
     static constexpr bool NT = (FLAGS & kFlagNonTemporal) != 0;
     // Which accesses carry the hint when the launch asks for it.  The state arrays are the only ones the NEXT step reads
     // again; actions are read once, rewards / flags / Pendulum's (cos, sin) are written and never read by a step.
-    // GYMRS_EXP_HINTS (developer builds, tools/devbuild.py) overrides the launch flag per class of access:
-    // bit 0 state loads, bit 1 state stores, bit 2 action loads, bit 3 reward / done / truncated / obs stores.
-#ifdef GYMRS_EXP_HINTS
-    static constexpr bool NT_SL = (GYMRS_EXP_HINTS & 1) != 0, NT_SS = (GYMRS_EXP_HINTS & 2) != 0, NT_A = (GYMRS_EXP_HINTS & 4) != 0,
-                          NT_O = (GYMRS_EXP_HINTS & 8) != 0;
-#else
+    // State loads, state stores, action loads, reward / done / truncated / obs stores:
     static constexpr bool NT_SL = NT || (FLAGS & kFlagNtStateLoads) != 0, NT_SS = NT, NT_A = NT, NT_O = NT || (FLAGS & kFlagNtOut) != 0;
-#endif
-    // Store policies (store_vec): 0 plain, 1 non-temporal, 2 written through (`sc1`; developer builds: GYMRS_EXP_SC1 bit 1 = state
-    // stores, bit 3 = reward / done / truncated / obs stores -- profiles/r04_visible_step_probe.log says why no product launch uses it)
-#ifdef GYMRS_EXP_SC1
-    static constexpr int POL_SS = (VEC == 4 && (GYMRS_EXP_SC1 & 2)) ? 2 : (NT_SS ? 1 : 0), POL_O = (VEC == 4 && (GYMRS_EXP_SC1 & 8)) ? 2 : (NT_O ? 1 : 0);
-#else
-    static constexpr int POL_SS = NT_SS ? 1 : 0, POL_O = NT_O ? 1 : 0;
-#endif
     // Episode bookkeeping of the per-step kernel goes through the reset log (StepArgs::reset_log) when nothing in the
     // step needs ep_start itself: statistics on, no time limit, constant reward (return = +-length).
     static constexpr bool LOGGED = STATS && !TLIM && Env::kConstReward && Env::kUseResetLog;
@@ -532,9 +506,9 @@ __device__ __forceinline__ void store_final_obs(const StepArgs& a, uint64_t base
         }
         obs_sincos<VEC>(th, oc, os);
         if (FULL) { // every lane of a full tile was stepped, and all of them reached the shared time limit
-            store_vec<float, VEC, R::POL_O>(fo, base, a.n, true, oc);
-            store_vec<float, VEC, R::POL_O>(fo + stride, base, a.n, true, os);
-            store_vec<float, VEC, R::POL_O>(fo + 2 * stride, base, a.n, true, td);
+            store_vec<float, VEC, R::NT_O>(fo, base, a.n, true, oc);
+            store_vec<float, VEC, R::NT_O>(fo + stride, base, a.n, true, os);
+            store_vec<float, VEC, R::NT_O>(fo + 2 * stride, base, a.n, true, td);
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -571,12 +545,12 @@ struct NoFinalSink {
 // finished episodes of a wave is just that sum -- no per-lane return accumulator in HBM (which cost 8 B per
 // lane-step: 29.6 vs 23.4 us per 2^22-lane step).  The caller loads/stores `open` (StepArgs::wave_open).
 // a.fold_step: a folding launch of a reset-logged per-step kernel (step_block): the step's done-masks stay in registers.
-// vblock: the index of the workgroup-sized tile (THREADS * VEC lanes) this is -- blockIdx.x, unless a workgroup steps several tiles.
+// The tile is the workgroup's own: blockIdx.x numbers it (THREADS * VEC lanes), which is where the wave's statistics slots come from.
 // sink (Sink::kOn): also handed the finished lanes' pre-reset observation, where store_final_obs is -- in a wave that re-arms a lane only.
 template <class Env, int VEC, uint32_t FLAGS, bool FULL, bool ROLL = false, int THREADS = Env::kThreads, class Sink = NoFinalSink>
 __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename Env::Consts& c, uint64_t base,
                                              TileRegs<Env, VEC, FLAGS>& d, ResetLds<Env, VEC, THREADS>& lds, unsigned long long& resets,
-                                             double& ret, double& open, StepOut<VEC>& out, uint32_t vblock, const Sink* sink = nullptr)
+                                             double& ret, double& open, StepOut<VEC>& out, const Sink* sink = nullptr)
 {
     static_assert(Env::kConstReward || Env::kNeverTerminates,
                   "return tracking assumes a constant reward (return = +-length) or one shared episode clock");
@@ -639,11 +613,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
     // SGPR pairs ARE out.masks -- merged with the general path as wave-uniform words, not through the byte-packed `done` word
     // (from which the re-arm code then re-derived them: an and / bfe and two compares per lane).  Every other instantiation
     // evaluates them once, behind the merge, as it always did.
-#ifdef GYMRS_EXP_NO_SPLIT // (developer builds: the per-part A/B of profiles/cartpole_fastpath_ab.log)
-    constexpr bool SPLIT = false;
-#else
     constexpr bool SPLIT = Env::kDivInRange && !ROLL && AUTO;
-#endif
     Vec<uint8_t, kVec>&done = out.done, &trunc = out.trunc;
     auto step_flags = [&](auto all_stepped) { // all_stepped: the fast path -- a full tile, every action valid
 #pragma unroll
@@ -755,15 +725,6 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
         open += (double)wave_sum(rs);
     }
 
-#ifdef GYMRS_EXP_EARLY_OUT // (developer builds: the step's reward / done / truncated leave BEFORE the re-arm pass; profiles/r04_wave_variants.log)
-    if (!ROLL && !Env::kElideConstReward) {
-#pragma unroll
-        for (int k = 0; k < kVec; ++k) out.reward.v[k] = rw[k];
-        store_vec<float, kVec, R::POL_O>(a.reward, base, a.n, FULL, out.reward);
-        if (!Env::kNeverTerminates) store_vec<uint8_t, kVec, R::POL_O>(a.done, base, a.n, FULL, out.done);
-        if (TLIM && !(Env::kNeverTerminates && a.skip_trunc_store)) store_vec<uint8_t, kVec, R::POL_O>(a.truncated, base, a.n, FULL, out.trunc);
-    }
-#endif
     // ---- auto-reset: wave __ballot done-mask -> LDS-staged Philox, all inside one wavefront ----
     if (AUTO) {
         constexpr int LPW = 64 * kVec; // lanes per wavefront = capacity of a wave's LDS segment
@@ -796,7 +757,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
                 // 2^20 CartPole lanes: the scattered ep_start stores cost 0.45 us per launch -- ~47k partial cache lines -- and the
                 // counter's load + store 0.07; this row entry costs 0.02.)  A folding launch consumes its masks from registers.
                 typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
-                const size_t wave_slot = (size_t)vblock * (THREADS / 64) + wave;
+                const size_t wave_slot = (size_t)blockIdx.x * (THREADS / 64) + wave;
                 ull2* row = reinterpret_cast<ull2*>(a.reset_log + (size_t)((uint32_t)a.tick & (kResetLogRows - 1u)) * a.reset_log_row_words +
                                                     wave_slot * kVec);
 #pragma unroll
@@ -831,7 +792,7 @@ __device__ __forceinline__ void advance_tile(const StepArgs& a, const typename E
                 }
             }
             if (STATS && !LOGGED) { // the wave's private statistics slot: plain read-modify-write, no atomics
-                unsigned long long* bs = a.block_stats + ((size_t)vblock * (THREADS / 64) + wave) * 2;
+                unsigned long long* bs = a.block_stats + ((size_t)blockIdx.x * (THREADS / 64) + wave) * 2;
                 if (!Env::kConstReward) { // every lane of the wave finished (shared clock): the open sum is their return
                     ret += open;
                     open = 0.0;
@@ -860,19 +821,14 @@ __device__ __forceinline__ void store_tile(const StepArgs& a, uint64_t base, con
     using R = TileRegs<Env, VEC, FLAGS>;
     constexpr bool AUTO = R::AUTO, STATS = R::STATS, TLIM = R::TLIM;
 #pragma unroll
-    for (int j = 0; j < Env::kState; ++j) store_vec<float, kVec, R::POL_SS>(a.s[j], base, a.n, FULL, d.st[j]);
-#ifdef GYMRS_EXP_EARLY_OUT
-    constexpr bool kOutStored = !ROLL && !Env::kElideConstReward; // (advance_tile stored them already)
-#else
-    constexpr bool kOutStored = false;
-#endif
-    if (!skip_reward && !kOutStored) store_vec<float, kVec, R::POL_O>(a.reward, base, a.n, FULL, out.reward);
+    for (int j = 0; j < Env::kState; ++j) store_vec<float, kVec, R::NT_SS>(a.s[j], base, a.n, FULL, d.st[j]);
+    if (!skip_reward) store_vec<float, kVec, R::NT_O>(a.reward, base, a.n, FULL, out.reward);
     // An env that never terminates never changes `done` (reset() zeroed it), and its `truncated` flag is the same
     // for every lane: neither is rewritten while it already holds the right value (2 of Pendulum's 34 real bytes).
-    if (!Env::kNeverTerminates && !kOutStored) store_vec<uint8_t, kVec, R::POL_O>(a.done, base, a.n, FULL, out.done);
-    if (TLIM && !kOutStored && !(Env::kNeverTerminates && a.skip_trunc_store)) store_vec<uint8_t, kVec, R::POL_O>(a.truncated, base, a.n, FULL, out.trunc);
-    if (Env::kHasBeyond && !AUTO) store_vec<uint8_t, kVec, R::POL_SS>(a.beyond, base, a.n, FULL, d.beyond);
-    if (ROLL && (STATS || TLIM)) store_vec<uint32_t, kVec, 0>(a.ep_start, base, a.n, FULL, d.ep_start);
+    if (!Env::kNeverTerminates) store_vec<uint8_t, kVec, R::NT_O>(a.done, base, a.n, FULL, out.done);
+    if (TLIM && !(Env::kNeverTerminates && a.skip_trunc_store)) store_vec<uint8_t, kVec, R::NT_O>(a.truncated, base, a.n, FULL, out.trunc);
+    if (Env::kHasBeyond && !AUTO) store_vec<uint8_t, kVec, R::NT_SS>(a.beyond, base, a.n, FULL, d.beyond);
+    if (ROLL && (STATS || TLIM)) store_vec<uint32_t, kVec, false>(a.ep_start, base, a.n, FULL, d.ep_start);
     if (Env::kHasObsExtra) {
         Vec<float, kVec> oc, os;
         bool med = true;
@@ -885,8 +841,8 @@ __device__ __forceinline__ void store_tile(const StepArgs& a, uint64_t base, con
 #pragma unroll
             for (int k = 0; k < kVec; ++k) sincosf_(d.st[0].v[k], &os.v[k], &oc.v[k]);
         }
-        store_vec<float, kVec, R::POL_O>(a.obs_cos, base, a.n, FULL, oc);
-        store_vec<float, kVec, R::POL_O>(a.obs_sin, base, a.n, FULL, os);
+        store_vec<float, kVec, R::NT_O>(a.obs_cos, base, a.n, FULL, oc);
+        store_vec<float, kVec, R::NT_O>(a.obs_sin, base, a.n, FULL, os);
     }
     GYMRS_STAMP(5); // stores issued
 #ifdef GYMRS_TRACE_TIMES

@@ -216,6 +216,23 @@ def test_grouped_rccl_branch_runs_with_one_rank(gymrs):
     sh.close()
 
 
+def test_retired_hook_bits_are_refused(gymrs):
+    """gymrs_dev_set_hooks knows the values 1, 16 and 32.  The values 2, 4 and 8 switched experiments that are over (tools/README.md, the retired
+    switches): a tool that still asks for one gets GYMRS_EINVAL instead of silently measuring the product, and the engine steps on as before."""
+    lib = gymrs.load_library()
+    lib.gymrs_dev_set_hooks.argtypes = [C.c_void_p, C.c_uint32]
+    with gymrs.BatchedEngine(gymrs.CARTPOLE, 64, flags=gymrs.AUTO_RESET | gymrs.TRACK_STATS) as eng:
+        eng.reset(seed=1)
+        assert lib.gymrs_dev_set_hooks(eng._h, 1 | 16 | 32) == 0
+        assert lib.gymrs_dev_set_hooks(eng._h, 0) == 0
+        for retired in (2, 4, 8):
+            assert lib.gymrs_dev_set_hooks(eng._h, retired) == 1  # GYMRS_EINVAL
+            assert b"gymrs_dev_set_hooks" in lib.gymrs_last_error()
+        eng.step_host(np.zeros(64, dtype=np.uint8))
+        eng.sync()
+        assert eng.stats()[3] == 64
+
+
 def test_sharder_statistics_report_a_tripped_chain(gymrs):
     """gymrs_sharded_stats is the sharder's only statistics read-out; it waits for every block's stream through the CHECKED synchronise, so a chain
     that tripped its XCD check (test hook bit 0: a poisoned table) fails THIS call -- with the shard named -- instead of handing out totals with GYMRS_OK."""

@@ -13,7 +13,7 @@ written by rollout_transitions(sample=True) on an engine with A | S | T and its 
 Each time is the median of `reps` repetitions of >= 100 ms (host clock around calls that end in a synchronise), with min and max.
 Also reports the bytes moved by construction per lane-step, the HBM rate that makes at the fused median, and the registers and
 scratch of every advantages kernel from the library's code-object metadata.  Every measurement runs under its own time limit.
-GYMRS_AMD_LIB selects another build of the library (tools/devbuild.py: the access-hint comparison)."""
+GYMRS_AMD_LIB selects another build of the library."""
 from __future__ import annotations
 
 import argparse

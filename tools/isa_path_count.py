@@ -38,14 +38,18 @@ def _tool(cands):
     raise SystemExit(f"none of {cands} found")
 
 
+def unbundle(lib, tmp):
+    """The gfx950 code objects of a library or an object file, unbundled into the directory `tmp` (a bare code object: a copy of it)."""
+    copy = Path(tmp) / Path(lib).name
+    shutil.copy(lib, copy)
+    subprocess.run([_tool(OBJDUMP_CANDIDATES), "--offloading", str(copy)], check=True, stdout=subprocess.DEVNULL, cwd=tmp)
+    return sorted(p for p in Path(tmp).iterdir() if "amdgcn" in p.name) or [copy]
+
+
 def disassemble(lib, needle):
     objdump = _tool(OBJDUMP_CANDIDATES)
     with tempfile.TemporaryDirectory() as tmp:
-        copy = Path(tmp) / Path(lib).name
-        shutil.copy(lib, copy)
-        subprocess.run([objdump, "--offloading", str(copy)], check=True, stdout=subprocess.DEVNULL, cwd=tmp)
-        objs = sorted(p for p in Path(tmp).iterdir() if "amdgcn" in p.name) or [copy]  # (a bare code object: no bundle)
-        for obj in objs:
+        for obj in unbundle(lib, tmp):
             syms = subprocess.run([objdump, "-t", str(obj)], check=True, capture_output=True, text=True).stdout
             names = [ln.split()[-1] for ln in syms.splitlines() if " F .text" in ln and needle in ln]
             if not names:
