@@ -372,6 +372,30 @@ impl Engine {
         check(ffi::gymrs_ppo_gradient(self.raw, &d));
     }
 
+    /// `gymrs_q_target_sync`: copy the current policy set into the engine-owned target set of `q_gradient` (device to device, in
+    /// stream order).  A `set_policy` of the same shape keeps the target; any other, or the policy's removal, discards it.
+    pub fn q_target_sync(&mut self) {
+        unsafe { check(ffi::gymrs_q_target_sync(self.raw)) };
+    }
+
+    /// `gymrs_q_target_ptr`: (device address, number of floats) of the target set, zero-copy.
+    pub fn q_target_ptr(&mut self) -> (*mut f32, u64) {
+        let (mut p, mut n) = (std::ptr::null_mut(), 0u64);
+        unsafe { check(ffi::gymrs_q_target_ptr(self.raw, &mut p, &mut n)) };
+        (p, n)
+    }
+
+    /// `gymrs_q_gradient`: the policy's logits are Q-values.  Writes the TD error of every lane-step to `d.td` and ADDS the gradient of
+    /// the Huber loss (to descend) to `d.grad` and `d.excluded` and, when `d.counts` is not null, the lane-steps seen and clamped.
+    /// Needs `q_target_sync` first.  Reads and writes no lane array.
+    ///
+    /// # Safety
+    /// Every row pointer of `d` must be a 16-byte aligned device address of the size the header names, `grad`, `excluded` and `counts`
+    /// 8-byte aligned, all valid until `sync()`.
+    pub unsafe fn q_gradient(&mut self, d: &ffi::GymrsQDesc) {
+        check(ffi::gymrs_q_gradient(self.raw, d));
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

@@ -211,6 +211,29 @@ pub struct GymrsPpoDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_Q_DOUBLE`: the bootstrap action is the first maximum of the ONLINE logits of the successor (Double DQN).
+pub const GYMRS_Q_DOUBLE: u32 = 1;
+
+/// `gymrs_q_desc`: what `gymrs_q_gradient` runs (include/gymrs_amd.h "Q-learning"), 120 bytes: the record by value (all of its rows are
+/// read; `truncated` may be null), the start and final observations, the `td` row it writes, and the tables it adds to (`counts` u64
+/// `[n_sets][2]` or null: the lane-steps seen and those with |delta| > kappa).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsQDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub gamma: f32,
+    pub kappa: f32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub final_obs: *const f32,
+    pub td: *mut f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub counts: *mut u64,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -347,6 +370,14 @@ extern "C" {
     pub fn gymrs_ppo_lane(kind: c_int, hidden: u32, scale: f32, clip_low: f32, clip_high: f32, weights: *const f32, n_steps: u32, x: *const f32,
                           actions: *const u8, advantages: *const f32, old_prob: *const f32, q: *mut i64, excluded: *mut u64, counts: *mut u64,
                           prob: *mut f32) -> c_int;
+    /// Q-learning over a transitions record: the engine-owned target set, the two-kernel call, and one lane of it on the host
+    pub fn gymrs_q_target_sync(e: *mut GymrsEngine) -> c_int;
+    pub fn gymrs_q_target_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_q_gradient(e: *mut GymrsEngine, d: *const GymrsQDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_q_lane(kind: c_int, hidden: u32, flags: u32, gamma: f32, kappa: f32, weights: *const f32, target_weights: *const f32, n_steps: u32,
+                        x: *const f32, x_next: *const f32, actions: *const u8, reward: *const f32, done: *const u8, q: *mut i64, excluded: *mut u64,
+                        td: *mut f32, counts: *mut u64) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -1,16 +1,19 @@
 #!/usr/bin/env python
-"""Epsilon-greedy data collection for a learner: explore inside the fused launch, validate greedily, know which actions explored.
+"""A Double-DQN style learner that never leaves the device: explore inside the fused launch, take the Q-gradient inside the library,
+update the weights in place, refresh the target set every few rounds, validate greedily.
 
 A linear Q-function on CartPole, Q(s, a) = W[a] . s + b[a], IS an affine policy of the engine (its argmax is the greedy action), so
-the engine plays it inside the kernel.  Every round
-  1. collects K steps of every lane in ONE launch with `rollout_closed_loop(K, explore=True, record=...)`: the action of a step is
-     random with probability epsilon (decaying round by round) and the argmax otherwise; the record's `actions` rows hold the action
-     taken;
+the engine plays it inside the kernel and differentiates it inside the kernel.  Every round
+  1. collects K whole transitions of every lane in ONE launch with `rollout_transitions(K, explore=True, ...)`: the action of a step
+     is random with probability epsilon (decaying round by round) and the argmax otherwise; `final_obs` keeps the observation an
+     ended lane showed before its re-arm, so truncated steps are kept and bootstrapped from it;
   2. recovers which recorded actions were exploratory with `explore_draw` from (global lane id, tick) alone -- no extra trajectory
      row -- and checks on a few lanes that an explored action is the draw's random action;
-  3. takes one semi-gradient Q-learning step on the batch (torch, on the device buffers the kernel wrote) and installs the new
-     weights with `set_policy` (the exploration settings survive it);
-  4. validates the new policy with a greedy launch (`fitness=True`, no `explore`): fewer episodes ended = longer balancing.
+  3. takes the Q-gradient with `q_gradient(K, double=True, ...)` right behind the collection, no synchronisation in between: TD
+     errors against the engine-owned target set, the Huber clamp, exact fixed-point sums;
+  4. descends it in place through `policy_weights_ptr` (one torch operation on the engine's weights: no round trip to the host);
+  5. every `--sync-every` rounds copies the online set into the target set with `q_target_sync`;
+  6. validates the new policy with a greedy launch (`fitness=True`, no `explore`): fewer episodes ended = longer balancing.
 
     python examples/epsilon_greedy_collection.py [--lanes 4096] [--steps 64] [--rounds 12]
 """
@@ -28,29 +31,39 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 gymrs = importlib.import_module("gym-rs_amd")
 
 
+class DeviceArray:
+    """`count` elements of `typestr` at a device address, for torch.as_tensor (zero-copy)"""
+
+    def __init__(self, ptr, count, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (ptr, False), "version": 3}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=64, help="K: steps per launch")
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--epsilon", type=float, default=0.5, help="of the first round; halves every third round")
+    ap.add_argument("--sync-every", type=int, default=3, help="rounds between two q_target_sync")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     n, steps, dev = args.lanes, args.steps, "cuda:0"
-    gamma, lr, explore_seed = 0.97, 0.05, 1234
+    gamma, kappa, lr, explore_seed = 0.97, 1.0, 0.05, 1234
     rng = np.random.default_rng(args.seed)
-    weights = (0.1 * rng.standard_normal(gymrs.policy_size(gymrs.CARTPOLE, 0))).astype(np.float32)  # W[2][4], b[2]
+    size = gymrs.policy_size(gymrs.CARTPOLE, 0)  # W[2][4], b[2]
 
     env = gymrs.BatchedEngine(gymrs.CARTPOLE, n, flags=gymrs.AUTO_RESET | gymrs.TRACK_STATS | gymrs.TIME_LIMIT)
     env.reset(seed=args.seed)
-    env.set_policy(weights, hidden=0, lanes_per_policy=n)
+    env.set_policy((0.1 * rng.standard_normal(size)).astype(np.float32), hidden=0, lanes_per_policy=n)
+    env.q_target_sync()
+    weights = torch.as_tensor(DeviceArray(*env.policy_weights_ptr()), device=dev)  # the engine's own buffer
 
     stride = (n + 15) // 16 * 16
-    obs = torch.empty((steps, 4, stride), dtype=torch.float32, device=dev)
-    act = torch.empty((steps, stride), dtype=torch.uint8, device=dev)
-    rew = torch.empty((steps, stride), dtype=torch.float32, device=dev)
-    done = torch.empty((steps, stride), dtype=torch.uint8, device=dev)
-    trunc = torch.empty((steps, stride), dtype=torch.uint8, device=dev)
+    obs, final = (torch.empty((steps, 4, stride), dtype=torch.float32, device=dev) for _ in range(2))
+    start = torch.empty((4, stride), dtype=torch.float32, device=dev)
+    rew, td = (torch.empty((steps, stride), dtype=torch.float32, device=dev) for _ in range(2))
+    act, done, trunc = (torch.empty((steps, stride), dtype=torch.uint8, device=dev) for _ in range(3))
+    grad, excluded, counts = (torch.zeros(shape, dtype=torch.int64, device=dev) for shape in ((1, size), (1,), (1, 2)))
     torch.cuda.synchronize()
     record = dict(obs=obs.data_ptr(), actions=act.data_ptr(), reward=rew.data_ptr(), done=done.data_ptr(), truncated=trunc.data_ptr(),
                   lane_stride=stride)
@@ -61,36 +74,33 @@ def main() -> int:
         env.set_exploration(explore_seed, epsilon=epsilon)
         _, threshold = env.exploration()  # epsilon on the grid of 1 / 65536
         t0 = env.tick()[0]                # row k of the record is the step from tick t0 + k
-        env.rollout_closed_loop(steps, explore=True, record=record)
-        env.sync()
+        # collection and the Q-gradient, back to back on the engine's stream
+        env.rollout_transitions(steps, record=record, final_obs=final.data_ptr(), start_obs=start.data_ptr(), explore=True)
+        env.q_gradient(steps, record=record, start_obs=start.data_ptr(), final_obs=final.data_ptr(), td=td.data_ptr(), grad=grad.data_ptr(),
+                       excluded=excluded.data_ptr(), counts=counts.data_ptr(), gamma=gamma, kappa=kappa, double=True)
+        env.sync()  # torch works on its own stream from here
 
         # which recorded actions were exploratory: recomputed from (global lane id, tick)
         explored, random_action = gymrs.explore_draw(explore_seed, threshold, 2, probe[None, :], t0 + np.arange(steps)[:, None])
         taken = act[:, :n].cpu().numpy()[:, probe]
         assert np.array_equal(taken[explored], random_action[explored])  # an explored step took the draw's action
 
-        # one semi-gradient Q-learning step on the transitions (obs[k - 1], act[k], rew[k], obs[k]); truncated steps are left out
-        # (their successor is a reset state), terminated ones do not bootstrap
-        w = torch.from_numpy(weights[:8].reshape(2, 4)).to(dev)
-        b = torch.from_numpy(weights[8:]).to(dev)
-        s, s2 = obs[:-1, :, :n], obs[1:, :, :n]
-        a = act[1:, :n].long()
-        q = torch.einsum("aj,kjn->kan", w, s) + b[None, :, None]
-        q2 = torch.einsum("aj,kjn->kan", w, s2) + b[None, :, None]
-        target = rew[1:, :n] + gamma * q2.max(dim=1).values * (done[1:, :n] == 0)
-        td = (target - q.gather(1, a[:, None, :]).squeeze(1)) * (trunc[1:, :n] == 0)
-        onehot = torch.nn.functional.one_hot(a, 2).permute(0, 2, 1).float()  # [K - 1][2][n]
-        grad_w = torch.einsum("kn,kan,kjn->aj", td, onehot, s) / td.numel()
-        grad_b = torch.einsum("kn,kan->a", td, onehot) / td.numel()
-        weights = torch.cat([(w + lr * grad_w).reshape(-1), b + lr * grad_b]).cpu().numpy().astype(np.float32)
-        torch.cuda.synchronize()
-        env.set_policy(weights, hidden=0, lanes_per_policy=n)  # keeps the exploration settings, discards the fitness table
+        # descend the Huber loss in place: grad is the exact fixed-point sum over all lane-steps, times 2^24
+        seen, clamped = (int(v) for v in counts[0])
+        weights -= (lr / max(1, seen) * 2.0**-24) * grad[0].double().float()
+        mean_td = float(td[:, :n].abs().mean())
+        grad.zero_(), excluded.zero_(), counts.zero_()
+        torch.cuda.synchronize()  # the engine reads the weights on its own stream
+        if (r + 1) % args.sync_every == 0:
+            env.q_target_sync()
 
-        # greedy validation: the same call without `explore`
+        # greedy validation: the closed-loop call without `explore`
+        env.policy_fitness_clear()
         env.rollout_closed_loop(steps, fitness=True)
         reward_sum, episodes, _, _ = env.policy_fitness()[0]
         print(f"round {r:2d}: epsilon {threshold / 65536:.4f} ({explored.mean():.1%} of {explored.size} probed steps explored), "
-              f"mean |TD| {float(td.abs().mean()):.3f}; greedy validation: {int(episodes)} episodes ended in {steps} x {n} lane-steps "
+              f"mean |TD| {mean_td:.3f}, {clamped / max(1, seen):.1%} of {seen} lane-steps clamped, "
+              f"{int((trunc[:, :n] != 0).sum())} truncated steps kept; greedy validation: {int(episodes)} episodes ended in {steps} x {n} lane-steps "
               f"(mean length {steps * n / max(1, int(episodes)):.1f})")
     env.close()
     return 0

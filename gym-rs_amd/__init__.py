@@ -51,6 +51,7 @@ from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
+from .engine import QDesc, Q_DOUBLE, q_lane
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -64,4 +65,5 @@ __all__ = [
     "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
     "PpoDesc", "ppo_lane",
+    "QDesc", "Q_DOUBLE", "q_lane",
 ]

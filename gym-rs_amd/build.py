@@ -27,7 +27,7 @@ HIP_SOURCES = [CSRC / "gymrs_step_cartpole.hip", CSRC / "gymrs_step_mountain_car
                CSRC / "gymrs_explore.hip", CSRC / "gymrs_explore_fitness.hip", CSRC / "gymrs_table_explore_cartpole.hip",
                CSRC / "gymrs_table_explore_mountain_car.hip", CSRC / "gymrs_transitions.hip", CSRC / "gymrs_table_transitions_cartpole.hip",
                CSRC / "gymrs_table_transitions_mountain_car.hip", CSRC / "gymrs_sample.hip", CSRC / "gymrs_sample_fitness.hip",
-               CSRC / "gymrs_table_sample_cartpole.hip", CSRC / "gymrs_table_sample_mountain_car.hip", CSRC / "gymrs_advantages.hip", CSRC / "gymrs_gradient.hip", CSRC / "gymrs_gradient_ppo.hip", CSRC / "gymrs_evaluate.hip", CSRC / "gymrs_aux.hip", CSRC / "gymrs_engine.hip", CSRC / "gymrs_engine_io.hip",
+               CSRC / "gymrs_table_sample_cartpole.hip", CSRC / "gymrs_table_sample_mountain_car.hip", CSRC / "gymrs_advantages.hip", CSRC / "gymrs_gradient.hip", CSRC / "gymrs_gradient_ppo.hip", CSRC / "gymrs_qlearn.hip", CSRC / "gymrs_evaluate.hip", CSRC / "gymrs_aux.hip", CSRC / "gymrs_engine.hip", CSRC / "gymrs_engine_io.hip",
                CSRC / "gymrs_engine_learn.hip",
                CSRC / "gymrs_aql.hip", CSRC / "gymrs_sharded.hip"]
 # The per-step kernels once more as a stand-alone gfx950 code object (device-only compile), embedded into the library by
@@ -54,6 +54,10 @@ HIPCC_FLAGS = [
     "-mllvm",
     "-amdgpu-kernarg-preload-count=12",
 ]
+
+# Flags of single translation units.  The Q-learning kernels are compiled without packed-f32 instructions: every operation of the rule
+# stays the scalar f32 instruction the host text compiles to.  (The older units keep the flags their code objects were built with.)
+SOURCE_FLAGS = {"gymrs_qlearn": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(target: Path, deps) -> bool:
@@ -105,7 +109,7 @@ def build_hip(force: bool = False, extra_flags=(), out: Path | None = None) -> P
         embeds = src.stem == "gymrs_aql"  # .incbin of the code object: compiled after it
         if force or extra_flags or not _newer(obj, [src] + hdr_deps) or (embeds and hsaco_stale):
             # (gymrs_aql.hip embeds the code object with .incbin "gymrs_aql_kernels.hsaco": found through -I, so no path travels in a -D string)
-            cmd = [hipcc, *HIPCC_FLAGS, *extra_flags, f"-I{ROOT / 'include'}", f"-I{CSRC}", *([f"-I{objdir}", f"-Wa,-I{objdir}"] if embeds else []), "-c", src, "-o", obj]
+            cmd = [hipcc, *HIPCC_FLAGS, *SOURCE_FLAGS.get(src.stem, []), *extra_flags, f"-I{ROOT / 'include'}", f"-I{CSRC}", *([f"-I{objdir}", f"-Wa,-I{objdir}"] if embeds else []), "-c", src, "-o", obj]
             (after if embeds else jobs).append(cmd)
     with ThreadPoolExecutor(max_workers=max(1, len(jobs))) as pool:
         list(pool.map(_run, jobs))

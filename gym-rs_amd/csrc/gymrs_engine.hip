@@ -515,6 +515,7 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->param_index);
     (void)hipFree(e->policy.dev);
     (void)hipFree(e->critic.dev);
+    (void)hipFree(e->q_target.dev);
     (void)hipFree(e->fitness_dev);
     (void)hipFree(e->eval_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));

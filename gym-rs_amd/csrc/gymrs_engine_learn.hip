@@ -1,12 +1,15 @@
 // gymrs_engine_learn.hip -- the learner surface of the C ABI (include/gymrs_amd.h): the policy and critic sets, the exploration and sampling
-// settings with their per-step calls and host draws, advantages, gradients and the clipped surrogate over a transitions record with their
-// host-only lanes, the per-policy fitness and evaluation tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
+// settings with their per-step calls and host draws, advantages, gradients, the clipped surrogate and Q-learning (with its target set) over a
+// transitions record with their host-only lanes, the per-policy fitness and evaluation tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
 // object and the refusals shared with the stepping paths: gymrs_engine_priv.h.
 #include "gymrs_engine_priv.h"
 #include "gymrs_evaluate.h"
 #include "gymrs_sample.h"
 #include "gymrs_advantages.h"
 #include "gymrs_gradient.h"
+#include "gymrs_qlearn.h"
+
+#include <algorithm>
 
 namespace {
 // ---- the checks more than one entry point words the same way --------------------------------------------------------------------
@@ -98,6 +101,25 @@ gymrs_status weights_view(const gymrs_engine* e, const WeightKind& k, float** de
     *dev_out = set.dev;
     if (n_floats) *n_floats = (uint64_t)set.args.stride * set.args.n_policies;
     return GYMRS_OK;
+}
+
+// ---- the target set of gymrs_q_gradient: a copy of the policy set the engine owns ----------------------------------------------------
+// The target goes with its buffer (launches already enqueued still read it: wait for them).
+gymrs_status discard_q_target(gymrs_engine* e)
+{
+    if (!e->q_target.dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(e->q_target.dev));
+    e->q_target = WeightSet{};
+    return GYMRS_OK;
+}
+
+// A new policy set of the target's shape keeps the target.
+bool q_target_fits(const gymrs_engine* e, const gymrs_policy_desc* d)
+{
+    const PolicyArgs& t = e->q_target.args;
+    return e->q_target.dev && t.hidden == d->hidden && t.n_policies == d->n_policies && t.lanes_per_policy == d->lanes_per_policy;
 }
 
 // ---- a per-policy table: policy.args.n_policies records on the device that appear at first use and go with the policy set -------------
@@ -301,6 +323,80 @@ void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, co
         ppo->counts[1] = ncut;
     }
 }
+
+// One lane of "Q-learning" by the shared text: the TD kernel's walk, then the gradient kernel's, with VEC = 1, chunk after chunk.
+template <int D, int A>
+void q_lane(uint32_t H, uint32_t flags, float gamma, float kappa, const float* weights, const float* target_weights, uint32_t K, const float* x,
+            const float* x_next, const uint8_t* actions, const float* reward, const uint8_t* done, int64_t* q, uint64_t* excluded, float* td,
+            uint64_t* counts)
+{
+    const HostWeights w{weights}, wt{target_weights};
+    std::vector<float> delta(K);
+    uint64_t seen = 0, ncut = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+        float xs[D][1], xn[D][1], y[A][1], yt[A][1], ysel[A][1], dl[1];
+        for (int j = 0; j < D; ++j) {
+            xs[j][0] = x[(size_t)k * D + j];
+            xn[j][0] = x_next[(size_t)k * D + j];
+        }
+        gradient_logits<D, A, 1, 1>(w, H, xs, y);
+        gradient_logits<D, A, 1, 1>(wt, H, xn, yt);
+        if (flags & GYMRS_Q_DOUBLE)
+            gradient_logits<D, A, 1, 1>(w, H, xn, ysel);
+        else
+            for (int b = 0; b < A; ++b) ysel[b][0] = yt[b][0];
+        const uint8_t act[1] = {actions[k]};
+        const float r[1] = {reward[k]};
+        const bool dn[1] = {done[k] != 0};
+        bool on[1];
+        q_td_step<A, 1>(y, yt, ysel, act, r, dn, gamma, dl, on);
+        delta[k] = dl[0];
+        seen += on[0] ? 1 : 0;
+        ncut += (on[0] && q_clamped(dl[0], kappa)) ? 1 : 0;
+    }
+    uint64_t excl = 0;
+    auto emit = [&](uint32_t s, const float (&L)[1]) {
+        long long v;
+        if (!gradient_fixed(L[0], v)) excl += 1;
+        q[s] = v;
+    };
+    const uint32_t chunks = H == 0 ? 1 : (H + kGradientChunk - 1) / kGradientChunk;
+    for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
+        const uint32_t h0 = chunk * kGradientChunk;
+        GradientAffine<D, A, 1> aff{};
+        GradientChunk<D, A, 1> chk{};
+        float db2[A][1] = {};
+        for (uint32_t k = 0; k < K; ++k) {
+            float xs[D][1], g[A][1];
+            bool on[1];
+            for (int j = 0; j < D; ++j) xs[j][0] = x[(size_t)k * D + j];
+            const float dl[1] = {delta[k]};
+            const uint8_t act[1] = {actions[k]};
+            q_head<A, 1>(dl, act, kappa, g, on);
+            if (H == 0) {
+                gradient_affine_step<D, A, 1, true>(xs, g, on, aff);
+            } else {
+                gradient_chunk_step<D, A, 1, true>(w, H, h0, xs, g, on, chk);
+                if (chunk == 0) gradient_bias_step<A, 1, true>(g, on, db2);
+            }
+        }
+        if (H == 0) {
+            gradient_affine_each<D, A, 1>(aff, emit);
+        } else {
+            gradient_chunk_each<D, A, 1>(H, h0, chk, emit);
+            if (chunk == 0) gradient_bias_each<D, A, 1>(H, db2, emit);
+        }
+    }
+    *excluded = excl;
+    if (td) std::copy(delta.begin(), delta.end(), td);
+    if (counts) {
+        counts[0] = seen;
+        counts[1] = ncut;
+    }
+}
+
+bool q_gamma_ok(float gamma) { return gamma >= 0.0f && gamma <= 1.0f; } // (false for a NaN)
+bool q_kappa_ok(float kappa) { return kappa > 0.0f; }                   // (false for a NaN; +inf is the squared loss)
 } // namespace
 
 GYMRS_HOST_INTERNAL gymrs_status policy_fitness_table(gymrs_engine* e) { return kFitness.table(e); }
@@ -321,11 +417,14 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
     if (!e) return fail(GYMRS_EINVAL, "gymrs_set_policy: NULL engine");
     if (!d) { // remove the policy, and the tables with it
         if (gymrs_status st = remove_weights(e, kPolicyKind)) return st;
+        if (gymrs_status st = discard_q_target(e)) return st;
         if (gymrs_status st = kEval.discard(e)) return st;
         return kFitness.discard(e);
     }
     if (gymrs_status st = check_weights(e, kPolicyKind, d, weights_host, "gymrs_set_policy")) return st;
     HIP_TRY(hipSetDevice(e->device));
+    if (!q_target_fits(e, d))
+        if (gymrs_status st = discard_q_target(e)) return st; // a target of another shape belongs to the set it was copied from
     // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
     // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
     if (e->fitness_dev && d->n_policies == e->policy.args.n_policies) {
@@ -634,6 +733,92 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d)
                     reinterpret_cast<unsigned long long*>(d->counts), d->clip_low, d->clip_high};
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_ppo_gradient(e->kind, a, e->policy.args, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- Q-learning: the target set, the host-side lane and the launch (include/gymrs_amd.h, "Q-learning") -----------------------------
+gymrs_status gymrs_q_target_sync(gymrs_engine* e)
+{
+    const std::string who = "gymrs_q_target_sync";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
+    const PolicyArgs& p = e->policy.args;
+    const uint64_t total = (uint64_t)p.stride * p.n_policies;
+    WeightSet& t = e->q_target;
+    HIP_TRY(hipSetDevice(e->device));
+    if (total > t.capacity) { // (a kept target has the policy's shape: only a first use gets here)
+        if (gymrs_status st = discard_q_target(e)) return st;
+        HIP_TRY(hipMalloc(&t.dev, (size_t)total * sizeof(float)));
+        t.capacity = total;
+    }
+    // stream-ordered, device to device: launches enqueued before this call read the old target
+    HIP_TRY(hipMemcpyAsync(t.dev, e->policy.dev, (size_t)total * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    t.args = p;
+    t.args.weights = t.dev;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_q_target_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
+{
+    const std::string who = "gymrs_q_target_ptr";
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
+    if (!e->q_target.dev) return fail(GYMRS_EINVAL, who + ": the engine has no target set (gymrs_q_target_sync)");
+    *dev_out = e->q_target.dev;
+    if (n_floats) *n_floats = (uint64_t)e->q_target.args.stride * e->q_target.args.n_policies;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_q_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float gamma, float kappa, const float* weights,
+                          const float* target_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
+                          const float* reward, const uint8_t* done, int64_t* q, uint64_t* excluded, float* td, uint64_t* counts)
+{
+    const std::string who = "gymrs_q_lane";
+    if (gymrs_status st = check_network(kind, hidden, who)) return st;
+    if (flags & ~GYMRS_Q_DOUBLE) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_Q_DOUBLE is the only one)");
+    if (!weights || !target_weights || !q || !excluded || (n_steps != 0 && (!x || !x_next || !actions || !reward || !done)))
+        return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!q_gamma_ok(gamma)) return fail(GYMRS_EINVAL, who + ": gamma must be in [0, 1]");
+    if (!q_kappa_ok(kappa)) return fail(GYMRS_EINVAL, who + ": kappa must be > 0 (+inf is the squared loss)");
+    if (kind == GYMRS_CARTPOLE)
+        q_lane<4, 2>(hidden, flags, gamma, kappa, weights, target_weights, n_steps, x, x_next, actions, reward, done, q, excluded, td, counts);
+    else
+        q_lane<2, 3>(hidden, flags, gamma, kappa, weights, target_weights, n_steps, x, x_next, actions, reward, done, q, excluded, td, counts);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_q_gradient"};
+    if (gymrs_status st = c.prologue("Q-gradients are")) return st;
+    if (d->reserved != 0) return c.refuse("reserved must be 0");
+    if (d->flags & ~GYMRS_Q_DOUBLE) return c.refuse("unknown flag bits (GYMRS_Q_DOUBLE is the only one)");
+    if (gymrs_status st = check_policy_set(e, c.who)) return st;
+    if (!e->q_target.dev) return c.refuse("the engine has no target set (gymrs_q_target_sync)");
+    if (!q_gamma_ok(d->gamma)) return c.refuse("gamma must be in [0, 1]");
+    if (!q_kappa_ok(d->kappa)) return c.refuse("kappa must be > 0 (+inf is the squared loss)");
+    const gymrs_trajectory& rec = d->record;
+    if (gymrs_status st = c.not_null({{rec.obs, "record.obs"}, {rec.actions, "record.actions"}, {rec.reward, "record.reward"}, {rec.done, "record.done"},
+                                      {d->start_obs, "start_obs"}, {d->final_obs, "final_obs"}, {d->td, "td"}, {d->grad, "grad"},
+                                      {d->excluded, "excluded"}}))
+        return st;
+    for (const void* in : {(const void*)rec.obs, (const void*)rec.actions, (const void*)rec.reward, (const void*)rec.done, (const void*)rec.truncated,
+                           (const void*)d->start_obs, (const void*)d->final_obs})
+        if (in == d->td) return c.refuse("td may not alias an input row");
+    if (gymrs_status st = c.aligned({rec.obs, rec.actions, rec.reward, rec.done, rec.truncated, d->start_obs, d->final_obs, d->td}, 16,
+                                    "every row buffer must be 16-byte aligned"))
+        return st;
+    if (gymrs_status st = c.aligned({d->grad, d->excluded, d->counts}, 8, "grad, excluded and counts must be 8-byte aligned")) return st;
+    if (gymrs_status st = c.lane_stride(rec.lane_stride)) return st;
+    if (d->n_steps == 0) return GYMRS_OK;
+    const QArgs a{rec.obs, static_cast<const uint8_t*>(rec.actions), rec.reward, rec.done, rec.truncated, d->final_obs, d->start_obs, d->td,
+                  reinterpret_cast<unsigned long long*>(d->grad), reinterpret_cast<unsigned long long*>(d->excluded),
+                  reinterpret_cast<unsigned long long*>(d->counts), /*stride, n, gid0*/ rec.lane_stride, e->n, e->gid0, d->n_steps, d->flags, d->gamma,
+                  d->kappa};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_q_gradient(e->kind, a, e->policy.args, e->q_target.args, e->stream));
     return GYMRS_OK;
 }
 

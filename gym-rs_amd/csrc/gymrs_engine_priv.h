@@ -190,6 +190,10 @@ struct gymrs_engine {
     // The policy set of the closed-loop calls (gymrs_set_policy) and the critic set of gymrs_advantages (gymrs_set_critic: the stride of
     // its args is critic_floats; gymrs_set_policy keeps it).  Not part of clone or snapshot.
     WeightSet policy, critic;
+    // The target set of gymrs_q_gradient (gymrs_q_target_sync): a copy of the policy set in a buffer of its own, allocated at first use;
+    // args = the policy's with the target's weights.  A gymrs_set_policy of the same hidden, n_policies and lanes_per_policy keeps it,
+    // any other (or the removal) discards it.  Not part of clone or snapshot.
+    WeightSet q_target;
     // The per-policy counters of gymrs_rollout_policy_fitness: policy.args.n_policies records, allocated (zeroed) at the first fitness
     // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
     // stays the same).  Not part of clone or snapshot.

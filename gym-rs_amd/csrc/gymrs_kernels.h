@@ -413,4 +413,26 @@ struct PpoArgs {
     float clip_low, clip_high;
 };
 hipError_t launch_ppo_gradient(gymrs_env_kind kind, const PpoArgs& a, const PolicyArgs& p, hipStream_t stream);
+// ---- Q-learning (gymrs_q_gradient; gymrs_qlearn.hip) ---------------------------------------------------------------------------
+// A gymrs_q_desc as its two kernels get it by value, before the online set (and, for the TD kernel, the target set).  Rows are
+// `stride` lanes apart (>= n, a multiple of 16) and 16-byte aligned; grad, excluded and counts are 8-byte aligned and ADDED to.
+struct QArgs {
+    const float* obs;             // [n_steps][obs_dim][stride]
+    const uint8_t* actions;       // [n_steps][stride]
+    const float* reward;          // [n_steps][stride]
+    const uint8_t* done;          // [n_steps][stride]
+    const uint8_t* truncated;     // [n_steps][stride] or NULL
+    const float* final_obs;       // [n_steps][obs_dim][stride]; read on ended lane-steps only
+    const float* start_obs;       // [obs_dim][stride]
+    float* td;                    // [n_steps][stride]: written by the TD kernel, read by the gradient kernel
+    unsigned long long* grad;     // [n_sets][S]
+    unsigned long long* excluded; // [n_sets]
+    unsigned long long* counts;   // [n_sets][2] or NULL
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    uint32_t flags; // GYMRS_Q_DOUBLE
+    float gamma, kappa;
+};
+// online and target differ in `weights` alone: both sets are keyed by the policy's key
+hipError_t launch_q_gradient(gymrs_env_kind kind, const QArgs& a, const PolicyArgs& online, const PolicyArgs& target, hipStream_t stream);
 } // namespace gymrs

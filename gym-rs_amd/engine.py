@@ -132,6 +132,17 @@ class PpoDesc(C.Structure):
                 ("prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class QDesc(C.Structure):
+    """``gymrs_q_desc`` (include/gymrs_amd.h), 120 bytes: the record by value, two observation buffers in, the td row out, two tables
+    and an optional pair of counters per set added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("gamma", C.c_float), ("kappa", C.c_float), ("record", Trajectory),
+                ("start_obs", C.c_void_p), ("final_obs", C.c_void_p), ("td", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p),
+                ("counts", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+Q_DOUBLE = 1  # GYMRS_Q_DOUBLE
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -341,6 +352,32 @@ def ppo_lane(kind: int, hidden: int, weights, x, actions, advantages, old_prob, 
                                    q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), counts.ctypes.data_as(up),
                                    pr.ctypes.data_as(fp) if prob else None))
     return (q, excluded.value, counts, pr) if prob else (q, excluded.value, counts)
+
+
+def q_lane(kind: int, hidden: int, weights, target_weights, x, x_next, actions, reward, done, *, gamma: float, kappa: float = float("inf"),
+           double: bool = False, flags: Optional[int] = None):
+    """``gymrs_q_lane`` (host only, no GPU): one lane's contribution to ``gymrs_q_gradient`` -- the definition of include/gymrs_amd.h,
+    "Q-learning", as code.  ``weights`` / ``target_weights``: ONE online and ONE target network (``policy_size`` floats each); ``x``
+    [K][D] the observation every step started from, ``x_next`` [K][D] the already selected successor, ``actions`` [K], ``reward`` [K],
+    ``done`` [K] (it alone decides the bootstrap).  Returns (q, excluded, td [K], counts): q is int64 [S], the gradient of the Huber
+    loss is q * 2**-24; counts is uint64 [2] = (lane-steps with an action in range, those with |delta| > kappa)."""
+    lib = load_library()
+    size = policy_size(kind, hidden)
+    w, wt, xs, xn, r = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (weights, target_weights, x, x_next, reward))
+    a, dn = (np.ascontiguousarray(v, dtype=np.uint8).reshape(-1) for v in (actions, done))
+    k, d = r.size, _OBS_DIM[kind]
+    if w.size != size or wt.size != size or xs.size != k * d or xn.size != k * d or a.size != k or dn.size != k:
+        raise ValueError(f"q_lane needs {size} weights per network and, per step, 2 x {d} observation components, an action, a reward and a done flag")
+    q = np.zeros(size, np.int64)
+    excluded = C.c_uint64()
+    td = np.zeros(k, np.float32)
+    counts = np.zeros(2, np.uint64)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    f = (Q_DOUBLE if double else 0) if flags is None else int(flags)
+    _check(lib, lib.gymrs_q_lane(int(kind), int(hidden), f, float(gamma), float(kappa), w.ctypes.data_as(fp), wt.ctypes.data_as(fp), k, xs.ctypes.data_as(fp),
+                                 xn.ctypes.data_as(fp), a.ctypes.data_as(bp), r.ctypes.data_as(fp), dn.ctypes.data_as(bp), q.ctypes.data_as(C.POINTER(C.c_int64)),
+                                 C.byref(excluded), td.ctypes.data_as(fp), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return q, excluded.value, td, counts
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -885,6 +922,31 @@ class BatchedEngine:
                        C.c_void_p(old_prob or None), C.c_void_p(prob or None), C.c_void_p(grad or None), C.c_void_p(excluded or None),
                        C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_ppo_gradient(self._h, C.byref(desc)))
+
+    # -- Q-learning over a transitions record: a target set, TD errors and the Q-gradient in one call -------------------
+    def q_target_sync(self) -> None:
+        """``gymrs_q_target_sync``: copy the current policy set into the engine-owned target set (device to device, in stream order).
+        A ``set_policy`` of the same shape keeps the target; any other, or the policy's removal, discards it."""
+        _check(self._lib, self._lib.gymrs_q_target_sync(self._h))
+
+    def q_target_ptr(self) -> Tuple[int, int]:
+        """(device address, number of floats) of the target set: zero-copy, for a Polyak average on the engine's stream.  Valid until
+        the target is discarded or the engine closed."""
+        return _view(self._lib, self._lib.gymrs_q_target_ptr, self._h)
+
+    def q_gradient(self, n_steps: int, *, record, start_obs: int, final_obs: int, td: int, grad: int, excluded: int, counts: Optional[int] = None,
+                   gamma: float, kappa: float = float("inf"), double: bool = False, flags: Optional[int] = None) -> None:
+        """``gymrs_q_gradient``: the policy's logits are Q-values.  Writes the TD error delta = Q(x, a) - (r + gamma * Q_target(x', b*))
+        of every lane-step to ``td`` (device f32 [n_steps][lane_stride]) and ADDS the gradient of sum huber_kappa(delta) -- the loss to
+        descend -- per policy to ``grad`` / ``excluded`` as ``policy_gradient`` does, and, with ``counts`` (device uint64
+        [n_policies][2]), the lane-steps seen and those with |delta| > kappa.  The successor x' is ``final_obs`` where the step ended an
+        episode; a done step bootstraps from 0, a truncated one from its final observation.  ``double`` (``GYMRS_Q_DOUBLE``) chooses b*
+        with the online set.  Needs ``q_target_sync`` first.  Two kernels on the engine's stream; reads and writes no lane array."""
+        traj = _record("q_gradient", self.n_envs, n_steps, record)
+        f = (Q_DOUBLE if double else 0) if flags is None else int(flags)
+        desc = QDesc(int(n_steps), f, float(gamma), float(kappa), traj, C.c_void_p(start_obs or None), C.c_void_p(final_obs or None),
+                     C.c_void_p(td or None), C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(counts or None), 0)
+        _check(self._lib, self._lib.gymrs_q_gradient(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

@@ -853,6 +853,79 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d);
 gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
                             const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
                             uint64_t counts[2], float* prob);
+/* Q-learning: TD errors and the Q-gradient over a transitions record, with a target set, Double-DQN action selection and a Huber
+ * clamp, as exact fixed-point integers.  The policy network's logits are the Q-values.  gymrs_q_gradient(e, d) writes the TD error of
+ * every lane-step to td and ADDS, for every set m and every parameter s of its network, the fixed point of the lane's f32 sum of
+ * d huber_kappa(delta) / d theta_s to grad[m][s].  All arithmetic is f32, every operation below is a single IEEE operation, fmaf =
+ * the fused multiply-add with ONE rounding, nothing is contracted or reordered, every `?:` is a select.
+ *     y[0..A)  = the logits of "closed-loop rollouts" under the ONLINE set, which is the engine's policy set
+ *     yt[0..A) = the same arithmetic under the TARGET set (gymrs_q_target_sync below)
+ * Lane i has the global id g = global_env_offset + i and uses set (g / lanes_per_policy) % n_policies, the policy's key, for both
+ * sets.  For k = 0 .. K-1, rows and columns as in gymrs_rollout_transitions:
+ *     x     = (k == 0 ? start_obs : obs[k-1]);  a = actions[k];  r = reward[k]
+ *     dn    = done[k] != 0;  ended = dn || (truncated != NULL && truncated[k] != 0)
+ *     x'    = ended ? final_obs[k] : obs[k]         (a select per component; final_obs is read on ended lane-steps only)
+ *     y     = online logits of x;   yt = target logits of x'
+ *     plain:            b* = first maximum of yt    (b* = 0; for b = 1..A-1: if (yt[b] > yt[b*]) b* = b; a NaN never wins)
+ *     GYMRS_Q_DOUBLE:   b* = first maximum of the ONLINE logits of x'
+ *     v      = yt[b*];  boot = dn ? +0.0f : v       (done wins over truncated, as in "advantages")
+ *     target = fmaf(gamma, boot, r)
+ *     q_a    = y[a] (a select chain);  delta = q_a - target
+ *     d      = delta > kappa ? kappa : (delta < -kappa ? -kappa : delta)
+ *                                                   (compares: false on NaN, a NaN passes through; kappa = +inf is the squared loss)
+ *     g[b]   = (b == a) ? d : +0.0f
+ *     a >= A: the lane-step contributes nothing (every accumulator keeps its value), td[k][i] = +0.0f, it is not counted
+ * Backward pass, accumulators, fixed point, excluded, the layout of the table and additivity over engines and launches: exactly the
+ * text of "gradients", with this g.  The table receives the gradient of  sum over k of huber_kappa(delta),  the loss to DESCEND:
+ * the learner subtracts it.
+ * td[k][i] = delta (unclamped; +0.0f where a >= A), written for i < n_envs: the learner's priorities and diagnostics.
+ * counts (may be NULL): device uint64 [n_sets][2], ADDED to, exact: counts[set][0] += 1 per lane-step with a < A, counts[set][1] += 1
+ * per such lane-step with |delta| > kappa (delta > kappa || delta < -kappa).
+ * What follows from the selects: an unselected final_obs element reaches no output; a NaN v on a done step reaches no output.
+ * The target set.
+ *   - gymrs_q_target_sync(e) copies the current policy set into an engine-owned target buffer, device to device, in stream order:
+ *     launches enqueued before it read the old target.  The buffer is allocated at first use.
+ *   - gymrs_q_target_ptr is the zero-copy view under the rules of gymrs_policy_weights_ptr (a learner on the engine's stream may
+ *     rewrite the target in place, e.g. a Polyak average); valid until the target is discarded or the engine destroyed.
+ *   - A gymrs_set_policy with the same hidden, n_policies and lanes_per_policy keeps the target (weights reinstalled every round);
+ *     any other set, or the policy's removal, discards it.  Like the policy it is NOT part of gymrs_engine_clone or of a snapshot.
+ *   - Both: GYMRS_EINVAL for a NULL argument, Pendulum, no policy set; gymrs_q_target_ptr also without a target set.
+ * gymrs_q_gradient runs in the engine's stream order as two kernels back to back (the TD errors, then the sums): a
+ * gymrs_rollout_transitions enqueued just before it needs no synchronisation in between.  It uses the engine only for the stream,
+ * the kind, n_envs, global_env_offset and the two sets: it reads and writes no lane array.  It reads lanes i < n_envs of every row
+ * only; the padding lanes of td keep their bytes.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, reserved != 0, unknown flag bits, no policy set (naming
+ *     gymrs_set_policy), no target set (naming gymrs_q_target_sync), gamma NaN or outside [0, 1], kappa NaN or <= 0, NULL obs /
+ *     actions / reward / done / start_obs / final_obs / td / grad / excluded, td equal to an input row, a row buffer not 16-byte
+ *     aligned, grad, excluded or counts not 8-byte aligned, lane_stride < n_envs or not a multiple of 16.
+ *   - gymrs_q_lane: host only, no GPU: the definition as code, as gymrs_gradient_lane is for "gradients".  From ONE online and ONE
+ *     target network (S floats each), K = n_steps, one lane's x[K][D], x_next[K][D] (the already selected successor x'),
+ *     actions[K], reward[K] and done[K] (done alone decides the bootstrap) it SETS q[0..S), *excluded, td[0..K) (when td != NULL)
+ *     and counts[0..2) (when counts != NULL).  GYMRS_EINVAL: Pendulum, hidden > 64, unknown flag bits, NULL arguments, a bad gamma or
+ *     kappa.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+#define GYMRS_Q_DOUBLE 1u
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* GYMRS_Q_DOUBLE, nothing else */
+    float gamma;                /* finite, 0 <= gamma <= 1 */
+    float kappa;                /* > 0, +inf allowed */
+    gymrs_trajectory record;    /* by value; READ: obs, actions, reward, done, truncated (may be NULL); lane_stride >= n_envs, a
+                                   multiple of 16 */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* final_obs;     /* [K][D][lane_stride], required, 16-byte aligned */
+    float* td;                  /* [K][lane_stride], required, WRITTEN for lanes < n_envs; padding keeps its bytes */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned, ADDED to */
+    uint64_t* excluded;         /* device uint64 [n_sets], ADDED to */
+    uint64_t* counts;           /* device uint64 [n_sets][2] or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_q_desc;                 /* 120 bytes */
+gymrs_status gymrs_q_target_sync(gymrs_engine* e);
+gymrs_status gymrs_q_target_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats);
+gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d);
+gymrs_status gymrs_q_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float gamma, float kappa, const float* weights,
+                          const float* target_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
+                          const float* reward, const uint8_t* done, int64_t* q, uint64_t* excluded, float* td, uint64_t* counts);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

@@ -103,6 +103,18 @@ inline std::uint64_t gradient_lane(gymrs_env_kind kind, std::uint32_t hidden, st
     return excluded;
 }
 
+// One lane's contribution to gymrs_q_gradient (gymrs_q_lane; host only, no GPU): q[0 .. S) is set from ONE online and ONE target
+// network, the number of excluded (lane, parameter) pairs returned; td (may be null) gets the TD error of every step, counts (may be
+// null) the lane-steps seen and clamped.  The definition of include/gymrs_amd.h, "Q-learning", as code.
+inline std::uint64_t q_lane(gymrs_env_kind kind, std::uint32_t hidden, std::uint32_t flags, float gamma, float kappa, const float* weights,
+                            const float* target_weights, std::uint32_t n_steps, const float* x, const float* x_next, const std::uint8_t* actions,
+                            const float* reward, const std::uint8_t* done, std::int64_t* q, float* td = nullptr, std::uint64_t* counts = nullptr)
+{
+    std::uint64_t excluded = 0;
+    check(gymrs_q_lane(kind, hidden, flags, gamma, kappa, weights, target_weights, n_steps, x, x_next, actions, reward, done, q, &excluded, td, counts));
+    return excluded;
+}
+
 // One lane's contribution to gymrs_ppo_gradient (gymrs_ppo_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
 // (lane, parameter) pairs returned; counts (may be null) gets the lane-steps seen and cut, prob (may be null) p[a] of every step.
 // The definition of include/gymrs_amd.h, "clipped surrogate", as code.
@@ -408,6 +420,17 @@ public:
         const gymrs_ppo_desc d{n_steps, 0u, scale, clip_low, clip_high, 0u, record, start_obs, advantages, old_prob, prob, grad, excluded, counts, 0};
         check(gymrs_ppo_gradient(e_, &d));
     }
+    // Q-learning (include/gymrs_amd.h, "Q-learning"): the target set is a copy of the policy set the engine owns (q_target_sync, in
+    // stream order; q_target_ptr is its zero-copy view); q_gradient writes the TD errors to d.td and ADDS the gradient of the Huber
+    // loss (to descend) to d.grad and d.excluded and, when d.counts is not null, the lane-steps seen and clamped
+    void q_target_sync() { check(gymrs_q_target_sync(e_)); }
+    float* q_target_ptr(std::uint64_t* n_floats = nullptr)
+    {
+        float* p = nullptr;
+        check(gymrs_q_target_ptr(e_, &p, n_floats));
+        return p;
+    }
+    void q_gradient(const gymrs_q_desc& d) { check(gymrs_q_gradient(e_, &d)); }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
