@@ -396,6 +396,31 @@ impl Engine {
         check(ffi::gymrs_q_gradient(self.raw, d));
     }
 
+    /// `gymrs_apply_gradient`: SGD or Adam for every set of `d.head` in one launch on the engine's stream, from the fixed-point table
+    /// `d.grad` into the engine's own weights; sets with `excluded != 0` are skipped and counted.  No synchronisation.
+    ///
+    /// # Safety
+    /// `grad` (`[n_sets][S]`), `excluded` (`[n_sets]`) and `skipped` (one word, or null) must be 8-byte aligned device addresses,
+    /// valid until `sync()`.
+    pub unsafe fn apply_gradient(&mut self, d: &ffi::GymrsOptimizerDesc) {
+        check(ffi::gymrs_apply_gradient(self.raw, d));
+    }
+
+    /// `gymrs_optimizer_reset`: the Adam state of `head` back to fresh (m = v = 0, pw = 1), in stream order.
+    pub fn optimizer_reset(&mut self, head: u32) {
+        unsafe { check(ffi::gymrs_optimizer_reset(self.raw, head)) };
+    }
+
+    /// `gymrs_get_optimizer_state`: (m, v, pw) of `head` for `n_sets` sets of `n_params` floats (synchronising).
+    ///
+    /// # Safety
+    /// `n_sets` and `n_params` must be the head's n_policies and its floats per network: the library copies that many.
+    pub unsafe fn optimizer_state(&mut self, head: u32, n_sets: usize, n_params: usize) -> (Vec<f32>, Vec<f32>, Vec<f32>) {
+        let (mut m, mut v, mut pw) = (vec![0f32; n_sets * n_params], vec![0f32; n_sets * n_params], vec![0f32; n_sets * 2]);
+        check(ffi::gymrs_get_optimizer_state(self.raw, head, m.as_mut_ptr(), v.as_mut_ptr(), pw.as_mut_ptr()));
+        (m, v, pw)
+    }
+
     /// The policy's action mixed with the exploration draw at the engine's current tick, one u8 per lane (`gymrs_explore_actions`):
     /// `explore_actions` + `step_device`, K times, is `rollout_closed_loop_explore(K, ..)`.
     ///

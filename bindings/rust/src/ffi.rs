@@ -234,6 +234,38 @@ pub struct GymrsQDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_OPT_HEAD_*`: the weight set `gymrs_apply_gradient` updates.
+pub const GYMRS_OPT_HEAD_POLICY: u32 = 0;
+pub const GYMRS_OPT_HEAD_CRITIC: u32 = 1;
+/// `GYMRS_OPT_SGD` / `GYMRS_OPT_ADAM`: the kind of step.
+pub const GYMRS_OPT_SGD: u32 = 0;
+pub const GYMRS_OPT_ADAM: u32 = 1;
+/// `GYMRS_OPT_ASCEND`: w + step in place of w - step.  `GYMRS_OPT_ZERO_GRAD`: the tables are zeroed after they were read.
+pub const GYMRS_OPT_ASCEND: u32 = 1;
+pub const GYMRS_OPT_ZERO_GRAD: u32 = 2;
+
+/// `gymrs_optimizer_desc`: what `gymrs_apply_gradient` runs (include/gymrs_amd.h "Optimizer"), 72 bytes: the head, the kind, the
+/// flags, seven floats (`max_norm` = +inf: no clip; `tau` > 0: the Q target follows), the two tables it reads (and zeroes with
+/// `GYMRS_OPT_ZERO_GRAD`) and one optional device counter it adds the skipped sets to.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsOptimizerDesc {
+    pub head: u32,
+    pub kind: u32,
+    pub flags: u32,
+    pub lr: f32,
+    pub grad_scale: f32,
+    pub beta1: f32,
+    pub beta2: f32,
+    pub eps: f32,
+    pub max_norm: f32,
+    pub tau: f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub skipped: *mut u64,
+    pub reserved: u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -378,6 +410,13 @@ extern "C" {
     pub fn gymrs_q_lane(kind: c_int, hidden: u32, flags: u32, gamma: f32, kappa: f32, weights: *const f32, target_weights: *const f32, n_steps: u32,
                         x: *const f32, x_next: *const f32, actions: *const u8, reward: *const f32, done: *const u8, q: *mut i64, excluded: *mut u64,
                         td: *mut f32, counts: *mut u64) -> c_int;
+    /// The optimizer: one launch per head, the engine-owned Adam state, and one set of it on the host
+    pub fn gymrs_apply_gradient(e: *mut GymrsEngine, d: *const GymrsOptimizerDesc) -> c_int;
+    pub fn gymrs_optimizer_reset(e: *mut GymrsEngine, head: u32) -> c_int;
+    pub fn gymrs_get_optimizer_state(e: *mut GymrsEngine, head: u32, m_out: *mut f32, v_out: *mut f32, pw_out: *mut f32) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_optimizer_set(d: *const GymrsOptimizerDesc, n_params: u64, q: *const i64, w: *mut f32, m: *mut f32, v: *mut f32, pw: *mut f32,
+                               target: *mut f32) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

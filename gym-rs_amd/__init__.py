@@ -52,6 +52,7 @@ from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
 from .engine import QDesc, Q_DOUBLE, q_lane
+from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -66,4 +67,5 @@ __all__ = [
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
     "PpoDesc", "ppo_lane",
     "QDesc", "Q_DOUBLE", "q_lane",
+    "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",
 ]

@@ -115,6 +115,11 @@ SIGNATURES = {
     "gymrs_q_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_q_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_float, f32p, f32p, C.c_uint32, f32p, f32p, C.POINTER(C.c_uint8), f32p,
                                C.POINTER(C.c_uint8), C.POINTER(C.c_int64), u64p, f32p, u64p]),
+    # the optimizer (gymrs_optimizer_desc 72 B), its Adam state and the host-only set
+    "gymrs_apply_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_optimizer_reset": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gymrs_get_optimizer_state": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, f32p]),
+    "gymrs_optimizer_set": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), f32p, f32p, f32p, f32p, f32p]),
     # episodic policy evaluation (gymrs_eval_desc 32 B in, gymrs_policy_eval 64 B records out)
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),

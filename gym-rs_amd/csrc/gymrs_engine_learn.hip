@@ -1,6 +1,7 @@
 // gymrs_engine_learn.hip -- the learner surface of the C ABI (include/gymrs_amd.h): the policy and critic sets, the exploration and sampling
 // settings with their per-step calls and host draws, advantages, gradients, the clipped surrogate and Q-learning (with its target set) over a
-// transitions record with their host-only lanes, the per-policy fitness and evaluation tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
+// transitions record with their host-only lanes, the optimizer with its Adam state and host-only set, the per-policy fitness and evaluation
+// tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
 // object and the refusals shared with the stepping paths: gymrs_engine_priv.h.
 #include "gymrs_engine_priv.h"
 #include "gymrs_evaluate.h"
@@ -8,6 +9,7 @@
 #include "gymrs_advantages.h"
 #include "gymrs_gradient.h"
 #include "gymrs_qlearn.h"
+#include "gymrs_optimizer.h"
 
 #include <algorithm>
 
@@ -120,6 +122,43 @@ bool q_target_fits(const gymrs_engine* e, const gymrs_policy_desc* d)
 {
     const PolicyArgs& t = e->q_target.args;
     return e->q_target.dev && t.hidden == d->hidden && t.n_policies == d->n_policies && t.lanes_per_policy == d->lanes_per_policy;
+}
+
+// ---- the Adam state of gymrs_apply_gradient, per head: under the target's lifetime rule ------------------------------------------------
+// The state goes with its buffer (launches already enqueued still read it: wait for them).
+gymrs_status discard_opt_state(gymrs_engine* e, uint32_t head)
+{
+    OptimizerState& st = e->opt_state[head];
+    if (!st.dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(st.dev));
+    st = OptimizerState{};
+    return GYMRS_OK;
+}
+
+// A new weight set of the state's shape keeps the state; any other discards it.
+gymrs_status keep_or_discard_opt_state(gymrs_engine* e, uint32_t head, const gymrs_policy_desc* d)
+{
+    const PolicyArgs& t = e->opt_state[head].shape;
+    if (t.hidden == d->hidden && t.n_policies == d->n_policies && t.lanes_per_policy == d->lanes_per_policy) return GYMRS_OK;
+    return discard_opt_state(e, head);
+}
+
+// The state of a head, made fresh at the first Adam call on it (the caller has checked that the head has a set).
+gymrs_status opt_state_of(gymrs_engine* e, uint32_t head, const WeightSet& set)
+{
+    OptimizerState& st = e->opt_state[head];
+    if (st.dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    st.shape = set.args;
+    HIP_TRY(hipMalloc(&st.dev, (size_t)(2 * st.words() + 2 * (uint64_t)st.shape.n_policies) * sizeof(float)));
+    if (hipError_t err = launch_optimizer_fresh(st.m(), st.v(), st.pw(), st.shape.n_policies, st.shape.stride, e->stream)) {
+        (void)hipFree(st.dev);
+        st = OptimizerState{};
+        HIP_TRY(err);
+    }
+    return GYMRS_OK;
 }
 
 // ---- a per-policy table: policy.args.n_policies records on the device that appear at first use and go with the policy set -------------
@@ -418,6 +457,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
     if (!d) { // remove the policy, and the tables with it
         if (gymrs_status st = remove_weights(e, kPolicyKind)) return st;
         if (gymrs_status st = discard_q_target(e)) return st;
+        if (gymrs_status st = discard_opt_state(e, GYMRS_OPT_HEAD_POLICY)) return st;
         if (gymrs_status st = kEval.discard(e)) return st;
         return kFitness.discard(e);
     }
@@ -425,6 +465,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
     HIP_TRY(hipSetDevice(e->device));
     if (!q_target_fits(e, d))
         if (gymrs_status st = discard_q_target(e)) return st; // a target of another shape belongs to the set it was copied from
+    if (gymrs_status st = keep_or_discard_opt_state(e, GYMRS_OPT_HEAD_POLICY, d)) return st; // so do the moments
     // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
     // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
     if (e->fitness_dev && d->n_policies == e->policy.args.n_policies) {
@@ -577,9 +618,13 @@ gymrs_status gymrs_critic_size(gymrs_env_kind kind, uint32_t hidden, uint64_t* n
 gymrs_status gymrs_set_critic(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
 {
     if (!e) return fail(GYMRS_EINVAL, "gymrs_set_critic: NULL engine");
-    if (!d) return remove_weights(e, kCriticKind);
+    if (!d) {
+        if (gymrs_status st = remove_weights(e, kCriticKind)) return st;
+        return discard_opt_state(e, GYMRS_OPT_HEAD_CRITIC);
+    }
     if (gymrs_status st = check_weights(e, kCriticKind, d, weights_host, "gymrs_set_critic")) return st;
     HIP_TRY(hipSetDevice(e->device));
+    if (gymrs_status st = keep_or_discard_opt_state(e, GYMRS_OPT_HEAD_CRITIC, d)) return st; // the moments belong to a set of their shape
     return install_weights(e, kCriticKind, d, weights_host);
 }
 
@@ -820,6 +865,145 @@ gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d)
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_q_gradient(e->kind, a, e->policy.args, e->q_target.args, e->stream));
     return GYMRS_OK;
+}
+
+// ---- the optimizer: the checks, the host-side set and the launch (include/gymrs_amd.h, "Optimizer") -------------------------------
+static bool finite_f(float x) { return x >= -std::numeric_limits<float>::max() && x <= std::numeric_limits<float>::max(); } // (false for a NaN)
+
+// What gymrs_apply_gradient and gymrs_optimizer_set refuse in the values of a descriptor.
+static gymrs_status check_optimizer_values(const gymrs_optimizer_desc* d, const std::string& who)
+{
+    if (d->kind != GYMRS_OPT_SGD && d->kind != GYMRS_OPT_ADAM) return fail(GYMRS_EINVAL, who + ": unknown kind (GYMRS_OPT_SGD or GYMRS_OPT_ADAM)");
+    if (d->flags & ~(GYMRS_OPT_ASCEND | GYMRS_OPT_ZERO_GRAD))
+        return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_OPT_ASCEND and GYMRS_OPT_ZERO_GRAD are the only ones)");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (!finite_f(d->lr)) return fail(GYMRS_EINVAL, who + ": lr must be finite");
+    if (!finite_f(d->grad_scale)) return fail(GYMRS_EINVAL, who + ": grad_scale must be finite");
+    if (!finite_non_negative(d->eps)) return fail(GYMRS_EINVAL, who + ": eps must be finite and >= 0");
+    if (!(d->beta1 >= 0.0f && d->beta1 < 1.0f)) return fail(GYMRS_EINVAL, who + ": beta1 must be in [0, 1)");
+    if (!(d->beta2 >= 0.0f && d->beta2 < 1.0f)) return fail(GYMRS_EINVAL, who + ": beta2 must be in [0, 1)");
+    if (!(d->max_norm > 0.0f)) return fail(GYMRS_EINVAL, who + ": max_norm must be > 0 (+inf turns the clip off)");
+    if (!(d->tau >= 0.0f && d->tau <= 1.0f)) return fail(GYMRS_EINVAL, who + ": tau must be in [0, 1]");
+    return GYMRS_OK;
+}
+
+static gymrs_status check_optimizer_head(const gymrs_engine* e, uint32_t head, const std::string& who)
+{
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (head != GYMRS_OPT_HEAD_POLICY && head != GYMRS_OPT_HEAD_CRITIC)
+        return fail(GYMRS_EINVAL, who + ": unknown head (GYMRS_OPT_HEAD_POLICY or GYMRS_OPT_HEAD_CRITIC)");
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_optimizer_set(const gymrs_optimizer_desc* d, uint64_t n_params, const int64_t* q, float* w, float* m, float* v, float* pw,
+                                 float* target)
+{
+    const std::string who = "gymrs_optimizer_set";
+    if (!d || !q || !w) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (n_params == 0) return fail(GYMRS_EINVAL, who + ": n_params must be >= 1");
+    if (gymrs_status st = check_optimizer_values(d, who)) return st;
+    const bool adam = d->kind == GYMRS_OPT_ADAM, ascend = (d->flags & GYMRS_OPT_ASCEND) != 0;
+    if (adam && (!m || !v || !pw)) return fail(GYMRS_EINVAL, who + ": GYMRS_OPT_ADAM needs m, v and pw");
+    if (d->tau > 0.0f && !target) return fail(GYMRS_EINVAL, who + ": tau > 0 needs target");
+    std::vector<float> g(n_params);
+    for (uint64_t s = 0; s < n_params; ++s) g[s] = opt_gradient(q[s], d->grad_scale);
+    if (d->max_norm < std::numeric_limits<float>::infinity()) { // the 64 slots and the butterfly, as written
+        double slot[64], next[64];
+        for (uint64_t l = 0; l < 64; ++l) {
+            slot[l] = 0.0;
+            for (uint64_t s = l; s < n_params; s += 64) slot[l] = slot[l] + opt_square(g[s]);
+        }
+        for (int mask = 32; mask >= 1; mask >>= 1) {
+            for (int l = 0; l < 64; ++l) next[l] = slot[l] + slot[l ^ mask];
+            std::copy(next, next + 64, slot);
+        }
+        bool clipped;
+        const float cs = opt_clip_scale(slot[0], d->max_norm, clipped);
+        if (clipped)
+            for (uint64_t s = 0; s < n_params; ++s) g[s] = g[s] * cs;
+    }
+    float c1 = 1.0f, c2 = 1.0f;
+    if (adam) opt_adam_advance(d->beta1, d->beta2, pw[0], pw[1], c1, c2);
+    for (uint64_t s = 0; s < n_params; ++s) {
+        const float step = adam ? opt_adam_step(g[s], d->lr, d->beta1, d->beta2, d->eps, c1, c2, m[s], v[s]) : opt_sgd_step(g[s], d->lr);
+        w[s] = opt_apply(w[s], step, ascend);
+        if (d->tau > 0.0f) target[s] = opt_target(d->tau, w[s], target[s]);
+    }
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_apply_gradient(gymrs_engine* e, const gymrs_optimizer_desc* d)
+{
+    const std::string who = "gymrs_apply_gradient";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (gymrs_status st = check_optimizer_head(e, d->head, who)) return st;
+    if (gymrs_status st = check_optimizer_values(d, who)) return st;
+    const bool critic = d->head == GYMRS_OPT_HEAD_CRITIC;
+    const WeightSet& set = critic ? e->critic : e->policy;
+    if (gymrs_status st = check_weight_set(set, critic ? "critic" : "policy", who)) return st;
+    if (d->tau > 0.0f) {
+        if (critic) return fail(GYMRS_EINVAL, who + ": tau > 0 is for the policy head (the critic has no target set)");
+        if (!e->q_target.dev) return fail(GYMRS_EINVAL, who + ": tau > 0 but the engine has no target set (gymrs_q_target_sync)");
+    }
+    if (!d->grad) return fail(GYMRS_EINVAL, who + ": grad is NULL");
+    if (!d->excluded) return fail(GYMRS_EINVAL, who + ": excluded is NULL");
+    for (const void* p : {(const void*)d->grad, (const void*)d->excluded, (const void*)d->skipped})
+        if (reinterpret_cast<uintptr_t>(p) % 8 != 0) return fail(GYMRS_EINVAL, who + ": grad, excluded and skipped must be 8-byte aligned");
+    if (set.args.stride > kMaxOptimizerParams) return fail(GYMRS_EINVAL, who + ": the set has more parameters per network than the kernel holds");
+    const bool adam = d->kind == GYMRS_OPT_ADAM;
+    if (adam)
+        if (gymrs_status st = opt_state_of(e, d->head, set)) return st;
+    const OptimizerState& state = e->opt_state[d->head];
+    const OptimizerArgs a{set.dev,
+                          adam ? state.m() : nullptr,
+                          adam ? state.v() : nullptr,
+                          adam ? state.pw() : nullptr,
+                          d->tau > 0.0f ? e->q_target.dev : nullptr,
+                          reinterpret_cast<unsigned long long*>(d->grad),
+                          reinterpret_cast<unsigned long long*>(d->excluded),
+                          reinterpret_cast<unsigned long long*>(d->skipped),
+                          set.args.n_policies,
+                          set.args.stride,
+                          d->kind,
+                          d->flags,
+                          d->lr,
+                          d->grad_scale,
+                          d->beta1,
+                          d->beta2,
+                          d->eps,
+                          d->max_norm,
+                          d->tau};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_apply_gradient(a, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_optimizer_reset(gymrs_engine* e, uint32_t head)
+{
+    const std::string who = "gymrs_optimizer_reset";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (gymrs_status st = check_optimizer_head(e, head, who)) return st;
+    const OptimizerState& state = e->opt_state[head];
+    if (!state.dev) return GYMRS_OK; // fresh already
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_optimizer_fresh(state.m(), state.v(), state.pw(), state.shape.n_policies, state.shape.stride, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_optimizer_state(gymrs_engine* e, uint32_t head, float* m_out, float* v_out, float* pw_out)
+{
+    const std::string who = "gymrs_get_optimizer_state";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (gymrs_status st = check_optimizer_head(e, head, who)) return st;
+    const OptimizerState& state = e->opt_state[head];
+    if (!state.dev) return fail(GYMRS_EINVAL, who + ": the head has no optimizer state (gymrs_apply_gradient with GYMRS_OPT_ADAM)");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t bytes = (size_t)state.words() * sizeof(float);
+    if (m_out) HIP_TRY(hipMemcpyAsync(m_out, state.m(), bytes, hipMemcpyDeviceToHost, e->stream));
+    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, state.v(), bytes, hipMemcpyDeviceToHost, e->stream));
+    if (pw_out) HIP_TRY(hipMemcpyAsync(pw_out, state.pw(), (size_t)state.shape.n_policies * 2 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
 }
 
 // ---- per-policy fitness: the table behind gymrs_rollout_policy_fitness -----------------------------------------------------

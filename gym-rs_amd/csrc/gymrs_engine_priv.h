@@ -68,6 +68,17 @@ struct WeightSet {
     uint64_t capacity = 0;
 };
 
+// The Adam state of one head: ONE allocation `dev` = m [n_sets][S], v [n_sets][S], pw [n_sets][2] (NULL = no state yet); `shape` is
+// the args of the weight set it was made for.
+struct OptimizerState {
+    float* dev = nullptr;
+    PolicyArgs shape{};
+    uint64_t words() const { return (uint64_t)shape.n_policies * shape.stride; }
+    float* m() const { return dev; }
+    float* v() const { return dev + words(); }
+    float* pw() const { return dev + 2 * words(); }
+};
+
 struct gymrs_engine {
     gymrs_env_kind kind;
     uint64_t n = 0, gid0 = 0;
@@ -194,6 +205,10 @@ struct gymrs_engine {
     // args = the policy's with the target's weights.  A gymrs_set_policy of the same hidden, n_policies and lanes_per_policy keeps it,
     // any other (or the removal) discards it.  Not part of clone or snapshot.
     WeightSet q_target;
+    // The Adam state of gymrs_apply_gradient, per head ([GYMRS_OPT_HEAD_POLICY], [GYMRS_OPT_HEAD_CRITIC]): allocated fresh at the first
+    // GYMRS_OPT_ADAM call on the head, under the target's lifetime rule (kept by a setter of the same shape, discarded otherwise).
+    // Not part of clone or snapshot.
+    OptimizerState opt_state[2];
     // The per-policy counters of gymrs_rollout_policy_fitness: policy.args.n_policies records, allocated (zeroed) at the first fitness
     // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
     // stays the same).  Not part of clone or snapshot.

@@ -435,4 +435,24 @@ struct QArgs {
 };
 // online and target differ in `weights` alone: both sets are keyed by the policy's key
 hipError_t launch_q_gradient(gymrs_env_kind kind, const QArgs& a, const PolicyArgs& online, const PolicyArgs& target, hipStream_t stream);
+// ---- the optimizer (gymrs_apply_gradient; gymrs_optimizer.hip) -----------------------------------------------------------------
+// A gymrs_optimizer_desc as its kernel gets it by value, with the buffers of the head it names.  Every table is [n_sets][S] (pw
+// [n_sets][2], excluded [n_sets]); grad, excluded and skipped are 8-byte aligned.  S <= kMaxOptimizerParams.
+struct OptimizerArgs {
+    float* weights;               // [n_sets][S]: the head's set, updated in place
+    float* m;                     // [n_sets][S] } the Adam state of the head (GYMRS_OPT_ADAM), else NULL
+    float* v;                     // [n_sets][S] }
+    float* pw;                    // [n_sets][2] }
+    float* target;                // [n_sets][S]: the Q target (tau > 0), else NULL
+    unsigned long long* grad;     // [n_sets][S] int64 bit patterns: read, zeroed with GYMRS_OPT_ZERO_GRAD
+    unsigned long long* excluded; // [n_sets]: read, zeroed with GYMRS_OPT_ZERO_GRAD
+    unsigned long long* skipped;  // one counter or NULL, ADDED to
+    uint32_t n_sets, S;
+    uint32_t kind, flags; // GYMRS_OPT_SGD / _ADAM; GYMRS_OPT_ASCEND | GYMRS_OPT_ZERO_GRAD
+    float lr, grad_scale, beta1, beta2, eps, max_norm, tau;
+};
+constexpr uint32_t kMaxOptimizerParams = 512; // 8 parameters in each of 64 lanes (the largest network has 450)
+hipError_t launch_apply_gradient(const OptimizerArgs& a, hipStream_t stream);
+// m = v = +0.0f, pw = 1.0f: a fresh Adam state, in stream order
+hipError_t launch_optimizer_fresh(float* m, float* v, float* pw, uint32_t n_sets, uint32_t S, hipStream_t stream);
 } // namespace gymrs

@@ -143,6 +143,26 @@ class QDesc(C.Structure):
 Q_DOUBLE = 1  # GYMRS_Q_DOUBLE
 
 
+class OptimizerDesc(C.Structure):
+    """``gymrs_optimizer_desc`` (include/gymrs_amd.h), 72 bytes: head, kind, flags, seven floats, two tables read (and zeroed with
+    ``OPT_ZERO_GRAD``), one optional counter added to."""
+    _fields_ = [("head", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32), ("lr", C.c_float), ("grad_scale", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float), ("tau", C.c_float),
+                ("grad", C.c_void_p), ("excluded", C.c_void_p), ("skipped", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+OPT_HEAD_POLICY, OPT_HEAD_CRITIC = 0, 1  # GYMRS_OPT_HEAD_*
+OPT_SGD, OPT_ADAM = 0, 1                 # GYMRS_OPT_SGD / _ADAM
+OPT_ASCEND, OPT_ZERO_GRAD = 1, 2         # GYMRS_OPT_ASCEND / _ZERO_GRAD
+
+
+def _optimizer_desc(head, kind, lr, grad_scale, beta1, beta2, eps, max_norm, tau, ascend, zero_grad, flags, grad=0, excluded=0,
+                    skipped=None) -> OptimizerDesc:
+    f = ((OPT_ASCEND if ascend else 0) | (OPT_ZERO_GRAD if zero_grad else 0)) if flags is None else int(flags)
+    return OptimizerDesc(int(head), int(kind), f, float(lr), float(grad_scale), float(beta1), float(beta2), float(eps), float(max_norm),
+                         float(tau), C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(skipped or None), 0)
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -378,6 +398,24 @@ def q_lane(kind: int, hidden: int, weights, target_weights, x, x_next, actions, 
                                  xn.ctypes.data_as(fp), a.ctypes.data_as(bp), r.ctypes.data_as(fp), dn.ctypes.data_as(bp), q.ctypes.data_as(C.POINTER(C.c_int64)),
                                  C.byref(excluded), td.ctypes.data_as(fp), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
     return q, excluded.value, td, counts
+
+
+def optimizer_set(q, w, *, kind: int = OPT_SGD, lr: float, grad_scale: float, m=None, v=None, pw=None, target=None, beta1: float = 0.9,
+                  beta2: float = 0.999, eps: float = 1e-8, max_norm: float = float("inf"), tau: float = 0.0, ascend: bool = False,
+                  flags: Optional[int] = None):
+    """``gymrs_optimizer_set`` (host only, no GPU): one set's update by the definition of include/gymrs_amd.h, "Optimizer", as code.
+    ``q`` int64 [S] is one row of a gradient table, ``w`` f32 [S] the weights; ``OPT_ADAM`` needs ``m``, ``v`` [S] and ``pw`` [2],
+    ``tau`` > 0 needs ``target`` [S].  Returns fresh arrays (w, m, v, pw, target); what was not given stays ``None``."""
+    lib = load_library()
+    qq = np.ascontiguousarray(q, dtype=np.int64).reshape(-1)
+    out = [None if a is None else np.array(a, dtype=np.float32).reshape(-1) for a in (w, m, v, pw, target)]
+    if out[0] is None or out[0].size != qq.size or any(a is not None and a.size != n for a, n in zip(out[1:], (qq.size, qq.size, 2, qq.size))):
+        raise ValueError("optimizer_set needs S weights (and moments, target) for S table entries, and pw of 2 floats")
+    desc = _optimizer_desc(OPT_HEAD_POLICY, kind, lr, grad_scale, beta1, beta2, eps, max_norm, tau, ascend, False, flags)
+    fp = C.POINTER(C.c_float)
+    _check(lib, lib.gymrs_optimizer_set(C.byref(desc), qq.size, qq.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        *(None if a is None else a.ctypes.data_as(fp) for a in out)))
+    return tuple(out)
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -947,6 +985,37 @@ class BatchedEngine:
         desc = QDesc(int(n_steps), f, float(gamma), float(kappa), traj, C.c_void_p(start_obs or None), C.c_void_p(final_obs or None),
                      C.c_void_p(td or None), C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_q_gradient(self._h, C.byref(desc)))
+
+    # -- the optimizer: SGD or Adam per set, from a gradient table into the engine's own weights, in one launch --------------
+    def apply_gradient(self, *, grad: int, excluded: int, lr: float, grad_scale: float, critic: bool = False, adam: bool = False,
+                       beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, max_norm: float = float("inf"), tau: float = 0.0,
+                       ascend: bool = False, zero_grad: bool = False, skipped: Optional[int] = None, head: Optional[int] = None,
+                       kind: Optional[int] = None, flags: Optional[int] = None) -> None:
+        """``gymrs_apply_gradient``: w -= step (``ascend``: +=) for every set of the policy head (``critic``: the critic head), step =
+        lr * g (``adam``: Adam's, with engine-owned moments) and g = ``grad`` * ``grad_scale`` after an optional clip of each set's
+        norm to ``max_norm``.  ``grad`` (device int64 [n_sets][S]) and ``excluded`` (device uint64 [n_sets]) are the tables the
+        gradient calls added to; a set with ``excluded`` != 0 is skipped and counted in ``skipped`` (one device uint64, added to).
+        ``zero_grad`` zeroes both tables after reading them, so the next gradient launch needs no memset.  ``tau`` > 0 also moves the
+        Q target towards the new weights (policy head, after ``q_target_sync``).  One launch on the engine's stream, no
+        synchronisation; defined to the bit (include/gymrs_amd.h, "Optimizer")."""
+        desc = _optimizer_desc((OPT_HEAD_CRITIC if critic else OPT_HEAD_POLICY) if head is None else head,
+                               (OPT_ADAM if adam else OPT_SGD) if kind is None else kind, lr, grad_scale, beta1, beta2, eps, max_norm, tau,
+                               ascend, zero_grad, flags, grad, excluded, skipped)
+        _check(self._lib, self._lib.gymrs_apply_gradient(self._h, C.byref(desc)))
+
+    def optimizer_reset(self, critic: bool = False) -> None:
+        """``gymrs_optimizer_reset``: the head's Adam state back to fresh (m = v = 0, pw = 1) in stream order."""
+        _check(self._lib, self._lib.gymrs_optimizer_reset(self._h, OPT_HEAD_CRITIC if critic else OPT_HEAD_POLICY))
+
+    def optimizer_state(self, critic: bool = False):
+        """(m [n_sets][S], v [n_sets][S], pw [n_sets][2]) of the head's Adam state, f32 (synchronising).  Raises before the first Adam
+        call on the head."""
+        w, _, _ = self.critic() if critic else self.get_policy()
+        m, v, pw = np.empty_like(w), np.empty_like(w), np.empty((w.shape[0], 2), np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(self._lib, self._lib.gymrs_get_optimizer_state(self._h, OPT_HEAD_CRITIC if critic else OPT_HEAD_POLICY, m.ctypes.data_as(fp),
+                                                              v.ctypes.data_as(fp), pw.ctypes.data_as(fp)))
+        return m, v, pw
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

@@ -926,6 +926,84 @@ gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d);
 gymrs_status gymrs_q_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float gamma, float kappa, const float* weights,
                           const float* target_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
                           const float* reward, const uint8_t* done, int64_t* q, uint64_t* excluded, float* td, uint64_t* counts);
+/* Optimizer: the weight update itself, SGD or Adam, per set, from the fixed-point table of "gradients" / the clipped surrogate /
+ * "Q-learning" straight into the engine's weight buffers.  gymrs_apply_gradient(e, d) updates every set of ONE head in ONE launch.
+ * d->head is GYMRS_OPT_HEAD_POLICY (the policy set; S = gymrs_policy_size) or GYMRS_OPT_HEAD_CRITIC (the critic set; S =
+ * gymrs_critic_size); grad is [n_sets][S], excluded [n_sets], n_sets the head's n_policies: the layout the gradient calls write.
+ * All arithmetic below is f32 unless it says f64.  Every operation is a single IEEE operation, divide and square root correctly
+ * rounded, denormals kept; fmaf = the fused multiply-add with ONE rounding; nothing is contracted or reordered.
+ * For set m and parameter s:
+ *     q     = grad[m][s]                                      (int64)
+ *     g[s]  = (float)((double)q * (double)grad_scale)         (int64 -> f64 to nearest even, one f64 multiply, one f64 -> f32
+ *                                                              rounding; grad_scale is the caller's float, e.g. 2^-24 / (K * n))
+ *     set m is SKIPPED when excluded[m] != 0: its weights, its state and its target keep their bytes; *skipped += 1
+ *     norm clip (only when max_norm < +inf):
+ *         slot[l] = +0.0 (f64);  for s = l, l+64, l+128, .. < S ascending: slot[l] = slot[l] + (double)g[s]*(double)g[s]    l = 0..63
+ *         for mask = 32, 16, 8, 4, 2, 1:  slot[l] = slot[l] + slot[l ^ mask]             (all l at once; f64)
+ *         norm = (float)sqrt(slot[0])                                                     (f64 sqrt, then one rounding to f32)
+ *         if (norm > max_norm) { cs = max_norm / norm;  g[s] = g[s] * cs  for every s }   (the compare is false on NaN)
+ *     GYMRS_OPT_SGD:   step = lr * g[s]
+ *     GYMRS_OPT_ADAM:  per set two running products pw[m] = {p1, p2}, both 1.0f in a fresh state:
+ *         p1 = p1 * beta1;  p2 = p2 * beta2;  c1 = 1.0f - p1;  c2 = 1.0f - p2            (once per set per call)
+ *         mo = fmaf(beta1, mo_old, (1.0f - beta1) * g[s])
+ *         vo = fmaf(beta2, vo_old, (1.0f - beta2) * (g[s] * g[s]))
+ *         step = lr * ((mo / c1) / (sqrtf(vo / c2) + eps))
+ *     w' = (flags & GYMRS_OPT_ASCEND) ? w + step : w - step
+ *     tau > 0 (policy head only, needs the target set of "Q-learning"):  target' = fmaf(tau, w' - target, target)
+ *     GYMRS_OPT_ZERO_GRAD: after they were read, grad[m][*] = 0 and excluded[m] = 0, for skipped sets too
+ * The butterfly over 64 slots lets an implementation pack several small sets into one wave: slots at or beyond S hold +0.0, and
+ * adding +0.0 to a sum of squares is exact.
+ * What follows from the rule: non-finite weights stay legal; a grad_scale that overflows g gives the non-finite weights the
+ * arithmetic gives; a skipped set does not advance its pw.
+ * Stream order.  The call runs in the engine's stream order, right behind a gradient launch and with no synchronisation in
+ * between; launches enqueued after it see the new weights (and the zeroed table).  It uses the engine only for the stream, the
+ * weight set of the head, its Adam state and the target: it reads and writes no lane array.
+ * The Adam state is engine-owned, per head: m and v as f32 [n_sets][S], pw as f32 [n_sets][2].
+ *   - It is allocated at the first GYMRS_OPT_ADAM call on that head, fresh: m = v = +0.0f, pw = 1.0f.  GYMRS_OPT_SGD allocates
+ *     nothing and touches no state.
+ *   - It follows the lifetime rule of the target set: a gymrs_set_policy / gymrs_set_critic with the same hidden, n_policies and
+ *     lanes_per_policy keeps it; any other set, or the removal, discards it.  It is NOT part of gymrs_engine_clone or of a snapshot.
+ *   - gymrs_optimizer_reset(e, head) puts it back to fresh in stream order (a head without a state is fresh already: a no-op).
+ *   - gymrs_get_optimizer_state(e, head, m_out, v_out, pw_out) copies it to the host and synchronises; any of the three may be
+ *     NULL.  GYMRS_EINVAL when the head has no state.
+ * skipped may be NULL; otherwise it is ONE device uint64, ADDED to.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine / desc / grad / excluded; Pendulum; an unknown head, kind or flag bit, reserved
+ *     != 0; no set for the head (naming gymrs_set_policy / gymrs_set_critic); lr, grad_scale or eps NaN or infinite; eps < 0; beta1
+ *     or beta2 outside [0, 1) (checked for both kinds); max_norm NaN or <= 0 (+inf is "off"); tau outside [0, 1]; tau > 0 on the
+ *     critic head, or without a target set (naming gymrs_q_target_sync); grad / excluded / skipped not 8-byte aligned.
+ *   - gymrs_optimizer_set: host only, no GPU: the definition as code for ONE set that is not skipped, as gymrs_q_lane is for
+ *     "Q-learning".  From q[0..S) it updates w[0..S) in place, with GYMRS_OPT_ADAM also m[0..S), v[0..S) and pw[0..2), and with tau
+ *     > 0 target[0..S).  It reads kind, flags (GYMRS_OPT_ZERO_GRAD means nothing here), lr, grad_scale, beta1, beta2, eps, max_norm
+ *     and tau of d, and ignores head and the pointers.  GYMRS_EINVAL: NULL d / q / w, S == 0, the value checks above, Adam without
+ *     m / v / pw, tau > 0 without target.
+ * Out of scope: weight decay, learning-rate schedules (lr is per call: schedule on the host), momentum SGD.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+#define GYMRS_OPT_HEAD_POLICY 0u
+#define GYMRS_OPT_HEAD_CRITIC 1u
+#define GYMRS_OPT_SGD 0u
+#define GYMRS_OPT_ADAM 1u
+#define GYMRS_OPT_ASCEND 1u
+#define GYMRS_OPT_ZERO_GRAD 2u
+typedef struct {
+    uint32_t head;              /* GYMRS_OPT_HEAD_POLICY or GYMRS_OPT_HEAD_CRITIC */
+    uint32_t kind;              /* GYMRS_OPT_SGD or GYMRS_OPT_ADAM */
+    uint32_t flags;             /* GYMRS_OPT_ASCEND | GYMRS_OPT_ZERO_GRAD, nothing else */
+    float lr;                   /* finite */
+    float grad_scale;           /* finite */
+    float beta1, beta2;         /* in [0, 1) */
+    float eps;                  /* finite, >= 0 */
+    float max_norm;             /* > 0; +inf = no clip */
+    float tau;                  /* in [0, 1]; > 0: the policy head with a target set */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned; READ, zeroed with GYMRS_OPT_ZERO_GRAD */
+    uint64_t* excluded;         /* device uint64 [n_sets], 8-byte aligned; READ, zeroed with GYMRS_OPT_ZERO_GRAD */
+    uint64_t* skipped;          /* ONE device uint64 or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_optimizer_desc;         /* 72 bytes */
+gymrs_status gymrs_apply_gradient(gymrs_engine* e, const gymrs_optimizer_desc* d);
+gymrs_status gymrs_optimizer_reset(gymrs_engine* e, uint32_t head);
+gymrs_status gymrs_get_optimizer_state(gymrs_engine* e, uint32_t head, float* m_out, float* v_out, float* pw_out);
+gymrs_status gymrs_optimizer_set(const gymrs_optimizer_desc* d, uint64_t n_params, const int64_t* q, float* w, float* m, float* v, float* pw,
+                                 float* target);
 /* Episodic policy evaluation: E whole episodes per lane in ONE launch, with exact per-policy episodic statistics.
  * gymrs_evaluate_policy(e, d) plays, for every lane i of the engine (global id g = global_env_offset + i, policy p = (g /
  * lanes_per_policy) % n_policies) and every episode index ep in [0, E = d->episodes_per_lane), the episode (g, ep):

@@ -115,6 +115,15 @@ inline std::uint64_t q_lane(gymrs_env_kind kind, std::uint32_t hidden, std::uint
     return excluded;
 }
 
+// One set's update by gymrs_apply_gradient's rule (gymrs_optimizer_set; host only, no GPU): w[0 .. S) is updated in place from
+// q[0 .. S); m, v, pw[2] with GYMRS_OPT_ADAM and target with d.tau > 0 too (null otherwise).  The definition of include/gymrs_amd.h,
+// "Optimizer", as code.
+inline void optimizer_set(const gymrs_optimizer_desc& d, std::uint64_t n_params, const std::int64_t* q, float* w, float* m = nullptr,
+                          float* v = nullptr, float* pw = nullptr, float* target = nullptr)
+{
+    check(gymrs_optimizer_set(&d, n_params, q, w, m, v, pw, target));
+}
+
 // One lane's contribution to gymrs_ppo_gradient (gymrs_ppo_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
 // (lane, parameter) pairs returned; counts (may be null) gets the lane-steps seen and cut, prob (may be null) p[a] of every step.
 // The definition of include/gymrs_amd.h, "clipped surrogate", as code.
@@ -431,6 +440,12 @@ public:
         return p;
     }
     void q_gradient(const gymrs_q_desc& d) { check(gymrs_q_gradient(e_, &d)); }
+    // The optimizer (include/gymrs_amd.h, "Optimizer"): apply_gradient updates every set of d.head in ONE launch on the engine's stream
+    // (SGD or Adam, from the fixed-point table d.grad into the engine's own weights; no synchronisation); the Adam state is the
+    // engine's: optimizer_reset makes it fresh in stream order, optimizer_state copies it out (synchronising; any pointer may be null)
+    void apply_gradient(const gymrs_optimizer_desc& d) { check(gymrs_apply_gradient(e_, &d)); }
+    void optimizer_reset(std::uint32_t head) { check(gymrs_optimizer_reset(e_, head)); }
+    void optimizer_state(std::uint32_t head, float* m_out, float* v_out, float* pw_out) { check(gymrs_get_optimizer_state(e_, head, m_out, v_out, pw_out)); }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
