@@ -266,6 +266,40 @@ pub struct GymrsOptimizerDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_ES_MAX_POLICIES`: the largest population of `gymrs_es_init`.
+pub const GYMRS_ES_MAX_POLICIES: u32 = 1 << 20;
+
+/// `gymrs_es_desc`: the population `gymrs_es_init` installs (include/gymrs_amd.h "Evolution strategies"), 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsEsDesc {
+    pub hidden: u32,
+    pub n_policies: u32,
+    pub lanes_per_policy: u64,
+    pub seed: u64,
+    pub sigma: f32,
+    pub reserved: u32,
+}
+
+/// `gymrs_es_step_desc`: one generation step, 56 bytes: the optimizer's kind, flags (`GYMRS_OPT_ASCEND` only) and values, the sigma of
+/// the next population (0 keeps it), the caller's utilities (or null: from the evaluation table) and one optional device counter.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsEsStepDesc {
+    pub kind: u32,
+    pub flags: u32,
+    pub lr: f32,
+    pub grad_scale: f32,
+    pub beta1: f32,
+    pub beta2: f32,
+    pub eps: f32,
+    pub max_norm: f32,
+    pub sigma_next: f32,
+    pub reserved: u32,
+    pub utilities: *const f32,
+    pub skipped: *mut u64,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -417,6 +451,15 @@ extern "C" {
     #[allow(clippy::too_many_arguments)]
     pub fn gymrs_optimizer_set(d: *const GymrsOptimizerDesc, n_params: u64, q: *const i64, w: *mut f32, m: *mut f32, v: *mut f32, pw: *mut f32,
                                target: *mut f32) -> c_int;
+    /// Evolution strategies: the state, the step, the views and the host-only definitions
+    pub fn gymrs_es_init(e: *mut GymrsEngine, d: *const GymrsEsDesc, centre_host: *const f32) -> c_int;
+    pub fn gymrs_es_step(e: *mut GymrsEngine, d: *const GymrsEsStepDesc) -> c_int;
+    pub fn gymrs_get_es(e: *mut GymrsEngine, d_out: *mut GymrsEsDesc, generation: *mut u64, centre_out: *mut f32, capacity_floats: u64) -> c_int;
+    pub fn gymrs_es_centre_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;
+    pub fn gymrs_es_utilities_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_policies: *mut u32) -> c_int;
+    pub fn gymrs_get_es_optimizer_state(e: *mut GymrsEngine, m_out: *mut f32, v_out: *mut f32, pw_out: *mut f32) -> c_int;
+    pub fn gymrs_es_noise(seed: u64, generation: u64, pair: u64, s: u32, eps_out: *mut f32) -> c_int;
+    pub fn gymrs_es_utilities(records: *const GymrsPolicyEval, n_policies: u32, u_out: *mut f32) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -53,6 +53,7 @@ from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
 from .engine import QDesc, Q_DOUBLE, q_lane
 from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
+from .engine import EsDesc, EsStepDesc, ES_MAX_POLICIES, es_noise, es_utilities
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -68,4 +69,5 @@ __all__ = [
     "PpoDesc", "ppo_lane",
     "QDesc", "Q_DOUBLE", "q_lane",
     "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",
+    "EsDesc", "EsStepDesc", "ES_MAX_POLICIES", "es_noise", "es_utilities",
 ]

@@ -124,6 +124,15 @@ SIGNATURES = {
     "gymrs_evaluate_policy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_get_policy_eval": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "gymrs_policy_eval_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    # evolution strategies (gymrs_es_desc 32 B, gymrs_es_step_desc 56 B), its views and the host-only definitions
+    "gymrs_es_init": (C.c_int, [C.c_void_p, C.c_void_p, f32p]),
+    "gymrs_es_step": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_get_es": (C.c_int, [C.c_void_p, C.c_void_p, u64p, f32p, C.c_uint64]),
+    "gymrs_es_centre_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),
+    "gymrs_es_utilities_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    "gymrs_get_es_optimizer_state": (C.c_int, [C.c_void_p, f32p, f32p, f32p]),
+    "gymrs_es_noise": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, f32p]),
+    "gymrs_es_utilities": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process

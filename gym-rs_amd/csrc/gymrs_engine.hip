@@ -517,6 +517,9 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->critic.dev);
     (void)hipFree(e->q_target.dev);
     for (OptimizerState& st : e->opt_state) (void)hipFree(st.dev);
+    (void)hipFree(e->es.dev);
+    (void)hipFree(e->es.u);
+    (void)hipFree(e->es.fitness);
     (void)hipFree(e->fitness_dev);
     (void)hipFree(e->eval_dev);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));

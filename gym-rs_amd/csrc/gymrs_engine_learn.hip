@@ -10,6 +10,7 @@
 #include "gymrs_gradient.h"
 #include "gymrs_qlearn.h"
 #include "gymrs_optimizer.h"
+#include "gymrs_es.h"
 
 #include <algorithm>
 
@@ -72,8 +73,11 @@ gymrs_status install_weights(gymrs_engine* e, const WeightKind& k, const gymrs_p
         set.capacity = total;
     }
     // stream-ordered: launches enqueued before this call read the old set; the host weights are consumed before the call returns
-    HIP_TRY(hipMemcpyAsync(set.dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    // (weights_host == NULL: the caller writes the set on the device, gymrs_es_init)
+    if (weights_host) {
+        HIP_TRY(hipMemcpyAsync(set.dev, weights_host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     set.args = PolicyArgs{set.dev, d->lanes_per_policy, d->n_policies, d->hidden, (uint32_t)stride, 0};
     return GYMRS_OK;
 }
@@ -161,6 +165,91 @@ gymrs_status opt_state_of(gymrs_engine* e, uint32_t head, const WeightSet& set)
     return GYMRS_OK;
 }
 
+// ---- the evolution-strategies state of gymrs_es_init: under the target's lifetime rule ---------------------------------------------------
+// The state goes with its buffers (launches already enqueued still use them: wait for them).
+gymrs_status discard_es(gymrs_engine* e)
+{
+    EsState& es = e->es;
+    if (!es.dev) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(es.dev));
+    HIP_TRY(hipFree(es.u));
+    HIP_TRY(hipFree(es.fitness));
+    es = EsState{};
+    return GYMRS_OK;
+}
+
+// A new policy set of the state's shape keeps the state; any other discards it.
+bool es_fits(const gymrs_engine* e, const gymrs_policy_desc* d)
+{
+    const PolicyArgs& t = e->es.shape;
+    return e->es.dev && t.hidden == d->hidden && t.n_policies == d->n_policies && t.lanes_per_policy == d->lanes_per_policy;
+}
+
+// The state for the policy set that was just installed: the buffers of a kept state are reused (the caller discarded any other).
+gymrs_status es_state_for(gymrs_engine* e)
+{
+    EsState& es = e->es;
+    if (es.dev) return GYMRS_OK;
+    const size_t P = e->policy.args.n_policies;
+    hipError_t err = hipMalloc(&es.dev, sizeof(EsDeviceState));
+    if (!err) err = hipMalloc(&es.u, P * sizeof(float));
+    if (!err) err = hipMalloc(&es.fitness, P * sizeof(double));
+    if (err) {
+        (void)hipFree(es.dev);
+        (void)hipFree(es.u);
+        (void)hipFree(es.fitness);
+        es = EsState{};
+        HIP_TRY(err);
+    }
+    return GYMRS_OK;
+}
+
+// What the ES kernels get by value, without the step's own values.
+EsArgs es_args(const gymrs_engine* e)
+{
+    const EsState& es = e->es;
+    EsArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.st = es.dev;
+    a.weights = e->policy.dev;
+    a.u = es.u;
+    a.fitness = es.fitness;
+    a.seed = es.seed;
+    a.gen = es.gen;
+    a.P = es.shape.n_policies;
+    a.S = es.shape.stride;
+    a.sigma = a.sigma_new = es.sigma;
+    return a;
+}
+
+bool es_sigma_ok(float sigma) { return sigma > 0.0f && sigma <= std::numeric_limits<float>::max(); } // (false for a NaN)
+
+// slot[0] of the butterfly mask = 512 .. 1 over 1024 slots, as written in the header
+double es_fold(double* slot)
+{
+    double next[kEsChunk];
+    for (uint32_t mask = kEsChunk / 2; mask >= 1; mask >>= 1) {
+        for (uint32_t l = 0; l < kEsChunk; ++l) next[l] = slot[l] + slot[l ^ mask];
+        std::copy(next, next + kEsChunk, slot);
+    }
+    return slot[0];
+}
+
+// The two-level sum of value(p) over p < P: chunks of 1024, then the chunk sums.
+template <class Value>
+double es_sum(uint32_t P, Value value)
+{
+    double slot[kEsChunk], top[kEsChunk];
+    std::fill(top, top + kEsChunk, 0.0);
+    for (uint32_t c = 0; c * kEsChunk < P; ++c) {
+        for (uint32_t l = 0; l < kEsChunk; ++l) slot[l] = c * kEsChunk + l < P ? value(c * kEsChunk + l) : 0.0;
+        top[c] = es_fold(slot);
+    }
+    return es_fold(top);
+}
+
 // ---- a per-policy table: policy.args.n_policies records on the device that appear at first use and go with the policy set -------------
 // (the fitness counters, the episodic records).  `slot` is the engine's pointer to it, `init` fills a new table in stream order.
 template <class Record>
@@ -228,6 +317,26 @@ hipError_t zero_fitness(gymrs_policy_fitness* table, uint32_t n_policies, hipStr
 }
 const PolicyTable<gymrs_policy_fitness> kFitness{&gymrs_engine::fitness_dev, zero_fitness};
 const PolicyTable<gymrs_policy_eval> kEval{&gymrs_engine::eval_dev, launch_policy_eval_identity};
+
+// A checked policy set takes the place of the old one, and everything that belongs to a set follows its lifetime rule: what
+// gymrs_set_policy and gymrs_es_init (weights_host == NULL: it writes the set on the device) share.  The ES state is the caller's.
+gymrs_status replace_policy_set(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    if (!q_target_fits(e, d))
+        if (gymrs_status st = discard_q_target(e)) return st; // a target of another shape belongs to the set it was copied from
+    if (gymrs_status st = keep_or_discard_opt_state(e, GYMRS_OPT_HEAD_POLICY, d)) return st; // so do the moments
+    // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
+    // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
+    if (e->fitness_dev && d->n_policies == e->policy.args.n_policies) {
+        HIP_TRY(zero_fitness(e->fitness_dev, d->n_policies, e->stream));
+    } else if (gymrs_status st = kFitness.discard(e)) {
+        return st;
+    }
+    if (gymrs_status st = kEval.discard(e)) return st; // the episodic records belong to the set they were played with
+    e->es.evaluated = false;
+    return install_weights(e, kPolicyKind, d, weights_host);
+}
 
 // ---- a call over a transitions record: the checks gymrs_advantages, gymrs_policy_gradient and gymrs_ppo_gradient share, worded once ----
 // Each entry point lists its checks in its own order (the tests and callers depend on which refusal wins).
@@ -458,23 +567,14 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
         if (gymrs_status st = remove_weights(e, kPolicyKind)) return st;
         if (gymrs_status st = discard_q_target(e)) return st;
         if (gymrs_status st = discard_opt_state(e, GYMRS_OPT_HEAD_POLICY)) return st;
+        if (gymrs_status st = discard_es(e)) return st;
         if (gymrs_status st = kEval.discard(e)) return st;
         return kFitness.discard(e);
     }
     if (gymrs_status st = check_weights(e, kPolicyKind, d, weights_host, "gymrs_set_policy")) return st;
-    HIP_TRY(hipSetDevice(e->device));
-    if (!q_target_fits(e, d))
-        if (gymrs_status st = discard_q_target(e)) return st; // a target of another shape belongs to the set it was copied from
-    if (gymrs_status st = keep_or_discard_opt_state(e, GYMRS_OPT_HEAD_POLICY, d)) return st; // so do the moments
-    // a new set starts from zero counters: a table of another size goes (allocated again at its first use), one of the same
-    // size -- a search's next generation -- is kept and zeroed in stream order, after the launches that still add to it
-    if (e->fitness_dev && d->n_policies == e->policy.args.n_policies) {
-        HIP_TRY(zero_fitness(e->fitness_dev, d->n_policies, e->stream));
-    } else if (gymrs_status st = kFitness.discard(e)) {
-        return st;
-    }
-    if (gymrs_status st = kEval.discard(e)) return st; // the episodic records belong to the set they were played with
-    return install_weights(e, kPolicyKind, d, weights_host);
+    if (!es_fits(e, d))
+        if (gymrs_status st = discard_es(e)) return st; // an ES state of another shape belongs to the population it wrote
+    return replace_policy_set(e, d, weights_host);
 }
 
 gymrs_status gymrs_get_policy(gymrs_engine* e, gymrs_policy_desc* d_out, float* weights_out, uint64_t capacity_floats)
@@ -1006,6 +1106,151 @@ gymrs_status gymrs_get_optimizer_state(gymrs_engine* e, uint32_t head, float* m_
     return stream_sync_checked(e);
 }
 
+// ---- evolution strategies: the state, the step and the host-only definitions (include/gymrs_amd.h, "Evolution strategies") -----------
+gymrs_status gymrs_es_init(gymrs_engine* e, const gymrs_es_desc* d, const float* centre_host)
+{
+    const std::string who = "gymrs_es_init";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (gymrs_status st = check_network(e->kind, d->hidden, who)) return st;
+    if (d->n_policies < 2 || d->n_policies % 2 != 0 || d->n_policies > kEsMaxPolicies)
+        return fail(GYMRS_EINVAL, who + ": n_policies must be even, >= 2 and <= GYMRS_ES_MAX_POLICIES (antithetic pairs)");
+    if (d->lanes_per_policy == 0) return fail(GYMRS_EINVAL, who + ": lanes_per_policy must be >= 1");
+    if (!es_sigma_ok(d->sigma)) return fail(GYMRS_EINVAL, who + ": sigma must be finite and > 0");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (!centre_host) return fail(GYMRS_EINVAL, who + ": centre_host is NULL");
+    const gymrs_policy_desc pd{d->hidden, d->n_policies, d->lanes_per_policy};
+    if (policy_floats(e->kind, d->hidden) > kEsSlots) return fail(GYMRS_EINVAL, who + ": the network has more parameters than the kernels hold");
+    if (!es_fits(e, &pd))
+        if (gymrs_status st = discard_es(e)) return st;
+    if (gymrs_status st = replace_policy_set(e, &pd, nullptr)) return st; // the weights: written below, on the device
+    if (gymrs_status st = es_state_for(e)) return st;
+    EsState& es = e->es;
+    es.shape = e->policy.args;
+    es.seed = d->seed;
+    es.gen = 0;
+    es.sigma = d->sigma;
+    es.evaluated = false;
+    // the centre is consumed before the call returns: the one wait of this call
+    HIP_TRY(hipMemcpyAsync(&es.dev->theta[0][0], centre_host, (size_t)es.shape.stride * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(launch_es_init(es_args(e), e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_es_step(gymrs_engine* e, const gymrs_es_step_desc* d)
+{
+    const std::string who = "gymrs_es_step";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (d->flags & ~GYMRS_OPT_ASCEND) return fail(GYMRS_EINVAL, who + ": unknown flag bits (GYMRS_OPT_ASCEND is the only one)");
+    gymrs_optimizer_desc od;
+    std::memset(&od, 0, sizeof(od));
+    od.kind = d->kind, od.flags = d->flags, od.lr = d->lr, od.grad_scale = d->grad_scale, od.beta1 = d->beta1, od.beta2 = d->beta2;
+    od.eps = d->eps, od.max_norm = d->max_norm, od.reserved = d->reserved;
+    if (gymrs_status st = check_optimizer_values(&od, who)) return st;
+    if (d->sigma_next != 0.0f && !es_sigma_ok(d->sigma_next))
+        return fail(GYMRS_EINVAL, who + ": sigma_next must be 0 (sigma stays) or finite and > 0");
+    if (reinterpret_cast<uintptr_t>(d->utilities) % alignof(float) != 0) return fail(GYMRS_EINVAL, who + ": utilities must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d->skipped) % 8 != 0) return fail(GYMRS_EINVAL, who + ": skipped must be 8-byte aligned");
+    EsState& es = e->es;
+    if (!es.dev || !e->policy.dev) return fail(GYMRS_EINVAL, who + ": the engine has no evolution-strategies state (gymrs_es_init)");
+    if (!d->utilities && !(es.evaluated && e->eval_dev))
+        return fail(GYMRS_EINVAL, who + ": no evaluation ran since the population was written (gymrs_evaluate_policy), and no utilities were given");
+    EsArgs a = es_args(e);
+    a.records = d->utilities ? nullptr : e->eval_dev;
+    a.u_in = d->utilities;
+    a.skipped = reinterpret_cast<unsigned long long*>(d->skipped);
+    a.kind = d->kind, a.flags = d->flags, a.lr = d->lr, a.grad_scale = d->grad_scale, a.beta1 = d->beta1, a.beta2 = d->beta2;
+    a.eps = d->eps, a.max_norm = d->max_norm;
+    if (d->sigma_next > 0.0f) a.sigma_new = d->sigma_next;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_es_step(a, e->stream));
+    es.gen += 1; // the policy buffer holds the next generation (in stream order), which nothing has played yet
+    es.sigma = a.sigma_new;
+    es.evaluated = false;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_es(gymrs_engine* e, gymrs_es_desc* d_out, uint64_t* generation, float* centre_out, uint64_t capacity_floats)
+{
+    const std::string who = "gymrs_get_es";
+    if (!e || !d_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    const EsState& es = e->es;
+    if (!es.dev) return fail(GYMRS_EINVAL, who + ": the engine has no evolution-strategies state (gymrs_es_init)");
+    *d_out = gymrs_es_desc{es.shape.hidden, es.shape.n_policies, es.shape.lanes_per_policy, es.seed, es.sigma, 0};
+    if (generation) *generation = es.gen;
+    if (!centre_out && capacity_floats == 0) return GYMRS_OK; // a query of the description
+    if (!centre_out || capacity_floats < es.shape.stride) return fail(GYMRS_EINVAL, who + ": capacity_floats is smaller than the centre");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(centre_out, &es.dev->centre[0], (size_t)es.shape.stride * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
+}
+
+gymrs_status gymrs_es_centre_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats)
+{
+    const std::string who = "gymrs_es_centre_ptr";
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!e->es.dev) return fail(GYMRS_EINVAL, who + ": the engine has no evolution-strategies state (gymrs_es_init)");
+    *dev_out = &e->es.dev->centre[0];
+    if (n_floats) *n_floats = e->es.shape.stride;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_es_utilities_ptr(gymrs_engine* e, float** dev_out, uint32_t* n_policies)
+{
+    const std::string who = "gymrs_es_utilities_ptr";
+    if (!e || !dev_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!e->es.dev) return fail(GYMRS_EINVAL, who + ": the engine has no evolution-strategies state (gymrs_es_init)");
+    *dev_out = e->es.u;
+    if (n_policies) *n_policies = e->es.shape.n_policies;
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_get_es_optimizer_state(gymrs_engine* e, float* m_out, float* v_out, float* pw_out)
+{
+    const std::string who = "gymrs_get_es_optimizer_state";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    const EsState& es = e->es;
+    if (!es.dev) return fail(GYMRS_EINVAL, who + ": the engine has no evolution-strategies state (gymrs_es_init)");
+    HIP_TRY(hipSetDevice(e->device));
+    const uint32_t half = (uint32_t)es.gen & 1u; // the half the next step reads
+    const size_t bytes = (size_t)es.shape.stride * sizeof(float);
+    if (m_out) HIP_TRY(hipMemcpyAsync(m_out, &es.dev->m[half][0], bytes, hipMemcpyDeviceToHost, e->stream));
+    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, &es.dev->v[half][0], bytes, hipMemcpyDeviceToHost, e->stream));
+    if (pw_out) HIP_TRY(hipMemcpyAsync(pw_out, &es.dev->pw[half][0], 2 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    return stream_sync_checked(e);
+}
+
+gymrs_status gymrs_es_noise(uint64_t seed, uint64_t generation, uint64_t pair, uint32_t s, float* eps_out)
+{
+    if (!eps_out) return fail(GYMRS_EINVAL, "gymrs_es_noise: eps_out is NULL");
+    if (s >= kEsSlots) return fail(GYMRS_EINVAL, "gymrs_es_noise: s must be < 512 (nine bits of the key)");
+    *eps_out = es_noise(seed, generation, pair, s);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_es_utilities(const gymrs_policy_eval* records, uint32_t n_policies, float* u_out)
+{
+    const std::string who = "gymrs_es_utilities";
+    if (!records || !u_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (n_policies == 0 || n_policies > kEsMaxPolicies) return fail(GYMRS_EINVAL, who + ": n_policies must be in 1 .. GYMRS_ES_MAX_POLICIES");
+    const uint32_t P = n_policies;
+    auto valid = [&](uint32_t p) { return records[p].episodes > 0; };
+    auto F = [&](uint32_t p) { return es_fitness(records[p].return_sum, records[p].episodes); };
+    const double total = es_sum(P, [&](uint32_t p) { return valid(p) ? F(p) : 0.0; });
+    const double n_valid = es_sum(P, [&](uint32_t p) { return valid(p) ? 1.0 : 0.0; });
+    const double mean = total / n_valid;
+    const double total2 = es_sum(P, [&](uint32_t p) {
+        const double dev = F(p) - mean;
+        return valid(p) ? dev * dev : 0.0;
+    });
+    const double sd = es_sd(total2, n_valid);
+    for (uint32_t p = 0; p < P; ++p) u_out[p] = es_utility(valid(p), valid(p) ? F(p) : 0.0, mean, sd);
+    return GYMRS_OK;
+}
+
 // ---- per-policy fitness: the table behind gymrs_rollout_policy_fitness -----------------------------------------------------
 gymrs_status gymrs_policy_fitness_ptr(gymrs_engine* e, gymrs_policy_fitness** dev_out, uint32_t* n_policies)
 {
@@ -1065,6 +1310,7 @@ gymrs_status gymrs_evaluate_policy(gymrs_engine* e, const gymrs_eval_desc* d)
     a.table = e->eval_dev;
     a.box = make_sample_box(e->dflt_lo, e->dflt_hi, e->state_dim); // gymrs_reset without bounds
     HIP_TRY(launch_evaluate_policy(e->kind, e->table_k ? kFlagTable : 0u, a, launch_consts(e), e->policy.args, e->stream));
+    e->es.evaluated = true; // (an ES population, if that is the set: gymrs_es_step may read the table)
     return GYMRS_OK;
 }
 

@@ -79,6 +79,19 @@ struct OptimizerState {
     float* pw() const { return dev + 2 * words(); }
 };
 
+// The evolution-strategies state (gymrs_es_init): `dev` is the EsDeviceState, `u` and `fitness` the [P] rows of the utilities
+// (dev == NULL = no state).  Host side: the shape the state was made for, the noise key, and what the next step needs to know --
+// the generation whose population is in the policy buffer, its sigma, and whether an evaluation has played it.
+struct EsState {
+    EsDeviceState* dev = nullptr;
+    float* u = nullptr;
+    double* fitness = nullptr;
+    PolicyArgs shape{};
+    uint64_t seed = 0, gen = 0;
+    float sigma = 0.0f;
+    bool evaluated = false;
+};
+
 struct gymrs_engine {
     gymrs_env_kind kind;
     uint64_t n = 0, gid0 = 0;
@@ -209,6 +222,9 @@ struct gymrs_engine {
     // GYMRS_OPT_ADAM call on the head, under the target's lifetime rule (kept by a setter of the same shape, discarded otherwise).
     // Not part of clone or snapshot.
     OptimizerState opt_state[2];
+    // The evolution-strategies state of gymrs_es_init / gymrs_es_step: the centre, its own Adam state and the utilities' rows, under the
+    // target's lifetime rule as well.  Not part of clone or snapshot.
+    EsState es;
     // The per-policy counters of gymrs_rollout_policy_fitness: policy.args.n_policies records, allocated (zeroed) at the first fitness
     // call after a gymrs_set_policy; every gymrs_set_policy discards it (frees it, or zeroes it in stream order where n_policies
     // stays the same).  Not part of clone or snapshot.

@@ -455,4 +455,36 @@ constexpr uint32_t kMaxOptimizerParams = 512; // 8 parameters in each of 64 lane
 hipError_t launch_apply_gradient(const OptimizerArgs& a, hipStream_t stream);
 // m = v = +0.0f, pw = 1.0f: a fresh Adam state, in stream order
 hipError_t launch_optimizer_fresh(float* m, float* v, float* pw, uint32_t n_sets, uint32_t S, hipStream_t stream);
+// ---- evolution strategies (gymrs_es_init, gymrs_es_step; gymrs_es.hip) ----------------------------------------------------------
+constexpr uint32_t kEsMaxPolicies = 1u << 20; // GYMRS_ES_MAX_POLICIES: at most 1024 chunks of 1024 policies
+constexpr uint32_t kEsChunk = 1024;           // policies per chunk of the utilities' two-level sums
+constexpr uint32_t kEsSlots = 512;            // parameter slots of every table of the state (S <= 450; 9 bits of the noise key)
+// The engine-owned state on the device: ONE allocation.  Everything a step reads and writes in the same launch is a ping-pong pair:
+// half (gen & 1) is read by every block, the other half is written by block 0 alone (and becomes the next generation's).
+struct EsDeviceState {
+    unsigned long long grad[2][kEsSlots]; // G (int64 bit patterns): the step's half is added to, the other half is zeroed for the next step
+    unsigned long long excluded[2][2];    // [half][0]; [half][1] pads
+    float theta[2][kEsSlots], m[2][kEsSlots], v[2][kEsSlots];
+    float pw[2][2];
+    float centre[kEsSlots];               // the centre of the current generation at a fixed address (gymrs_es_centre_ptr); no kernel reads it
+    double chunk_sum[kEsChunk], chunk_count[kEsChunk], chunk_sq[kEsChunk]; // the utilities' first level: one entry per chunk
+};
+struct EsArgs {
+    EsDeviceState* st;
+    float* weights;                    // [P][S]: the policy set, WRITTEN (the population)
+    const void* records;               // [P] gymrs_policy_eval of the latest evaluation, or NULL with u_in
+    const float* u_in;                 // [P] the caller's utilities, or NULL
+    float* u;                          // [P] engine-owned: what the step used
+    double* fitness;                   // [P] engine-owned scratch: F[p], NaN where the policy is not valid
+    unsigned long long* skipped;       // one counter or NULL, ADDED to
+    uint64_t seed, gen;                // gen: the generation whose population was evaluated (the step writes gen + 1's)
+    uint32_t P, S;
+    uint32_t kind, flags;              // GYMRS_OPT_SGD / _ADAM; GYMRS_OPT_ASCEND
+    float lr, grad_scale, beta1, beta2, eps, max_norm;
+    float sigma, sigma_new;            // of the evaluated population; of the one that is written
+};
+// the centre is in st->theta[0] (stream order): fresh Adam state, zeroed tables, the population of generation 0
+hipError_t launch_es_init(const EsArgs& a, hipStream_t stream);
+// utilities (or the caller's), gradient, update, the population of generation gen + 1: no host synchronisation among the launches
+hipError_t launch_es_step(const EsArgs& a, hipStream_t stream);
 } // namespace gymrs

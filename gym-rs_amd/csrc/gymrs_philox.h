@@ -12,7 +12,7 @@
 //   key     = (seed lo, seed hi)
 //   counter = (gid lo, gid hi, tick lo, (tick hi & 0xffff) | stream << 16)
 //   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests), stream 2 = epsilon-greedy exploration,
-//   stream 3 = softmax action sampling
+//   stream 3 = softmax action sampling, stream 4 = the noise of evolution strategies (gid = the pair, tick = generation and parameter)
 #pragma once
 #include "gymrs_math.h"
 
@@ -99,6 +99,10 @@ GYMRS_HD uint8_t explore_random(uint32_t word, uint32_t n_actions) { return (uin
 constexpr uint32_t kStreamSample = 3;
 GYMRS_HD u32x4 sample_block(uint64_t seed, uint64_t gid, uint64_t tick) { return draw4(seed, gid >> 2, tick, kStreamSample); }
 GYMRS_HD uint32_t sample_word(uint64_t seed, uint64_t gid, uint64_t tick) { return pick_word(sample_block(seed, gid, tick), (uint32_t)gid & 3u); }
+
+// The noise of evolution strategies (stream 4; include/gymrs_amd.h, "Evolution strategies"): one whole block per (pair, generation,
+// parameter).  What the block becomes is in gymrs_es.h.
+constexpr uint32_t kStreamEs = 4;
 
 // u32 -> uniform f32 on [low, high): 24 random bits, u * scale + low, kept below `high` (half-open like
 // rand's Uniform::new, cartpole.rs:363).  Everything that does not depend on the random word is prepared

@@ -63,6 +63,17 @@ __device__ __forceinline__ long long wave_sum_i64(int32_t v)
     return (long long)hi * 65536 + (long long)lo;
 }
 
+// The same for a 64-bit signed input, in three limbs: two unsigned 20-bit limbs (64 x 2^20 fits 32 bits) and the signed 24-bit top
+// (64 x 2^23 fits 32 bits).  Exact whenever the sum itself fits 64 bits; 18 DPP adds where wave_sum_u64 spends 24.  Must be called
+// with every work-item of the wave active.
+__device__ __forceinline__ long long wave_sum_i64(long long v)
+{
+    const uint32_t lo = wave_sum_u32((uint32_t)v & 0xfffffu);
+    const uint32_t mid = wave_sum_u32((uint32_t)(v >> 20) & 0xfffffu);
+    const int32_t hi = (int32_t)wave_sum_u32((uint32_t)(int32_t)(v >> 40));
+    return (long long)((unsigned long long)(long long)hi << 40) + (long long)((unsigned long long)mid << 20) + (long long)lo;
+}
+
 // Sum of a 64-bit value over the wavefront, modulo 2^64 (wave-uniform): 16-bit quarters summed on their own (64 x 2^16 fits 32
 // bits).  Must be called with every work-item of the wave active.
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)

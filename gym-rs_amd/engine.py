@@ -163,6 +163,23 @@ def _optimizer_desc(head, kind, lr, grad_scale, beta1, beta2, eps, max_norm, tau
                          float(tau), C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(skipped or None), 0)
 
 
+class EsDesc(C.Structure):
+    """``gymrs_es_desc`` (include/gymrs_amd.h), 32 bytes."""
+    _fields_ = [("hidden", C.c_uint32), ("n_policies", C.c_uint32), ("lanes_per_policy", C.c_uint64), ("seed", C.c_uint64),
+                ("sigma", C.c_float), ("reserved", C.c_uint32)]
+
+
+class EsStepDesc(C.Structure):
+    """``gymrs_es_step_desc`` (include/gymrs_amd.h), 56 bytes: kind, flags, seven floats, the optional utilities row, one optional
+    counter added to."""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("lr", C.c_float), ("grad_scale", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float), ("sigma_next", C.c_float), ("reserved", C.c_uint32),
+                ("utilities", C.c_void_p), ("skipped", C.c_void_p)]
+
+
+ES_MAX_POLICIES = 1 << 20  # GYMRS_ES_MAX_POLICIES
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -416,6 +433,29 @@ def optimizer_set(q, w, *, kind: int = OPT_SGD, lr: float, grad_scale: float, m=
     _check(lib, lib.gymrs_optimizer_set(C.byref(desc), qq.size, qq.ctypes.data_as(C.POINTER(C.c_int64)),
                                         *(None if a is None else a.ctypes.data_as(fp) for a in out)))
     return tuple(out)
+
+
+def es_noise(seed: int, generation: int, pair, s) -> np.ndarray:
+    """``gymrs_es_noise`` (host only, no GPU): eps(generation, pair, s) of include/gymrs_amd.h, "Evolution strategies", as f32;
+    ``pair`` and ``s`` broadcast against each other."""
+    lib = load_library()
+    pairs, ss = np.broadcast_arrays(np.asarray(pair, dtype=np.uint64), np.asarray(s, dtype=np.uint32))
+    out = np.empty(pairs.shape, np.float32)
+    eps = C.c_float()
+    for i in np.ndindex(*pairs.shape):
+        _check(lib, lib.gymrs_es_noise(int(seed) & (2**64 - 1), int(generation) & (2**64 - 1), int(pairs[i]), int(ss[i]), C.byref(eps)))
+        out[i] = eps.value
+    return out
+
+
+def es_utilities(records) -> np.ndarray:
+    """``gymrs_es_utilities`` (host only, no GPU): the f32 utilities of P policies from their episodic records, int64 (P, 8) as
+    ``BatchedEngine.policy_eval`` returns them."""
+    lib = load_library()
+    rec = np.ascontiguousarray(records, dtype=np.int64).reshape(-1, 8)
+    out = np.empty(rec.shape[0], np.float32)
+    _check(lib, lib.gymrs_es_utilities(rec.ctypes.data_as(C.c_void_p), rec.shape[0], out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -1016,6 +1056,60 @@ class BatchedEngine:
         _check(self._lib, self._lib.gymrs_get_optimizer_state(self._h, OPT_HEAD_CRITIC if critic else OPT_HEAD_POLICY, m.ctypes.data_as(fp),
                                                               v.ctypes.data_as(fp), pw.ctypes.data_as(fp)))
         return m, v, pw
+
+    # -- evolution strategies: the centre, the population and the update stay on the device --------------------------------
+    def es_init(self, centre, *, n_policies: int, sigma: float, seed: int = 0, hidden: int = 0, lanes_per_policy: int = 1,
+                reserved: int = 0) -> None:
+        """``gymrs_es_init``: install a population of ``n_policies`` (even) policies around ``centre`` (``policy_size`` floats) as
+        the engine's policy set -- written by a kernel from the noise keyed by ``seed`` -- with a fresh Adam state and generation 0.
+        Every policy call then works on that set; a generation is ``evaluate_policy`` followed by ``es_step``."""
+        c = np.ascontiguousarray(centre, dtype=np.float32).reshape(-1)
+        if 0 <= int(hidden) <= 64 and self.kind != PENDULUM and c.size != policy_size(self.kind, hidden):  # (the library words the other refusals)
+            raise ValueError(f"es_init needs a centre of {policy_size(self.kind, hidden)} floats")
+        desc = EsDesc(int(hidden), int(n_policies), int(lanes_per_policy), int(seed) & (2**64 - 1), float(sigma), int(reserved))
+        _check(self._lib, self._lib.gymrs_es_init(self._h, C.byref(desc), c.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def es_step(self, *, lr: float, grad_scale: float, adam: bool = False, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                max_norm: float = float("inf"), sigma_next: float = 0.0, ascend: bool = True, utilities: Optional[int] = None,
+                skipped: Optional[int] = None, kind: Optional[int] = None, flags: Optional[int] = None, reserved: int = 0) -> None:
+        """``gymrs_es_step``: utilities from the latest ``evaluate_policy`` (or ``utilities``, the device address of P f32), the
+        gradient of the centre, the optimizer's update (``grad_scale`` is typically 2**-24 / (P * sigma)) and the population of
+        the next generation, in stream order with no synchronisation.  A step whose gradient excluded a term leaves the centre
+        alone and adds 1 to ``skipped`` (one device uint64).  ``sigma_next`` > 0 becomes the sigma of the new population."""
+        desc = EsStepDesc((OPT_ADAM if adam else OPT_SGD) if kind is None else int(kind), (OPT_ASCEND if ascend else 0) if flags is None else int(flags),
+                          float(lr), float(grad_scale), float(beta1), float(beta2), float(eps), float(max_norm), float(sigma_next), int(reserved),
+                          C.c_void_p(utilities or None), C.c_void_p(skipped or None))
+        _check(self._lib, self._lib.gymrs_es_step(self._h, C.byref(desc)))
+
+    def es_state(self, centre: bool = True):
+        """dict(hidden, n_policies, lanes_per_policy, seed, sigma, generation) of the ES state and, with ``centre``, the centre as
+        f32 (synchronising)."""
+        desc, gen = EsDesc(), C.c_uint64()
+        _check(self._lib, self._lib.gymrs_get_es(self._h, C.byref(desc), C.byref(gen), None, 0))
+        out = dict(hidden=int(desc.hidden), n_policies=int(desc.n_policies), lanes_per_policy=int(desc.lanes_per_policy), seed=int(desc.seed),
+                   sigma=float(desc.sigma), generation=int(gen.value))
+        if centre:
+            c = np.empty(policy_size(self.kind, desc.hidden), np.float32)
+            _check(self._lib, self._lib.gymrs_get_es(self._h, C.byref(desc), None, c.ctypes.data_as(C.POINTER(C.c_float)), c.size))
+            out["centre"] = c
+        return out
+
+    def es_optimizer_state(self):
+        """(m [S], v [S], pw [2]) of the centre's Adam state, f32 (synchronising): fresh after ``es_init``."""
+        size = policy_size(self.kind, self.es_state(centre=False)["hidden"])
+        m, v, pw = np.empty(size, np.float32), np.empty(size, np.float32), np.empty(2, np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(self._lib, self._lib.gymrs_get_es_optimizer_state(self._h, m.ctypes.data_as(fp), v.ctypes.data_as(fp), pw.ctypes.data_as(fp)))
+        return m, v, pw
+
+    def es_centre_ptr(self) -> Tuple[int, int]:
+        """(device address, number of floats) of the current centre: zero-copy, at an address that stays the same while the state
+        lives; every ``es_step`` rewrites it in stream order."""
+        return _view(self._lib, self._lib.gymrs_es_centre_ptr, self._h)
+
+    def es_utilities_ptr(self) -> Tuple[int, int]:
+        """(device address, n_policies) of the f32 utilities the last ``es_step`` used: zero-copy."""
+        return _view(self._lib, self._lib.gymrs_es_utilities_ptr, self._h, C.c_uint32)
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

@@ -1064,6 +1064,98 @@ gymrs_status gymrs_sharded_evaluate_policy(gymrs_sharded* h, const gymrs_eval_de
 gymrs_status gymrs_sharded_get_policy_eval(gymrs_sharded* h, uint32_t first, uint32_t count, gymrs_policy_eval* host_out);
 
 /* ---- `#[derive(Serialize)]` view (core.rs:25; cartpole.rs:51-87, mountain_car.rs:46-80) -------- */
+/* Evolution strategies: antithetic, Gaussian-like ES around ONE centre, defined to the bit and held on the device.  The centre theta[S]
+ * (S = gymrs_policy_size(kind, hidden) <= 450), sigma, seed, a generation counter gen (uint64, from 0) and an Adam state of the
+ * centre's own (m, v, pw) belong to the engine.  The population is the engine's policy set, written on the device; the noise is never
+ * stored: it is regenerated from its key wherever it is needed.  A generation is gymrs_evaluate_policy followed by gymrs_es_step, in
+ * stream order, with no host round trip.
+ * P = n_policies, even, 2 <= P <= GYMRS_ES_MAX_POLICIES.  Policies 2j and 2j + 1 are pair j.  All arithmetic is f32 unless it says
+ * f64; every operation is a single IEEE operation in the order written, fmaf rounds once.
+ * Noise (Philox stream 4; the streams 0 .. 3 of reset, actions, exploration and sampling are untouched):
+ *     b = the Philox4x32-10 block keyed (seed, gid = j, tick = ((gen & (2^39 - 1)) << 9) | s, stream 4)
+ *     h = the sum of the eight 16-bit halves of b's four words          (uint32, 0 .. 524280)
+ *     n = (int32)h - 262140                                             (exact, symmetric about 0)
+ *     eps(gen, j, s) = (float)n * kEsNoiseScale,   kEsNoiseScale = (float)(1 / sqrt(2863311530)) = 0x1.3988e2p-16f
+ *                                                                = 1.8688124328036793e-05
+ *   THIS IS NOT A GAUSSIAN: it is the centred sum of eight uniform 16-bit integers, scaled to unit variance.  Its excess kurtosis is
+ *   -0.15 and its support ends at about +-4.9 standard deviations.  It needs no transcendental function, so it is trivially bit-exact.
+ * Population:   w[2j][s] = fmaf(sigma, eps, theta[s]);   w[2j+1][s] = fmaf(-sigma, eps, theta[s])
+ * Utilities, from the gymrs_policy_eval table of the latest gymrs_evaluate_policy (f64 throughout):
+ *     valid[p] = episodes > 0;   F[p] = (double)return_sum / (double)episodes
+ *     a sum over the valid p runs in a fixed two-level order: chunk c holds the policies [1024c, 1024c + 1024); slot l of a chunk
+ *     starts at the value of policy 1024c + l, or +0.0 where that policy is not valid or is past P; then slot[l] = slot[l] +
+ *     slot[l ^ mask] for mask = 512, 256, .. 1 (all l at once), and slot[0] is the chunk's sum.  The at most 1024 chunk sums are
+ *     combined by the same butterfly (slots past the last chunk hold +0.0).
+ *     n_valid = the number of valid p;  mean = sum(F) / n_valid;  sum2 = sum((F - mean) * (F - mean)) in the same order
+ *     sd = sqrt(sum2 / n_valid)
+ *     u[p] = (valid[p] && sd > 0) ? (float)((F[p] - mean) / sd) : +0.0f
+ *   Or the caller passes its own utilities (device f32 [P]; for instance centred ranks from an argsort on the engine's stream): then
+ *   the table is not read.  Rank shaping inside the library is out of scope.
+ * Gradient, per pair j and parameter s:
+ *     d = u[2j] - u[2j+1];   t = d * eps(gen, j, s)
+ *     t finite and |t| < 2^30:  G[s] += (int64)rint((double)t * 2^24)          otherwise nothing is added and excluded += 1
+ *   The sum is in integers: exact and independent of the order.
+ * Update: exactly the rule of "Optimizer" for one set, with q = G, tau = 0 and the caller's kind, flags (GYMRS_OPT_ASCEND only), lr,
+ *   grad_scale (typically 2^-24 / (P * sigma)), beta1, beta2, eps and max_norm; gymrs_optimizer_set is its definition as code.  With
+ *   excluded != 0 the centre and the state stay as they are and *skipped += 1.
+ * Then gen += 1, sigma becomes sigma_next when that is > 0, and the population of the new generation is written from the new centre
+ * with the new sigma -- on a skipped step too.
+ *   - gymrs_es_init(e, d, centre_host) installs a policy set of P policies the way gymrs_set_policy does -- the fitness, evaluation,
+ *     target and optimizer-state lifetimes behave as documented for "a set of another shape" (or the same shape) -- except that the
+ *     weights are written by a kernel, not copied from the host: generation 0 around centre_host[S], a fresh Adam state, gen = 0.  It
+ *     waits only for its own copy of the centre.
+ *   - Between steps every policy call works on the installed set: gymrs_get_policy, gymrs_policy_weights_ptr, the rollouts,
+ *     gymrs_evaluate_policy.  A later gymrs_set_policy discards the ES state unless hidden, n_policies and lanes_per_policy stay the
+ *     same (the target set's rule); the removal discards it.  It is NOT part of gymrs_engine_clone or of a snapshot.
+ *   - gymrs_es_step(e, d) runs in the engine's stream order and synchronises nothing.  Without d->utilities it needs the evaluation
+ *     table: GYMRS_EINVAL naming gymrs_evaluate_policy when no evaluation ran since the population was written.  d->skipped may be
+ *     NULL; otherwise it is ONE device uint64, ADDED to.
+ *   - gymrs_get_es(e, d_out, generation, centre_out, capacity_floats) describes the state (generation may be NULL) and, with room for
+ *     S floats, copies the centre to the host and synchronises; centre_out == NULL with capacity_floats == 0 is a query of the
+ *     description.  gymrs_es_centre_ptr is the zero-copy view of the current centre (S floats at an address that stays the same from
+ *     gymrs_es_init to the end of the state; rewritten by every step in stream order); gymrs_es_utilities_ptr is the view of the u[P]
+ *     the last step used (the caller's row is copied there).  gymrs_get_es_optimizer_state(e, m_out, v_out, pw_out) copies the
+ *     centre's Adam state (m and v: S floats, pw: 2) to the host and synchronises; any of the three may be NULL.  The state is fresh
+ *     (m = v = +0.0f, pw = 1.0f) from gymrs_es_init on, and GYMRS_OPT_SGD steps leave it as it is.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or descriptor; Pendulum; hidden > 64; P odd, below 2 or above the bound;
+ *     lanes_per_policy == 0; sigma (or a non-zero sigma_next) NaN, infinite or <= 0; reserved != 0; an unknown kind or flag bit; the
+ *     value checks of "Optimizer"; no ES state (naming gymrs_es_init); utilities not 4-byte aligned, skipped not 8-byte aligned.  A
+ *     refused call leaves the state untouched.
+ *   - gymrs_es_noise and gymrs_es_utilities: host only, no GPU: the definition as code.  gymrs_es_noise gives eps(generation, pair,
+ *     s) (s < 512); gymrs_es_utilities gives u[0..P) from P records (1 <= P <= GYMRS_ES_MAX_POLICIES).
+ * What follows from the rule: a policy without an episode in this engine (fewer lanes than P * lanes_per_policy) has utility 0 and
+ * its pair pulls with the other member's utility alone; when every valid return is equal, every utility is 0 and the step moves the
+ * centre by what the optimizer makes of a zero gradient (Adam's moments decay).  What one step costs per kernel, next to the same
+ * generation step through the host (gymrs_get_policy_eval, numpy, gymrs_set_policy): profiles/evolution_strategies.md.
+ * Out of scope: CMA-ES and per-parameter sigma, several centres per engine, mirrored sampling other than antithetic pairs, a true
+ * Gaussian.  The ABI version stays 3: the feature is detected by its symbols.  There is no sharded counterpart. */
+#define GYMRS_ES_MAX_POLICIES 1048576u
+typedef struct {
+    uint32_t hidden, n_policies;   /* n_policies = P: even, 2 .. GYMRS_ES_MAX_POLICIES */
+    uint64_t lanes_per_policy;     /* >= 1 */
+    uint64_t seed;                 /* the key of the noise */
+    float sigma;                   /* finite, > 0 */
+    uint32_t reserved;             /* 0 */
+} gymrs_es_desc;                   /* 32 bytes */
+typedef struct {
+    uint32_t kind, flags;          /* GYMRS_OPT_SGD or GYMRS_OPT_ADAM; GYMRS_OPT_ASCEND, nothing else */
+    float lr, grad_scale;          /* finite */
+    float beta1, beta2;            /* in [0, 1) */
+    float eps;                     /* finite, >= 0 */
+    float max_norm;                /* > 0; +inf = no clip */
+    float sigma_next;              /* 0 keeps sigma; otherwise finite and > 0 */
+    uint32_t reserved;             /* 0 */
+    const float* utilities;        /* device f32 [P], 4-byte aligned, or NULL: from the evaluation table */
+    uint64_t* skipped;             /* ONE device uint64 or NULL, 8-byte aligned, ADDED to */
+} gymrs_es_step_desc;              /* 56 bytes */
+gymrs_status gymrs_es_init(gymrs_engine* e, const gymrs_es_desc* d, const float* centre_host);
+gymrs_status gymrs_es_step(gymrs_engine* e, const gymrs_es_step_desc* d);
+gymrs_status gymrs_get_es(gymrs_engine* e, gymrs_es_desc* d_out, uint64_t* generation, float* centre_out, uint64_t capacity_floats);
+gymrs_status gymrs_es_centre_ptr(gymrs_engine* e, float** dev_out, uint64_t* n_floats);
+gymrs_status gymrs_es_utilities_ptr(gymrs_engine* e, float** dev_out, uint32_t* n_policies);
+gymrs_status gymrs_get_es_optimizer_state(gymrs_engine* e, float* m_out, float* v_out, float* pw_out);
+gymrs_status gymrs_es_noise(uint64_t seed, uint64_t generation, uint64_t pair, uint32_t s, float* eps_out);
+gymrs_status gymrs_es_utilities(const gymrs_policy_eval* records, uint32_t n_policies, float* u_out);
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible
  * fields in declaration order with the reference's field names -- CartPole: action_space, observation_space
  * {low, high}, render_mode, state {x, x_dot, theta, theta_dot}, metadata {render_modes, render_fps, marker},

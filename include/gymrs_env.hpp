@@ -124,6 +124,16 @@ inline void optimizer_set(const gymrs_optimizer_desc& d, std::uint64_t n_params,
     check(gymrs_optimizer_set(&d, n_params, q, w, m, v, pw, target));
 }
 
+// The definitions of "Evolution strategies" as code (host only, no GPU): the noise of one (generation, pair, parameter), and the
+// utilities u[0 .. n) of n evaluation records.
+inline float es_noise(std::uint64_t seed, std::uint64_t generation, std::uint64_t pair, std::uint32_t s)
+{
+    float eps = 0.0f;
+    check(gymrs_es_noise(seed, generation, pair, s, &eps));
+    return eps;
+}
+inline void es_utilities(const gymrs_policy_eval* records, std::uint32_t n_policies, float* u_out) { check(gymrs_es_utilities(records, n_policies, u_out)); }
+
 // One lane's contribution to gymrs_ppo_gradient (gymrs_ppo_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
 // (lane, parameter) pairs returned; counts (may be null) gets the lane-steps seen and cut, prob (may be null) p[a] of every step.
 // The definition of include/gymrs_amd.h, "clipped surrogate", as code.
@@ -446,6 +456,30 @@ public:
     void apply_gradient(const gymrs_optimizer_desc& d) { check(gymrs_apply_gradient(e_, &d)); }
     void optimizer_reset(std::uint32_t head) { check(gymrs_optimizer_reset(e_, head)); }
     void optimizer_state(std::uint32_t head, float* m_out, float* v_out, float* pw_out) { check(gymrs_get_optimizer_state(e_, head, m_out, v_out, pw_out)); }
+    // Evolution strategies (include/gymrs_amd.h, "Evolution strategies"): es_init installs the population of generation 0 around
+    // centre_host as the policy set (written on the device); a generation is evaluate_policy followed by es_step, in stream order with
+    // no synchronisation.  es_state copies the description (and, with room, the centre) out; the two views are zero-copy.
+    void es_init(const gymrs_es_desc& d, const float* centre_host) { check(gymrs_es_init(e_, &d, centre_host)); }
+    void es_step(const gymrs_es_step_desc& d) { check(gymrs_es_step(e_, &d)); }
+    gymrs_es_desc es_state(std::uint64_t* generation = nullptr, float* centre_out = nullptr, std::uint64_t capacity_floats = 0)
+    {
+        gymrs_es_desc d{};
+        check(gymrs_get_es(e_, &d, generation, centre_out, capacity_floats));
+        return d;
+    }
+    void es_optimizer_state(float* m_out, float* v_out, float* pw_out) { check(gymrs_get_es_optimizer_state(e_, m_out, v_out, pw_out)); }
+    float* es_centre_ptr(std::uint64_t* n_floats = nullptr)
+    {
+        float* p = nullptr;
+        check(gymrs_es_centre_ptr(e_, &p, n_floats));
+        return p;
+    }
+    float* es_utilities_ptr(std::uint32_t* n_policies = nullptr)
+    {
+        float* p = nullptr;
+        check(gymrs_es_utilities_ptr(e_, &p, n_policies));
+        return p;
+    }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
         std::vector<gymrs_policy_fitness> out(count);
