@@ -300,6 +300,19 @@ pub struct GymrsEsStepDesc {
     pub skipped: *mut u64,
 }
 
+/// `GYMRS_ES_RANK_INVALID`: the `rank2` of a policy that played no episode.
+pub const GYMRS_ES_RANK_INVALID: u32 = 0xffff_ffff;
+
+/// `gymrs_es_ranks_desc`: the rows `gymrs_es_ranks` writes, 24 bytes: the utilities (required), twice the average rank (or null).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsEsRanksDesc {
+    pub utilities: *mut f32,
+    pub rank2: *mut u32,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
 /// `GYMRS_EVAL_COMMON_STARTS`: every policy meets the same `lanes_per_policy x E` start states.
 pub const GYMRS_EVAL_COMMON_STARTS: u32 = 1;
 /// `GYMRS_EVAL_LANE_PARAMS`: every lane plays with the row of the parameter table `gymrs_step` would use for it (no table: no change).
@@ -460,6 +473,8 @@ extern "C" {
     pub fn gymrs_get_es_optimizer_state(e: *mut GymrsEngine, m_out: *mut f32, v_out: *mut f32, pw_out: *mut f32) -> c_int;
     pub fn gymrs_es_noise(seed: u64, generation: u64, pair: u64, s: u32, eps_out: *mut f32) -> c_int;
     pub fn gymrs_es_utilities(records: *const GymrsPolicyEval, n_policies: u32, u_out: *mut f32) -> c_int;
+    pub fn gymrs_es_ranks(e: *mut GymrsEngine, d: *const GymrsEsRanksDesc) -> c_int;
+    pub fn gymrs_es_rank_utilities(records: *const GymrsPolicyEval, n_policies: u32, u_out: *mut f32, rank2_out: *mut u32) -> c_int;
     pub fn gymrs_set_exploration(e: *mut GymrsEngine, x: *const GymrsExploration) -> c_int;
     pub fn gymrs_get_exploration(e: *mut GymrsEngine, x_out: *mut GymrsExploration) -> c_int;
     pub fn gymrs_explore_actions(e: *mut GymrsEngine, actions_dev: *mut c_void) -> c_int;

@@ -8,7 +8,7 @@ synchronisation inside the loop.  What the centre itself earns is watched by a s
 its one policy is overwritten with the centre (device to device), played, and its record kept in a device row that is read once,
 after the loop.
 
-    python examples/evolution_strategies.py [--policies 4096] [--hidden 0] [--generations 30] [--sigma 0.1] [--lr 0.05]
+    python examples/evolution_strategies.py [--policies 4096] [--hidden 0] [--generations 30] [--sigma 0.1] [--lr 0.05] [--ranks]
 """
 from __future__ import annotations
 
@@ -40,6 +40,7 @@ def main() -> int:
     ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ranks", action="store_true", help="shape by centred ranks (es_ranks) instead of the z-score of the mean return")
     args = ap.parse_args()
     P, size = args.policies, gymrs.policy_size(gymrs.CARTPOLE, args.hidden)
     centre0 = (0.1 * np.random.default_rng(args.seed).standard_normal(size)).astype(np.float32)
@@ -59,12 +60,16 @@ def main() -> int:
     probe_record = torch.as_tensor(DeviceRow(probe.policy_eval_ptr()[0], 8, "<i8"), device="cuda")
     with torch.cuda.stream(stream):
         history = torch.zeros((args.generations, 8), dtype=torch.int64, device="cuda")
+        ranks = torch.zeros(P, dtype=torch.float32, device="cuda") if args.ranks else None
         for gen in range(args.generations):  # nothing in this loop waits for the device
             probe_weights.copy_(centre)
             probe.evaluate_policy(1, seed=10_000 + gen)
             history[gen].copy_(probe_record)
             env.evaluate_policy(args.episodes, seed=gen * args.episodes)
-            env.es_step(adam=True, lr=args.lr, grad_scale=2.0**-24 / (P * args.sigma), max_norm=10.0)
+            if ranks is not None:  # centred ranks instead of z-scores: evaluate, ranks, step, still without a host round trip
+                env.es_ranks(ranks.data_ptr())
+            env.es_step(adam=True, lr=args.lr, grad_scale=2.0**-24 / (P * args.sigma), max_norm=10.0,
+                        utilities=None if ranks is None else ranks.data_ptr())
     env.sync()
     for gen, row in enumerate(history.cpu().numpy()):
         print(f"generation {gen}: mean return of the centre {row[0] / row[2]:.1f} over {row[2]} episodes")

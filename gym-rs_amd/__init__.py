@@ -54,6 +54,7 @@ from .engine import PpoDesc, ppo_lane
 from .engine import QDesc, Q_DOUBLE, q_lane
 from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
 from .engine import EsDesc, EsStepDesc, ES_MAX_POLICIES, es_noise, es_utilities
+from .engine import EsRanksDesc, ES_RANK_INVALID, es_rank_utilities
 
 __all__ = [
     "ActionReward", "RewardRange", "BoxR", "Discrete", "BatchedEngine", "GymrsError", "InvalidActionError",
@@ -70,4 +71,5 @@ __all__ = [
     "QDesc", "Q_DOUBLE", "q_lane",
     "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",
     "EsDesc", "EsStepDesc", "ES_MAX_POLICIES", "es_noise", "es_utilities",
+    "EsRanksDesc", "ES_RANK_INVALID", "es_rank_utilities",
 ]

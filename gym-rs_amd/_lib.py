@@ -133,6 +133,9 @@ SIGNATURES = {
     "gymrs_get_es_optimizer_state": (C.c_int, [C.c_void_p, f32p, f32p, f32p]),
     "gymrs_es_noise": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, f32p]),
     "gymrs_es_utilities": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
+    # centred ranks (gymrs_es_ranks_desc 24 B) and their host-only definition
+    "gymrs_es_ranks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_es_rank_utilities": (C.c_int, [C.c_void_p, C.c_uint32, f32p, C.POINTER(C.c_uint32)]),
     "gymrs_env_json": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]),
     "gymrs_params_from_json": (C.c_int, [C.c_int, C.c_char_p, C.c_void_p, f64p, C.POINTER(C.c_int)]),
     # one batch over several GPUs in one process

@@ -318,6 +318,18 @@ hipError_t zero_fitness(gymrs_policy_fitness* table, uint32_t n_policies, hipStr
 const PolicyTable<gymrs_policy_fitness> kFitness{&gymrs_engine::fitness_dev, zero_fitness};
 const PolicyTable<gymrs_policy_eval> kEval{&gymrs_engine::eval_dev, launch_policy_eval_identity};
 
+// The evaluation table goes, and with it the scratch of gymrs_es_ranks (launches already enqueued still use it: wait for them).
+gymrs_status discard_eval(gymrs_engine* e)
+{
+    if (gymrs_status st = kEval.discard(e)) return st;
+    if (!e->rank_scratch) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(e->rank_scratch));
+    e->rank_scratch = nullptr;
+    return GYMRS_OK;
+}
+
 // A checked policy set takes the place of the old one, and everything that belongs to a set follows its lifetime rule: what
 // gymrs_set_policy and gymrs_es_init (weights_host == NULL: it writes the set on the device) share.  The ES state is the caller's.
 gymrs_status replace_policy_set(gymrs_engine* e, const gymrs_policy_desc* d, const float* weights_host)
@@ -333,7 +345,7 @@ gymrs_status replace_policy_set(gymrs_engine* e, const gymrs_policy_desc* d, con
     } else if (gymrs_status st = kFitness.discard(e)) {
         return st;
     }
-    if (gymrs_status st = kEval.discard(e)) return st; // the episodic records belong to the set they were played with
+    if (gymrs_status st = discard_eval(e)) return st; // the episodic records belong to the set they were played with
     e->es.evaluated = false;
     return install_weights(e, kPolicyKind, d, weights_host);
 }
@@ -568,7 +580,7 @@ gymrs_status gymrs_set_policy(gymrs_engine* e, const gymrs_policy_desc* d, const
         if (gymrs_status st = discard_q_target(e)) return st;
         if (gymrs_status st = discard_opt_state(e, GYMRS_OPT_HEAD_POLICY)) return st;
         if (gymrs_status st = discard_es(e)) return st;
-        if (gymrs_status st = kEval.discard(e)) return st;
+        if (gymrs_status st = discard_eval(e)) return st;
         return kFitness.discard(e);
     }
     if (gymrs_status st = check_weights(e, kPolicyKind, d, weights_host, "gymrs_set_policy")) return st;
@@ -1248,6 +1260,61 @@ gymrs_status gymrs_es_utilities(const gymrs_policy_eval* records, uint32_t n_pol
     });
     const double sd = es_sd(total2, n_valid);
     for (uint32_t p = 0; p < P; ++p) u_out[p] = es_utility(valid(p), valid(p) ? F(p) : 0.0, mean, sd);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_es_ranks(gymrs_engine* e, const gymrs_es_ranks_desc* d)
+{
+    const std::string who = "gymrs_es_ranks";
+    if (!e) return fail(GYMRS_EINVAL, who + ": NULL engine");
+    if (!d) return fail(GYMRS_EINVAL, who + ": NULL desc");
+    if (gymrs_status st = check_discrete_env(e->kind, who)) return st;
+    if (gymrs_status st = check_policy_set(e, who)) return st;
+    if (d->flags != 0) return fail(GYMRS_EINVAL, who + ": unknown flag bits (flags must be 0)");
+    if (d->reserved != 0) return fail(GYMRS_EINVAL, who + ": reserved must be 0");
+    if (!d->utilities) return fail(GYMRS_EINVAL, who + ": utilities is NULL");
+    if (reinterpret_cast<uintptr_t>(d->utilities) % alignof(float) != 0) return fail(GYMRS_EINVAL, who + ": utilities must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d->rank2) % alignof(uint32_t) != 0) return fail(GYMRS_EINVAL, who + ": rank2 must be 4-byte aligned");
+    const uint32_t P = e->policy.args.n_policies;
+    if (P > kEsMaxPolicies) return fail(GYMRS_EINVAL, who + ": the policy set has more than GYMRS_ES_MAX_POLICIES policies");
+    if (!e->eval_dev) return fail(GYMRS_EINVAL, who + ": the engine has no evaluation table yet (gymrs_evaluate_policy)");
+    HIP_TRY(hipSetDevice(e->device));
+    EsRanksArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.records = e->eval_dev;
+    a.u = d->utilities;
+    a.rank2 = d->rank2;
+    a.P = P;
+    if (P > kEsRankTile) { // (a set of one tile is one launch and needs no scratch)
+        if (!e->rank_scratch) HIP_TRY(hipMalloc(&e->rank_scratch, es_rank_scratch_bytes(P)));
+        es_rank_scratch_rows(a, e->rank_scratch);
+    }
+    HIP_TRY(launch_es_ranks(a, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_es_rank_utilities(const gymrs_policy_eval* records, uint32_t n_policies, float* u_out, uint32_t* rank2_out)
+{
+    const std::string who = "gymrs_es_rank_utilities";
+    if (!records || !u_out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (n_policies == 0 || n_policies > kEsMaxPolicies) return fail(GYMRS_EINVAL, who + ": n_policies must be in 1 .. GYMRS_ES_MAX_POLICIES");
+    auto valid = [&](uint32_t p) { return records[p].episodes > 0; };
+    auto F = [&](uint32_t p) { return es_fitness(records[p].return_sum, records[p].episodes); };
+    std::vector<double> sorted;
+    for (uint32_t p = 0; p < n_policies; ++p)
+        if (valid(p)) sorted.push_back(F(p));
+    std::sort(sorted.begin(), sorted.end()); // (no NaN among them: a strict weak order)
+    const uint32_t n = (uint32_t)sorted.size();
+    for (uint32_t p = 0; p < n_policies; ++p) {
+        uint32_t rank2 = GYMRS_ES_RANK_INVALID;
+        if (valid(p)) {
+            const auto range = std::equal_range(sorted.begin(), sorted.end(), F(p));
+            const uint32_t less = (uint32_t)(range.first - sorted.begin()), equal = (uint32_t)(range.second - range.first);
+            rank2 = 2u * less + equal - 1u;
+        }
+        u_out[p] = es_rank_utility(valid(p), n, (long long)rank2 - (long long)(n - 1u));
+        if (rank2_out) rank2_out[p] = rank2;
+    }
     return GYMRS_OK;
 }
 

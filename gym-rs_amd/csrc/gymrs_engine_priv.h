@@ -232,6 +232,9 @@ struct gymrs_engine {
     // The per-policy episodic records of gymrs_evaluate_policy: policy.args.n_policies records holding the latest call's results, allocated
     // (as identities) at first use after a gymrs_set_policy; every gymrs_set_policy frees it.  Not part of clone or snapshot.
     gymrs_policy_eval* eval_dev = nullptr;
+    // The scratch of gymrs_es_ranks for a set of more than one tile (es_rank_scratch_bytes(n_policies): sorted keys, their policies, the
+    // tiles' counts), allocated at first use; it has the evaluation table's lifetime.  Not part of clone or snapshot.
+    void* rank_scratch = nullptr;
     // The exploration settings (gymrs_set_exploration): what the exploring kernels get by value, so a change takes effect in
     // stream order.  gymrs_set_policy keeps them.  Not part of clone or snapshot.
     ExploreArgs explore{};

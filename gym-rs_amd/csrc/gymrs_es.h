@@ -49,6 +49,9 @@ GYMRS_HD double es_sd(double sum2, double n_valid) { return __builtin_sqrt(sum2 
 
 GYMRS_HD float es_utility(bool valid, double F, double mean, double sd) { return (valid && sd > 0.0) ? (float)((F - mean) / sd) : 0.0f; }
 
+// the centred-rank utility (gymrs_es_ranks): c = rank2 - (n - 1) of a policy among the n valid ones, exact; one f64 division, one cast
+GYMRS_HD float es_rank_utility(bool valid, uint32_t n, long long c) { return (valid && n > 1u) ? (float)((double)c / (double)(2ull * (n - 1u))) : 0.0f; }
+
 // one term of G[s]: false = the term is excluded (q = 0)
 GYMRS_HD bool es_term(float d, float eps, long long& q) { return gradient_fixed(d * eps, q); }
 

@@ -487,4 +487,22 @@ struct EsArgs {
 hipError_t launch_es_init(const EsArgs& a, hipStream_t stream);
 // utilities (or the caller's), gradient, update, the population of generation gen + 1: no host synchronisation among the launches
 hipError_t launch_es_step(const EsArgs& a, hipStream_t stream);
+// ---- centred ranks (gymrs_es_ranks; gymrs_es_ranks.hip) ------------------------------------------------------------------------------
+constexpr uint32_t kEsRankTile = 4096; // policies one workgroup sorts in LDS
+// The scratch of a population of more than one tile, ONE allocation: the sorted keys, their policies and the valid count of every tile.
+constexpr uint32_t es_rank_tiles(uint32_t P) { return (P + kEsRankTile - 1) / kEsRankTile; }
+constexpr size_t es_rank_scratch_bytes(uint32_t P) { return (size_t)es_rank_tiles(P) * (kEsRankTile * 12u + 4u); }
+struct EsRanksArgs {
+    const void* records;      // [P] gymrs_policy_eval, read
+    float* u;                 // [P] the caller's, WRITTEN
+    uint32_t* rank2;          // [P] the caller's or NULL, WRITTEN
+    unsigned long long* keys; // [tiles][T] } the scratch (P > kEsRankTile; else NULL: the single launch needs none)
+    uint32_t* index;          // [tiles][T] }
+    uint32_t* counts;         // [tiles]    }
+    uint32_t P;
+};
+// the scratch of es_rank_scratch_bytes(P) bytes, 16-byte aligned, cut into the three rows of `a`
+void es_rank_scratch_rows(EsRanksArgs& a, void* scratch);
+// one launch (P <= kEsRankTile) or two, in stream order
+hipError_t launch_es_ranks(const EsRanksArgs& a, hipStream_t stream);
 } // namespace gymrs

@@ -180,6 +180,14 @@ class EsStepDesc(C.Structure):
 ES_MAX_POLICIES = 1 << 20  # GYMRS_ES_MAX_POLICIES
 
 
+class EsRanksDesc(C.Structure):
+    """``gymrs_es_ranks_desc`` (include/gymrs_amd.h), 24 bytes: the utilities row, the optional rank2 row, two zero words."""
+    _fields_ = [("utilities", C.c_void_p), ("rank2", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ES_RANK_INVALID = 0xFFFFFFFF  # GYMRS_ES_RANK_INVALID
+
+
 class Exploration(C.Structure):
     """``gymrs_exploration`` (include/gymrs_amd.h), 16 bytes: epsilon = threshold / 65536."""
     _fields_ = [("seed", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
@@ -456,6 +464,17 @@ def es_utilities(records) -> np.ndarray:
     out = np.empty(rec.shape[0], np.float32)
     _check(lib, lib.gymrs_es_utilities(rec.ctypes.data_as(C.c_void_p), rec.shape[0], out.ctypes.data_as(C.POINTER(C.c_float))))
     return out
+
+
+def es_rank_utilities(records) -> Tuple[np.ndarray, np.ndarray]:
+    """``gymrs_es_rank_utilities`` (host only, no GPU): (u f32 [P], rank2 uint32 [P]), the centred, tie-averaged rank utilities of P
+    policies from their episodic records, int64 (P, 8) as ``BatchedEngine.policy_eval`` returns them."""
+    lib = load_library()
+    rec = np.ascontiguousarray(records, dtype=np.int64).reshape(-1, 8)
+    u, rank2 = np.empty(rec.shape[0], np.float32), np.empty(rec.shape[0], np.uint32)
+    _check(lib, lib.gymrs_es_rank_utilities(rec.ctypes.data_as(C.c_void_p), rec.shape[0], u.ctypes.data_as(C.POINTER(C.c_float)),
+                                            rank2.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return u, rank2
 
 
 def params_from_json(kind: int, text: str, params=None):
@@ -1110,6 +1129,14 @@ class BatchedEngine:
     def es_utilities_ptr(self) -> Tuple[int, int]:
         """(device address, n_policies) of the f32 utilities the last ``es_step`` used: zero-copy."""
         return _view(self._lib, self._lib.gymrs_es_utilities_ptr, self._h, C.c_uint32)
+
+    def es_ranks(self, utilities_dev: int, rank2_dev: int = 0, *, flags: int = 0, reserved: int = 0) -> None:
+        """``gymrs_es_ranks``: the centred, tie-averaged rank utilities of every policy from the latest ``evaluate_policy``, written
+        to ``utilities_dev`` (device address of P f32) and, unless 0, twice the average rank to ``rank2_dev`` (P uint32,
+        ``ES_RANK_INVALID`` where a policy played no episode); in stream order with no synchronisation.  Pass ``utilities_dev`` on as
+        ``es_step(utilities=...)``; any policy set will do, ``es_init`` is not needed."""
+        desc = EsRanksDesc(C.c_void_p(utilities_dev or None), C.c_void_p(rank2_dev or None), int(flags), int(reserved))
+        _check(self._lib, self._lib.gymrs_es_ranks(self._h, C.byref(desc)))
 
     # -- epsilon-greedy exploration inside the closed-loop calls ----------------------------------------------
     def set_exploration(self, seed: Optional[int] = 0, *, epsilon: Optional[float] = None, threshold: Optional[int] = None) -> None:

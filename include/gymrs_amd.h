@@ -1089,8 +1089,30 @@ gymrs_status gymrs_sharded_get_policy_eval(gymrs_sharded* h, uint32_t first, uin
  *     n_valid = the number of valid p;  mean = sum(F) / n_valid;  sum2 = sum((F - mean) * (F - mean)) in the same order
  *     sd = sqrt(sum2 / n_valid)
  *     u[p] = (valid[p] && sd > 0) ? (float)((F[p] - mean) / sd) : +0.0f
- *   Or the caller passes its own utilities (device f32 [P]; for instance centred ranks from an argsort on the engine's stream): then
- *   the table is not read.  Rank shaping inside the library is out of scope.
+ *   Or the caller passes its own utilities (device f32 [P]): then the table is not read.  Centred ranks with ties averaged come from
+ *   gymrs_es_ranks (below), on the device and in stream order: hand its row to gymrs_es_step as d->utilities.
+ * Centred ranks (gymrs_es_ranks), from the same table, for any policy set of P <= GYMRS_ES_MAX_POLICIES policies (odd P and a set that
+ * no gymrs_es_init wrote included: random search, PBT and elite selection rank with it too):
+ *     valid[p] = episodes > 0;   F[p] = (double)return_sum / (double)episodes     (one IEEE division; never NaN, never -0.0)
+ *     n        = the number of valid p
+ *     less[p]  = #{ valid q : F[q] <  F[p] }        (IEEE compares on the f64 values)
+ *     equal[p] = #{ valid q : F[q] == F[p] }        (counts p itself)
+ *     rank2[p] = 2 * less[p] + equal[p] - 1         (uint32: twice the 0-based average rank; 0 .. 2n - 2)
+ *     c[p]     = (int64)rank2[p] - (int64)(n - 1)   (exact; the c of the valid p sum to 0)
+ *     u[p]     = (valid[p] && n > 1) ? (float)((double)c[p] / (double)(2 * (n - 1))) : +0.0f      (in [-0.5, 0.5])
+ *     rank2[p] = GYMRS_ES_RANK_INVALID where !valid[p]
+ *   Everything up to c is an integer: the result depends neither on scheduling nor on the order a sort leaves ties in.
+ *   - gymrs_es_ranks(e, d) runs in the engine's stream order and synchronises nothing.  It reads the evaluation table and writes
+ *     d->utilities, d->rank2 (may be NULL) and, for a set of more than 4096 policies, an engine-owned scratch (the sorted keys, their
+ *     policies and the count of every tile of 4096) that is allocated at first use and has the table's lifetime: every gymrs_set_policy
+ *     and gymrs_es_init discards it, and it is not part of clone or snapshot.  No lane array, tick, statistic, weight or ES state is
+ *     read or written; gymrs_es_init is not needed.  A table of identities gives +0.0f / GYMRS_ES_RANK_INVALID everywhere.  The row is
+ *     the caller's own buffer: aliasing the view of gymrs_es_utilities_ptr is not promised.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc; Pendulum; no policy set; no evaluation table yet (naming
+ *     gymrs_evaluate_policy); more than GYMRS_ES_MAX_POLICIES policies; utilities NULL; either pointer not 4-byte aligned; flags or
+ *     reserved != 0.
+ *   - gymrs_es_rank_utilities(records, P, u_out, rank2_out): host only, no GPU: the definition as code (rank2_out may be NULL;
+ *     1 <= P <= GYMRS_ES_MAX_POLICIES).  What the kernels cost next to a sort and two searches in torch: profiles/es_ranks.md.
  * Gradient, per pair j and parameter s:
  *     d = u[2j] - u[2j+1];   t = d * eps(gen, j, s)
  *     t finite and |t| < 2^30:  G[s] += (int64)rint((double)t * 2^24)          otherwise nothing is added and excluded += 1
@@ -1156,6 +1178,15 @@ gymrs_status gymrs_es_utilities_ptr(gymrs_engine* e, float** dev_out, uint32_t* 
 gymrs_status gymrs_get_es_optimizer_state(gymrs_engine* e, float* m_out, float* v_out, float* pw_out);
 gymrs_status gymrs_es_noise(uint64_t seed, uint64_t generation, uint64_t pair, uint32_t s, float* eps_out);
 gymrs_status gymrs_es_utilities(const gymrs_policy_eval* records, uint32_t n_policies, float* u_out);
+#define GYMRS_ES_RANK_INVALID 0xffffffffu
+typedef struct {
+    float* utilities;              /* device f32 [P], 4-byte aligned, required, WRITTEN */
+    uint32_t* rank2;               /* device u32 [P] or NULL, 4-byte aligned, WRITTEN */
+    uint32_t flags;                /* 0 */
+    uint32_t reserved;             /* 0 */
+} gymrs_es_ranks_desc;             /* 24 bytes */
+gymrs_status gymrs_es_ranks(gymrs_engine* e, const gymrs_es_ranks_desc* d);
+gymrs_status gymrs_es_rank_utilities(const gymrs_policy_eval* records, uint32_t n_policies, float* u_out, uint32_t* rank2_out);
 /* What serde_json::to_string(&env) prints for the reference env that lane `lane` stands for: the serde-visible
  * fields in declaration order with the reference's field names -- CartPole: action_space, observation_space
  * {low, high}, render_mode, state {x, x_dot, theta, theta_dot}, metadata {render_modes, render_fps, marker},

@@ -133,6 +133,11 @@ inline float es_noise(std::uint64_t seed, std::uint64_t generation, std::uint64_
     return eps;
 }
 inline void es_utilities(const gymrs_policy_eval* records, std::uint32_t n_policies, float* u_out) { check(gymrs_es_utilities(records, n_policies, u_out)); }
+// The centred, tie-averaged rank utilities of gymrs_es_ranks as code (host only, no GPU); rank2_out may be NULL.
+inline void es_rank_utilities(const gymrs_policy_eval* records, std::uint32_t n_policies, float* u_out, std::uint32_t* rank2_out = nullptr)
+{
+    check(gymrs_es_rank_utilities(records, n_policies, u_out, rank2_out));
+}
 
 // One lane's contribution to gymrs_ppo_gradient (gymrs_ppo_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
 // (lane, parameter) pairs returned; counts (may be null) gets the lane-steps seen and cut, prob (may be null) p[a] of every step.
@@ -479,6 +484,13 @@ public:
         float* p = nullptr;
         check(gymrs_es_utilities_ptr(e_, &p, n_policies));
         return p;
+    }
+    // Centred ranks of the latest evaluate_policy on the device (any policy set): utilities_dev [P] f32 is written, rank2_dev [P] u32
+    // too unless NULL; in stream order.  Pass utilities_dev on as gymrs_es_step_desc::utilities.
+    void es_ranks(float* utilities_dev, std::uint32_t* rank2_dev = nullptr)
+    {
+        const gymrs_es_ranks_desc d{utilities_dev, rank2_dev, 0u, 0u};
+        check(gymrs_es_ranks(e_, &d));
     }
     std::vector<gymrs_policy_fitness> policy_fitness(std::uint32_t first, std::uint32_t count)
     {
