@@ -211,6 +211,26 @@ pub struct GymrsPpoDesc {
     pub reserved: u64,
 }
 
+/// `gymrs_entropy_desc`: what `gymrs_entropy_gradient` runs (include/gymrs_amd.h "Entropy"), 128 bytes: the entropy coefficient, the
+/// record by value (`obs`, and `actions` with `old_prob`), `old_prob` (or null: no KL estimate), the gradient tables of
+/// `gymrs_ppo_desc`, `sums` i64 `[n_sets][2]` (the fixed points of the entropy and k3 KL sums) and `counts` u64 `[n_sets][2]` (or null).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsEntropyDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub scale: f32,
+    pub coef: f32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub old_prob: *const f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub sums: *mut i64,
+    pub counts: *mut u64,
+    pub reserved: u64,
+}
+
 /// `GYMRS_Q_DOUBLE`: the bootstrap action is the first maximum of the ONLINE logits of the successor (Double DQN).
 pub const GYMRS_Q_DOUBLE: u32 = 1;
 
@@ -449,6 +469,12 @@ extern "C" {
     pub fn gymrs_ppo_lane(kind: c_int, hidden: u32, scale: f32, clip_low: f32, clip_high: f32, weights: *const f32, n_steps: u32, x: *const f32,
                           actions: *const u8, advantages: *const f32, old_prob: *const f32, q: *mut i64, excluded: *mut u64, counts: *mut u64,
                           prob: *mut f32) -> c_int;
+    /// the entropy bonus and the k3 KL estimate over a transitions record in one launch, one lane of it on the host, and its log2
+    pub fn gymrs_entropy_gradient(e: *mut GymrsEngine, d: *const GymrsEntropyDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_entropy_lane(kind: c_int, hidden: u32, scale: f32, coef: f32, weights: *const f32, n_steps: u32, x: *const f32, actions: *const u8,
+                              old_prob: *const f32, q: *mut i64, excluded: *mut u64, sums: *mut i64, counts: *mut u64) -> c_int;
+    pub fn gymrs_entropy_log2(v: f32, out: *mut f32) -> c_int;
     /// Q-learning over a transitions record: the engine-owned target set, the two-kernel call, and one lane of it on the host
     pub fn gymrs_q_target_sync(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_q_target_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;

@@ -35,7 +35,10 @@ def main() -> int:
     ap.add_argument("--limit", type=int, default=100, help="max_episode_steps")
     ap.add_argument("--hidden", type=int, default=16, help="H of the critic (0: affine)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--entropy", type=float, default=0.0, help="c_ent: the entropy bonus coefficient (entropy_gradient into the policy's table)")
+    ap.add_argument("--target-kl", type=float, default=None, help="report the k3 KL estimate of every epoch and the first epoch beyond this value")
     args = ap.parse_args()
+    with_entropy = args.entropy != 0.0 or args.target_kl is not None
     n, steps, H, E, dev = args.lanes, args.steps, args.hidden, args.epochs, "cuda:0"
     gamma, lam, lr_pi, lr_v = 0.97, 0.9, 0.02, 0.01
     rng = np.random.default_rng(args.seed)
@@ -64,6 +67,7 @@ def main() -> int:
         g_pi, g_v = (torch.zeros((1, t.size), dtype=torch.int64, device=dev) for t in (policy, critic))
         x_pi, x_v, skipped = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(3))
         counts = torch.zeros((E, 1, 2), dtype=torch.int64, device=dev)  # a row per epoch
+        ent_sums, ent_counts = (torch.zeros((E, 1, 2), dtype=torch.int64, device=dev) for _ in range(2))  # entropy and KL: a row per epoch too
         record = dict(obs=obs.data_ptr(), actions=act.data_ptr(), reward=rew.data_ptr(), done=done.data_ptr(), truncated=trunc.data_ptr(),
                       lane_stride=stride)
         rows = dict(record=record, start_obs=start.data_ptr())
@@ -77,12 +81,17 @@ def main() -> int:
             A, R = adv[:, :n], ret[:, :n]
             norm_adv[:, :n] = (A - A.mean()) / (A.std() + 1e-6)
             counts.zero_()
+            ent_sums.zero_()
+            ent_counts.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for e in range(E):  # nothing in here waits for the device
                 torch.sub(val[:, :n], R, out=coef_v[:, :n])  # d/d phi of 0.5 * mean((V - R)^2)
                 env.ppo_gradient(steps, advantages=norm_adv.data_ptr(), old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(),
                                  counts=counts[e].data_ptr(), clip=args.clip, temperature=1.0, **rows)
+                if with_entropy:  # the bonus goes into the same table: the one apply_gradient below ascends the sum of both
+                    env.entropy_gradient(steps, old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), sums=ent_sums[e].data_ptr(),
+                                         counts=ent_counts[e].data_ptr(), coef=args.entropy, temperature=1.0, **rows)
                 env.policy_gradient(steps, coef=coef_v.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(), critic=True, **rows)
                 env.apply_gradient(grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), skipped=skipped.data_ptr(), adam=True, lr=lr_pi, grad_scale=grad_scale,
                                    ascend=True, zero_grad=True)  # ascend the clipped objective
@@ -101,6 +110,12 @@ def main() -> int:
             print(f"round {r:2d}: {steps * n} sampled transitions, {ends} episode ends, clip fraction per epoch "
                   f"{' '.join(f'{f:.3f}' for f in fractions)}, {int(skipped[0])} updates skipped so far, {epoch_ms:.3f} ms per epoch; greedy validation: "
                   f"{int(reward_sum) / max(1, int(episodes) + n):.1f} steps per episode")
+            if with_entropy:  # read once per round, like counts
+                s, c = ent_sums.cpu().numpy()[:, 0], ent_counts.cpu().numpy()[:, 0]
+                entropy, kl = (s[:, j] * 2.0**-24 / np.maximum(1, c[:, j]) for j in (0, 1))
+                beyond = [e for e in range(E) if args.target_kl is not None and kl[e] > args.target_kl]
+                print(f"          entropy per epoch {' '.join(f'{v:.4f}' for v in entropy)}, KL estimate per epoch {' '.join(f'{v:.5f}' for v in kl)}"
+                      + (f", beyond the target from epoch {beyond[0]}" if beyond else ""))
     env.close()
     return 0
 

@@ -43,6 +43,8 @@ def main() -> int:
     ap.add_argument("--limit", type=int, default=100, help="max_episode_steps")
     ap.add_argument("--hidden", type=int, default=16, help="H of the critic (0: affine)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--entropy", type=float, default=0.0, help="c_ent: the entropy bonus coefficient (entropy_gradient into the policy's table)")
+    ap.add_argument("--target-kl", type=float, default=None, help="report the k3 KL estimate of every epoch and the first epoch beyond this value")
     args = ap.parse_args()
     n, steps, H, dev = args.lanes, args.steps, args.hidden, "cuda:0"
     gamma, lam, lr_pi, lr_v = 0.97, 0.9, 2.0, 0.05
@@ -70,6 +72,8 @@ def main() -> int:
     g_pi, g_v = (torch.zeros((1, t.numel()), dtype=torch.int64, device=dev) for t in (pi_table, v_table))
     x_pi, x_v = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
     counts = torch.zeros((1, 2), dtype=torch.int64, device=dev)
+    with_entropy = args.entropy != 0.0 or args.target_kl is not None
+    ent_sums, ent_counts = (torch.zeros((args.epochs, 1, 2), dtype=torch.int64, device=dev) for _ in range(2))  # entropy and KL: a row per epoch
     torch.cuda.synchronize()
     record = dict(obs=obs.data_ptr(), actions=act.data_ptr(), reward=rew.data_ptr(), done=done.data_ptr(), truncated=trunc.data_ptr(),
                   lane_stride=stride)
@@ -88,13 +92,19 @@ def main() -> int:
         A, R = adv[:, :n], ret[:, :n]
         norm_adv[:, :n] = (A - A.mean()) / (A.std() + 1e-6)
         fractions = []
-        for _ in range(args.epochs):
+        ent_sums.zero_()
+        ent_counts.zero_()
+        for e in range(args.epochs):
             coef_v[:, :n] = val[:, :n] - R  # d/d phi of 0.5 * mean((V - R)^2), V of the record's critic in the first epoch
             for t in (g_pi, g_v, x_pi, x_v, counts):
                 t.zero_()  # the launches ADD
             torch.cuda.synchronize()  # torch wrote on its stream; the launches read on the engine's
             env.ppo_gradient(steps, record=record, start_obs=start.data_ptr(), advantages=norm_adv.data_ptr(), old_prob=old_prob.data_ptr(),
                              grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), counts=counts.data_ptr(), clip=args.clip, temperature=1.0)
+            if with_entropy:  # the bonus goes into the same table: the update below ascends the sum of both
+                env.entropy_gradient(steps, record=record, start_obs=start.data_ptr(), old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(),
+                                     excluded=x_pi.data_ptr(), sums=ent_sums[e].data_ptr(), counts=ent_counts[e].data_ptr(), coef=args.entropy,
+                                     temperature=1.0)
             env.policy_gradient(steps, record=record, start_obs=start.data_ptr(), coef=coef_v.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(),
                                 critic=True)
             env.sync()
@@ -115,6 +125,12 @@ def main() -> int:
         print(f"round {r:2d}: {steps * n} sampled transitions, {ends} episode ends, clip fraction per epoch "
               f"{' '.join(f'{f:.3f}' for f in fractions)}, excluded {int(x_pi[0])} + {int(x_v[0])}; greedy validation: "
               f"{int(reward_sum) / max(1, int(episodes) + n):.1f} steps per episode")
+        if with_entropy:  # read once per round
+            sm, ct = ent_sums.cpu().numpy()[:, 0], ent_counts.cpu().numpy()[:, 0]
+            entropy, kl = (sm[:, j] * 2.0**-24 / np.maximum(1, ct[:, j]) for j in (0, 1))
+            beyond = [e for e in range(args.epochs) if args.target_kl is not None and kl[e] > args.target_kl]
+            print(f"          entropy per epoch {' '.join(f'{v:.4f}' for v in entropy)}, KL estimate per epoch {' '.join(f'{v:.5f}' for v in kl)}"
+                  + (f", beyond the target from epoch {beyond[0]}" if beyond else ""))
     env.close()
     return 0
 

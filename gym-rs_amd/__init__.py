@@ -51,6 +51,7 @@ from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
+from .engine import EntropyDesc, entropy_lane, entropy_log2
 from .engine import QDesc, Q_DOUBLE, q_lane
 from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
 from .engine import EsDesc, EsStepDesc, ES_MAX_POLICIES, es_noise, es_utilities
@@ -68,6 +69,7 @@ __all__ = [
     "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
     "PpoDesc", "ppo_lane",
+    "EntropyDesc", "entropy_lane", "entropy_log2",
     "QDesc", "Q_DOUBLE", "q_lane",
     "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",
     "EsDesc", "EsStepDesc", "ES_MAX_POLICIES", "es_noise", "es_utilities",

@@ -109,6 +109,11 @@ SIGNATURES = {
     "gymrs_ppo_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_ppo_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p, f32p,
                                  C.POINTER(C.c_int64), u64p, u64p, f32p]),
+    # the entropy bonus and the KL estimate over a transitions record (gymrs_entropy_desc 128 B), the host-only lane and the logarithm
+    "gymrs_entropy_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_entropy_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p,
+                                     C.POINTER(C.c_int64), u64p, C.POINTER(C.c_int64), u64p]),
+    "gymrs_entropy_log2": (C.c_int, [C.c_float, f32p]),
     # Q-learning over a transitions record (gymrs_q_desc 120 B), its target set and the host-only lane
     "gymrs_q_target_sync": (C.c_int, [C.c_void_p]),
     "gymrs_q_target_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),

@@ -1,5 +1,5 @@
 // gymrs_engine_learn.hip -- the learner surface of the C ABI (include/gymrs_amd.h): the policy and critic sets, the exploration and sampling
-// settings with their per-step calls and host draws, advantages, gradients, the clipped surrogate and Q-learning (with its target set) over a
+// settings with their per-step calls and host draws, advantages, gradients, the clipped surrogate, the entropy bonus and Q-learning (with its target set) over a
 // transitions record with their host-only lanes, the optimizer with its Adam state and host-only set, the per-policy fitness and evaluation
 // tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
 // object and the refusals shared with the stepping paths: gymrs_engine_priv.h.
@@ -8,6 +8,7 @@
 #include "gymrs_sample.h"
 #include "gymrs_advantages.h"
 #include "gymrs_gradient.h"
+#include "gymrs_entropy.h"
 #include "gymrs_qlearn.h"
 #include "gymrs_optimizer.h"
 #include "gymrs_es.h"
@@ -484,6 +485,65 @@ void gradient_lane(uint32_t H, float scale, const float* weights, uint32_t K, co
     }
 }
 
+// One lane of "Entropy" by the shared text: the kernel's walk with VEC = 1, chunk after chunk.  old_prob == NULL: no KL estimate.
+template <int D, int A>
+void entropy_lane(uint32_t H, float scale, float coef, const float* weights, uint32_t K, const float* x, const uint8_t* actions, const float* old_prob,
+                  int64_t* q, uint64_t* excluded, int64_t* sums_out, uint64_t* counts)
+{
+    const HostWeights w{weights};
+    uint64_t excl = 0;
+    EntropySums<1> sums{};
+    auto emit = [&](uint32_t s, const float (&L)[1]) {
+        long long v;
+        if (!gradient_fixed(L[0], v)) excl += 1;
+        q[s] = v;
+    };
+    const uint32_t chunks = H == 0 ? 1 : (H + kGradientChunk - 1) / kGradientChunk;
+    for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
+        const uint32_t h0 = chunk * kGradientChunk;
+        GradientAffine<D, A, 1> aff{};
+        GradientChunk<D, A, 1> chk{};
+        float db2[A][1] = {};
+        for (uint32_t k = 0; k < K; ++k) {
+            float xs[D][1], y[A][1], g[A][1], hn[1], pr[A][1];
+            bool on[1];
+            for (int j = 0; j < D; ++j) xs[j][0] = x[(size_t)k * D + j];
+            gradient_logits<D, A, 1, 1>(w, H, xs, y);
+            entropy_head<A, 1>(y, scale, coef, g, on, hn, pr);
+            if (chunk == 0) {
+                const uint8_t act[1] = {old_prob ? actions[k] : uint8_t(0)};
+                const float po[1] = {old_prob ? old_prob[k] : 0.0f};
+                if (old_prob)
+                    entropy_sums_step<A, 1, true>(on, hn, pr, act, po, sums);
+                else
+                    entropy_sums_step<A, 1, false>(on, hn, pr, act, po, sums);
+            }
+            if (H == 0) {
+                gradient_affine_step<D, A, 1, true>(xs, g, on, aff);
+            } else {
+                gradient_chunk_step<D, A, 1, true>(w, H, h0, xs, g, on, chk);
+                if (chunk == 0) gradient_bias_step<A, 1, true>(g, on, db2);
+            }
+        }
+        if (H == 0) {
+            gradient_affine_each<D, A, 1>(aff, emit);
+        } else {
+            gradient_chunk_each<D, A, 1>(H, h0, chk, emit);
+            if (chunk == 0) gradient_bias_each<D, A, 1>(H, db2, emit);
+        }
+    }
+    long long v;
+    if (!gradient_fixed(sums.h[0], v)) excl += 1;
+    sums_out[0] = v;
+    if (!gradient_fixed(sums.kl[0], v)) excl += 1;
+    sums_out[1] = v;
+    *excluded = excl;
+    if (counts) {
+        counts[0] = sums.n_h[0];
+        counts[1] = sums.n_kl[0];
+    }
+}
+
 // One lane of "Q-learning" by the shared text: the TD kernel's walk, then the gradient kernel's, with VEC = 1, chunk after chunk.
 template <int D, int A>
 void q_lane(uint32_t H, uint32_t flags, float gamma, float kappa, const float* weights, const float* target_weights, uint32_t K, const float* x,
@@ -893,6 +953,61 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d)
     return GYMRS_OK;
 }
 
+// ---- entropy bonus and KL estimate: the logarithm, the host-side lane and the launch (include/gymrs_amd.h, "Entropy") ---------------
+static bool finite_f(float x) { return x >= -std::numeric_limits<float>::max() && x <= std::numeric_limits<float>::max(); } // (false for a NaN)
+
+gymrs_status gymrs_entropy_log2(float v, float* out)
+{
+    const std::string who = "gymrs_entropy_log2";
+    if (!out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!(v >= 0x1p-126f && finite_f(v))) return fail(GYMRS_EINVAL, who + ": v must be finite and >= 2^-126");
+    *out = entropy_log2(v);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_entropy_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float coef, const float* weights, uint32_t n_steps, const float* x,
+                                const uint8_t* actions, const float* old_prob, int64_t* q, uint64_t* excluded, int64_t sums[2], uint64_t counts[2])
+{
+    const std::string who = "gymrs_entropy_lane";
+    if (gymrs_status st = check_network(kind, hidden, who)) return st;
+    if (!weights || !q || !excluded || !sums || (n_steps != 0 && !x)) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (old_prob && n_steps != 0 && !actions) return fail(GYMRS_EINVAL, who + ": actions is NULL (the KL estimate reads them)");
+    if (!finite_non_negative(scale)) return fail(GYMRS_EINVAL, who + ": scale must be finite and >= 0");
+    if (!finite_f(coef)) return fail(GYMRS_EINVAL, who + ": coef must be finite");
+    if (kind == GYMRS_CARTPOLE)
+        entropy_lane<4, 2>(hidden, scale, coef, weights, n_steps, x, actions, old_prob, q, excluded, sums, counts);
+    else
+        entropy_lane<2, 3>(hidden, scale, coef, weights, n_steps, x, actions, old_prob, q, excluded, sums, counts);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_entropy_gradient(gymrs_engine* e, const gymrs_entropy_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_entropy_gradient"};
+    if (gymrs_status st = c.prologue("gradients are")) return st;
+    if (d->reserved != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    if (gymrs_status st = check_policy_set(e, c.who)) return st;
+    if (gymrs_status st = c.scale(d->scale)) return st;
+    if (!finite_f(d->coef)) return c.refuse("coef must be finite");
+    const gymrs_trajectory& rec = d->record;
+    if (gymrs_status st = c.not_null({{rec.obs, "record.obs"}, {d->start_obs, "start_obs"}, {d->grad, "grad"}, {d->excluded, "excluded"}, {d->sums, "sums"}}))
+        return st;
+    if (d->old_prob)
+        if (gymrs_status st = c.not_null({{rec.actions, "record.actions", " (the KL estimate reads them with old_prob)"}})) return st;
+    const void* actions = d->old_prob ? rec.actions : nullptr;
+    if (gymrs_status st = c.aligned({rec.obs, actions, d->start_obs, d->old_prob}, 16, "every row buffer must be 16-byte aligned")) return st;
+    if (gymrs_status st = c.aligned({d->grad, d->excluded, d->sums, d->counts}, 8, "grad, excluded, sums and counts must be 8-byte aligned")) return st;
+    if (gymrs_status st = c.lane_stride(rec.lane_stride)) return st;
+    if (d->n_steps == 0) return GYMRS_OK;
+    const EntropyArgs a{rec.obs, d->start_obs, static_cast<const uint8_t*>(actions), d->old_prob, reinterpret_cast<unsigned long long*>(d->grad),
+                        reinterpret_cast<unsigned long long*>(d->excluded), reinterpret_cast<unsigned long long*>(d->sums),
+                        reinterpret_cast<unsigned long long*>(d->counts), /*stride, n, gid0*/ rec.lane_stride, e->n, e->gid0, d->n_steps, d->scale, d->coef};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_entropy_gradient(e->kind, a, e->policy.args, e->stream));
+    return GYMRS_OK;
+}
+
 // ---- Q-learning: the target set, the host-side lane and the launch (include/gymrs_amd.h, "Q-learning") -----------------------------
 gymrs_status gymrs_q_target_sync(gymrs_engine* e)
 {
@@ -980,8 +1095,6 @@ gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d)
 }
 
 // ---- the optimizer: the checks, the host-side set and the launch (include/gymrs_amd.h, "Optimizer") -------------------------------
-static bool finite_f(float x) { return x >= -std::numeric_limits<float>::max() && x <= std::numeric_limits<float>::max(); } // (false for a NaN)
-
 // What gymrs_apply_gradient and gymrs_optimizer_set refuse in the values of a descriptor.
 static gymrs_status check_optimizer_values(const gymrs_optimizer_desc* d, const std::string& who)
 {

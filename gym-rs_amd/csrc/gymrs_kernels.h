@@ -413,6 +413,23 @@ struct PpoArgs {
     float clip_low, clip_high;
 };
 hipError_t launch_ppo_gradient(gymrs_env_kind kind, const PpoArgs& a, const PolicyArgs& p, hipStream_t stream);
+// ---- entropy bonus and KL estimate (gymrs_entropy_gradient; gymrs_entropy.hip) --------------------------------------------------
+// A gymrs_entropy_desc as the kernel gets it by value, before the policy set.  Rows are `stride` lanes apart (>= n, a multiple of 16)
+// and 16-byte aligned; grad, excluded, sums and counts are 8-byte aligned and ADDED to.
+struct EntropyArgs {
+    const float* obs;             // [n_steps][obs_dim][stride]; rows 0 .. n_steps - 2 are read
+    const float* start_obs;       // [obs_dim][stride]
+    const uint8_t* actions;       // [n_steps][stride]; read with old_prob only
+    const float* old_prob;        // [n_steps][stride] or NULL: no KL estimate
+    unsigned long long* grad;     // [n_sets][S], S = the set's PolicyArgs::stride
+    unsigned long long* excluded; // [n_sets]
+    unsigned long long* sums;     // [n_sets][2] int64 bit patterns: the entropy, the KL estimate
+    unsigned long long* counts;   // [n_sets][2] or NULL
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    float scale, coef;
+};
+hipError_t launch_entropy_gradient(gymrs_env_kind kind, const EntropyArgs& a, const PolicyArgs& p, hipStream_t stream);
 // ---- Q-learning (gymrs_q_gradient; gymrs_qlearn.hip) ---------------------------------------------------------------------------
 // A gymrs_q_desc as its two kernels get it by value, before the online set (and, for the TD kernel, the target set).  Rows are
 // `stride` lanes apart (>= n, a multiple of 16) and 16-byte aligned; grad, excluded and counts are 8-byte aligned and ADDED to.

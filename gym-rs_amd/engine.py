@@ -132,6 +132,14 @@ class PpoDesc(C.Structure):
                 ("prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class EntropyDesc(C.Structure):
+    """``gymrs_entropy_desc`` (include/gymrs_amd.h), 128 bytes: the record by value, one row in and one optional row in, three tables
+    and an optional pair of counters per set added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float), ("coef", C.c_float), ("record", Trajectory),
+                ("start_obs", C.c_void_p), ("old_prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p), ("sums", C.c_void_p),
+                ("counts", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class QDesc(C.Structure):
     """``gymrs_q_desc`` (include/gymrs_amd.h), 120 bytes: the record by value, two observation buffers in, the td row out, two tables
     and an optional pair of counters per set added to."""
@@ -397,6 +405,47 @@ def ppo_lane(kind: int, hidden: int, weights, x, actions, advantages, old_prob, 
                                    q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), counts.ctypes.data_as(up),
                                    pr.ctypes.data_as(fp) if prob else None))
     return (q, excluded.value, counts, pr) if prob else (q, excluded.value, counts)
+
+
+def entropy_log2(v: float) -> float:
+    """``gymrs_entropy_log2`` (host only, no GPU): the bit-defined f32 log2 of include/gymrs_amd.h, "Entropy", for a finite
+    ``v >= 2**-126``."""
+    lib = load_library()
+    out = C.c_float()
+    _check(lib, lib.gymrs_entropy_log2(float(v), C.byref(out)))
+    return out.value
+
+
+def entropy_lane(kind: int, hidden: int, weights, x, actions=None, old_prob=None, *, coef: float, temperature: Optional[float] = None,
+                 scale: Optional[float] = None):
+    """``gymrs_entropy_lane`` (host only, no GPU): one lane's contribution to ``gymrs_entropy_gradient`` -- the definition of
+    include/gymrs_amd.h, "Entropy", as code.  ``weights``: ONE policy; ``x`` [K][D]; ``actions`` [K] and ``old_prob`` [K] together, or
+    neither (no KL estimate).  Returns (q, excluded, sums, counts): q is int64 [S], the gradient of coef * entropy is q * 2**-24; sums
+    is int64 [2] = the fixed points of (the lane's entropy sum in nats, its k3 KL sum); counts is uint64 [2] = the lane-steps in each."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    size = policy_size(kind, hidden)
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    k = xs.size // _OBS_DIM[kind]
+    if w.size != size or xs.size != k * _OBS_DIM[kind]:
+        raise ValueError(f"entropy_lane needs {size} weights and {_OBS_DIM[kind]} observation components per step")
+    a = po = None
+    if old_prob is not None:
+        if actions is None:
+            raise ValueError("entropy_lane needs actions with old_prob")
+        a = np.ascontiguousarray(actions, dtype=np.uint8).reshape(-1)
+        po = np.ascontiguousarray(old_prob, dtype=np.float32).reshape(-1)
+        if a.size != k or po.size != k:
+            raise ValueError("entropy_lane needs one action and one old probability per step")
+    s = _sampling(0, temperature, scale).scale
+    q = np.zeros(size, np.int64)
+    excluded = C.c_uint64()
+    sums, counts = np.zeros(2, np.int64), np.zeros(2, np.uint64)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    _check(lib, lib.gymrs_entropy_lane(int(kind), int(hidden), float(s), float(coef), w.ctypes.data_as(fp), int(k), xs.ctypes.data_as(fp),
+                                       a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None, po.ctypes.data_as(fp) if po is not None else None,
+                                       q.ctypes.data_as(ip), C.byref(excluded), sums.ctypes.data_as(ip), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return q, excluded.value, sums, counts
 
 
 def q_lane(kind: int, hidden: int, weights, target_weights, x, x_next, actions, reward, done, *, gamma: float, kappa: float = float("inf"),
@@ -1019,6 +1068,22 @@ class BatchedEngine:
                        C.c_void_p(old_prob or None), C.c_void_p(prob or None), C.c_void_p(grad or None), C.c_void_p(excluded or None),
                        C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_ppo_gradient(self._h, C.byref(desc)))
+
+    # -- the entropy bonus and the KL estimate over a transitions record: one launch beside ppo_gradient ----------------
+    def entropy_gradient(self, n_steps: int, *, record, start_obs: int, grad: int, excluded: int, sums: int, coef: float,
+                         old_prob: Optional[int] = None, counts: Optional[int] = None, temperature: Optional[float] = None,
+                         scale: Optional[float] = None, flags: int = 0) -> None:
+        """``gymrs_entropy_gradient``: ADDS the gradient of ``coef`` * (the entropy of the policy at every lane-step, in nats) per
+        policy to ``grad`` and ``excluded`` in the layout of ``ppo_gradient`` (one ``apply_gradient(ascend=True)`` consumes the sum of
+        both), the fixed point (* 2**-24) of the entropy sum and, with ``old_prob`` (the row ``ppo_gradient`` reads), of the k3
+        estimate of KL(recorded || current) to ``sums`` (device int64 [n_policies][2]) and, with ``counts`` (device uint64
+        [n_policies][2]), the lane-steps in each sum.  ``record``: only ``obs`` is read, and ``actions`` with ``old_prob``.  Exactly
+        one of ``temperature`` / ``scale``.  Reads and writes no lane array."""
+        traj = _record("entropy_gradient", self.n_envs, n_steps, record, unread=("actions", "reward", "done"))
+        s = _sampling(0, temperature, scale).scale
+        desc = EntropyDesc(int(n_steps), int(flags), float(s), float(coef), traj, C.c_void_p(start_obs or None), C.c_void_p(old_prob or None),
+                           C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(sums or None), C.c_void_p(counts or None), 0)
+        _check(self._lib, self._lib.gymrs_entropy_gradient(self._h, C.byref(desc)))
 
     # -- Q-learning over a transitions record: a target set, TD errors and the Q-gradient in one call -------------------
     def q_target_sync(self) -> None:

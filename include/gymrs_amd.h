@@ -853,6 +853,84 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d);
 gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
                             const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
                             uint64_t counts[2], float* prob);
+/* Entropy: the entropy bonus of a PPO loss and the KL estimate that stops its epochs, over a transitions record in ONE launch, as
+ * exact fixed-point integers.  gymrs_entropy_gradient(e, d) is a third head beside the score-function head of "gradients" and the
+ * "clipped surrogate": it ADDS to grad[m][s] the fixed point of the lane's f32 sum of  d (coef * Hn) / d theta_s,  Hn = the entropy
+ * (in nats) of the sampling rule's distribution at a lane-step.  The table has the layout of the other two heads, so one
+ * gymrs_apply_gradient(GYMRS_OPT_ASCEND) consumes the sum of the clipped surrogate and this bonus.  All arithmetic is f32, every
+ * operation below is a single IEEE operation, fmaf = the fused multiply-add with ONE rounding, nothing is contracted or reordered,
+ * every `?:` is a select.
+ * The logarithm.  The sampling rule works in base 2 (w[b] = 2^d[b]), so log2 p[b] = d[b] - log2(total) with total in [1, A]: one
+ * small bit-defined log2 is all that is missing.  entropy_log2(v), for v finite and v >= 2^-126:
+ *     v = m * 2^e with m in [1, 2)  (frexp; exact),   t = m - 1.0f  (exact)
+ *     Q(t) = Horner with fmaf from c8 down to c0:  acc = c8; acc = fmaf(acc, t, c7); ... ; acc = fmaf(acc, t, c0)
+ *            c0 .. c8 = 0x1.715466p+0, -0x1.714ef8p-1, 0x1.ebcb78p-2, -0x1.6c7e8ep-2, 0x1.1255d2p-2, -0x1.76f800p-3, 0x1.925438p-4,
+ *                       -0x1.19ef3ap-5, 0x1.739d30p-8
+ *     r = t * Q(t)  (one multiply),   entropy_log2(v) = (float)e + r  (one add)
+ * entropy_log2(1) == +0 exactly and every power of two gives its exponent; near 1 the result keeps its relative accuracy, which the
+ * KL term needs.  Its maximum absolute error against f64 log2 over all 2^23 f32 values of [1, 2), evaluated with true fmaf, is 1.41e-7
+ * (measured: 1.4052e-7, below 1.41e-7; tests/test_entropy_host.py repeats the measurement): the order of P's 6.7e-8 in "sampling".
+ * Per lane-step.  x, the set key, y[], greedy, d[], w[], total, p[] and beta exactly as "gradients" and "sampling" define them
+ * under d->scale; coef = the descriptor's scalar:
+ *     on    = total > 0.0f                      (else the lane-step contributes nothing and is not counted)
+ *     lt    = entropy_log2(total)
+ *     l[b]  = d[b] - lt                         (log2 p[b])
+ *     t[b]  = w[b] > 0.0f ? p[b] * l[b] : +0.0f
+ *     h2    = -(t[0] + t[1] + ..)               (index order; the entropy in bits)
+ *     Hn    = h2 * 0x1.62e430p-1f               (in nats)
+ *     u[b]  = w[b] > 0.0f ? p[b] * (l[b] + h2) : +0.0f
+ *     ck    = (coef * beta) * 0x1.62e430p-1f
+ *     g[b]  = -(ck * u[b])                      (d (coef * Hn) / d y[b])
+ * Backward pass, accumulators, fixed point, excluded, the layout of the table and additivity over engines and launches: exactly the
+ * text of "gradients", with this g and `on` in the place of a < A.  The table receives the gradient of  coef * sum over k of Hn,  a
+ * bonus to ASCEND like the clipped surrogate.  No action and no coefficient row is read.
+ * KL, only when old_prob != NULL (then actions is read too).  For a lane-step with a < A and on, pa = p[a]:
+ *     ratio = pa / old_prob[k][i]               (one IEEE divide, as in "clipped surrogate")
+ *     ok    = ratio is finite and ratio >= 2^-126
+ *     kl    = (ratio - 1.0f) - entropy_log2(ratio) * 0x1.62e430p-1f
+ * the k3 estimator of KL(recorded policy || current policy); it is accumulated and counted only where ok: an old_prob of 0, +inf or
+ * NaN, a negative one and a ratio below 2^-126 are left out.
+ * sums: device int64 [n_sets][2], ADDED to.  Every lane keeps two f32 running sums in step order, +0.0f before k = 0:  sH = sH + Hn
+ * where on,  sK = sK + kl  where counted.  After the walk  sums[set][0] += the fixed point of sH  and  sums[set][1] += that of sK  (q
+ * = rint(L * 2^24) as in "gradients"); a sum that cannot be fixed adds nothing and excluded[set] += 1.  The mean entropy of a set is
+ * sums[set][0] * 2^-24 / counts[set][0], its KL estimate sums[set][1] * 2^-24 / counts[set][1].
+ * counts (may be NULL): device uint64 [n_sets][2], ADDED to, exact: counts[set][0] += 1 per lane-step with on, counts[set][1] += 1 per
+ * lane-step in the KL sum.  What follows from the selects:
+ *   - all logits NaN (or m infinite) gives total == 0: the lane-step adds nothing anywhere and is not counted;
+ *   - an action of weight 0 (a logit gap past -126 / scale, a NaN logit) has t = u = g = +0: its -inf or NaN l[b] reaches no output;
+ *   - the g[b] of a lane-step sum to 0 within rounding; scale == 0 is the uniform policy: Hn = ln A as rounded, g = 0.
+ *   - gymrs_entropy_gradient runs in the engine's stream order and uses the engine only for the stream, the kind, n_envs,
+ *     global_env_offset and the policy set: it reads and writes no lane array.  It reads lanes i < n_envs of every row only: the
+ *     padding lanes may hold anything, NaN included, and count for nothing.  reward, done and truncated of the record are not read
+ *     and may be NULL; actions may be NULL when old_prob is.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: what gymrs_ppo_gradient refuses where it applies (NULL engine or desc, Pendulum, reserved != 0,
+ *     flags != 0, no policy set (naming gymrs_set_policy), scale NaN, infinite or negative, NULL obs / start_obs / grad / excluded, a
+ *     row buffer not 16-byte aligned, a table not 8-byte aligned, lane_stride < n_envs or not a multiple of 16), and: coef NaN or
+ *     infinite, NULL sums, old_prob with NULL actions.
+ *   - gymrs_entropy_lane: host only, no GPU: the definition as code, as gymrs_ppo_lane is for "clipped surrogate".  From ONE policy's
+ *     weights, K = n_steps, one lane's x[K][D], actions[K] and old_prob[K] (both may be NULL: no KL) it SETS q[0..S), *excluded,
+ *     sums[0..2) and counts[0..2) (when counts != NULL).  GYMRS_EINVAL: Pendulum, hidden > 64, NULL arguments, old_prob without
+ *     actions, a bad scale or coef.
+ *   - gymrs_entropy_log2: host only: *out = entropy_log2(v).  GYMRS_EINVAL: NULL out, v NaN, infinite or below 2^-126.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* 0, reserved */
+    float scale;                /* log2(e) / temperature, finite, >= 0, as gymrs_gradient_desc */
+    float coef;                 /* the entropy coefficient c_ent, finite */
+    gymrs_trajectory record;    /* by value; READ: obs, and actions with old_prob; lane_stride >= n_envs, a multiple of 16 */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* old_prob;      /* [K][lane_stride] or NULL (no KL estimate), 16-byte aligned */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned, ADDED to */
+    uint64_t* excluded;         /* device uint64 [n_sets], ADDED to */
+    int64_t* sums;              /* device int64 [n_sets][2], 8-byte aligned, ADDED to */
+    uint64_t* counts;           /* device uint64 [n_sets][2] or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_entropy_desc;           /* 128 bytes */
+gymrs_status gymrs_entropy_gradient(gymrs_engine* e, const gymrs_entropy_desc* d);
+gymrs_status gymrs_entropy_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float coef, const float* weights, uint32_t n_steps, const float* x,
+                                const uint8_t* actions, const float* old_prob, int64_t* q, uint64_t* excluded, int64_t sums[2], uint64_t counts[2]);
+gymrs_status gymrs_entropy_log2(float v, float* out);
 /* Q-learning: TD errors and the Q-gradient over a transitions record, with a target set, Double-DQN action selection and a Huber
  * clamp, as exact fixed-point integers.  The policy network's logits are the Q-values.  gymrs_q_gradient(e, d) writes the TD error of
  * every lane-step to td and ADDS, for every set m and every parameter s of its network, the fixed point of the lane's f32 sum of

@@ -151,6 +151,24 @@ inline std::uint64_t ppo_lane(gymrs_env_kind kind, std::uint32_t hidden, float s
     return excluded;
 }
 
+// One lane's contribution to gymrs_entropy_gradient (gymrs_entropy_lane; host only, no GPU): q[0 .. S) and sums[0 .. 2) are set, the
+// number of excluded sums returned; actions and old_prob may both be null (no KL estimate), counts may be null.  entropy_log2 is the
+// rule's own logarithm.  The definition of include/gymrs_amd.h, "Entropy", as code.
+inline std::uint64_t entropy_lane(gymrs_env_kind kind, std::uint32_t hidden, float scale, float coef, const float* weights, std::uint32_t n_steps,
+                                  const float* x, const std::uint8_t* actions, const float* old_prob, std::int64_t* q, std::int64_t* sums,
+                                  std::uint64_t* counts = nullptr)
+{
+    std::uint64_t excluded = 0;
+    check(gymrs_entropy_lane(kind, hidden, scale, coef, weights, n_steps, x, actions, old_prob, q, &excluded, sums, counts));
+    return excluded;
+}
+inline float entropy_log2(float v)
+{
+    float out = 0.0f;
+    check(gymrs_entropy_log2(v, &out));
+    return out;
+}
+
 // ---- batched form: the shape the hot path is built for ---------------------------------------------
 class VecEnv {
 public:
@@ -443,6 +461,16 @@ public:
     {
         const gymrs_ppo_desc d{n_steps, 0u, scale, clip_low, clip_high, 0u, record, start_obs, advantages, old_prob, prob, grad, excluded, counts, 0};
         check(gymrs_ppo_gradient(e_, &d));
+    }
+    // the entropy bonus and the KL estimate (gymrs_entropy_gradient): ADDS the gradient of coef * the policy's entropy (to ascend) to
+    // grad and excluded in ppo_gradient's layout, the fixed points of the entropy sum and, when old_prob is not null, of the k3 KL
+    // estimate to sums (device int64 [n_sets][2]) and, when counts is not null, the lane-steps in each
+    void entropy_gradient(const gymrs_entropy_desc& d) { check(gymrs_entropy_gradient(e_, &d)); }
+    void entropy_gradient(std::uint32_t n_steps, const gymrs_trajectory& record, const float* start_obs, const float* old_prob, std::int64_t* grad,
+                          std::uint64_t* excluded, std::int64_t* sums, std::uint64_t* counts, float scale, float coef)
+    {
+        const gymrs_entropy_desc d{n_steps, 0u, scale, coef, record, start_obs, old_prob, grad, excluded, sums, counts, 0};
+        check(gymrs_entropy_gradient(e_, &d));
     }
     // Q-learning (include/gymrs_amd.h, "Q-learning"): the target set is a copy of the policy set the engine owns (q_target_sync, in
     // stream order; q_target_ptr is its zero-copy view); q_gradient writes the TD errors to d.td and ADDS the gradient of the Huber

@@ -36,7 +36,7 @@ LIMIT_S = 180  # per measurement
 from bench_policy_rollout import kernel_source_sha16  # noqa: E402
 
 
-def kernel_resources(lib: Path) -> dict:
+def kernel_resources(lib: Path, pattern: str = r"gradient_(?:ppo_)?kernel") -> dict:
     """VGPR / AGPR / SGPR / scratch / spill counts of gradient_kernel<..>, from the code-object metadata (no GPU needed).  Called
     before the HIP runtime is up: it starts child processes."""
     llvm = next((d for d in (Path("/opt/rocm/llvm/bin"), Path(shutil.which("llvm-readelf") or "/nonexistent").parent) if (d / "llvm-readelf").exists()), None)
@@ -49,7 +49,7 @@ def kernel_resources(lib: Path) -> dict:
         for co in sorted(Path(tmp).glob("lib.so.*amdgcn*")):
             notes = subprocess.run([str(llvm / "llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout
             for block in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-                name = re.search(r"\.name:\s+(\S*gradient_(?:ppo_)?kernel\S*)", block)  # gymrs_policy_gradient's and gymrs_ppo_gradient's
+                name = re.search(rf"\.name:\s+(\S*{pattern}\S*)", block)  # by default gymrs_policy_gradient's and gymrs_ppo_gradient's
                 if not name:
                     continue
                 field = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", block).group(1))  # noqa: E731
