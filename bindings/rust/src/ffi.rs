@@ -254,6 +254,71 @@ pub struct GymrsQDesc {
     pub reserved: u64,
 }
 
+/// `gymrs_replay`: a replay store in caller-owned device memory (include/gymrs_amd.h "Replay"), 56 bytes: `s` / `s_next` are
+/// `[D][capacity]`, the rest `[capacity]`; priorities are integers in 0 ..= 2^24 and 0 is never drawn.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsReplay {
+    pub s: *mut f32,
+    pub s_next: *mut f32,
+    pub action: *mut u8,
+    pub reward: *mut f32,
+    pub done: *mut u8,
+    pub priority: *mut u32,
+    pub capacity: u64,
+}
+
+/// `gymrs_replay_push_desc`, 152 bytes: the record flattened into the ring at `head` with one `priority`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsReplayPushDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub final_obs: *const f32,
+    pub store: GymrsReplay,
+    pub head: u64,
+    pub priority: u32,
+    pub pad_: u32,
+    pub reserved: u64,
+}
+
+/// `gymrs_replay_sample_desc`, 176 bytes: `n_samples` entries of `[0, count)` drawn as a function of (priorities, `seed`, `draw`) and
+/// gathered into lane j of `batch` / `start_obs`; `idx`, `prio` (may be null) and `total` are written.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsReplaySampleDesc {
+    pub store: GymrsReplay,
+    pub count: u64,
+    pub n_samples: u32,
+    pub flags: u32,
+    pub seed: u64,
+    pub draw: u64,
+    pub batch: Trajectory,
+    pub start_obs: *mut f32,
+    pub idx: *mut u32,
+    pub prio: *mut u32,
+    pub total: *mut u64,
+    pub reserved: u64,
+}
+
+/// `gymrs_replay_update_desc`, 104 bytes: `priority[idx[j]]` = the rule of `gymrs_replay_priority` on `td[j]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsReplayUpdateDesc {
+    pub store: GymrsReplay,
+    pub idx: *const u32,
+    pub td: *const f32,
+    pub n_samples: u32,
+    pub flags: u32,
+    pub alpha: f32,
+    pub eps: f32,
+    pub cap: f32,
+    pub pad_: f32,
+    pub reserved: u64,
+}
+
 /// `GYMRS_OPT_HEAD_*`: the weight set `gymrs_apply_gradient` updates.
 pub const GYMRS_OPT_HEAD_POLICY: u32 = 0;
 pub const GYMRS_OPT_HEAD_CRITIC: u32 = 1;
@@ -483,6 +548,12 @@ extern "C" {
     pub fn gymrs_q_lane(kind: c_int, hidden: u32, flags: u32, gamma: f32, kappa: f32, weights: *const f32, target_weights: *const f32, n_steps: u32,
                         x: *const f32, x_next: *const f32, actions: *const u8, reward: *const f32, done: *const u8, q: *mut i64, excluded: *mut u64,
                         td: *mut f32, counts: *mut u64) -> c_int;
+    /// Prioritized replay: push, the draw with its gather, the priority update, and the two rules on the host
+    pub fn gymrs_replay_push(e: *mut GymrsEngine, d: *const GymrsReplayPushDesc) -> c_int;
+    pub fn gymrs_replay_sample(e: *mut GymrsEngine, d: *const GymrsReplaySampleDesc) -> c_int;
+    pub fn gymrs_replay_update(e: *mut GymrsEngine, d: *const GymrsReplayUpdateDesc) -> c_int;
+    pub fn gymrs_replay_priority(td: f32, alpha: f32, eps: f32, cap: f32, out: *mut u32) -> c_int;
+    pub fn gymrs_replay_draw(priority: *const u32, count: u64, n_samples: u32, seed: u64, draw: u64, idx: *mut u32, total: *mut u64) -> c_int;
     /// The optimizer: one launch per head, the engine-owned Adam state, and one set of it on the host
     pub fn gymrs_apply_gradient(e: *mut GymrsEngine, d: *const GymrsOptimizerDesc) -> c_int;
     pub fn gymrs_optimizer_reset(e: *mut GymrsEngine, head: u32) -> c_int;

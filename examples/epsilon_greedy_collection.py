@@ -15,7 +15,12 @@ the engine plays it inside the kernel and differentiates it inside the kernel.  
   5. every `--sync-every` rounds copies the online set into the target set with `q_target_sync`;
   6. validates the new policy with a greedy launch (`fitness=True`, no `explore`): fewer episodes ended = longer balancing.
 
-    python examples/epsilon_greedy_collection.py [--lanes 4096] [--steps 64] [--rounds 12]
+With `--replay CAPACITY` step 3 and 4 become prioritized experience replay (include/gymrs_amd.h, "Replay"): the round's record is
+pushed into a ring of CAPACITY transitions in device memory (`replay_push`), and `--updates` times a minibatch of B = lanes transitions
+is drawn in proportion to the priorities (`replay_sample`), differentiated with `q_gradient(1, record=batch, final_obs=batch obs)`,
+re-prioritised from the TD errors it wrote (`replay_update`) and applied with `apply_gradient` -- all on the engine's stream.
+
+    python examples/epsilon_greedy_collection.py [--lanes 4096] [--steps 64] [--rounds 12] [--replay 1048576 [--updates 8]]
 """
 from __future__ import annotations
 
@@ -46,6 +51,8 @@ def main() -> int:
     ap.add_argument("--epsilon", type=float, default=0.5, help="of the first round; halves every third round")
     ap.add_argument("--sync-every", type=int, default=3, help="rounds between two q_target_sync")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--replay", type=int, default=0, metavar="CAPACITY", help="learn from a prioritized replay store of this many transitions")
+    ap.add_argument("--updates", type=int, default=8, help="minibatches per round with --replay")
     args = ap.parse_args()
     n, steps, dev = args.lanes, args.steps, "cuda:0"
     gamma, kappa, lr, explore_seed = 0.97, 1.0, 0.05, 1234
@@ -68,6 +75,20 @@ def main() -> int:
     record = dict(obs=obs.data_ptr(), actions=act.data_ptr(), reward=rew.data_ptr(), done=done.data_ptr(), truncated=trunc.data_ptr(),
                   lane_stride=stride)
     probe = np.arange(0, n, max(1, n // 32))[:32]  # the lanes whose explored mask is recomputed on the host
+    if args.replay:
+        cap = max((args.replay + 15) // 16 * 16, (steps * n + 15) // 16 * 16)
+        ring = dict(s=torch.zeros((4, cap), device=dev), s_next=torch.zeros((4, cap), device=dev), action=torch.zeros(cap, dtype=torch.uint8, device=dev),
+                    reward=torch.zeros(cap, device=dev), done=torch.zeros(cap, dtype=torch.uint8, device=dev),
+                    priority=torch.zeros(cap, dtype=torch.int32, device=dev))
+        store = gymrs.Replay(*(ring[k].data_ptr() for k in ("s", "s_next", "action", "reward", "done", "priority")), cap)
+        b_obs, b_start = (torch.empty((4, stride), dtype=torch.float32, device=dev) for _ in range(2))
+        b_rew, b_td = (torch.empty(stride, dtype=torch.float32, device=dev) for _ in range(2))
+        b_act, b_done = (torch.empty(stride, dtype=torch.uint8, device=dev) for _ in range(2))
+        b_idx, b_prio = (torch.empty(stride, dtype=torch.int32, device=dev) for _ in range(2))
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        batch = dict(obs=b_obs.data_ptr(), actions=b_act.data_ptr(), reward=b_rew.data_ptr(), done=b_done.data_ptr(), lane_stride=stride)
+        draws = 0
 
     for r in range(args.rounds):
         epsilon = args.epsilon * 0.5 ** (r // 3)
@@ -76,8 +97,19 @@ def main() -> int:
         t0 = env.tick()[0]                # row k of the record is the step from tick t0 + k
         # collection and the Q-gradient, back to back on the engine's stream
         env.rollout_transitions(steps, record=record, final_obs=final.data_ptr(), start_obs=start.data_ptr(), explore=True)
-        env.q_gradient(steps, record=record, start_obs=start.data_ptr(), final_obs=final.data_ptr(), td=td.data_ptr(), grad=grad.data_ptr(),
-                       excluded=excluded.data_ptr(), counts=counts.data_ptr(), gamma=gamma, kappa=kappa, double=True)
+        if args.replay:
+            env.replay_push(store, steps, record=record, start_obs=start.data_ptr(), final_obs=final.data_ptr())  # fresh: the highest priority
+            for _ in range(args.updates):
+                env.replay_sample(store, n, seed=args.seed, draw=draws, batch=batch, start_obs=b_start.data_ptr(), idx=b_idx.data_ptr(),
+                                  prio=b_prio.data_ptr(), total=total.data_ptr())
+                env.q_gradient(1, record=batch, start_obs=b_start.data_ptr(), final_obs=b_obs.data_ptr(), td=b_td.data_ptr(), grad=grad.data_ptr(),
+                               excluded=excluded.data_ptr(), counts=counts.data_ptr(), gamma=gamma, kappa=kappa, double=True)
+                env.replay_update(store, n, idx=b_idx.data_ptr(), td=b_td.data_ptr(), alpha=0.6, eps=1e-3, cap=4.0)
+                env.apply_gradient(grad=grad.data_ptr(), excluded=excluded.data_ptr(), lr=lr, grad_scale=2.0**-24 / n, zero_grad=True)
+                draws += 1
+        else:
+            env.q_gradient(steps, record=record, start_obs=start.data_ptr(), final_obs=final.data_ptr(), td=td.data_ptr(), grad=grad.data_ptr(),
+                           excluded=excluded.data_ptr(), counts=counts.data_ptr(), gamma=gamma, kappa=kappa, double=True)
         env.sync()  # torch works on its own stream from here
 
         # which recorded actions were exploratory: recomputed from (global lane id, tick)
@@ -87,8 +119,9 @@ def main() -> int:
 
         # descend the Huber loss in place: grad is the exact fixed-point sum over all lane-steps, times 2^24
         seen, clamped = (int(v) for v in counts[0])
-        weights -= (lr / max(1, seen) * 2.0**-24) * grad[0].double().float()
-        mean_td = float(td[:, :n].abs().mean())
+        if not args.replay:
+            weights -= (lr / max(1, seen) * 2.0**-24) * grad[0].double().float()
+        mean_td = float((b_td[:n] if args.replay else td[:, :n]).abs().mean())
         grad.zero_(), excluded.zero_(), counts.zero_()
         torch.cuda.synchronize()  # the engine reads the weights on its own stream
         if (r + 1) % args.sync_every == 0:
@@ -100,7 +133,9 @@ def main() -> int:
         reward_sum, episodes, _, _ = env.policy_fitness()[0]
         print(f"round {r:2d}: epsilon {threshold / 65536:.4f} ({explored.mean():.1%} of {explored.size} probed steps explored), "
               f"mean |TD| {mean_td:.3f}, {clamped / max(1, seen):.1%} of {seen} lane-steps clamped, "
-              f"{int((trunc[:, :n] != 0).sum())} truncated steps kept; greedy validation: {int(episodes)} episodes ended in {steps} x {n} lane-steps "
+              f"{int((trunc[:, :n] != 0).sum())} truncated steps kept"
+              + (f", store {store.count} of {store.capacity}, mass {int(total[0]) / 2.0**24:.0f} x 2^24" if args.replay else "") + "; "
+              f"greedy validation: {int(episodes)} episodes ended in {steps} x {n} lane-steps "
               f"(mean length {steps * n / max(1, int(episodes)):.1f})")
     env.close()
     return 0

@@ -53,6 +53,7 @@ from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
 from .engine import EntropyDesc, entropy_lane, entropy_log2
 from .engine import QDesc, Q_DOUBLE, q_lane
+from .engine import Replay, ReplayPushDesc, ReplaySampleDesc, ReplayUpdateDesc, REPLAY_MAX_PRIORITY, REPLAY_NONE, replay_priority, replay_draw
 from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
 from .engine import EsDesc, EsStepDesc, ES_MAX_POLICIES, es_noise, es_utilities
 from .engine import EsRanksDesc, ES_RANK_INVALID, es_rank_utilities
@@ -71,6 +72,7 @@ __all__ = [
     "PpoDesc", "ppo_lane",
     "EntropyDesc", "entropy_lane", "entropy_log2",
     "QDesc", "Q_DOUBLE", "q_lane",
+    "Replay", "ReplayPushDesc", "ReplaySampleDesc", "ReplayUpdateDesc", "REPLAY_MAX_PRIORITY", "REPLAY_NONE", "replay_priority", "replay_draw",
     "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",
     "EsDesc", "EsStepDesc", "ES_MAX_POLICIES", "es_noise", "es_utilities",
     "EsRanksDesc", "ES_RANK_INVALID", "es_rank_utilities",

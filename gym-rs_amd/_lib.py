@@ -120,6 +120,12 @@ SIGNATURES = {
     "gymrs_q_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_q_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_float, f32p, f32p, C.c_uint32, f32p, f32p, C.POINTER(C.c_uint8), f32p,
                                C.POINTER(C.c_uint8), C.POINTER(C.c_int64), u64p, f32p, u64p]),
+    # prioritized replay (gymrs_replay_push_desc 152 B, _sample_desc 176 B, _update_desc 104 B) and the two host-only rules
+    "gymrs_replay_push": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_replay_sample": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_replay_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_replay_priority": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
+    "gymrs_replay_draw": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), u64p]),
     # the optimizer (gymrs_optimizer_desc 72 B), its Adam state and the host-only set
     "gymrs_apply_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_optimizer_reset": (C.c_int, [C.c_void_p, C.c_uint32]),

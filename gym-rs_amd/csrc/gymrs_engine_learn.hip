@@ -1,6 +1,6 @@
 // gymrs_engine_learn.hip -- the learner surface of the C ABI (include/gymrs_amd.h): the policy and critic sets, the exploration and sampling
 // settings with their per-step calls and host draws, advantages, gradients, the clipped surrogate, the entropy bonus and Q-learning (with its target set) over a
-// transitions record with their host-only lanes, the optimizer with its Adam state and host-only set, the per-policy fitness and evaluation
+// transitions record, prioritized replay (push, sample, update and the host-only rules) with their host-only lanes, the optimizer with its Adam state and host-only set, the per-policy fitness and evaluation
 // tables.  Host code only: the kernels are behind gymrs_kernels.h.  The engine
 // object and the refusals shared with the stepping paths: gymrs_engine_priv.h.
 #include "gymrs_engine_priv.h"
@@ -10,6 +10,7 @@
 #include "gymrs_gradient.h"
 #include "gymrs_entropy.h"
 #include "gymrs_qlearn.h"
+#include "gymrs_replay.h"
 #include "gymrs_optimizer.h"
 #include "gymrs_es.h"
 
@@ -1091,6 +1092,114 @@ gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d)
                   d->kappa};
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_q_gradient(e->kind, a, e->policy.args, e->q_target.args, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- prioritized replay: the checks, the host-only rules and the launches (include/gymrs_amd.h, "Replay") --------------------------
+// What the three calls refuse in a store.  `rows`: the call reads or writes the transitions, not the priorities alone.
+static gymrs_status check_replay_store(const RecordCall& c, const gymrs_replay& st, bool rows)
+{
+    if (rows)
+        if (gymrs_status s = c.not_null({{st.s, "store.s"}, {st.s_next, "store.s_next"}, {st.action, "store.action"}, {st.reward, "store.reward"},
+                                         {st.done, "store.done"}}))
+            return s;
+    if (gymrs_status s = c.not_null({{st.priority, "store.priority"}})) return s;
+    if (st.capacity < 16 || st.capacity > kReplayMaxCapacity || st.capacity % 16 != 0)
+        return c.refuse("store.capacity must be a multiple of 16 in 16 .. 2^26");
+    if (rows) {
+        if (gymrs_status s = c.aligned({st.s, st.s_next, st.reward, st.priority}, 16, "store.s, s_next, reward and priority must be 16-byte aligned")) return s;
+        if (gymrs_status s = c.aligned({st.action, st.done}, 4, "store.action and done must be 4-byte aligned")) return s;
+    }
+    return c.aligned({st.priority}, 4, "store.priority must be 4-byte aligned");
+}
+
+static ReplayStore replay_store(const gymrs_replay& st) { return ReplayStore{st.s, st.s_next, st.action, st.reward, st.done, st.priority, st.capacity}; }
+
+gymrs_status gymrs_replay_priority(float td, float alpha, float eps, float cap, uint32_t* out)
+{
+    const std::string who = "gymrs_replay_priority";
+    if (!out) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!replay_rule_ok(alpha, eps, cap)) return fail(GYMRS_EINVAL, who + ": needs 2^-126 <= eps <= cap < inf and 0 <= alpha <= 1");
+    *out = replay_priority(td, alpha, eps, cap);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_replay_draw(const uint32_t* priority, uint64_t count, uint32_t n_samples, uint64_t seed, uint64_t draw, uint32_t* idx, uint64_t* total)
+{
+    const std::string who = "gymrs_replay_draw";
+    if (!priority || !idx) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (count == 0 || count > kReplayMaxCapacity) return fail(GYMRS_EINVAL, who + ": count must be in 1 .. 2^26");
+    if (n_samples == 0 || n_samples > kReplayMaxSamples) return fail(GYMRS_EINVAL, who + ": n_samples must be in 1 .. 2^24");
+    replay_draw_host(priority, count, n_samples, seed, draw, idx, total);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_replay_push(gymrs_engine* e, const gymrs_replay_push_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_replay_push"};
+    if (gymrs_status st = c.prologue("replay stores are")) return st;
+    if (d->reserved != 0 || d->pad_ != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    const gymrs_trajectory& rec = d->record;
+    if (gymrs_status st = c.not_null({{rec.obs, "record.obs"}, {rec.actions, "record.actions"}, {rec.reward, "record.reward"}, {rec.done, "record.done"},
+                                      {d->start_obs, "start_obs"}, {d->final_obs, "final_obs"}}))
+        return st;
+    if (gymrs_status st = check_replay_store(c, d->store, true)) return st;
+    if (gymrs_status st = c.aligned({rec.obs, rec.actions, rec.reward, rec.done, rec.truncated, d->start_obs, d->final_obs}, 16,
+                                    "every row buffer must be 16-byte aligned"))
+        return st;
+    if (gymrs_status st = c.lane_stride(rec.lane_stride)) return st;
+    if (d->head >= d->store.capacity) return c.refuse("head must be below store.capacity");
+    if (e->n > d->store.capacity || d->n_steps > d->store.capacity / e->n) return c.refuse("n_steps * n_envs must not exceed store.capacity");
+    if (d->priority > kReplayMaxPriority) return c.refuse("priority must be <= 2^24");
+    if (d->n_steps == 0) return GYMRS_OK;
+    const ReplayPushArgs a{replay_store(d->store), rec.obs, static_cast<const uint8_t*>(rec.actions), rec.reward, rec.done, rec.truncated, d->start_obs,
+                           d->final_obs, /*stride, n, head*/ rec.lane_stride, e->n, d->head, d->n_steps, d->priority};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_replay_push(e->kind, a, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_replay_sample(gymrs_engine* e, const gymrs_replay_sample_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_replay_sample"};
+    if (gymrs_status st = c.prologue("replay stores are")) return st;
+    if (d->reserved != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    const gymrs_trajectory& b = d->batch;
+    if (gymrs_status st = c.not_null({{b.obs, "batch.obs"}, {b.actions, "batch.actions"}, {b.reward, "batch.reward"}, {b.done, "batch.done"},
+                                      {d->start_obs, "start_obs"}, {d->idx, "idx"}, {d->total, "total"}}))
+        return st;
+    if (gymrs_status st = check_replay_store(c, d->store, true)) return st;
+    if (d->count == 0 || d->count > d->store.capacity) return c.refuse("count must be in 1 .. store.capacity");
+    if (d->n_samples == 0 || d->n_samples > kReplayMaxSamples) return c.refuse("n_samples must be in 1 .. 2^24");
+    if (gymrs_status st = c.aligned({b.obs, b.actions, b.reward, b.done, d->start_obs}, 16, "every row buffer must be 16-byte aligned")) return st;
+    if (gymrs_status st = c.aligned({d->idx, d->prio}, 4, "idx and prio must be 4-byte aligned")) return st;
+    if (gymrs_status st = c.aligned({d->total}, 8, "total must be 8-byte aligned")) return st;
+    if (b.lane_stride < d->n_samples || b.lane_stride % 16 != 0) return c.refuse("batch.lane_stride must be >= n_samples and a multiple of 16");
+    HIP_TRY(hipSetDevice(e->device));
+    if (d->store.capacity > kReplayTile && !e->replay_scratch) HIP_TRY(hipMalloc(&e->replay_scratch, kReplayScratchBytes)); // (a store of one tile needs none)
+    const ReplaySampleArgs a{replay_store(d->store), d->count, d->seed, d->draw, b.obs, static_cast<uint8_t*>(b.actions), b.reward, b.done, d->start_obs,
+                             d->idx, d->prio, reinterpret_cast<unsigned long long*>(d->total),
+                             d->store.capacity > kReplayTile ? static_cast<unsigned long long*>(e->replay_scratch) : nullptr, b.lane_stride, d->n_samples};
+    HIP_TRY(launch_replay_sample(e->kind, a, e->stream));
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_replay_update(gymrs_engine* e, const gymrs_replay_update_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_replay_update"};
+    if (gymrs_status st = c.prologue("replay stores are")) return st;
+    if (d->reserved != 0 || f2u(d->pad_) != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    if (gymrs_status st = c.not_null({{d->idx, "idx"}, {d->td, "td"}})) return st;
+    if (gymrs_status st = check_replay_store(c, d->store, false)) return st;
+    if (d->n_samples > kReplayMaxSamples) return c.refuse("n_samples must be <= 2^24");
+    if (gymrs_status st = c.aligned({d->idx, d->td}, 4, "idx and td must be 4-byte aligned")) return st;
+    if (!replay_rule_ok(d->alpha, d->eps, d->cap)) return c.refuse("needs 2^-126 <= eps <= cap < inf and 0 <= alpha <= 1");
+    const ReplayUpdateArgs a{d->store.priority, d->store.capacity, d->idx, d->td, d->n_samples, d->alpha, d->eps, d->cap};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_replay_update(a, e->stream));
     return GYMRS_OK;
 }
 

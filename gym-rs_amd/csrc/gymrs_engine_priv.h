@@ -235,6 +235,9 @@ struct gymrs_engine {
     // The scratch of gymrs_es_ranks for a set of more than one tile (es_rank_scratch_bytes(n_policies): sorted keys, their policies, the
     // tiles' counts), allocated at first use; it has the evaluation table's lifetime.  Not part of clone or snapshot.
     void* rank_scratch = nullptr;
+    // The scratch of gymrs_replay_sample for a store of more than one tile (kReplayScratchBytes: tile sums, tile bases, the total),
+    // allocated at first use and kept until the engine goes.  Not part of clone or snapshot.
+    void* replay_scratch = nullptr;
     // The exploration settings (gymrs_set_exploration): what the exploring kernels get by value, so a change takes effect in
     // stream order.  gymrs_set_policy keeps them.  Not part of clone or snapshot.
     ExploreArgs explore{};

@@ -452,6 +452,61 @@ struct QArgs {
 };
 // online and target differ in `weights` alone: both sets are keyed by the policy's key
 hipError_t launch_q_gradient(gymrs_env_kind kind, const QArgs& a, const PolicyArgs& online, const PolicyArgs& target, hipStream_t stream);
+// ---- prioritized replay (gymrs_replay_push / _sample / _update; gymrs_replay.hip) ------------------------------------------------
+constexpr uint32_t kReplayTile = 4096;        // priorities one workgroup sums, scans and searches
+constexpr uint32_t kReplayMaxTiles = 1u << 14; // a store of 2^26 entries
+// The scratch of a draw from a store of more than one tile, ONE allocation of fixed size: sums [kReplayMaxTiles], bases
+// [kReplayMaxTiles] and the total, all uint64.
+constexpr size_t kReplayScratchBytes = (2u * (size_t)kReplayMaxTiles + 2u) * sizeof(unsigned long long);
+// A gymrs_replay as the kernels get it: [D][capacity] observation rows, [capacity] everything else; capacity a multiple of 16
+struct ReplayStore {
+    float* s;
+    float* s_next;
+    uint8_t* action;
+    float* reward;
+    uint8_t* done;
+    uint32_t* priority;
+    uint64_t capacity;
+};
+struct ReplayPushArgs {
+    ReplayStore st;
+    const float* obs;         // [n_steps][D][stride]
+    const uint8_t* actions;   // [n_steps][stride]
+    const float* reward;      // [n_steps][stride]
+    const uint8_t* done;      // [n_steps][stride]
+    const uint8_t* truncated; // [n_steps][stride] or NULL
+    const float* start_obs;   // [D][stride]
+    const float* final_obs;   // [n_steps][D][stride]; read on ended lane-steps only
+    uint64_t stride, n, head; // head < capacity; n_steps * n <= capacity
+    uint32_t n_steps, priority;
+};
+struct ReplaySampleArgs {
+    ReplayStore st;
+    uint64_t count, seed, draw;
+    float* obs;               // [D][stride]: s'
+    uint8_t* actions;         // [stride]
+    float* reward;            // [stride]
+    uint8_t* done;            // [stride]
+    float* start_obs;         // [D][stride]: s
+    uint32_t* idx;            // [B]
+    uint32_t* prio;           // [B] or NULL
+    unsigned long long* total;
+    unsigned long long* scratch; // kReplayScratchBytes, or NULL for a store of one tile
+    uint64_t stride;
+    uint32_t B;
+};
+struct ReplayUpdateArgs {
+    uint32_t* priority;
+    uint64_t capacity;
+    const uint32_t* idx;
+    const float* td;
+    uint32_t B;
+    float alpha, eps, cap;
+};
+hipError_t launch_replay_push(gymrs_env_kind kind, const ReplayPushArgs& a, hipStream_t stream);
+// one launch (capacity <= kReplayTile) or three, in stream order
+hipError_t launch_replay_sample(gymrs_env_kind kind, const ReplaySampleArgs& a, hipStream_t stream);
+hipError_t launch_replay_update(const ReplayUpdateArgs& a, hipStream_t stream);
 // ---- the optimizer (gymrs_apply_gradient; gymrs_optimizer.hip) -----------------------------------------------------------------
 // A gymrs_optimizer_desc as its kernel gets it by value, with the buffers of the head it names.  Every table is [n_sets][S] (pw
 // [n_sets][2], excluded [n_sets]); grad, excluded and skipped are 8-byte aligned.  S <= kMaxOptimizerParams.

@@ -12,7 +12,8 @@
 //   key     = (seed lo, seed hi)
 //   counter = (gid lo, gid hi, tick lo, (tick hi & 0xffff) | stream << 16)
 //   stream 0 = reset sampling, stream 1 = synthetic action generation (bench / tests), stream 2 = epsilon-greedy exploration,
-//   stream 3 = softmax action sampling, stream 4 = the noise of evolution strategies (gid = the pair, tick = generation and parameter)
+//   stream 3 = softmax action sampling, stream 4 = the noise of evolution strategies (gid = the pair, tick = generation and parameter),
+//   stream 5 = the draws of prioritized replay (gid = sample j >> 2, tick = the draw counter; gymrs_replay.h)
 #pragma once
 #include "gymrs_math.h"
 

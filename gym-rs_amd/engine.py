@@ -151,6 +151,39 @@ class QDesc(C.Structure):
 Q_DOUBLE = 1  # GYMRS_Q_DOUBLE
 
 
+class Replay(C.Structure):
+    """``gymrs_replay`` (include/gymrs_amd.h), 56 bytes: the store in caller-owned device memory.  ``s`` / ``s_next`` are
+    [D][capacity] f32, the rest [capacity].  ``head`` and ``count`` (plain attributes, not part of the struct) are the ring position
+    and the fill that the C caller advances itself: ``BatchedEngine.replay_push`` keeps them here."""
+    _fields_ = [("s", C.c_void_p), ("s_next", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("priority", C.c_void_p), ("capacity", C.c_uint64)]
+    head = 0
+    count = 0
+
+
+class ReplayPushDesc(C.Structure):
+    """``gymrs_replay_push_desc`` (include/gymrs_amd.h), 152 bytes."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("record", Trajectory), ("start_obs", C.c_void_p), ("final_obs", C.c_void_p),
+                ("store", Replay), ("head", C.c_uint64), ("priority", C.c_uint32), ("pad_", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class ReplaySampleDesc(C.Structure):
+    """``gymrs_replay_sample_desc`` (include/gymrs_amd.h), 176 bytes."""
+    _fields_ = [("store", Replay), ("count", C.c_uint64), ("n_samples", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+                ("draw", C.c_uint64), ("batch", Trajectory), ("start_obs", C.c_void_p), ("idx", C.c_void_p), ("prio", C.c_void_p),
+                ("total", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class ReplayUpdateDesc(C.Structure):
+    """``gymrs_replay_update_desc`` (include/gymrs_amd.h), 104 bytes."""
+    _fields_ = [("store", Replay), ("idx", C.c_void_p), ("td", C.c_void_p), ("n_samples", C.c_uint32), ("flags", C.c_uint32),
+                ("alpha", C.c_float), ("eps", C.c_float), ("cap", C.c_float), ("pad_", C.c_float), ("reserved", C.c_uint64)]
+
+
+REPLAY_MAX_PRIORITY = 1 << 24  # the priority of a fresh transition and of an unknown error
+REPLAY_NONE = 0xFFFFFFFF       # idx of a draw from a store without mass
+
+
 class OptimizerDesc(C.Structure):
     """``gymrs_optimizer_desc`` (include/gymrs_amd.h), 72 bytes: head, kind, flags, seven floats, two tables read (and zeroed with
     ``OPT_ZERO_GRAD``), one optional counter added to."""
@@ -513,6 +546,26 @@ def es_utilities(records) -> np.ndarray:
     out = np.empty(rec.shape[0], np.float32)
     _check(lib, lib.gymrs_es_utilities(rec.ctypes.data_as(C.c_void_p), rec.shape[0], out.ctypes.data_as(C.POINTER(C.c_float))))
     return out
+
+
+def replay_priority(td: float, *, alpha: float, eps: float, cap: float) -> int:
+    """``gymrs_replay_priority`` (host only, no GPU): the integer priority in 1 .. 2**24 of a TD error, the rule of
+    include/gymrs_amd.h, "Replay": round(2**24 * (min(|td| + eps, cap) / cap) ** alpha) in the bit-defined f32 arithmetic."""
+    lib = load_library()
+    out = C.c_uint32()
+    _check(lib, lib.gymrs_replay_priority(float(td), float(alpha), float(eps), float(cap), C.byref(out)))
+    return out.value
+
+
+def replay_draw(priority, n_samples: int, *, seed: int, draw: int) -> Tuple[np.ndarray, int]:
+    """``gymrs_replay_draw`` (host only, no GPU): (idx uint32 [n_samples], total) of the stratified proportional draw of
+    include/gymrs_amd.h, "Replay", over the priorities ``priority`` [count]."""
+    lib = load_library()
+    p = np.ascontiguousarray(priority, dtype=np.uint32).reshape(-1)
+    idx, total = np.empty(max(int(n_samples), 0), np.uint32), C.c_uint64()
+    _check(lib, lib.gymrs_replay_draw(p.ctypes.data_as(C.POINTER(C.c_uint32)), p.size, int(n_samples), int(seed) & (2**64 - 1),
+                                      int(draw) & (2**64 - 1), idx.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(total)))
+    return idx, total.value
 
 
 def es_rank_utilities(records) -> Tuple[np.ndarray, np.ndarray]:
@@ -1109,6 +1162,40 @@ class BatchedEngine:
         desc = QDesc(int(n_steps), f, float(gamma), float(kappa), traj, C.c_void_p(start_obs or None), C.c_void_p(final_obs or None),
                      C.c_void_p(td or None), C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_q_gradient(self._h, C.byref(desc)))
+
+    # -- prioritized replay: a store in caller-owned device memory, filled, drawn from and re-prioritised on the engine's stream -----
+    def replay_push(self, store: Replay, n_steps: int, *, record, start_obs: int, final_obs: int, priority: int = REPLAY_MAX_PRIORITY,
+                    head: Optional[int] = None, flags: int = 0) -> None:
+        """``gymrs_replay_push``: flatten a transitions record (``rollout_transitions``) into the ring at ``store.head`` (or ``head``),
+        entry (head + k * n_envs + i) % capacity for step k and lane i, every one with ``priority``.  A truncated step is stored with
+        done = 0 and its final observation as successor.  Afterwards ``store.head`` and ``store.count`` are advanced."""
+        traj = _record("replay_push", self.n_envs, n_steps, record)
+        at = store.head if head is None else int(head)
+        desc = ReplayPushDesc(int(n_steps), int(flags), traj, C.c_void_p(start_obs or None), C.c_void_p(final_obs or None), store, at,
+                              int(priority), 0, 0)
+        _check(self._lib, self._lib.gymrs_replay_push(self._h, C.byref(desc)))
+        pushed = int(n_steps) * self.n_envs
+        store.head = (at + pushed) % store.capacity
+        store.count = min(store.capacity, store.count + pushed)
+
+    def replay_sample(self, store: Replay, n_samples: int, *, seed: int, draw: int, batch, start_obs: int, idx: int, total: int,
+                      prio: Optional[int] = None, count: Optional[int] = None, flags: int = 0) -> None:
+        """``gymrs_replay_sample``: draw ``n_samples`` entries of [0, ``store.count``) in proportion to their priorities (stratified; a
+        pure function of the priorities, ``seed`` and ``draw``) and gather them into lane j of ``batch`` (``obs`` = the successor,
+        ``actions``, ``reward``, ``done``) and ``start_obs``: what ``q_gradient`` reads with n_steps = 1, final_obs = batch obs.
+        ``idx`` (uint32 [n_samples]), ``total`` (one uint64) and optionally ``prio`` (uint32 [n_samples]) are device addresses."""
+        traj = _record("replay_sample", int(n_samples), 1, batch)
+        desc = ReplaySampleDesc(store, store.count if count is None else int(count), int(n_samples), int(flags), int(seed) & (2**64 - 1),
+                                int(draw) & (2**64 - 1), traj, C.c_void_p(start_obs or None), C.c_void_p(idx or None), C.c_void_p(prio or None),
+                                C.c_void_p(total or None), 0)
+        _check(self._lib, self._lib.gymrs_replay_sample(self._h, C.byref(desc)))
+
+    def replay_update(self, store: Replay, n_samples: int, *, idx: int, td: int, alpha: float, eps: float, cap: float, flags: int = 0) -> None:
+        """``gymrs_replay_update``: priority[idx[j]] = ``replay_priority(td[j])`` for j < n_samples, from the ``idx`` row of
+        ``replay_sample`` and the ``td`` row of ``q_gradient``; an index >= capacity is skipped."""
+        desc = ReplayUpdateDesc(store, C.c_void_p(idx or None), C.c_void_p(td or None), int(n_samples), int(flags), float(alpha), float(eps),
+                                float(cap), 0.0, 0)
+        _check(self._lib, self._lib.gymrs_replay_update(self._h, C.byref(desc)))
 
     # -- the optimizer: SGD or Adam per set, from a gradient table into the engine's own weights, in one launch --------------
     def apply_gradient(self, *, grad: int, excluded: int, lr: float, grad_scale: float, critic: bool = False, adam: bool = False,

@@ -1004,6 +1004,99 @@ gymrs_status gymrs_q_gradient(gymrs_engine* e, const gymrs_q_desc* d);
 gymrs_status gymrs_q_lane(gymrs_env_kind kind, uint32_t hidden, uint32_t flags, float gamma, float kappa, const float* weights,
                           const float* target_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
                           const float* reward, const uint8_t* done, int64_t* q, uint64_t* excluded, float* td, uint64_t* counts);
+/* Replay: prioritized experience replay on the device.  A store in caller-owned device memory (the engine owns none of it; it may be
+ * far larger than the engine) and three calls that fill it, draw from it and re-prioritise it.  Priorities are integers in 0 .. 2^24
+ * (0 is never drawn) and the draw is integers alone: a draw is a pure function of (priorities, seed, draw counter), independent of
+ * scheduling and of how the work is tiled.  The sampled minibatch is what gymrs_q_gradient reads with n_steps = 1.
+ * The store: s and s_next are [D][capacity] f32 (component j of entry e at j * capacity + e), action / reward / done / priority are
+ * [capacity]; capacity is a multiple of 16 in 16 .. 2^26.  The kernels move four entries per access: s, s_next, reward and
+ * priority are 16-byte aligned, action and done 4-byte (gymrs_replay_update writes single priorities: 4-byte there).
+ * All three calls run on the engine's stream in stream order.  They use the engine for the stream, the kind, n_envs (push) and obs_dim
+ * only and read and write no lane array.  CartPole and MountainCar only.
+ * gymrs_replay_push(e, d) flattens a transitions record (the rows of gymrs_rollout_transitions) into the ring: for k < K = n_steps and
+ * i < n_envs, entry (head + k * n_envs + i) % capacity receives
+ *     s = (k == 0 ? start_obs : obs[k-1]);  action = actions[k];  reward = reward[k]
+ *     ended = done[k] != 0 || (truncated != NULL && truncated[k] != 0);  s_next = ended ? final_obs[k] : obs[k]   (the select of "Q-learning")
+ *     done = done[k] != 0 ? 1 : 0      (a truncated step is stored with done = 0 and bootstraps from its final observation)
+ *     priority = d->priority
+ * K * n_envs <= capacity and head < capacity are required.  The caller advances head and count itself (both are deterministic: there is
+ * no device cursor).  Padding lanes are not pushed.  n_steps == 0 is a no-op after the checks.
+ * The priority rule (gymrs_replay_priority; what gymrs_replay_update applies per sample).  f32, every operation a single IEEE operation,
+ * entropy_log2 as in "Entropy" (gymrs_entropy_log2), sample_weight = the 2^d of "sampling":
+ *     v = fabsf(td) + eps;   v = !(v <= cap) ? cap : v          (NaN and +inf land on cap: an unknown error has the highest priority)
+ *     d = alpha * (entropy_log2(v) - entropy_log2(cap));   d = d > 0.0f ? 0.0f : d
+ *     w = sample_weight(d);   p = (uint32_t)rintf(w * 16777216.0f);   p = p < 1 ? 1 : p
+ * Preconditions, refused otherwise: 2^-126 <= eps <= cap < inf, 0 <= alpha <= 1.  alpha = 0 gives p = 2^24 everywhere: uniform replay.
+ * gymrs_replay_update(e, d) writes priority[idx[j]] = p(td[j]) for j < n_samples; an idx[j] >= capacity is skipped (the 0xffffffff of
+ * an empty draw among them).  Duplicate indices of one draw carry the same td; where they carry different values, one of them wins.
+ * The draw (gymrs_replay_draw; gymrs_replay_sample).  Stratified, proportional, all integers; B = n_samples:
+ *     P[e] = the inclusive prefix sum (uint64) of priority[0 .. count);  T = P[count-1] (< 2^50);  q = T / B;  rem = T % B
+ *     for sample j:  lo = j * q + min(j, rem);  w = q + (j < rem)
+ *                    r = word (j & 3) of the Philox block (seed, gid = j >> 2, tick = draw, stream 5)   (the low 48 bits of draw count)
+ *                    o = floor(r * w / 2^32);  u = min(lo + o, T - 1)
+ *                    idx[j] = the smallest e with P[e] > u          (an entry of priority 0 is never drawn, whatever its position)
+ *     *total = T.  T == 0: idx[j] = 0xffffffff and prio[j] = 0 for every j, and no batch element is written.
+ * gymrs_replay_sample also gathers the minibatch, in the layout gymrs_q_gradient reads with n_steps = 1, at lane j:
+ *     start_obs[c * stride + j] = s,  batch.obs[c * stride + j] = s_next  (c < D, stride = batch.lane_stride >= B, a multiple of 16),
+ *     batch.actions[j], batch.reward[j], batch.done[j];  batch.truncated is ignored;  prio[j] = priority[idx[j]] (prio may be NULL): the
+ *     numerators of importance weights, with *total their denominator.  Padding lanes keep their bytes.
+ * A learner then calls gymrs_q_gradient on an engine of n_envs == B with record = batch, final_obs = batch.obs, truncated = NULL (td may
+ * not alias an input, final_obs may equal obs), and gymrs_replay_update with the td row it wrote.  The scratch of a draw from a store
+ * of more than 4096 entries (256 KB) is engine-owned and allocated at first use.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine, desc or required pointer (everything but truncated and prio), Pendulum, reserved or
+ *     flags != 0, a row buffer (s, s_next, reward, priority, the record's and the batch's rows) not 16-byte aligned, action / done / idx /
+ *     prio / td (and the priority row of an update) not 4-byte aligned, total not 8-byte aligned, capacity out of range or not a multiple of 16, count == 0 or > capacity,
+ *     n_samples outside 1 .. 2^24, head >= capacity, K * n_envs > capacity, priority > 2^24, a bad alpha / eps / cap, lane_stride below
+ *     n_envs (push) or n_samples (sample) or not a multiple of 16.
+ *   - gymrs_replay_priority, gymrs_replay_draw: host only, no GPU: the definitions as code.  GYMRS_EINVAL for a NULL argument, a bad
+ *     alpha / eps / cap, count == 0 or > 2^26, n_samples outside 1 .. 2^24.
+ * Out of scope: importance-sampling weights inside the kernels (gymrs_q_gradient has no per-sample weight row; prio[] and total give a
+ * learner all it needs to form them), n-step returns, a sharded store.  The ABI version stays 3: the feature is detected by the symbol. */
+typedef struct {            /* caller-owned device memory, like a record; 56 bytes */
+    float*    s;            /* [D][capacity]  16-byte aligned */
+    float*    s_next;       /* [D][capacity] */
+    uint8_t*  action;       /* [capacity] */
+    float*    reward;       /* [capacity] */
+    uint8_t*  done;         /* [capacity]   1 = do not bootstrap */
+    uint32_t* priority;     /* [capacity]   integer priorities, 0 .. 2^24; 0 = never drawn */
+    uint64_t  capacity;     /* multiple of 16, 16 .. 2^26 */
+} gymrs_replay;
+typedef struct {
+    uint32_t n_steps, flags;    /* K; 0 */
+    gymrs_trajectory record;    /* by value; READ: obs, actions, reward, done, truncated (may be NULL); lane_stride >= n_envs */
+    const float* start_obs;     /* [D][lane_stride] */
+    const float* final_obs;     /* [K][D][lane_stride]; read on ended lane-steps only */
+    gymrs_replay store;
+    uint64_t head;              /* < capacity: where entry (k = 0, i = 0) goes */
+    uint32_t priority, pad_;    /* <= 2^24; 0 */
+    uint64_t reserved;          /* 0 */
+} gymrs_replay_push_desc;       /* 152 bytes */
+typedef struct {
+    gymrs_replay store;
+    uint64_t count;             /* entries [0, count) take part, 1 .. capacity */
+    uint32_t n_samples, flags;  /* B, 1 .. 2^24; 0 */
+    uint64_t seed, draw;
+    gymrs_trajectory batch;     /* by value; WRITTEN: obs [1][D][lane_stride], actions, reward, done; truncated is ignored */
+    float* start_obs;           /* [D][lane_stride], WRITTEN */
+    uint32_t* idx;              /* [B], WRITTEN */
+    uint32_t* prio;             /* [B] or NULL, WRITTEN */
+    uint64_t* total;            /* one uint64, WRITTEN */
+    uint64_t reserved;          /* 0 */
+} gymrs_replay_sample_desc;     /* 176 bytes */
+typedef struct {
+    gymrs_replay store;         /* only priority and capacity are used; the other pointers may be NULL */
+    const uint32_t* idx;        /* [B] */
+    const float* td;            /* [B] */
+    uint32_t n_samples, flags;  /* B, 0 .. 2^24; 0 */
+    float alpha, eps, cap, pad_;
+    uint64_t reserved;          /* 0 */
+} gymrs_replay_update_desc;     /* 104 bytes */
+gymrs_status gymrs_replay_push(gymrs_engine* e, const gymrs_replay_push_desc* d);
+gymrs_status gymrs_replay_sample(gymrs_engine* e, const gymrs_replay_sample_desc* d);
+gymrs_status gymrs_replay_update(gymrs_engine* e, const gymrs_replay_update_desc* d);
+gymrs_status gymrs_replay_priority(float td, float alpha, float eps, float cap, uint32_t* out);
+gymrs_status gymrs_replay_draw(const uint32_t* priority, uint64_t count, uint32_t n_samples, uint64_t seed, uint64_t draw, uint32_t* idx,
+                               uint64_t* total);
 /* Optimizer: the weight update itself, SGD or Adam, per set, from the fixed-point table of "gradients" / the clipped surrogate /
  * "Q-learning" straight into the engine's weight buffers.  gymrs_apply_gradient(e, d) updates every set of ONE head in ONE launch.
  * d->head is GYMRS_OPT_HEAD_POLICY (the policy set; S = gymrs_policy_size) or GYMRS_OPT_HEAD_CRITIC (the critic set; S =

@@ -115,6 +115,22 @@ inline std::uint64_t q_lane(gymrs_env_kind kind, std::uint32_t hidden, std::uint
     return excluded;
 }
 
+// The two rules of include/gymrs_amd.h, "Replay", as code (host only, no GPU): the integer priority in 1 .. 2^24 of a TD error, and the
+// stratified proportional draw over priority[0 .. count), which sets idx[0 .. n_samples) and returns the total mass.
+inline std::uint32_t replay_priority(float td, float alpha, float eps, float cap)
+{
+    std::uint32_t p = 0;
+    check(gymrs_replay_priority(td, alpha, eps, cap, &p));
+    return p;
+}
+inline std::uint64_t replay_draw(const std::uint32_t* priority, std::uint64_t count, std::uint32_t n_samples, std::uint64_t seed, std::uint64_t draw,
+                                 std::uint32_t* idx)
+{
+    std::uint64_t total = 0;
+    check(gymrs_replay_draw(priority, count, n_samples, seed, draw, idx, &total));
+    return total;
+}
+
 // One set's update by gymrs_apply_gradient's rule (gymrs_optimizer_set; host only, no GPU): w[0 .. S) is updated in place from
 // q[0 .. S); m, v, pw[2] with GYMRS_OPT_ADAM and target with d.tau > 0 too (null otherwise).  The definition of include/gymrs_amd.h,
 // "Optimizer", as code.
@@ -483,6 +499,13 @@ public:
         return p;
     }
     void q_gradient(const gymrs_q_desc& d) { check(gymrs_q_gradient(e_, &d)); }
+    // Prioritized replay (include/gymrs_amd.h, "Replay") over a store in the caller's device memory, on the engine's stream: replay_push
+    // flattens a transitions record into the ring at d.head (the caller advances head and count), replay_sample draws d.n_samples entries
+    // in proportion to their priorities and gathers them into the batch q_gradient reads with n_steps = 1, replay_update writes the
+    // priorities of the drawn entries from the td row
+    void replay_push(const gymrs_replay_push_desc& d) { check(gymrs_replay_push(e_, &d)); }
+    void replay_sample(const gymrs_replay_sample_desc& d) { check(gymrs_replay_sample(e_, &d)); }
+    void replay_update(const gymrs_replay_update_desc& d) { check(gymrs_replay_update(e_, &d)); }
     // The optimizer (include/gymrs_amd.h, "Optimizer"): apply_gradient updates every set of d.head in ONE launch on the engine's stream
     // (SGD or Adam, from the fixed-point table d.grad into the engine's own weights; no synchronisation); the Adam state is the
     // engine's: optimizer_reset makes it fresh in stream order, optimizer_state copies it out (synchronising; any pointer may be null)
