@@ -231,6 +231,59 @@ pub struct GymrsEntropyDesc {
     pub reserved: u64,
 }
 
+/// `GYMRS_VALUE_CLIP`: the value loss is 0.5 * max((V - R)^2, (V_clip - R)^2) with V_clip within `clip` of `old_values`.
+pub const GYMRS_VALUE_CLIP: u32 = 1;
+
+/// `gymrs_value_desc`: what `gymrs_value_gradient` runs (include/gymrs_amd.h "Value loss"), 136 bytes: the record by value (`obs` only),
+/// `returns`, `old_values` (with the flag), the optional `values` row it writes, the critic's gradient tables, `sums` i64 `[n_sets][2]`
+/// and `counts` u64 `[n_sets][2]` (both or null).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsValueDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub clip: f32,
+    pub pad_: u32,
+    pub record: Trajectory,
+    pub start_obs: *const f32,
+    pub returns: *const f32,
+    pub old_values: *const f32,
+    pub values: *mut f32,
+    pub grad: *mut i64,
+    pub excluded: *mut u64,
+    pub sums: *mut i64,
+    pub counts: *mut u64,
+    pub reserved: u64,
+}
+
+/// `gymrs_advantage_stats`: one set's integer sums and the two numbers `gymrs_normalize_advantages` used, 40 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct GymrsAdvantageStats {
+    pub s1: i64,
+    pub n: u64,
+    pub s2: u64,
+    pub non_members: u64,
+    pub mean: f32,
+    pub inv: f32,
+}
+
+/// `gymrs_normalize_desc`: what `gymrs_normalize_advantages` runs (include/gymrs_amd.h "Advantage normalisation"), 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsNormalizeDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub eps: f32,
+    pub n_sets: u32,
+    pub lanes_per_policy: u64,
+    pub lane_stride: u64,
+    pub adv: *const f32,
+    pub out: *mut f32,
+    pub stats: *mut GymrsAdvantageStats,
+    pub reserved: u64,
+}
+
 /// `GYMRS_Q_DOUBLE`: the bootstrap action is the first maximum of the ONLINE logits of the successor (Double DQN).
 pub const GYMRS_Q_DOUBLE: u32 = 1;
 
@@ -540,6 +593,13 @@ extern "C" {
     pub fn gymrs_entropy_lane(kind: c_int, hidden: u32, scale: f32, coef: f32, weights: *const f32, n_steps: u32, x: *const f32, actions: *const u8,
                               old_prob: *const f32, q: *mut i64, excluded: *mut u64, sums: *mut i64, counts: *mut u64) -> c_int;
     pub fn gymrs_entropy_log2(v: f32, out: *mut f32) -> c_int;
+    /// the value loss over a transitions record and one lane of it on the host; per-set advantage normalisation and one set on the host
+    pub fn gymrs_value_gradient(e: *mut GymrsEngine, d: *const GymrsValueDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_value_lane(kind: c_int, hidden: u32, clip: f32, weights: *const f32, n_steps: u32, x: *const f32, returns: *const f32,
+                            old_values: *const f32, q: *mut i64, excluded: *mut u64, sums: *mut i64, counts: *mut u64, values: *mut f32) -> c_int;
+    pub fn gymrs_normalize_advantages(e: *mut GymrsEngine, d: *const GymrsNormalizeDesc) -> c_int;
+    pub fn gymrs_normalize_host(a: *const f32, count: u64, eps: f32, out: *mut f32, st: *mut GymrsAdvantageStats) -> c_int;
     /// Q-learning over a transitions record: the engine-owned target set, the two-kernel call, and one lane of it on the host
     pub fn gymrs_q_target_sync(e: *mut GymrsEngine) -> c_int;
     pub fn gymrs_q_target_ptr(e: *mut GymrsEngine, dev_out: *mut *mut f32, n_floats: *mut u64) -> c_int;

@@ -2,13 +2,14 @@
 """PPO on CartPole with the weight update inside the library too: the loop of `examples/ppo_cartpole.py` with
 `apply_gradient(adam=True, zero_grad=True)` in place of the torch update.
 
-The engine rides torch's stream, so the few torch expressions left (the normalised advantages, the value row V - R) are ordered with
-the launches, and an epoch is five launches and one subtraction with nothing in between: `ppo_gradient`, the critic's
-`policy_gradient`, one `apply_gradient` per head (Adam from the fixed-point tables into the engine's own weights; the tables come
-back zeroed for the next epoch) and `advantages` for V under the new critic.  No `torch.cuda.synchronize()` inside the epoch loop,
-no memset, no optimizer state outside the engine.  The counters of every epoch go to a row of their own and are read once per round.
+The engine rides torch's stream.  The advantages are normalised by `normalize_advantages` once per round, and an epoch is four or
+five launches with no torch expression in between: `ppo_gradient`, (`entropy_gradient`,) `value_gradient` -- the critic head with
+its coefficient V - R computed in the kernel from V under the current critic, so no values row has to be refreshed --, and one
+`apply_gradient` per head (Adam from the fixed-point tables into the engine's own weights; the tables come back zeroed for the next
+epoch).  No `torch.cuda.synchronize()` inside the epoch loop, no memset, no optimizer state outside the engine.  The counters of
+every epoch go to a row of their own and are read once per round.
 
-    python examples/adam_on_device.py [--lanes 4096] [--steps 64] [--rounds 8] [--epochs 4] [--clip 0.2] [--limit 100] [--hidden 16]
+    python examples/adam_on_device.py [--lanes 4096] [--steps 64] [--rounds 8] [--epochs 4] [--clip 0.2] [--clip-vf X] [--limit 100] [--hidden 16]
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=4, help="E: passes over one record")
     ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--clip-vf", type=float, default=None, help="clip the value loss within X of the values the record was scored with (GYMRS_VALUE_CLIP)")
     ap.add_argument("--limit", type=int, default=100, help="max_episode_steps")
     ap.add_argument("--hidden", type=int, default=16, help="H of the critic (0: affine)")
     ap.add_argument("--seed", type=int, default=0)
@@ -63,11 +65,15 @@ def main() -> int:
         obs, final, start, rew = f32(steps, 4, stride), f32(steps, 4, stride), f32(4, stride), f32(steps, stride)
         act, done, trunc = u8(steps, stride), u8(steps, stride), u8(steps, stride)
         adv, ret, val = f32(steps, stride), f32(steps, stride), f32(steps, stride)
-        norm_adv, coef_v, zero, old_prob = f32(steps, stride), f32(steps, stride), f32(steps, stride), f32(steps, stride)
+        norm_adv, zero, old_prob = f32(steps, stride), f32(steps, stride), f32(steps, stride)
+        adv_stats = torch.zeros(5, dtype=torch.int64, device=dev)  # one gymrs_advantage_stats
+        v_now = f32(steps, stride)  # V under the current critic: with this row given, value_gradient never allocates or synchronises
         g_pi, g_v = (torch.zeros((1, t.size), dtype=torch.int64, device=dev) for t in (policy, critic))
         x_pi, x_v, skipped = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(3))
         counts = torch.zeros((E, 1, 2), dtype=torch.int64, device=dev)  # a row per epoch
         ent_sums, ent_counts = (torch.zeros((E, 1, 2), dtype=torch.int64, device=dev) for _ in range(2))  # entropy and KL: a row per epoch too
+        v_sums, v_counts = (torch.zeros((E, 1, 2), dtype=torch.int64, device=dev) for _ in range(2))  # squared errors, lane-steps seen and cut
+        value_clip = dict(old_values=val.data_ptr(), clip=args.clip_vf) if args.clip_vf is not None else {}
         record = dict(obs=obs.data_ptr(), actions=act.data_ptr(), reward=rew.data_ptr(), done=done.data_ptr(), truncated=trunc.data_ptr(),
                       lane_stride=stride)
         rows = dict(record=record, start_obs=start.data_ptr())
@@ -78,27 +84,26 @@ def main() -> int:
                            lam=lam, critic=True, **rows)
             # old_prob: the prob row of the weights the record was drawn from (a zero coefficient row: the tables stay zero)
             env.policy_gradient(steps, coef=zero.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), prob=old_prob.data_ptr(), temperature=1.0, **rows)
-            A, R = adv[:, :n], ret[:, :n]
-            norm_adv[:, :n] = (A - A.mean()) / (A.std() + 1e-6)
+            env.normalize_advantages(steps, adv=adv.data_ptr(), out=norm_adv.data_ptr(), stats=adv_stats.data_ptr(), lane_stride=stride, lanes_per_policy=n)
             counts.zero_()
+            v_sums.zero_()
+            v_counts.zero_()
             ent_sums.zero_()
             ent_counts.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for e in range(E):  # nothing in here waits for the device
-                torch.sub(val[:, :n], R, out=coef_v[:, :n])  # d/d phi of 0.5 * mean((V - R)^2)
                 env.ppo_gradient(steps, advantages=norm_adv.data_ptr(), old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(),
                                  counts=counts[e].data_ptr(), clip=args.clip, temperature=1.0, **rows)
                 if with_entropy:  # the bonus goes into the same table: the one apply_gradient below ascends the sum of both
                     env.entropy_gradient(steps, old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), sums=ent_sums[e].data_ptr(),
                                          counts=ent_counts[e].data_ptr(), coef=args.entropy, temperature=1.0, **rows)
-                env.policy_gradient(steps, coef=coef_v.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(), critic=True, **rows)
+                env.value_gradient(steps, returns=ret.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(), sums=v_sums[e].data_ptr(),
+                                   counts=v_counts[e].data_ptr(), values=v_now.data_ptr(), **value_clip, **rows)  # d/d phi of 0.5 * sum (V - R)^2, V computed in the kernel
                 env.apply_gradient(grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(), skipped=skipped.data_ptr(), adam=True, lr=lr_pi, grad_scale=grad_scale,
                                    ascend=True, zero_grad=True)  # ascend the clipped objective
                 env.apply_gradient(grad=g_v.data_ptr(), excluded=x_v.data_ptr(), skipped=skipped.data_ptr(), critic=True, adam=True, lr=lr_v,
                                    grad_scale=grad_scale, max_norm=10.0, zero_grad=True)
-                env.advantages(steps, final_obs=final.data_ptr(), advantages=coef_v.data_ptr(), values=val.data_ptr(), gamma=gamma, lam=lam, critic=True,
-                               **rows)  # V under the new critic for the next epoch's value row
             torch.cuda.synchronize()
             epoch_ms = (time.perf_counter() - t0) * 1e3 / max(1, E)
 
@@ -110,6 +115,9 @@ def main() -> int:
             print(f"round {r:2d}: {steps * n} sampled transitions, {ends} episode ends, clip fraction per epoch "
                   f"{' '.join(f'{f:.3f}' for f in fractions)}, {int(skipped[0])} updates skipped so far, {epoch_ms:.3f} ms per epoch; greedy validation: "
                   f"{int(reward_sum) / max(1, int(episodes) + n):.1f} steps per episode")
+            vs, vc = v_sums.cpu().numpy()[:, 0], v_counts.cpu().numpy()[:, 0]
+            print(f"          value loss per epoch {' '.join(f'{v:.4f}' for v in 0.5 * vs[:, 1] * 2.0**-24 / np.maximum(1, vc[:, 0]))}"
+                  + (f", value clip fraction per epoch {' '.join(f'{v:.3f}' for v in vc[:, 1] / np.maximum(1, vc[:, 0]))}" if value_clip else ""))
             if with_entropy:  # read once per round, like counts
                 s, c = ent_sums.cpu().numpy()[:, 0], ent_counts.cpu().numpy()[:, 0]
                 entropy, kl = (s[:, j] * 2.0**-24 / np.maximum(1, c[:, j]) for j in (0, 1))

@@ -5,12 +5,14 @@
 lane-step, as in `examples/in_kernel_gradients.py`.  One `policy_gradient` call (zero coefficients, its tables are thrown away)
 records `old_prob`: its `prob` row is the record's, p[a] under the weights the actions were drawn from.  Then E epochs over the same
 record.  Each epoch is one `ppo_gradient` launch -- the ratio p[a] / old_prob, the clip decision and the weight are computed in the
-kernel, and the per-policy counters give the clip fraction --, one critic `policy_gradient` launch with the row V - R, and an update
-in place in the engine's own tables through `policy_weights_ptr` / `critic_weights_ptr`:
+kernel, and the per-policy counters give the clip fraction --, one `value_gradient` launch -- the critic head with V - R computed in
+the kernel from V under the current critic (`--clip-vf X`: the clipped value loss against the values the record was scored with) --,
+and an update in place in the engine's own tables through `policy_weights_ptr` / `critic_weights_ptr`.  The advantages are
+standardised by `normalize_advantages` once per round.
 
     policy += lr * grad.double() * 2**-24 / (K * n)        (the clipped objective is ascended)
 
-    python examples/ppo_cartpole.py [--lanes 4096] [--steps 64] [--rounds 8] [--epochs 4] [--clip 0.2] [--limit 100] [--hidden 16]
+    python examples/ppo_cartpole.py [--lanes 4096] [--steps 64] [--rounds 8] [--epochs 4] [--clip 0.2] [--clip-vf X] [--limit 100] [--hidden 16]
 """
 from __future__ import annotations
 
@@ -40,6 +42,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=4, help="E: passes over one record")
     ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--clip-vf", type=float, default=None, help="clip the value loss within X of the values the record was scored with (GYMRS_VALUE_CLIP)")
     ap.add_argument("--limit", type=int, default=100, help="max_episode_steps")
     ap.add_argument("--hidden", type=int, default=16, help="H of the critic (0: affine)")
     ap.add_argument("--seed", type=int, default=0)
@@ -68,7 +71,9 @@ def main() -> int:
     obs, final, start, rew = f32(steps, 4, stride), f32(steps, 4, stride), f32(4, stride), f32(steps, stride)
     act, done, trunc = u8(steps, stride), u8(steps, stride), u8(steps, stride)
     adv, ret, val = f32(steps, stride), f32(steps, stride), f32(steps, stride)
-    norm_adv, coef_v, zero, old_prob = f32(steps, stride), f32(steps, stride), f32(steps, stride), f32(steps, stride)
+    norm_adv, zero, old_prob = f32(steps, stride), f32(steps, stride), f32(steps, stride)
+    adv_stats = torch.zeros(5, dtype=torch.int64, device=dev)  # one gymrs_advantage_stats
+    value_clip = dict(old_values=val.data_ptr(), clip=args.clip_vf) if args.clip_vf is not None else {}
     g_pi, g_v = (torch.zeros((1, t.numel()), dtype=torch.int64, device=dev) for t in (pi_table, v_table))
     x_pi, x_v = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
     counts = torch.zeros((1, 2), dtype=torch.int64, device=dev)
@@ -88,14 +93,12 @@ def main() -> int:
         torch.cuda.synchronize()
         env.policy_gradient(steps, record=record, start_obs=start.data_ptr(), coef=zero.data_ptr(), grad=g_pi.data_ptr(), excluded=x_pi.data_ptr(),
                             prob=old_prob.data_ptr(), temperature=1.0)
+        env.normalize_advantages(steps, adv=adv.data_ptr(), out=norm_adv.data_ptr(), stats=adv_stats.data_ptr(), lane_stride=stride, lanes_per_policy=n)
         env.sync()
-        A, R = adv[:, :n], ret[:, :n]
-        norm_adv[:, :n] = (A - A.mean()) / (A.std() + 1e-6)
         fractions = []
         ent_sums.zero_()
         ent_counts.zero_()
         for e in range(args.epochs):
-            coef_v[:, :n] = val[:, :n] - R  # d/d phi of 0.5 * mean((V - R)^2), V of the record's critic in the first epoch
             for t in (g_pi, g_v, x_pi, x_v, counts):
                 t.zero_()  # the launches ADD
             torch.cuda.synchronize()  # torch wrote on its stream; the launches read on the engine's
@@ -105,18 +108,15 @@ def main() -> int:
                 env.entropy_gradient(steps, record=record, start_obs=start.data_ptr(), old_prob=old_prob.data_ptr(), grad=g_pi.data_ptr(),
                                      excluded=x_pi.data_ptr(), sums=ent_sums[e].data_ptr(), counts=ent_counts[e].data_ptr(), coef=args.entropy,
                                      temperature=1.0)
-            env.policy_gradient(steps, record=record, start_obs=start.data_ptr(), coef=coef_v.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(),
-                                critic=True)
+            # d/d phi of 0.5 * sum (V - R)^2 (or its clipped form), V under the current critic computed in the kernel
+            env.value_gradient(steps, record=record, start_obs=start.data_ptr(), returns=ret.data_ptr(), grad=g_v.data_ptr(), excluded=x_v.data_ptr(),
+                               **value_clip)
             env.sync()
             seen, cut = (int(v) for v in counts[0])
             fractions.append(cut / max(1, seen))
             pi_table += (lr_pi * g_pi[0].double() * 2.0**-24 / (steps * n)).float()  # ascend the clipped objective, in the engine's tables
             v_table -= (lr_v * g_v[0].double() * 2.0**-24 / (steps * n)).float()
             torch.cuda.synchronize()
-            # V under the new critic for the next epoch's value row
-            env.advantages(steps, record=record, final_obs=final.data_ptr(), start_obs=start.data_ptr(), advantages=coef_v.data_ptr(),
-                           values=val.data_ptr(), gamma=gamma, lam=lam, critic=True)
-            env.sync()
 
         ends = int(((done | trunc) != 0)[:, :n].sum())
         env.rollout_closed_loop(steps, fitness=True)  # greedy validation with the new weights

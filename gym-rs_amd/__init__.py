@@ -52,6 +52,8 @@ from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
 from .engine import EntropyDesc, entropy_lane, entropy_log2
+from .engine import ValueDesc, VALUE_CLIP, value_lane
+from .engine import NormalizeDesc, AdvantageStats, ADVANTAGE_STATS_DTYPE, normalize_host
 from .engine import QDesc, Q_DOUBLE, q_lane
 from .engine import Replay, ReplayPushDesc, ReplaySampleDesc, ReplayUpdateDesc, REPLAY_MAX_PRIORITY, REPLAY_NONE, replay_priority, replay_draw
 from .engine import OptimizerDesc, OPT_HEAD_POLICY, OPT_HEAD_CRITIC, OPT_SGD, OPT_ADAM, OPT_ASCEND, OPT_ZERO_GRAD, optimizer_set
@@ -71,6 +73,8 @@ __all__ = [
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
     "PpoDesc", "ppo_lane",
     "EntropyDesc", "entropy_lane", "entropy_log2",
+    "ValueDesc", "VALUE_CLIP", "value_lane",
+    "NormalizeDesc", "AdvantageStats", "ADVANTAGE_STATS_DTYPE", "normalize_host",
     "QDesc", "Q_DOUBLE", "q_lane",
     "Replay", "ReplayPushDesc", "ReplaySampleDesc", "ReplayUpdateDesc", "REPLAY_MAX_PRIORITY", "REPLAY_NONE", "replay_priority", "replay_draw",
     "OptimizerDesc", "OPT_HEAD_POLICY", "OPT_HEAD_CRITIC", "OPT_SGD", "OPT_ADAM", "OPT_ASCEND", "OPT_ZERO_GRAD", "optimizer_set",

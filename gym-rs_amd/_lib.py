@@ -114,6 +114,13 @@ SIGNATURES = {
     "gymrs_entropy_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p,
                                      C.POINTER(C.c_int64), u64p, C.POINTER(C.c_int64), u64p]),
     "gymrs_entropy_log2": (C.c_int, [C.c_float, f32p]),
+    # the value loss over a transitions record (gymrs_value_desc 136 B) and the host-only lane
+    "gymrs_value_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_value_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, f32p, C.c_uint32, f32p, f32p, f32p, C.POINTER(C.c_int64), u64p,
+                                   C.POINTER(C.c_int64), u64p, f32p]),
+    # per-set advantage normalisation (gymrs_normalize_desc 64 B, gymrs_advantage_stats 40 B) and the host-only set
+    "gymrs_normalize_advantages": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_normalize_host": (C.c_int, [f32p, C.c_uint64, C.c_float, f32p, C.c_void_p]),
     # Q-learning over a transitions record (gymrs_q_desc 120 B), its target set and the host-only lane
     "gymrs_q_target_sync": (C.c_int, [C.c_void_p]),
     "gymrs_q_target_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), u64p]),

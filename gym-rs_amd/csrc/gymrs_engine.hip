@@ -524,6 +524,7 @@ gymrs_status gymrs_engine_destroy(gymrs_engine* e)
     (void)hipFree(e->eval_dev);
     (void)hipFree(e->rank_scratch);
     (void)hipFree(e->replay_scratch);
+    (void)hipFree(e->value_scratch);
     if (e->err_seen) (void)hipHostFree(const_cast<uint32_t*>(e->err_seen));
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     (void)hipFree(e->tick_dev);

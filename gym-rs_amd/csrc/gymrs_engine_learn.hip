@@ -9,6 +9,8 @@
 #include "gymrs_advantages.h"
 #include "gymrs_gradient.h"
 #include "gymrs_entropy.h"
+#include "gymrs_value.h"
+#include "gymrs_normalize.h"
 #include "gymrs_qlearn.h"
 #include "gymrs_replay.h"
 #include "gymrs_optimizer.h"
@@ -616,6 +618,37 @@ void q_lane(uint32_t H, uint32_t flags, float gamma, float kappa, const float* w
     }
 }
 
+// One lane of "Value loss" by the shared text: the forward walk (v, c, sums, counts), then the critic head's lane fed c.
+template <int D>
+void value_lane(uint32_t H, float clip, const float* weights, uint32_t K, const float* x, const float* returns, const float* old_values, int64_t* q,
+                       uint64_t* excluded, int64_t* sums_out, uint64_t* counts, float* values)
+{
+    const HostWeights w{weights};
+    std::vector<float> c(K);
+    ValueSums<1> sums{};
+    for (uint32_t k = 0; k < K; ++k) {
+        float xs[D][1], v[1], g[1][1];
+        for (int j = 0; j < D; ++j) xs[j][0] = x[(size_t)k * D + j];
+        critic_values<D, 1, 1>(w, H, xs, v);
+        const float R[1] = {returns[k]}, vo[1] = {old_values ? old_values[k] : 0.0f};
+        value_head<1, true>(v, R, vo, clip, old_values != nullptr, g, sums);
+        c[k] = g[0][0];
+        if (values) values[k] = v[0];
+    }
+    gradient_lane<D, 1, true>(H, 0.0f, weights, K, x, nullptr, c.data(), q, excluded, nullptr);
+    if (sums_out) {
+        long long f;
+        if (!gradient_fixed(sums.s0[0], f)) *excluded += 1;
+        sums_out[0] = f;
+        if (!gradient_fixed(sums.s1[0], f)) *excluded += 1;
+        sums_out[1] = f;
+    }
+    if (counts) {
+        counts[0] = sums.seen[0];
+        counts[1] = sums.cut[0];
+    }
+}
+
 bool q_gamma_ok(float gamma) { return gamma >= 0.0f && gamma <= 1.0f; } // (false for a NaN)
 bool q_kappa_ok(float kappa) { return kappa > 0.0f; }                   // (false for a NaN; +inf is the squared loss)
 } // namespace
@@ -1006,6 +1039,115 @@ gymrs_status gymrs_entropy_gradient(gymrs_engine* e, const gymrs_entropy_desc* d
                         reinterpret_cast<unsigned long long*>(d->counts), /*stride, n, gid0*/ rec.lane_stride, e->n, e->gid0, d->n_steps, d->scale, d->coef};
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_entropy_gradient(e->kind, a, e->policy.args, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- value loss: the host-side lane and the launch (include/gymrs_amd.h, "Value loss") -----------------------------------------------
+static_assert(sizeof(gymrs_value_desc) == 136 && sizeof(gymrs_normalize_desc) == 64 && sizeof(gymrs_advantage_stats) == 40, "descriptor sizes");
+
+static bool value_clip_ok(float clip) { return clip > 0.0f && clip <= std::numeric_limits<float>::max(); } // (false for a NaN)
+
+gymrs_status gymrs_value_lane(gymrs_env_kind kind, uint32_t hidden, float clip, const float* weights, uint32_t n_steps, const float* x,
+                              const float* returns, const float* old_values, int64_t* q, uint64_t* excluded, int64_t sums[2], uint64_t counts[2],
+                              float* values)
+{
+    const std::string who = "gymrs_value_lane";
+    if (gymrs_status st = check_network(kind, hidden, who)) return st;
+    if (!weights || !q || !excluded || (n_steps != 0 && (!x || !returns))) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (old_values && !value_clip_ok(clip)) return fail(GYMRS_EINVAL, who + ": clip must be finite and > 0 with old_values");
+    if (kind == GYMRS_CARTPOLE)
+        value_lane<4>(hidden, clip, weights, n_steps, x, returns, old_values, q, excluded, sums, counts, values);
+    else
+        value_lane<2>(hidden, clip, weights, n_steps, x, returns, old_values, q, excluded, sums, counts, values);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_value_gradient(gymrs_engine* e, const gymrs_value_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_value_gradient"};
+    if (gymrs_status st = c.prologue("gradients are")) return st;
+    if (d->reserved != 0 || d->pad_ != 0) return c.refuse("reserved and pad_ must be 0");
+    if (d->flags & ~GYMRS_VALUE_CLIP) return c.refuse("unknown flag bits (GYMRS_VALUE_CLIP is the only one)");
+    const bool clipped = (d->flags & GYMRS_VALUE_CLIP) != 0;
+    if (!e->critic.dev) return c.refuse("the engine has no critic set (gymrs_set_critic)");
+    if (clipped && !value_clip_ok(d->clip)) return c.refuse("clip must be finite and > 0 with GYMRS_VALUE_CLIP");
+    const gymrs_trajectory& rec = d->record;
+    if (gymrs_status st = c.not_null({{rec.obs, "record.obs"}, {d->start_obs, "start_obs"}, {d->returns, "returns"}, {d->grad, "grad"},
+                                      {d->excluded, "excluded"}}))
+        return st;
+    if (clipped)
+        if (gymrs_status st = c.not_null({{d->old_values, "old_values", " (GYMRS_VALUE_CLIP reads it)"}})) return st;
+    if (!clipped && d->old_values) return c.refuse("old_values without GYMRS_VALUE_CLIP");
+    if (d->values && (d->values == d->returns || d->values == d->old_values)) return c.refuse("values may not alias returns or old_values");
+    if (gymrs_status st = c.aligned({rec.obs, d->start_obs, d->returns, d->old_values, d->values}, 16, "every row buffer must be 16-byte aligned")) return st;
+    if (gymrs_status st = c.aligned({d->grad, d->excluded, d->sums, d->counts}, 8, "grad, excluded, sums and counts must be 8-byte aligned")) return st;
+    if (gymrs_status st = c.lane_stride(rec.lane_stride)) return st;
+    if (d->n_steps == 0) return GYMRS_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    float* v_row = d->values;
+    if (!v_row && e->critic.args.hidden != 0) { // the chunks of hidden units read V from a row: the engine's
+        const uint64_t need = (uint64_t)d->n_steps * rec.lane_stride;
+        if (need > e->value_scratch_floats) { // (launches already enqueued still use the old one: wait for them)
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipFree(e->value_scratch));
+            e->value_scratch = nullptr;
+            e->value_scratch_floats = 0;
+            HIP_TRY(hipMalloc(&e->value_scratch, (size_t)need * sizeof(float)));
+            e->value_scratch_floats = need;
+        }
+        v_row = e->value_scratch;
+    }
+    const ValueArgs a{rec.obs, d->start_obs, d->returns, d->old_values, v_row, reinterpret_cast<unsigned long long*>(d->grad),
+                      reinterpret_cast<unsigned long long*>(d->excluded), reinterpret_cast<unsigned long long*>(d->sums),
+                      reinterpret_cast<unsigned long long*>(d->counts), /*stride, n, gid0*/ rec.lane_stride, e->n, e->gid0, d->n_steps, d->clip};
+    HIP_TRY(launch_value_gradient(e->kind, a, e->critic.args, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- advantage normalisation: the host-side set and the launch (include/gymrs_amd.h, "Advantage normalisation") ------------------------
+static bool normalize_eps_ok(float eps) { return eps > 0.0f && eps <= std::numeric_limits<float>::max(); } // (false for a NaN)
+
+gymrs_status gymrs_normalize_host(const float* a, uint64_t count, float eps, float* out, gymrs_advantage_stats* st)
+{
+    const std::string who = "gymrs_normalize_host";
+    if (!st || (count != 0 && (!a || !out))) return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (!normalize_eps_ok(eps)) return fail(GYMRS_EINVAL, who + ": eps must be finite and > 0");
+    unsigned long long s1 = 0, s2 = 0, n = 0, non_members = 0; // modulo 2^64, as the device adds
+    for (uint64_t j = 0; j < count; ++j) {
+        if (normalize_member(a[j])) {
+            s1 += (unsigned long long)normalize_q1(a[j]);
+            n += 1;
+        } else {
+            non_members += 1;
+        }
+    }
+    const float mean = normalize_mean((long long)s1, n);
+    for (uint64_t j = 0; j < count; ++j)
+        if (normalize_member(a[j])) s2 += normalize_q2(a[j], mean);
+    const float inv = normalize_inv(s2, n, eps);
+    for (uint64_t j = 0; j < count; ++j) out[j] = normalize_out(a[j], mean, inv);
+    *st = gymrs_advantage_stats{(long long)s1, n, s2, non_members, mean, inv};
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_normalize_advantages(gymrs_engine* e, const gymrs_normalize_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_normalize_advantages"};
+    if (!e) return c.refuse("NULL engine");
+    if (!d) return c.refuse("NULL desc");
+    if (d->reserved != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    if (!normalize_eps_ok(d->eps)) return c.refuse("eps must be finite and > 0");
+    if (d->n_sets == 0) return c.refuse("n_sets must be >= 1");
+    if (d->lanes_per_policy == 0) return c.refuse("lanes_per_policy must be >= 1");
+    if (gymrs_status st = c.not_null({{d->adv, "adv"}, {d->out, "out"}, {d->stats, "stats"}})) return st;
+    if (gymrs_status st = c.aligned({d->adv, d->out}, 16, "adv and out must be 16-byte aligned")) return st;
+    if (gymrs_status st = c.aligned({d->stats}, 8, "stats must be 8-byte aligned")) return st;
+    if (gymrs_status st = c.lane_stride(d->lane_stride)) return st;
+    if (d->n_steps == 0) return GYMRS_OK;
+    const NormalizeArgs a{d->adv, d->out, d->stats, /*stride, n, gid0*/ d->lane_stride, e->n, e->gid0, d->lanes_per_policy, d->n_sets, d->n_steps, d->eps, 0};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_normalize(a, e->stream));
     return GYMRS_OK;
 }
 

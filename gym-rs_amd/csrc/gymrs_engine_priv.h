@@ -238,6 +238,11 @@ struct gymrs_engine {
     // The scratch of gymrs_replay_sample for a store of more than one tile (kReplayScratchBytes: tile sums, tile bases, the total),
     // allocated at first use and kept until the engine goes.  Not part of clone or snapshot.
     void* replay_scratch = nullptr;
+    // The v row of gymrs_value_gradient for a critic with a hidden layer when the caller gives no `values` (value_scratch_floats >=
+    // n_steps * lane_stride), allocated at first use, replaced by a larger one when a larger record comes (after the launches that
+    // still use it) and kept until the engine goes.  Not part of clone or snapshot.
+    float* value_scratch = nullptr;
+    uint64_t value_scratch_floats = 0;
     // The exploration settings (gymrs_set_exploration): what the exploring kernels get by value, so a change takes effect in
     // stream order.  gymrs_set_policy keeps them.  Not part of clone or snapshot.
     ExploreArgs explore{};

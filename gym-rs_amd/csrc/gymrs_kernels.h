@@ -430,6 +430,41 @@ struct EntropyArgs {
     float scale, coef;
 };
 hipError_t launch_entropy_gradient(gymrs_env_kind kind, const EntropyArgs& a, const PolicyArgs& p, hipStream_t stream);
+// ---- value loss (gymrs_value_gradient; gymrs_value.hip) --------------------------------------------------------------------------
+// A gymrs_value_desc as its kernels get it by value, before the critic set.  Rows are `stride` lanes apart (>= n, a multiple of 16)
+// and 16-byte aligned; grad, excluded, sums and counts are 8-byte aligned and ADDED to.
+struct ValueArgs {
+    const float* obs;             // [n_steps][obs_dim][stride]; rows 0 .. n_steps - 2 are read
+    const float* start_obs;       // [obs_dim][stride]
+    const float* returns;         // [n_steps][stride]
+    const float* old_values;      // [n_steps][stride], or NULL: no clip
+    float* v_row;                 // [n_steps][stride]: `values`, or with a hidden layer and no `values` the engine's scratch; NULL: affine, not asked for
+    unsigned long long* grad;     // [n_sets][S], S = the set's PolicyArgs::stride
+    unsigned long long* excluded; // [n_sets]
+    unsigned long long* sums;     // [n_sets][2] int64 bit patterns or NULL
+    unsigned long long* counts;   // [n_sets][2] or NULL
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    float clip; // read with old_values
+};
+// p is the critic set.  One launch (affine) or two in stream order (the forward pass into v_row, then the chunks of hidden units).
+hipError_t launch_value_gradient(gymrs_env_kind kind, const ValueArgs& a, const PolicyArgs& p, hipStream_t stream);
+// ---- advantage normalisation (gymrs_normalize_advantages; gymrs_normalize.hip) ------------------------------------------------------
+constexpr uint32_t kNormalizeSmallItems = 512;  // 4-lane row items (n_steps * ceil(n / 4)) one workgroup walks in the one-launch path ...
+constexpr uint32_t kNormalizeSmallSets = 64;    // ... whose sets have their sums in LDS
+struct NormalizeArgs {
+    const float* adv;            // [n_steps][stride]
+    float* out;                  // [n_steps][stride]; may be adv
+    gymrs_advantage_stats* stats; // [n_sets], WRITTEN
+    uint64_t stride, n, gid0;
+    uint64_t lanes_per_policy;   // >= 1
+    uint32_t n_sets;             // >= 1
+    uint32_t n_steps;
+    float eps;
+    uint32_t pad_;
+};
+// one launch (at most kNormalizeSmallItems items and kNormalizeSmallSets sets) or four, in stream order
+hipError_t launch_normalize(const NormalizeArgs& a, hipStream_t stream);
 // ---- Q-learning (gymrs_q_gradient; gymrs_qlearn.hip) ---------------------------------------------------------------------------
 // A gymrs_q_desc as its two kernels get it by value, before the online set (and, for the TD kernel, the target set).  Rows are
 // `stride` lanes apart (>= n, a multiple of 16) and 16-byte aligned; grad, excluded and counts are 8-byte aligned and ADDED to.

@@ -140,6 +140,31 @@ class EntropyDesc(C.Structure):
                 ("counts", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class ValueDesc(C.Structure):
+    """``gymrs_value_desc`` (include/gymrs_amd.h), 136 bytes: the record by value, three rows in (one optional), one optional row out,
+    two tables and two optional pairs per set added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("clip", C.c_float), ("pad_", C.c_uint32), ("record", Trajectory),
+                ("start_obs", C.c_void_p), ("returns", C.c_void_p), ("old_values", C.c_void_p), ("values", C.c_void_p), ("grad", C.c_void_p),
+                ("excluded", C.c_void_p), ("sums", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+VALUE_CLIP = 1  # GYMRS_VALUE_CLIP
+
+
+class AdvantageStats(C.Structure):
+    """``gymrs_advantage_stats`` (include/gymrs_amd.h), 40 bytes: one set's integer sums and the two numbers pass 3 used."""
+    _fields_ = [("s1", C.c_int64), ("n", C.c_uint64), ("s2", C.c_uint64), ("non_members", C.c_uint64), ("mean", C.c_float), ("inv", C.c_float)]
+
+
+ADVANTAGE_STATS_DTYPE = np.dtype([("s1", "<i8"), ("n", "<u8"), ("s2", "<u8"), ("non_members", "<u8"), ("mean", "<f4"), ("inv", "<f4")])
+
+
+class NormalizeDesc(C.Structure):
+    """``gymrs_normalize_desc`` (include/gymrs_amd.h), 64 bytes."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("eps", C.c_float), ("n_sets", C.c_uint32), ("lanes_per_policy", C.c_uint64),
+                ("lane_stride", C.c_uint64), ("adv", C.c_void_p), ("out", C.c_void_p), ("stats", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class QDesc(C.Structure):
     """``gymrs_q_desc`` (include/gymrs_amd.h), 120 bytes: the record by value, two observation buffers in, the td row out, two tables
     and an optional pair of counters per set added to."""
@@ -479,6 +504,45 @@ def entropy_lane(kind: int, hidden: int, weights, x, actions=None, old_prob=None
                                        a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None, po.ctypes.data_as(fp) if po is not None else None,
                                        q.ctypes.data_as(ip), C.byref(excluded), sums.ctypes.data_as(ip), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
     return q, excluded.value, sums, counts
+
+
+def value_lane(kind: int, hidden: int, weights, x, returns, old_values=None, *, clip: float = 0.0):
+    """``gymrs_value_lane`` (host only, no GPU): one lane's contribution to ``gymrs_value_gradient`` -- the definition of
+    include/gymrs_amd.h, "Value loss", as code.  ``weights``: ONE critic; ``x`` [K][D], ``returns`` [K]; ``old_values`` [K] with ``clip``
+    is GYMRS_VALUE_CLIP, None the plain squared error.  Returns (q, excluded, sums, counts, values): q is int64 [S]; sums is int64 [2] =
+    the fixed points of (sum e1^2, sum of the larger squares); counts is uint64 [2] = (lane-steps, cut ones); values is f32 [K]."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    size = critic_size(kind, hidden)
+    r = np.ascontiguousarray(returns, dtype=np.float32).reshape(-1)
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if w.size != size or xs.size != r.size * _OBS_DIM[kind]:
+        raise ValueError(f"value_lane needs {size} weights and {_OBS_DIM[kind]} observation components per step")
+    vo = None
+    if old_values is not None:
+        vo = np.ascontiguousarray(old_values, dtype=np.float32).reshape(-1)
+        if vo.size != r.size:
+            raise ValueError("value_lane needs one old value per step")
+    q = np.zeros(size, np.int64)
+    excluded = C.c_uint64()
+    sums, counts, values = np.zeros(2, np.int64), np.zeros(2, np.uint64), np.empty(r.size, np.float32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    _check(lib, lib.gymrs_value_lane(int(kind), int(hidden), float(clip), w.ctypes.data_as(fp), int(r.size), xs.ctypes.data_as(fp), r.ctypes.data_as(fp),
+                                     vo.ctypes.data_as(fp) if vo is not None else None, q.ctypes.data_as(ip), C.byref(excluded), sums.ctypes.data_as(ip),
+                                     counts.ctypes.data_as(C.POINTER(C.c_uint64)), values.ctypes.data_as(fp)))
+    return q, excluded.value, sums, counts, values
+
+
+def normalize_host(a, *, eps: float = 1e-6):
+    """``gymrs_normalize_host`` (host only, no GPU): the rule of include/gymrs_amd.h, "Advantage normalisation", for ONE set.
+    Returns (out f32 [count], stats): stats is a numpy record of ``ADVANTAGE_STATS_DTYPE``."""
+    lib = load_library()
+    src = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    out = np.empty(src.size, np.float32)
+    st = np.zeros(1, ADVANTAGE_STATS_DTYPE)
+    fp = C.POINTER(C.c_float)
+    _check(lib, lib.gymrs_normalize_host(src.ctypes.data_as(fp), int(src.size), float(eps), out.ctypes.data_as(fp), C.c_void_p(st.ctypes.data)))
+    return out, st[0]
 
 
 def q_lane(kind: int, hidden: int, weights, target_weights, x, x_next, actions, reward, done, *, gamma: float, kappa: float = float("inf"),
@@ -1137,6 +1201,34 @@ class BatchedEngine:
         desc = EntropyDesc(int(n_steps), int(flags), float(s), float(coef), traj, C.c_void_p(start_obs or None), C.c_void_p(old_prob or None),
                            C.c_void_p(grad or None), C.c_void_p(excluded or None), C.c_void_p(sums or None), C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_entropy_gradient(self._h, C.byref(desc)))
+
+    # -- the value loss over a transitions record: the critic head with its coefficient computed in the kernel -----------
+    def value_gradient(self, n_steps: int, *, record, start_obs: int, returns: int, grad: int, excluded: int, old_values: Optional[int] = None,
+                       clip: Optional[float] = None, values: Optional[int] = None, sums: Optional[int] = None, counts: Optional[int] = None,
+                       flags: Optional[int] = None) -> None:
+        """``gymrs_value_gradient``: ``policy_gradient(critic=True)`` whose coefficient is computed in the kernel: V(x) - returns, or
+        with ``clip`` (then ``old_values`` is required: GYMRS_VALUE_CLIP) the gradient of 0.5 * max((V - R)^2, (V_clip - R)^2).  ADDS
+        the gradient of the loss (to descend) per critic to ``grad`` and ``excluded``; ``values`` receives V under the current
+        critic; ``sums`` (device int64 [n_sets][2]) the fixed points of the squared errors, ``counts`` (device uint64 [n_sets][2]) the
+        lane-steps seen and cut.  ``record``: only ``obs`` is read.  Reads and writes no lane array.  With a hidden critic and no
+        ``values`` the engine keeps a scratch row; the call that allocates or grows it synchronises the engine's stream."""
+        traj = _record("value_gradient", self.n_envs, n_steps, record, unread=("actions", "reward", "done"))
+        f = (VALUE_CLIP if clip is not None else 0) if flags is None else int(flags)
+        desc = ValueDesc(int(n_steps), f, float(clip or 0.0), 0, traj, C.c_void_p(start_obs or None), C.c_void_p(returns or None),
+                         C.c_void_p(old_values or None), C.c_void_p(values or None), C.c_void_p(grad or None), C.c_void_p(excluded or None),
+                         C.c_void_p(sums or None), C.c_void_p(counts or None), 0)
+        _check(self._lib, self._lib.gymrs_value_gradient(self._h, C.byref(desc)))
+
+    # -- per-set standardisation of an advantages row, exact and order-independent -----------------------------------
+    def normalize_advantages(self, n_steps: int, *, adv: int, out: int, stats: int, lane_stride: int, lanes_per_policy: int = 1, n_sets: int = 1,
+                             eps: float = 1e-6, flags: int = 0) -> None:
+        """``gymrs_normalize_advantages``: ``out[k][i] = (adv[k][i] - mean) / (sd + eps)`` with mean and sd (n - 1) per set from integer
+        sums, the set of lane i being ``((global_env_offset + i) // lanes_per_policy) % n_sets``.  ``stats``: device memory of
+        ``n_sets`` records of ``ADVANTAGE_STATS_DTYPE`` (40 bytes each), written.  ``out`` may be ``adv``.  Works for every env kind.
+        The statistics are over this engine's lanes: engines that cut one batch each standardise their own part."""
+        desc = NormalizeDesc(int(n_steps), int(flags), float(eps), int(n_sets), int(lanes_per_policy), int(lane_stride), C.c_void_p(adv or None),
+                             C.c_void_p(out or None), C.c_void_p(stats or None), 0)
+        _check(self._lib, self._lib.gymrs_normalize_advantages(self._h, C.byref(desc)))
 
     # -- Q-learning over a transitions record: a target set, TD errors and the Q-gradient in one call -------------------
     def q_target_sync(self) -> None:

@@ -931,6 +931,119 @@ gymrs_status gymrs_entropy_gradient(gymrs_engine* e, const gymrs_entropy_desc* d
 gymrs_status gymrs_entropy_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float coef, const float* weights, uint32_t n_steps, const float* x,
                                 const uint8_t* actions, const float* old_prob, int64_t* q, uint64_t* excluded, int64_t sums[2], uint64_t counts[2]);
 gymrs_status gymrs_entropy_log2(float v, float* out);
+/* Value loss: the critic head with its coefficient computed in the kernel.  gymrs_value_gradient(e, d) is to
+ * gymrs_policy_gradient(GYMRS_GRADIENT_CRITIC) what gymrs_ppo_gradient is to the policy head: the coefficient of a lane-step is not
+ * read from a row, it is computed from the critic's own value, a returns row and (GYMRS_VALUE_CLIP) an old-values row.  Everything
+ * else is the text of "gradients": x = (k == 0 ? start_obs : obs[k-1]), the critic's set key, the backward pass, one f32 accumulator
+ * per (lane, parameter) walked in ascending k, the fixed point, excluded, the layout of the table, additivity over engines and
+ * launches.  All arithmetic is f32, every operation is a single IEEE operation, every `?:` is a select.  For lane i and step k:
+ *     v   = V(x)                      (the critic forward of "advantages", under the engine's critic set)
+ *     R   = returns[k][i]
+ *     e1  = v - R
+ *     plain:             c = e1
+ *     GYMRS_VALUE_CLIP:  vo = old_values[k][i];  dl = v - vo
+ *                        hi = dl > clip;  lo = dl < -clip          (compares: false on NaN)
+ *                        vc = hi ? vo + clip : (lo ? vo - clip : v)
+ *                        e2 = vc - R
+ *                        cut = (hi || lo) && (e2 * e2 > e1 * e1)
+ *                        c  = cut ? +0.0f : e1
+ *     g[0] = c                        (then exactly the critic head's backward pass)
+ * The table receives the gradient of  sum over k of 0.5 * max(e1^2, e2^2)  (without the flag 0.5 * e1^2), the loss to DESCEND.  By
+ * definition the call equals gymrs_policy_gradient(GYMRS_GRADIENT_CRITIC) fed coef[k][i] = c, integer for integer.  What follows
+ * from the rule: dl == +-clip is not clipped and e2^2 == e1^2 is not cut (strict compares); a NaN R makes c NaN and puts the lane's
+ * pairs into excluded; a NaN vo compares false both ways, so the lane-step is neither clipped nor cut: c = e1.
+ * values (may be NULL): [K][lane_stride], receives v for i < n_envs (padding keeps its bytes); it may not alias returns or
+ * old_values; it must not overlap record.obs or start_obs either (not checked: with a hidden layer the second launch would read
+ * observations the first one overwrote).  With a hidden layer the v row is needed between the call's two launches: without `values`
+ * the engine keeps a scratch row of K * lane_stride floats for it (allocated at first use, grown when a larger record comes, freed
+ * with the engine).  Such a call that has to allocate or grow the row SYNCHRONISES the engine's stream (hipStreamSynchronize, hipFree,
+ * hipMalloc) and cannot be captured into a graph; every other call, and every call that passes `values`, enqueues only.
+ * sums (may be NULL): device int64 [n_sets][2], ADDED to like the sums of "Entropy".  Every lane keeps two f32 running sums in step
+ * order, +0.0f before k = 0:  s0 = fmaf(e1, e1, s0),  s1 = fmaf(es, es, s1)  with es = cut ? e2 : e1; each is fixed once per lane
+ * (q = rint(L * 2^24) as in "gradients"); a sum that cannot be fixed adds nothing and excluded[set] += 1.
+ * counts (may be NULL): device uint64 [n_sets][2], ADDED to, exact: counts[set][0] += the lane-steps seen, counts[set][1] += the cut
+ * ones.  The mean squared error of a set is sums[set][0] * 2^-24 / counts[set][0].
+ *   - The call runs in the engine's stream order and uses the engine only for the stream, the kind, n_envs, global_env_offset, the
+ *     critic set and the scratch row.  It reads lanes i < n_envs of every row only.  Of the record only obs is read.  n_steps == 0 is
+ *     a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, reserved or pad_ != 0, unknown flag bits, no critic set (naming
+ *     gymrs_set_critic), with the flag a clip that is NaN, infinite or <= 0 or a NULL old_values, old_values without the flag, NULL obs
+ *     / start_obs / returns / grad / excluded, a row not 16-byte aligned, a table not 8-byte aligned, values == returns or values ==
+ *     old_values, lane_stride < n_envs or not a multiple of 16.
+ *   - gymrs_value_lane: host only, no GPU: the definition as code, as gymrs_ppo_lane is for "clipped surrogate".  From ONE critic's
+ *     weights, K = n_steps, one lane's x[K][D], returns[K] and old_values[K] (NULL: plain; else GYMRS_VALUE_CLIP with `clip`) it SETS
+ *     q[0..S), *excluded and, where the pointer is not NULL, sums[0..2), counts[0..2), values[0..K).  A sum that cannot be fixed
+ *     counts in *excluded only when sums != NULL, as on the device.  GYMRS_EINVAL: Pendulum, hidden > 64, NULL arguments, a bad clip.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+#define GYMRS_VALUE_CLIP 1u
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* GYMRS_VALUE_CLIP, nothing else */
+    float clip;                 /* with the flag: finite, > 0 (PPO2 / SB3 clip_range_vf); without: not read */
+    uint32_t pad_;              /* 0 */
+    gymrs_trajectory record;    /* by value; READ: obs only; lane_stride >= n_envs, a multiple of 16 */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* returns;       /* [K][lane_stride], required, 16-byte aligned */
+    const float* old_values;    /* [K][lane_stride], 16-byte aligned: required with the flag, NULL without */
+    float* values;              /* [K][lane_stride] or NULL; not returns, not old_values */
+    int64_t* grad;              /* device int64 [n_sets][S], 8-byte aligned, ADDED to */
+    uint64_t* excluded;         /* device uint64 [n_sets], ADDED to */
+    int64_t* sums;              /* device int64 [n_sets][2] or NULL, 8-byte aligned, ADDED to */
+    uint64_t* counts;           /* device uint64 [n_sets][2] or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_value_desc;             /* 136 bytes */
+gymrs_status gymrs_value_gradient(gymrs_engine* e, const gymrs_value_desc* d);
+gymrs_status gymrs_value_lane(gymrs_env_kind kind, uint32_t hidden, float clip, const float* weights, uint32_t n_steps, const float* x,
+                              const float* returns, const float* old_values, int64_t* q, uint64_t* excluded, int64_t sums[2], uint64_t counts[2],
+                              float* values);
+/* Advantage normalisation: out = (A - mean) / (sd + eps) per set, exact and order-independent.  gymrs_normalize_advantages(e, d)
+ * writes out[k][i] from A = adv[k][i] for k < K, i < n_envs.  Statistics are per set under the policy's key: lane i has the global
+ * id g = global_env_offset + i and set (g / lanes_per_policy) % n_sets, both numbers from the descriptor: the call needs no policy
+ * set, uses the engine for the stream, n_envs and global_env_offset only and works for every env kind.  out may equal adv.
+ *     member  = A is finite and |A| < 8192.0f
+ *     pass 1:   q1 = (int64) rint((double)A * 2^24);  S1[set] += q1,  n[set] += 1                     over members
+ *               mean = (float)((double)S1 / ((double)n * 2^24))                                       (n == 0: mean = +0.0f)
+ *     pass 2:   dm = A - mean;  sq = dm * dm;  q2 = (uint64) rint((double)sq * 2^24);  S2[set] += q2   over members
+ *               var = (double)S2 / 2^24 / (double)(n - 1);  sd = sqrt(var)      (f64, correctly rounded; n < 2: sd = 0)
+ *               inv = (float)(1.0 / (sd + (double)eps))
+ *     pass 3:   out = (A - mean) * inv        for EVERY lane-step with i < n_envs (a non-member gets the same arithmetic: NaN stays NaN)
+ * All sums are integers modulo 2^64: within ONE engine the result does not depend on scheduling or tiling.  The statistics are over
+ * the members the engine holds.  Unlike the other calls of this header the call is NOT additive over engines: of engines that cut
+ * one batch by their global_env_offset only S1, n and non_members add up to the one engine's.  Every engine centres pass 2 on the mean
+ * of its OWN members, so its S2 differs from its share of the whole's by n_p * (mean_p - mean)^2, and mean, inv and out are per
+ * engine: standardise a batch that is cut over engines in one engine, or accept per-shard statistics.  Resolution: 2^-24 on an element
+ * and on a square.  |dm| < 16384, so sq < 2^28 always fixes.  No wrap while, per set, the sum of sq is < 2^40 (and |sum of A| < 2^39).
+ * stats (required): device memory of gymrs_advantage_stats[n_sets], WRITTEN: the launch zeroes and fills it, the caller zeroes
+ * nothing; non_members counts the lane-steps left out of the statistics.
+ *   - The call runs in the engine's stream order.  Padding lanes [n_envs, lane_stride) are not read and keep their bytes in out.
+ *     n_steps == 0 is a no-op after the checks (stats is not written).
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, reserved != 0, flags != 0, NULL adv / out / stats, adv or out not 16-byte
+ *     aligned, stats not 8-byte aligned, lane_stride < n_envs or not a multiple of 16, lanes_per_policy == 0, n_sets == 0, eps NaN,
+ *     infinite or <= 0.
+ *   - gymrs_normalize_host: host only, no GPU: the same text for ONE set: from a[0..count) it SETS out[0..count) and *st.
+ *     GYMRS_EINVAL: NULL st, NULL a or out with count > 0, a bad eps.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+typedef struct {
+    int64_t s1;                 /* sum of q1 over the members */
+    uint64_t n;                 /* members */
+    uint64_t s2;                /* sum of q2 over the members */
+    uint64_t non_members;       /* lane-steps with a NaN, an infinity or |A| >= 8192 */
+    float mean, inv;            /* what pass 3 used */
+} gymrs_advantage_stats;        /* 40 bytes */
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* 0, reserved */
+    float eps;                  /* finite, > 0 */
+    uint32_t n_sets;            /* >= 1 */
+    uint64_t lanes_per_policy;  /* >= 1 */
+    uint64_t lane_stride;       /* >= n_envs, a multiple of 16 */
+    const float* adv;           /* [K][lane_stride], required, 16-byte aligned */
+    float* out;                 /* [K][lane_stride], required, 16-byte aligned; may be adv */
+    gymrs_advantage_stats* stats; /* device [n_sets], required, 8-byte aligned, WRITTEN */
+    uint64_t reserved;          /* 0 */
+} gymrs_normalize_desc;         /* 64 bytes */
+gymrs_status gymrs_normalize_advantages(gymrs_engine* e, const gymrs_normalize_desc* d);
+gymrs_status gymrs_normalize_host(const float* a, uint64_t count, float eps, float* out, gymrs_advantage_stats* st);
 /* Q-learning: TD errors and the Q-gradient over a transitions record, with a target set, Double-DQN action selection and a Huber
  * clamp, as exact fixed-point integers.  The policy network's logits are the Q-values.  gymrs_q_gradient(e, d) writes the TD error of
  * every lane-step to td and ADDS, for every set m and every parameter s of its network, the fixed point of the lane's f32 sum of

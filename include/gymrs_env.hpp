@@ -178,6 +178,23 @@ inline std::uint64_t entropy_lane(gymrs_env_kind kind, std::uint32_t hidden, flo
     check(gymrs_entropy_lane(kind, hidden, scale, coef, weights, n_steps, x, actions, old_prob, q, &excluded, sums, counts));
     return excluded;
 }
+// One lane's contribution to gymrs_value_gradient (gymrs_value_lane; host only, no GPU): q[0 .. S) is set, the number of excluded
+// sums returned; old_values null: the plain squared error; sums, counts and values may be null.  normalize_host is the rule of
+// "Advantage normalisation" for one set.
+inline std::uint64_t value_lane(gymrs_env_kind kind, std::uint32_t hidden, float clip, const float* weights, std::uint32_t n_steps, const float* x,
+                                const float* returns, const float* old_values, std::int64_t* q, std::int64_t* sums = nullptr,
+                                std::uint64_t* counts = nullptr, float* values = nullptr)
+{
+    std::uint64_t excluded = 0;
+    check(gymrs_value_lane(kind, hidden, clip, weights, n_steps, x, returns, old_values, q, &excluded, sums, counts, values));
+    return excluded;
+}
+inline gymrs_advantage_stats normalize_host(const float* a, std::uint64_t count, float eps, float* out)
+{
+    gymrs_advantage_stats st{};
+    check(gymrs_normalize_host(a, count, eps, out, &st));
+    return st;
+}
 inline float entropy_log2(float v)
 {
     float out = 0.0f;
@@ -488,6 +505,11 @@ public:
         const gymrs_entropy_desc d{n_steps, 0u, scale, coef, record, start_obs, old_prob, grad, excluded, sums, counts, 0};
         check(gymrs_entropy_gradient(e_, &d));
     }
+    // the value loss (gymrs_value_gradient): the critic head with its coefficient computed in the kernel from V(x), d.returns and,
+    // with GYMRS_VALUE_CLIP, d.old_values; ADDS the gradient of the loss (to descend) to d.grad and d.excluded
+    void value_gradient(const gymrs_value_desc& d) { check(gymrs_value_gradient(e_, &d)); }
+    // per-set advantage normalisation (gymrs_normalize_advantages): d.out = (d.adv - mean) / (sd + eps) from integer sums; d.stats is written
+    void normalize_advantages(const gymrs_normalize_desc& d) { check(gymrs_normalize_advantages(e_, &d)); }
     // Q-learning (include/gymrs_amd.h, "Q-learning"): the target set is a copy of the policy set the engine owns (q_target_sync, in
     // stream order; q_target_ptr is its zero-copy view); q_gradient writes the TD errors to d.td and ADDS the gradient of the Huber
     // loss (to descend) to d.grad and d.excluded and, when d.counts is not null, the lane-steps seen and clamped
