@@ -211,6 +211,32 @@ pub struct GymrsPpoDesc {
     pub reserved: u64,
 }
 
+/// `gymrs_vtrace_desc`: what `gymrs_vtrace` runs (include/gymrs_amd.h "V-trace"), 152 bytes: the six scalars, the record by value, the two
+/// observation buffers and the `old_prob` row in, `vs` and `pg_advantages` out, `values`, `prob` (or null) out and `counts` u64
+/// `[n_policies][3]` (or null): the lane-steps seen, with ratio > rho_bar, with ratio > c_bar, added to.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct GymrsVtraceDesc {
+    pub n_steps: u32,
+    pub flags: u32,
+    pub gamma: f32,
+    pub lambda: f32,
+    pub scale: f32,
+    pub rho_bar: f32,
+    pub c_bar: f32,
+    pub pg_rho_bar: f32,
+    pub record: Trajectory,
+    pub final_obs: *const f32,
+    pub start_obs: *const f32,
+    pub old_prob: *const f32,
+    pub vs: *mut f32,
+    pub pg_advantages: *mut f32,
+    pub values: *mut f32,
+    pub prob: *mut f32,
+    pub counts: *mut u64,
+    pub reserved: u64,
+}
+
 /// `gymrs_entropy_desc`: what `gymrs_entropy_gradient` runs (include/gymrs_amd.h "Entropy"), 128 bytes: the entropy coefficient, the
 /// record by value (`obs`, and `actions` with `old_prob`), `old_prob` (or null: no KL estimate), the gradient tables of
 /// `gymrs_ppo_desc`, `sums` i64 `[n_sets][2]` (the fixed points of the entropy and k3 KL sums) and `counts` u64 `[n_sets][2]` (or null).
@@ -587,6 +613,13 @@ extern "C" {
     pub fn gymrs_ppo_lane(kind: c_int, hidden: u32, scale: f32, clip_low: f32, clip_high: f32, weights: *const f32, n_steps: u32, x: *const f32,
                           actions: *const u8, advantages: *const f32, old_prob: *const f32, q: *mut i64, excluded: *mut u64, counts: *mut u64,
                           prob: *mut f32) -> c_int;
+    /// V-trace targets and policy-gradient advantages over a transitions record in one launch, and one lane of it on the host
+    pub fn gymrs_vtrace(e: *mut GymrsEngine, d: *const GymrsVtraceDesc) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    pub fn gymrs_vtrace_lane(kind: c_int, policy_hidden: u32, critic_hidden: u32, policy_weights: *const f32, critic_weights: *const f32, n_steps: u32,
+                             x: *const f32, x_next: *const f32, actions: *const u8, reward: *const f32, done: *const u8, ended: *const u8,
+                             old_prob: *const f32, gamma: f32, lambda: f32, scale: f32, rho_bar: f32, c_bar: f32, pg_rho_bar: f32, vs: *mut f32,
+                             pg_advantages: *mut f32, values: *mut f32, prob: *mut f32, counts: *mut u64) -> c_int;
     /// the entropy bonus and the k3 KL estimate over a transitions record in one launch, one lane of it on the host, and its log2
     pub fn gymrs_entropy_gradient(e: *mut GymrsEngine, d: *const GymrsEntropyDesc) -> c_int;
     #[allow(clippy::too_many_arguments)]

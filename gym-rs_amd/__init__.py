@@ -51,6 +51,7 @@ from .engine import Sampling, CLOSED_LOOP_SAMPLE, sample_draw
 from .engine import AdvantagesDesc, ADVANTAGES_CRITIC, critic_size, critic_value
 from .engine import GradientDesc, GRADIENT_CRITIC, gradient_lane
 from .engine import PpoDesc, ppo_lane
+from .engine import VtraceDesc, vtrace_lane
 from .engine import EntropyDesc, entropy_lane, entropy_log2
 from .engine import ValueDesc, VALUE_CLIP, value_lane
 from .engine import NormalizeDesc, AdvantageStats, ADVANTAGE_STATS_DTYPE, normalize_host
@@ -72,6 +73,7 @@ __all__ = [
     "AdvantagesDesc", "ADVANTAGES_CRITIC", "critic_size", "critic_value",
     "GradientDesc", "GRADIENT_CRITIC", "gradient_lane",
     "PpoDesc", "ppo_lane",
+    "VtraceDesc", "vtrace_lane",
     "EntropyDesc", "entropy_lane", "entropy_log2",
     "ValueDesc", "VALUE_CLIP", "value_lane",
     "NormalizeDesc", "AdvantageStats", "ADVANTAGE_STATS_DTYPE", "normalize_host",

@@ -114,6 +114,10 @@ SIGNATURES = {
     "gymrs_entropy_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, C.c_float, f32p, C.c_uint32, f32p, C.POINTER(C.c_uint8), f32p,
                                      C.POINTER(C.c_int64), u64p, C.POINTER(C.c_int64), u64p]),
     "gymrs_entropy_log2": (C.c_int, [C.c_float, f32p]),
+    # V-trace over a transitions record (gymrs_vtrace_desc 152 B) and the host-only lane
+    "gymrs_vtrace": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gymrs_vtrace_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, f32p, f32p, C.c_uint32, f32p, f32p, C.POINTER(C.c_uint8), f32p,
+                                    C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), f32p] + [C.c_float] * 6 + [f32p, f32p, f32p, f32p, u64p]),
     # the value loss over a transitions record (gymrs_value_desc 136 B) and the host-only lane
     "gymrs_value_gradient": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gymrs_value_lane": (C.c_int, [C.c_int, C.c_uint32, C.c_float, f32p, C.c_uint32, f32p, f32p, f32p, C.POINTER(C.c_int64), u64p,

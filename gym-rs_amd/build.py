@@ -27,7 +27,7 @@ HIP_SOURCES = [CSRC / "gymrs_step_cartpole.hip", CSRC / "gymrs_step_mountain_car
                CSRC / "gymrs_explore.hip", CSRC / "gymrs_explore_fitness.hip", CSRC / "gymrs_table_explore_cartpole.hip",
                CSRC / "gymrs_table_explore_mountain_car.hip", CSRC / "gymrs_transitions.hip", CSRC / "gymrs_table_transitions_cartpole.hip",
                CSRC / "gymrs_table_transitions_mountain_car.hip", CSRC / "gymrs_sample.hip", CSRC / "gymrs_sample_fitness.hip",
-               CSRC / "gymrs_table_sample_cartpole.hip", CSRC / "gymrs_table_sample_mountain_car.hip", CSRC / "gymrs_advantages.hip", CSRC / "gymrs_gradient.hip", CSRC / "gymrs_gradient_ppo.hip", CSRC / "gymrs_entropy.hip", CSRC / "gymrs_value.hip", CSRC / "gymrs_normalize.hip", CSRC / "gymrs_qlearn.hip", CSRC / "gymrs_replay.hip", CSRC / "gymrs_optimizer.hip", CSRC / "gymrs_es.hip", CSRC / "gymrs_es_ranks.hip", CSRC / "gymrs_evaluate.hip", CSRC / "gymrs_aux.hip", CSRC / "gymrs_engine.hip", CSRC / "gymrs_engine_io.hip",
+               CSRC / "gymrs_table_sample_cartpole.hip", CSRC / "gymrs_table_sample_mountain_car.hip", CSRC / "gymrs_advantages.hip", CSRC / "gymrs_gradient.hip", CSRC / "gymrs_gradient_ppo.hip", CSRC / "gymrs_vtrace.hip", CSRC / "gymrs_entropy.hip", CSRC / "gymrs_value.hip", CSRC / "gymrs_normalize.hip", CSRC / "gymrs_qlearn.hip", CSRC / "gymrs_replay.hip", CSRC / "gymrs_optimizer.hip", CSRC / "gymrs_es.hip", CSRC / "gymrs_es_ranks.hip", CSRC / "gymrs_evaluate.hip", CSRC / "gymrs_aux.hip", CSRC / "gymrs_engine.hip", CSRC / "gymrs_engine_io.hip",
                CSRC / "gymrs_engine_learn.hip",
                CSRC / "gymrs_aql.hip", CSRC / "gymrs_sharded.hip"]
 # The per-step kernels once more as a stand-alone gfx950 code object (device-only compile), embedded into the library by

@@ -8,6 +8,7 @@
 #include "gymrs_sample.h"
 #include "gymrs_advantages.h"
 #include "gymrs_gradient.h"
+#include "gymrs_vtrace.h"
 #include "gymrs_entropy.h"
 #include "gymrs_value.h"
 #include "gymrs_normalize.h"
@@ -649,6 +650,54 @@ void value_lane(uint32_t H, float clip, const float* weights, uint32_t K, const 
     }
 }
 
+// ---- "V-trace": the scalars both entry points refuse in the same words, and the lane
+struct VtraceScalars {
+    float gamma, lambda, scale, rho_bar, c_bar, pg_rho_bar;
+};
+bool vtrace_bar_ok(float bar) { return bar > 0.0f; } // (false for a NaN; +inf is no clipping)
+// what the lane and the launch refuse in the same words; "" = fine
+const char* vtrace_scalars_refused(const VtraceScalars& s)
+{
+    if (!(s.gamma >= 0.0f && s.gamma <= 1.0f)) return "gamma must be in [0, 1]";
+    if (!(s.lambda >= 0.0f && s.lambda <= 1.0f)) return "lambda must be in [0, 1]";
+    if (!finite_non_negative(s.scale)) return "scale must be finite and >= 0";
+    if (!vtrace_bar_ok(s.rho_bar) || !vtrace_bar_ok(s.c_bar) || !vtrace_bar_ok(s.pg_rho_bar)) return "rho_bar, c_bar and pg_rho_bar must be > 0 (+inf: no clipping)";
+    return "";
+}
+
+// One lane of "V-trace" by the shared text: the kernel's forward phase and scan with one lane, row K-1 down to row 0.
+template <int D, int A>
+void vtrace_lane(uint32_t Hp, uint32_t Hc, const float* wp_, const float* wc_, uint32_t K, const float* x, const float* x_next, const uint8_t* actions,
+                 const float* reward, const uint8_t* done, const uint8_t* ended, const float* old_prob, const VtraceScalars& s, float* vs, float* pg,
+                 float* values, float* prob, uint64_t* counts)
+{
+    const HostWeights wp{wp_}, wc{wc_};
+    uint64_t cnt[3] = {0, 0, 0};
+    float acc = 0.0f;
+    for (uint32_t k = K; k-- > 0;) {
+        float xs[D][1], xn[D][1], y[A][1], v_cur[1], v_succ[1], yl[A];
+        for (int j = 0; j < D; ++j) {
+            xs[j][0] = x[(size_t)k * D + j];
+            xn[j][0] = x_next[(size_t)k * D + j];
+        }
+        gradient_logits<D, A, 1, 1>(wp, Hp, xs, y);
+        critic_values<D, 1, 1>(wc, Hc, xs, v_cur);
+        critic_values<D, 1, 1>(wc, Hc, xn, v_succ);
+        for (int b = 0; b < A; ++b) yl[b] = y[b][0];
+        const float pa = vtrace_prob<A>(yl, actions[k], s.scale);
+        const bool valid = actions[k] < (uint8_t)A;
+        const VtraceWeights w = vtrace_weights(pa, old_prob[k], valid, s.gamma, s.lambda, s.rho_bar, s.c_bar, s.pg_rho_bar);
+        vtrace_step(s.gamma, reward[k], done[k] != 0, ended[k] != 0, v_succ[0], v_cur[0], w.rho, w.gc, w.rho_pg, acc, vs[k], pg[k]);
+        if (values) values[k] = v_cur[0];
+        if (prob) prob[k] = pa;
+        cnt[0] += valid ? 1 : 0;
+        cnt[1] += w.over_rho ? 1 : 0;
+        cnt[2] += w.over_c ? 1 : 0;
+    }
+    if (counts)
+        for (int c = 0; c < 3; ++c) counts[c] = cnt[c];
+}
+
 bool q_gamma_ok(float gamma) { return gamma >= 0.0f && gamma <= 1.0f; } // (false for a NaN)
 bool q_kappa_ok(float kappa) { return kappa > 0.0f; }                   // (false for a NaN; +inf is the squared loss)
 } // namespace
@@ -984,6 +1033,62 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d)
                     reinterpret_cast<unsigned long long*>(d->counts), d->clip_low, d->clip_high};
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(launch_ppo_gradient(e->kind, a, e->policy.args, e->stream));
+    return GYMRS_OK;
+}
+
+// ---- V-trace: the host-side lane and the launch (include/gymrs_amd.h, "V-trace") ----------------------------------------------------
+static_assert(sizeof(gymrs_vtrace_desc) == 152, "descriptor size");
+
+gymrs_status gymrs_vtrace_lane(gymrs_env_kind kind, uint32_t policy_hidden, uint32_t critic_hidden, const float* policy_weights,
+                               const float* critic_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
+                               const float* reward, const uint8_t* done, const uint8_t* ended, const float* old_prob, float gamma, float lambda,
+                               float scale, float rho_bar, float c_bar, float pg_rho_bar, float* vs, float* pg_advantages, float* values, float* prob,
+                               uint64_t counts[3])
+{
+    const std::string who = "gymrs_vtrace_lane";
+    if (gymrs_status st = check_network(kind, policy_hidden, who)) return st;
+    if (gymrs_status st = check_network(kind, critic_hidden, who)) return st;
+    if (!policy_weights || !critic_weights || (n_steps != 0 && (!x || !x_next || !actions || !reward || !done || !ended || !old_prob || !vs || !pg_advantages)))
+        return fail(GYMRS_EINVAL, who + ": NULL argument");
+    if (prob && prob == old_prob) return fail(GYMRS_EINVAL, who + ": prob and old_prob may not alias");
+    const VtraceScalars s{gamma, lambda, scale, rho_bar, c_bar, pg_rho_bar};
+    if (const char* why = vtrace_scalars_refused(s); *why) return fail(GYMRS_EINVAL, who + ": " + why);
+    if (kind == GYMRS_CARTPOLE)
+        vtrace_lane<4, 2>(policy_hidden, critic_hidden, policy_weights, critic_weights, n_steps, x, x_next, actions, reward, done, ended, old_prob, s, vs,
+                          pg_advantages, values, prob, counts);
+    else
+        vtrace_lane<2, 3>(policy_hidden, critic_hidden, policy_weights, critic_weights, n_steps, x, x_next, actions, reward, done, ended, old_prob, s, vs,
+                          pg_advantages, values, prob, counts);
+    return GYMRS_OK;
+}
+
+gymrs_status gymrs_vtrace(gymrs_engine* e, const gymrs_vtrace_desc* d)
+{
+    const RecordCall c{e, d, "gymrs_vtrace"};
+    if (gymrs_status st = c.prologue("V-trace targets are")) return st;
+    if (d->reserved != 0) return c.refuse("reserved must be 0");
+    if (d->flags != 0) return c.refuse("unknown flag bits (flags must be 0)");
+    if (gymrs_status st = check_policy_set(e, c.who)) return st;
+    if (!e->critic.dev) return c.refuse("the engine has no critic set (gymrs_set_critic)");
+    if (const char* why = vtrace_scalars_refused({d->gamma, d->lambda, d->scale, d->rho_bar, d->c_bar, d->pg_rho_bar}); *why) return c.refuse(why);
+    const gymrs_trajectory& rec = d->record;
+    if (gymrs_status st = c.not_null({{rec.obs, "record.obs"}, {rec.actions, "record.actions"}, {rec.reward, "record.reward"}, {rec.done, "record.done"},
+                                      {d->start_obs, "start_obs"}, {d->old_prob, "old_prob"}, {d->vs, "vs"}, {d->pg_advantages, "pg_advantages"}}))
+        return st;
+    if (d->prob == d->old_prob) return c.refuse("prob and old_prob may not alias");
+    if (gymrs_status st = c.aligned({rec.obs, rec.actions, rec.reward, rec.done, rec.truncated, d->final_obs, d->start_obs, d->old_prob, d->vs,
+                                     d->pg_advantages, d->values, d->prob},
+                                    16, "every row buffer must be 16-byte aligned"))
+        return st;
+    if (gymrs_status st = c.aligned({d->counts}, 8, "counts must be 8-byte aligned")) return st;
+    if (gymrs_status st = c.lane_stride(rec.lane_stride)) return st;
+    if (d->n_steps == 0) return GYMRS_OK;
+    const VtraceArgs a{rec.obs, static_cast<const uint8_t*>(rec.actions), rec.reward, rec.done, rec.truncated, d->final_obs, d->start_obs, d->old_prob,
+                       d->vs, d->pg_advantages, d->values, d->prob, reinterpret_cast<unsigned long long*>(d->counts),
+                       /*stride, n, gid0*/ rec.lane_stride, e->n, e->gid0, d->n_steps, d->gamma, d->lambda, d->scale, d->rho_bar, d->c_bar, d->pg_rho_bar,
+                       /*pad_*/ 0};
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(launch_vtrace(e->kind, a, e->policy.args, e->critic.args, e->stream));
     return GYMRS_OK;
 }
 

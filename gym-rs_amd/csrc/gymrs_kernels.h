@@ -386,6 +386,31 @@ struct AdvantageArgs {
 };
 // critic == NULL: V = +0.0f everywhere (no observation is read)
 hipError_t launch_advantages(gymrs_env_kind kind, const AdvantageArgs& a, const PolicyArgs* critic, hipStream_t stream);
+// ---- V-trace (gymrs_vtrace; gymrs_vtrace.hip) -----------------------------------------------------------------------------------
+constexpr int kVtraceTile = 64;      // consecutive lanes a workgroup owns
+constexpr uint32_t kVtraceRows = 16; // R: rows of the record per pass of a workgroup (profiles/vtrace.md)
+// A gymrs_vtrace_desc as its kernel gets it by value, before the policy set and the critic set.  Rows are `stride` lanes apart
+// (>= n, a multiple of 16) and 16-byte aligned; counts is 8-byte aligned and ADDED to.
+struct VtraceArgs {
+    const float* obs;           // [n_steps][obs_dim][stride]
+    const uint8_t* actions;     // [n_steps][stride]
+    const float* reward;        // [n_steps][stride]
+    const uint8_t* done;        // [n_steps][stride]
+    const uint8_t* truncated;   // [n_steps][stride] or NULL
+    const float* final_obs;     // [n_steps][obs_dim][stride] or NULL; read on truncated-only steps
+    const float* start_obs;     // [obs_dim][stride]
+    const float* old_prob;      // [n_steps][stride]
+    float* vs;                  // [n_steps][stride]
+    float* pg;                  // [n_steps][stride]
+    float* values;              // [n_steps][stride] or NULL
+    float* prob;                // [n_steps][stride] or NULL
+    unsigned long long* counts; // [n_policies][3] or NULL
+    uint64_t stride, n, gid0;
+    uint32_t n_steps;
+    float gamma, lambda, scale, rho_bar, c_bar, pg_rho_bar;
+    uint32_t pad_;
+};
+hipError_t launch_vtrace(gymrs_env_kind kind, const VtraceArgs& a, const PolicyArgs& policy, const PolicyArgs& critic, hipStream_t stream);
 // ---- gradients (gymrs_policy_gradient; gymrs_gradient.hip) ---------------------------------------------------------------------
 // A gymrs_gradient_desc as the kernel gets it by value, before the set (the policy's PolicyArgs, or the critic's).  Rows are
 // `stride` lanes apart (>= n, a multiple of 16) and 16-byte aligned; grad and excluded are 8-byte aligned and ADDED to.

@@ -44,6 +44,26 @@ __device__ __forceinline__ void policy_select(const PolicyArgs& p, uint64_t g0, 
     }
 }
 
+// The same for a kernel whose workgroup owns a tile of TILE consecutive lanes that its waves share row by row (gymrs_vtrace_impl.h):
+// g0 = the global id of the work-item's first lane, tile_g0 = of the tile's (workgroup-uniform).  `uniform` (workgroup-uniform): the
+// TILE lanes all use pol[0].  No cross-lane operation: it may be called under any exec mask.
+template <int VEC, int TILE>
+__device__ __forceinline__ void policy_select_tile(const PolicyArgs& p, uint64_t g0, uint64_t tile_g0, uint32_t (&pol)[VEC], bool& uniform)
+{
+    uniform = p.n_policies == 1 || p.lanes_per_policy - tile_g0 % p.lanes_per_policy >= (uint64_t)TILE;
+    const uint64_t q0 = g0 / p.lanes_per_policy;
+    uint64_t r = g0 - q0 * p.lanes_per_policy;
+    uint32_t m = (uint32_t)(q0 % p.n_policies);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        pol[k] = m;
+        if (++r == p.lanes_per_policy) {
+            r = 0;
+            if (++m == p.n_policies) m = 0;
+        }
+    }
+}
+
 // The weights as a work-item reads them.  UNI: one wave-uniform base in the constant address space (scalar loads);
 // else one policy index per lane (vector loads from the table).
 template <int VEC, bool UNI>

@@ -132,6 +132,15 @@ class PpoDesc(C.Structure):
                 ("prob", C.c_void_p), ("grad", C.c_void_p), ("excluded", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+class VtraceDesc(C.Structure):
+    """``gymrs_vtrace_desc`` (include/gymrs_amd.h), 152 bytes: six scalars, the record by value, three buffers in, two rows out, two
+    optional rows out and an optional triple of counters per policy set added to."""
+    _fields_ = [("n_steps", C.c_uint32), ("flags", C.c_uint32), ("gamma", C.c_float), ("lam", C.c_float), ("scale", C.c_float),
+                ("rho_bar", C.c_float), ("c_bar", C.c_float), ("pg_rho_bar", C.c_float), ("record", Trajectory), ("final_obs", C.c_void_p),
+                ("start_obs", C.c_void_p), ("old_prob", C.c_void_p), ("vs", C.c_void_p), ("pg_advantages", C.c_void_p), ("values", C.c_void_p),
+                ("prob", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class EntropyDesc(C.Structure):
     """``gymrs_entropy_desc`` (include/gymrs_amd.h), 128 bytes: the record by value, one row in and one optional row in, three tables
     and an optional pair of counters per set added to."""
@@ -463,6 +472,35 @@ def ppo_lane(kind: int, hidden: int, weights, x, actions, advantages, old_prob, 
                                    q.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(excluded), counts.ctypes.data_as(up),
                                    pr.ctypes.data_as(fp) if prob else None))
     return (q, excluded.value, counts, pr) if prob else (q, excluded.value, counts)
+
+
+def vtrace_lane(kind: int, policy_hidden: int, critic_hidden: int, policy_weights, critic_weights, x, x_next, actions, reward, done, ended,
+                old_prob, *, gamma: float, lam: float, rho_bar: float = 1.0, c_bar: float = 1.0, pg_rho_bar: float = 1.0,
+                temperature: Optional[float] = None, scale: Optional[float] = None):
+    """``gymrs_vtrace_lane`` (host only, no GPU): one lane of ``gymrs_vtrace`` -- the definition of include/gymrs_amd.h, "V-trace", as
+    code.  ONE policy and ONE critic; ``x`` [K][D] (the observation each action was drawn from), ``x_next`` [K][D] (the successor,
+    already selected), ``actions``, ``reward``, ``done``, ``ended``, ``old_prob`` [K].  Exactly one of ``temperature`` / ``scale``.
+    Returns (vs, pg_advantages, values, prob, counts): f32 [K] each, counts uint64 [3] = (lane-steps with an action in range, of those
+    ratio > rho_bar, of those ratio > c_bar)."""
+    lib = load_library()
+    f32 = lambda v: np.ascontiguousarray(v, dtype=np.float32).reshape(-1)  # noqa: E731
+    u8 = lambda v: np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)  # noqa: E731
+    wp, wc, xs, xn, r, po = f32(policy_weights), f32(critic_weights), f32(x), f32(x_next), f32(reward), f32(old_prob)
+    a, dn, en = u8(actions), u8(done), u8(ended)
+    if wp.size != policy_size(kind, policy_hidden) or wc.size != critic_size(kind, critic_hidden):
+        raise ValueError("vtrace_lane needs one policy's and one critic's weights")
+    if xs.size != r.size * _OBS_DIM[kind] or xn.size != xs.size or any(v.size != r.size for v in (po, a, dn, en)):
+        raise ValueError(f"vtrace_lane needs {_OBS_DIM[kind]} observation components and one of every row per step")
+    s = _sampling(0, temperature, scale).scale
+    vs, pg, values, prob = (np.empty(r.size, np.float32) for _ in range(4))
+    counts = np.zeros(3, np.uint64)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    _check(lib, lib.gymrs_vtrace_lane(int(kind), int(policy_hidden), int(critic_hidden), wp.ctypes.data_as(fp), wc.ctypes.data_as(fp), int(r.size),
+                                      xs.ctypes.data_as(fp), xn.ctypes.data_as(fp), a.ctypes.data_as(bp), r.ctypes.data_as(fp), dn.ctypes.data_as(bp),
+                                      en.ctypes.data_as(bp), po.ctypes.data_as(fp), float(gamma), float(lam), float(s), float(rho_bar), float(c_bar),
+                                      float(pg_rho_bar), vs.ctypes.data_as(fp), pg.ctypes.data_as(fp), values.ctypes.data_as(fp),
+                                      prob.ctypes.data_as(fp), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return vs, pg, values, prob, counts
 
 
 def entropy_log2(v: float) -> float:
@@ -1185,6 +1223,25 @@ class BatchedEngine:
                        C.c_void_p(old_prob or None), C.c_void_p(prob or None), C.c_void_p(grad or None), C.c_void_p(excluded or None),
                        C.c_void_p(counts or None), 0)
         _check(self._lib, self._lib.gymrs_ppo_gradient(self._h, C.byref(desc)))
+
+    # -- V-trace targets and policy-gradient advantages over a transitions record: both networks and the scan in one launch ---------
+    def vtrace(self, n_steps: int, *, record, start_obs: int, old_prob: int, vs: int, pg_advantages: int, final_obs: Optional[int] = None,
+               values: Optional[int] = None, prob: Optional[int] = None, counts: Optional[int] = None, gamma: float, lam: float = 1.0,
+               rho_bar: float = 1.0, c_bar: float = 1.0, pg_rho_bar: float = 1.0, temperature: Optional[float] = None,
+               scale: Optional[float] = None, flags: int = 0) -> None:
+        """``gymrs_vtrace``: the off-policy corrected counterpart of ``advantages``.  From the record, the ``old_prob`` row (the ``prob``
+        row of the policy the record was drawn from), the CURRENT policy set and the critic set it writes ``vs`` (the ``returns`` row of
+        ``value_gradient``) and ``pg_advantages`` (the ``coef`` / ``advantages`` row of ``policy_gradient`` / ``ppo_gradient``), and
+        optionally ``values`` (V under the current critic), ``prob`` (the current p[a]; not ``old_prob``) and, ADDED to, ``counts``
+        (device uint64 [n_policies][3]: lane-steps seen, with ratio > rho_bar, with ratio > c_bar).  One launch on the engine's stream:
+        no sync is needed behind ``apply_gradient``.  A bar of ``inf`` does not clip.  Exactly one of ``temperature`` / ``scale``.
+        Reads and writes no lane array."""
+        traj = _record("vtrace", self.n_envs, n_steps, record)
+        s = _sampling(0, temperature, scale).scale
+        desc = VtraceDesc(int(n_steps), int(flags), float(gamma), float(lam), float(s), float(rho_bar), float(c_bar), float(pg_rho_bar), traj,
+                          C.c_void_p(final_obs or None), C.c_void_p(start_obs or None), C.c_void_p(old_prob or None), C.c_void_p(vs or None),
+                          C.c_void_p(pg_advantages or None), C.c_void_p(values or None), C.c_void_p(prob or None), C.c_void_p(counts or None), 0)
+        _check(self._lib, self._lib.gymrs_vtrace(self._h, C.byref(desc)))
 
     # -- the entropy bonus and the KL estimate over a transitions record: one launch beside ppo_gradient ----------------
     def entropy_gradient(self, n_steps: int, *, record, start_obs: int, grad: int, excluded: int, sums: int, coef: float,

@@ -853,6 +853,84 @@ gymrs_status gymrs_ppo_gradient(gymrs_engine* e, const gymrs_ppo_desc* d);
 gymrs_status gymrs_ppo_lane(gymrs_env_kind kind, uint32_t hidden, float scale, float clip_low, float clip_high, const float* weights, uint32_t n_steps,
                             const float* x, const uint8_t* actions, const float* advantages, const float* old_prob, int64_t* q, uint64_t* excluded,
                             uint64_t counts[2], float* prob);
+/* V-trace: off-policy corrected targets and policy-gradient advantages (Espeholt et al. 2018, IMPALA) over a transitions record in ONE
+ * launch, defined to the bit.  gymrs_advantages is exact only while the record was drawn from the policy being updated; after the first
+ * gymrs_apply_gradient on a record, or for a record collected under weights one update old, the targets want the importance ratio of
+ * the CURRENT policy to the recorded one, clipped twice, inside the backward scan.  gymrs_vtrace(e, d) evaluates both networks inside
+ * the kernel and does the scan in one pass.  All arithmetic is f32, every operation below is a single IEEE operation, fmaf = the fused
+ * multiply-add with ONE rounding, nothing is contracted or reordered, every `?:` is a select.
+ * By reference: the logits y[] of an observation are those of "closed-loop rollouts"; p[] under d->scale is that of "sampling" /
+ * "gradients", and pa = p[a] is the value gymrs_policy_gradient writes to prob, bit for bit; V() is the critic of "advantages".  Lane i
+ * has the global id g = global_env_offset + i; its policy is (g / lanes_per_policy) % n_policies under the policy set's key, its critic
+ * the same expression under the critic set's key.  Rows and columns as in gymrs_rollout_transitions.
+ * The scan.  K = d->n_steps, A = number of actions, acc[K] = +0.0f; for lane i, k = K-1 down to 0:
+ *     ended   = done[k] != 0 || (truncated != NULL && truncated[k] != 0)
+ *     x_cur   = k == 0 ? start_obs : obs[k-1]
+ *     x_next  = (final_obs != NULL && ended) ? final_obs[k] : obs[k]
+ *     v_cur   = V(x_cur);   v_next = done[k] != 0 ? +0.0f : V(x_next)
+ *     valid   = actions[k] < A
+ *     ratio   = valid ? pa / old_prob[k] : +0.0f          (pa from the CURRENT policy at x_cur; one IEEE divide)
+ *     rho     = (ratio > rho_bar)    ? rho_bar    : ratio
+ *     cc      = lambda * ((ratio > c_bar) ? c_bar : ratio)
+ *     rho_pg  = (ratio > pg_rho_bar) ? pg_rho_bar : ratio
+ *     td      = fmaf(gamma, v_next, reward[k]) - v_cur
+ *     carry   = ended ? +0.0f : acc[k+1]
+ *     gc      = gamma * cc
+ *     acc[k]  = fmaf(gc, carry, rho * td)
+ *     vs[k]   = acc[k] + v_cur
+ *     vs_next = carry + v_next                            (the bits of vs[k+1] where the episode went on)
+ *     pg_advantages[k] = rho_pg * (fmaf(gamma, vs_next, reward[k]) - v_cur)
+ *     values[k] = v_cur;   prob[k] = valid ? pa : +0.0f
+ * What follows from the selects: an unselected final_obs element reaches no output (that buffer is written on ended lane-steps only);
+ * a NaN acc[k+1] behind an episode end reaches no output; a NaN V(obs[k]) on a done step reaches no output.  A NaN ratio (a NaN
+ * old_prob, 0 / 0) fails every compare and is NOT clipped: it travels down the lane's column through acc to the next episode end and no
+ * further.  old_prob = 0 with pa > 0 gives ratio = +inf, which finite bars clip.  A lane-step with actions[k] >= A has ratio +0.0f: its
+ * td does not enter, the trace is cut there (gc = +0.0f), its pg_advantages is +-0 and it is not counted.
+ * The property the tests use: where old_prob[k] == pa exactly (finite, non-zero) and all three bars are >= 1, ratio == 1.0f, and acc and
+ * vs equal the `advantages` and `returns` of gymrs_advantages with GYMRS_ADVANTAGES_CRITIC, the same gamma and lambda, bit for bit:
+ * gamma * (lambda * 1.0f) is the bits of gamma * lambda, and 1.0f * td those of td.
+ * vs is the `returns` row of gymrs_value_gradient; pg_advantages is the `coef` / `advantages` row of gymrs_policy_gradient /
+ * gymrs_ppo_gradient (through gymrs_normalize_advantages where the learner standardises).
+ * counts (may be NULL): device uint64 [n_policies][3], ADDED to, exact, per POLICY set: [0] += 1 per lane-step with valid, [1] += 1 per
+ * such lane-step with ratio > rho_bar, [2] += 1 per such lane-step with ratio > c_bar.  Additive over engines that cut a batch.
+ *   - gymrs_vtrace runs in the engine's stream order: a gymrs_apply_gradient or gymrs_rollout_transitions enqueued just before it needs
+ *     no synchronisation in between.  It uses the engine only for the stream, the kind, n_envs, global_env_offset, the policy set and
+ *     the critic set: it reads and writes no lane array.  It writes elements [k][i] for i < n_envs only: the padding lanes [n_envs,
+ *     lane_stride) keep their bytes and may hold anything.  n_steps == 0 is a no-op after the checks.
+ *   - GYMRS_EINVAL, naming the cause: NULL engine or desc, Pendulum, flags != 0 or reserved != 0, no policy set (naming
+ *     gymrs_set_policy), no critic set (naming gymrs_set_critic; both are required, there is no critic-less variant), gamma or lambda
+ *     NaN or outside [0, 1], scale NaN, infinite or negative, a bar that is NaN or <= 0 (+inf is legal: no clipping), NULL obs /
+ *     actions / reward / done / start_obs / old_prob / vs / pg_advantages, prob == old_prob, a row buffer not 16-byte aligned, counts
+ *     not 8-byte aligned, lane_stride < n_envs or not a multiple of 16.
+ *   - gymrs_vtrace_lane: host only, no GPU: the definition as code for ONE lane.  From one policy's weights (hidden width
+ *     policy_hidden) and one critic's (critic_hidden), K = n_steps, x[K][D] (x_cur per step), x_next[K][D] (already selected),
+ *     actions[K], reward[K], done[K], ended[K] (done[k] != 0 implies ended), old_prob[K] and the six scalars it SETS vs[0..K),
+ *     pg_advantages[0..K) and, where not NULL, values[0..K), prob[0..K) and counts[0..3).  GYMRS_EINVAL: Pendulum, a hidden width
+ *     > 64, NULL arguments, prob == old_prob, the scalars as above.
+ * The ABI version stays 3: the feature is detected by the symbol.  There is no sharded counterpart. */
+typedef struct {
+    uint32_t n_steps;           /* K */
+    uint32_t flags;             /* 0, reserved */
+    float gamma, lambda;        /* in [0, 1] */
+    float scale;                /* log2(e) / temperature, finite, >= 0, as gymrs_gradient_desc */
+    float rho_bar, c_bar, pg_rho_bar; /* > 0; +inf = no clipping */
+    gymrs_trajectory record;    /* by value; READ: obs, actions, reward, done, truncated (may be NULL); lane_stride >= n_envs, a multiple of 16 */
+    const float* final_obs;     /* [K][D][lane_stride] or NULL, 16-byte aligned */
+    const float* start_obs;     /* [D][lane_stride], required, 16-byte aligned */
+    const float* old_prob;      /* [K][lane_stride], required: the prob row of the policy the record was drawn from */
+    float* vs;                  /* [K][lane_stride], required */
+    float* pg_advantages;       /* [K][lane_stride], required */
+    float* values;              /* [K][lane_stride] or NULL */
+    float* prob;                /* [K][lane_stride] or NULL; not old_prob */
+    uint64_t* counts;           /* device uint64 [n_policies][3] or NULL, 8-byte aligned, ADDED to */
+    uint64_t reserved;          /* 0 */
+} gymrs_vtrace_desc;            /* 152 bytes */
+gymrs_status gymrs_vtrace(gymrs_engine* e, const gymrs_vtrace_desc* d);
+gymrs_status gymrs_vtrace_lane(gymrs_env_kind kind, uint32_t policy_hidden, uint32_t critic_hidden, const float* policy_weights,
+                               const float* critic_weights, uint32_t n_steps, const float* x, const float* x_next, const uint8_t* actions,
+                               const float* reward, const uint8_t* done, const uint8_t* ended, const float* old_prob, float gamma, float lambda,
+                               float scale, float rho_bar, float c_bar, float pg_rho_bar, float* vs, float* pg_advantages, float* values, float* prob,
+                               uint64_t counts[3]);
 /* Entropy: the entropy bonus of a PPO loss and the KL estimate that stops its epochs, over a transitions record in ONE launch, as
  * exact fixed-point integers.  gymrs_entropy_gradient(e, d) is a third head beside the score-function head of "gradients" and the
  * "clipped surrogate": it ADDS to grad[m][s] the fixed point of the lane's f32 sum of  d (coef * Hn) / d theta_s,  Hn = the entropy

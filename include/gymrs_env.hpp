@@ -495,6 +495,10 @@ public:
         const gymrs_ppo_desc d{n_steps, 0u, scale, clip_low, clip_high, 0u, record, start_obs, advantages, old_prob, prob, grad, excluded, counts, 0};
         check(gymrs_ppo_gradient(e_, &d));
     }
+    // V-trace (gymrs_vtrace): from the record, d.old_prob, the CURRENT policy set and the critic set, d.vs (the returns row of
+    // value_gradient) and d.pg_advantages (the coef / advantages row of policy_gradient / ppo_gradient) in one launch; d.values, d.prob
+    // and d.counts (device uint64 [n_policies][3], added to) may be null
+    void vtrace(const gymrs_vtrace_desc& d) { check(gymrs_vtrace(e_, &d)); }
     // the entropy bonus and the KL estimate (gymrs_entropy_gradient): ADDS the gradient of coef * the policy's entropy (to ascend) to
     // grad and excluded in ppo_gradient's layout, the fixed points of the entropy sum and, when old_prob is not null, of the k3 KL
     // estimate to sums (device int64 [n_sets][2]) and, when counts is not null, the lane-steps in each
